@@ -80,12 +80,17 @@ def main():
                     help="where the full result goes (regimes' per-iteration arrays, per-kernel notes): default "
                          "gpurun_out/bench_detail.json when that directory exists, else ./bench_detail.json; stdout carries "
                          "one compact line (< 8 KB) only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, a fixed seeded "
+                         "sample of the per-point assignments; under 64 MB in all), for comparing two builds output for output")
     ap.add_argument("--workload", choices=["headline", "config3", "config5"], default="headline",
                     help="headline: BASELINE.json's metric config (N=1e8, d=1024, K=100).  config3: MNIST-shaped "
                          "60000 x 784 -> 1024, K=10.  config5: one GPU's shard of the 1e9 x 784 one-pass config "
                          "(1.25e8 points per GPU, K=10), 8-bit points streamed from pinned host memory through the "
                          "sparsifier; reports the ingest rate beside the Lloyd rate")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "config3":
         args.n_total, args.dim, args.clusters = 6e4, 784, 10
     elif args.workload == "config5":
@@ -226,6 +231,7 @@ def main():
             self.runs_completed, self.run_lengths = 0, []
             self.forms = []
             self.calls, self.cold_calls = 0, []     # fused calls issued / which of them were a run's first (cold) iteration
+            self.last_out, self.last_centers = None, None   # the last step's host result; its centres if a restart followed (--dump-outputs)
 
         def restart(self):
             self.centers.copy_(self.c0)
@@ -241,6 +247,7 @@ def main():
                 out = self.eng.iterate(self.centers, want_mind=False).cpu().numpy()
             else:
                 out = self.eng.iterate_host(self.centers, want_mind=False)
+            self.last_out = out
             self.it += 1
             if self.it == 1:
                 self.cold_calls.append(self.calls)
@@ -266,12 +273,16 @@ def main():
                 dist.all_reduce(o2, op=dist.ReduceOp.SUM)
             return float(np.sqrt(o2.item()))
 
-        def steps(self, k):
-            for _ in range(k):
+        def steps(self, k, keep_last=False):
+            """k iterations; keep_last: when the last one ends a run, its centres are kept in last_centers before the restart"""
+            self.last_centers = None
+            for i in range(k):
                 _, _, done = self.step()
                 if done:
                     self.run_lengths.append(self.it)
                     self.runs_completed += 1
+                    if keep_last and i == k - 1:
+                        self.last_centers = self.centers.clone()
                     self.restart()
 
     def read_tlog(cap):
@@ -327,7 +338,7 @@ def main():
     _lib.check(L.spkm_timing_log(ctx.handle, 2))   # screen path: two pairs per call (screen, exact accumulation)
     sync_all()
     t0 = time.perf_counter()
-    loop.steps(args.steps)
+    loop.steps(args.steps, keep_last=bool(args.dump_outputs))
     sync_all()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -336,6 +347,8 @@ def main():
         elapsed = float(t.item())
 
     eng = loop.eng
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop, n_local, K)
     # the exchange as the library saw it (a SCALE record then proves RCCL ran over N ranks) and what ONE all-reduce of the
     # reduce buffer costs here, timed by itself after the window (20 back-to-back, barrier on both sides, max over ranks)
     from sparsifiedkmeans_amd.engine import comm_info
@@ -572,6 +585,35 @@ def main():
         emit(result, args.detail_out)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_POINTS = 1 << 20     # assignments of this many points (all of them on smaller shards), seeded choice
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, loop, n_local, K):
+    """What the last timed step handed its caller, as float64 .npy files under ``d``: the centres it produced
+    (centers [K, p2]), the assignments of a fixed seeded sample of this rank's points (sample_index, assign: 0-based
+    cluster), the cluster counts (nk) and the squared centre shift (dff2).  The objective is not written: the timed
+    loop leaves it out of every iteration but a run's last (spkm_shard_set_lazy_stats)."""
+    import torch
+
+    centers = loop.last_centers if loop.last_centers is not None else loop.centers
+    out = loop.last_out
+    m = min(n_local, DUMP_SAMPLE_POINTS)
+    idx = np.arange(n_local) if m == n_local else np.sort(np.random.default_rng(0).choice(n_local, m, replace=False))
+    sel = torch.from_numpy(idx).to(loop.eng.assign.device)
+    arrays = {"centers": centers.cpu().numpy().astype(np.float64),
+              "sample_index": idx.astype(np.float64),
+              "assign": loop.eng.assign[sel].cpu().numpy().astype(np.float64),
+              "nk": np.asarray(out[2:2 + K], np.float64),
+              "dff2": np.asarray(out[0:1], np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _strict(o):

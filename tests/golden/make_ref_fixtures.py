@@ -14,8 +14,12 @@ Round 4: ref_dist_* / ref_beta_* / ref_ip_* are outputs of private/SparseMatrixM
 setup_kmeans.m:19,26,33's `-O`).  They pin rows a1-a3, a11, a12: K in {1, 2, 3, 4, 7, 10, 100} (every branch of the
 switch), ragged and empty columns, duplicate centroids (exact ties for MATLAB's first-index `min`), fixed-stride
 columns of s = 51 entries at p = 1024 (the benchmark's point shape: what the fused screen path takes).
+ref_grid_sha256.json: SHA-256 digests of the reference's outputs on tests/test_oracle.py's seeded grids (the FWHT shapes
+and SURVEY 8(c)(i)'s sparse grid), too large to store as vectors: with them those tests require the reference's bits
+where the reference tree is absent.
 Run from the repo root in the build container:  python tests/golden/make_ref_fixtures.py
 """
+import json
 import os
 import sys
 
@@ -37,6 +41,33 @@ def main():
             assert np.array_equal(O.ref_fwht(x, "pthreads", nt), y)
         np.savez_compressed(os.path.join(HERE, f"ref_fwht_{m}x{n}.npz"), kind="ref_fwht", x=x, out=y)
     sparse_fixtures()
+    grid_digests()
+
+
+def grid_digests():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle as T
+    from util import parts
+
+    assert O.ref_available("native") and O.ref_available("sparse")
+    d = {}
+    for m, n in T.FWHT_GRID:
+        d[f"fwht_{m}x{n}"] = T._sha256(O.ref_fwht(T._fwht_input(m, n), "native"))
+    for p in T.SPARSE_P:
+        for K in T.SPARSE_K:
+            for n, X, Cm in T._sparse_grid(p, K):
+                jc, ir, x = parts(X)
+                d[f"dist_p{p}_K{K}_n{n}"] = T._sha256(O.ref_dist_csc(p, n, jc, ir, x, Cm))
+                if K == 1:
+                    c = Cm[:, 0]
+                    for beta in T.BETAS:
+                        d[f"beta{beta}_p{p}_n{n}"] = T._sha256(O.ref_dist_csc_beta(n, jc, ir, x, c, beta))
+                    ip, nx2 = O.ref_innerprod_csc(n, jc, ir, x, c)
+                    d[f"ip_p{p}_n{n}"], d[f"nx2_p{p}_n{n}"] = T._sha256(ip), T._sha256(nx2)
+                    d[f"nsq_p{p}_n{n}"] = T._sha256(O.ref_colnormsq_csc(n, jc, x))
+    with open(T.REF_SHA256, "w") as f:
+        json.dump(d, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def sparse_fixtures():

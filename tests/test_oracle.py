@@ -1,5 +1,7 @@
 """CPU: the C oracle against the independent numpy restatement (bit-for-bit), the identities the
 reference documents, its edge cases, and the committed regression fixtures."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -67,26 +69,61 @@ def test_fwht_bitwise_and_identities(oracle, m):
 
 
 REF_ROOT = "/root/reference"
+REF_SHA256 = os.path.join(GOLDEN, "ref_grid_sha256.json")
+FWHT_GRID = [(2, 1), (2, 7), (8, 3), (64, 1), (64, 13), (1024, 17), (4096, 4), (16, 4096)]
+SPARSE_K = [1, 2, 3, 4, 7, 10, 100]
+SPARSE_P = [2, 64, 512, 1024]
+BETAS = (0.37, 1.0, -0.5)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_ROOT, "private", "hadamard.c")),
-                    reason="the reference tree is not on this machine (oracle/_ref is built from it in place)")
-@pytest.mark.parametrize("m,n", [(2, 1), (2, 7), (8, 3), (64, 1), (64, 13), (1024, 17), (4096, 4), (16, 4096)])
-def test_fwht_oracle_equals_the_reference_build(oracle, m, n):
-    """PINS rows a13 / a14: orc_fwht / orc_fwht_threads / numpy_ref.fwht against the reference's OWN
-    hadamard_apply_vector / hadamard_apply_matrix / worker (private/hadamard.c:57-92, private/hadamard_pthreads.c:57-119
-    cut out at build time and compiled with setup_kmeans.m:53,55-57's flags -- oracle/Makefile, no stand-in header)."""
-    oracle.build(force=True)
-    assert oracle.ref_available("native") and oracle.ref_available("portable") and oracle.ref_available("pthreads")
+def _ref_tree(name):
+    return os.path.exists(os.path.join(REF_ROOT, "private", name))
+
+
+def _sha256(a):
+    """digest of an f64 array's values: -0.0 as +0.0 and every NaN as one NaN, so that equal digests mean what
+    np.array_equal(..., equal_nan=True) means"""
+    a = np.ascontiguousarray(a, np.float64) + 0.0
+    a[np.isnan(a)] = np.nan
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def _pin(key, want):
+    """``want`` holds the bits the reference's own build gave for input ``key`` (tests/golden/ref_grid_sha256.json,
+    written by make_ref_fixtures.py): where the reference tree is here ``want`` is that build's output and this checks
+    the stored digest, elsewhere ``want`` is the oracle's output and this checks it against the reference's."""
+    with open(REF_SHA256) as f:
+        digests = json.load(f)
+    assert _sha256(want) == digests[key], key
+
+
+def _fwht_input(m, n):
     rng = np.random.default_rng(1000 * m + n)
     x = rng.standard_normal((m, n)) * np.exp(rng.uniform(-30, 30, (1, n)))
     x[:, 0] = np.round(x[:, 0])                                   # an integer column among them
-    want = oracle.ref_fwht(x, "native")                           # -O3 -march=native (setup_kmeans.m:53)
-    assert np.array_equal(oracle.ref_fwht(x, "portable"), want)   # the build that travels: same bits (add / sub only)
+    return x
+
+
+@pytest.mark.parametrize("m,n", FWHT_GRID)
+def test_fwht_oracle_equals_the_reference_build(oracle, m, n):
+    """PINS rows a13 / a14: orc_fwht / orc_fwht_threads / numpy_ref.fwht against the reference's OWN
+    hadamard_apply_vector / hadamard_apply_matrix / worker (private/hadamard.c:57-92, private/hadamard_pthreads.c:57-119
+    cut out at build time and compiled with setup_kmeans.m:53,55-57's flags -- oracle/Makefile, no stand-in header).
+    Without the reference tree the same bits are required through the digests of that build's outputs (_pin)."""
+    x = _fwht_input(m, n)
+    if _ref_tree("hadamard.c"):
+        oracle.build(force=True)
+        assert oracle.ref_available("native") and oracle.ref_available("portable") and oracle.ref_available("pthreads")
+        want = oracle.ref_fwht(x, "native")                       # -O3 -march=native (setup_kmeans.m:53)
+        assert np.array_equal(oracle.ref_fwht(x, "portable"), want)   # the build that travels: same bits (add / sub only)
+        for nt in (1, 4, 8):                                      # NTHREADS of SURVEY 8(c)(i)
+            assert np.array_equal(oracle.ref_fwht(x, "pthreads", nt), want)   # the reference's worker, our partition
+    else:
+        want = oracle.fwht(x)
+    _pin(f"fwht_{m}x{n}", want)
     assert np.array_equal(oracle.fwht(x), want)
     assert np.array_equal(R.fwht(x), want)
-    for nt in (1, 4, 8):                                          # NTHREADS of SURVEY 8(c)(i)
-        assert np.array_equal(oracle.ref_fwht(x, "pthreads", nt), want)   # the reference's worker, our partition
+    for nt in (1, 4, 8):
         assert np.array_equal(oracle.fwht(x, threads=nt), want)
 
 
@@ -115,26 +152,37 @@ def _grid_csc(p, n, K, seed):
     return X, Cm
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_ROOT, "private", "SparseMatrixMinusCluster.c")),
-                    reason="the reference tree is not on this machine (oracle/_ref is built from it in place)")
-@pytest.mark.parametrize("K", [1, 2, 3, 4, 7, 10, 100])
-@pytest.mark.parametrize("p", [2, 64, 512, 1024])
+def _sparse_grid(p, K):
+    """(n, X, Cm) of SURVEY 8(c)(i)'s grid at (p, K)"""
+    for n in (1, 257, 4096):
+        if p * n * K > 3e7 and n == 4096:
+            n = 1024                                                     # (K = 100, p >= 512: keep the CPU suite short)
+        yield (n,) + _grid_csc(p, n, K, seed=7919 * K + 31 * p + n)
+
+
+@pytest.mark.parametrize("K", SPARSE_K)
+@pytest.mark.parametrize("p", SPARSE_P)
 def test_sparse_oracle_equals_the_reference_build(oracle, K, p):
     """PINS rows a1-a3, a11, a12: orc_dist_csc / orc_dist_csc_beta / orc_innerprod_csc / orc_colnormsq_csc (and the
     numpy restatement) against the reference's OWN loops -- private/SparseMatrixMinusCluster.c:131-183 (`switch (K)`,
     every branch: K = 1, 2, 3, general) and :121-129 (beta), SparseMatrixInnerProduct.c:86-100,
     SparseMatrixColumnNormSq.c:70-77 -- cut out at build time and compiled with setup_kmeans.m:19,26,33's `-O`
-    (oracle/Makefile, oracle/ref_sparse_shim.c; no stand-in header).  SURVEY 8(c)(i)'s grid."""
-    oracle.build(force=True)
-    assert oracle.ref_available("sparse") and oracle.ref_available("sparse_O2")
-    for n in (1, 257, 4096):
-        if p * n * K > 3e7 and n == 4096:
-            n = 1024                                                     # (K = 100, p >= 512: keep the CPU suite short)
-        X, Cm = _grid_csc(p, n, K, seed=7919 * K + 31 * p + n)
+    (oracle/Makefile, oracle/ref_sparse_shim.c; no stand-in header).  SURVEY 8(c)(i)'s grid.  Without the reference
+    tree the same bits are required through the digests of that build's outputs (_pin)."""
+    here = _ref_tree("SparseMatrixMinusCluster.c")
+    if here:
+        oracle.build(force=True)
+        assert oracle.ref_available("sparse") and oracle.ref_available("sparse_O2")
+    for n, X, Cm in _sparse_grid(p, K):
         jc, ir, x = parts(X)
-        want = oracle.ref_dist_csc(p, n, jc, ir, x, Cm)
-        assert np.array_equal(oracle.ref_dist_csc(p, n, jc, ir, x, Cm, "sparse_O2"), want)   # mex's stock -O2: same bits
-        assert np.array_equal(oracle.dist_csc(p, n, jc, ir, x, Cm), want)
+        ours = oracle.dist_csc(p, n, jc, ir, x, Cm)
+        if here:
+            want = oracle.ref_dist_csc(p, n, jc, ir, x, Cm)
+            assert np.array_equal(oracle.ref_dist_csc(p, n, jc, ir, x, Cm, "sparse_O2"), want)   # mex's stock -O2: same bits
+        else:
+            want = ours
+        _pin(f"dist_p{p}_K{K}_n{n}", want)
+        assert np.array_equal(ours, want)
         if n <= 257:
             assert np.array_equal(R.dist_csc(p, n, jc, ir, x, Cm), want)
         # findClusterAssignments.m:169 on the reference's distances == orc_assign (gamma empty: no centres/gamma step)
@@ -145,14 +193,21 @@ def test_sparse_oracle_equals_the_reference_build(oracle, K, p):
             assert not np.any(a == K - 1)                                # the duplicate never wins: first index
         if K == 1:
             c = Cm[:, 0]
-            for beta in (0.37, 1.0, -0.5):
-                assert np.array_equal(oracle.dist_csc_beta(n, jc, ir, x, c, beta),
-                                      oracle.ref_dist_csc_beta(n, jc, ir, x, c, beta), equal_nan=True)
+            for beta in BETAS:
+                got = oracle.dist_csc_beta(n, jc, ir, x, c, beta)
+                rb = oracle.ref_dist_csc_beta(n, jc, ir, x, c, beta) if here else got
+                _pin(f"beta{beta}_p{p}_n{n}", rb)
+                assert np.array_equal(got, rb, equal_nan=True)
             ip, nx2 = oracle.innerprod_csc(n, jc, ir, x, c)
-            rip, rnx2 = oracle.ref_innerprod_csc(n, jc, ir, x, c)
+            rip, rnx2 = oracle.ref_innerprod_csc(n, jc, ir, x, c) if here else (ip, nx2)
+            _pin(f"ip_p{p}_n{n}", rip)
+            _pin(f"nx2_p{p}_n{n}", rnx2)
             assert np.array_equal(ip, rip) and np.array_equal(nx2, rnx2)
-            assert np.array_equal(oracle.colnormsq_csc(n, jc, x), oracle.ref_colnormsq_csc(n, jc, x))
-            assert np.array_equal(rnx2, oracle.ref_colnormsq_csc(n, jc, x))
+            nsq = oracle.colnormsq_csc(n, jc, x)
+            rnsq = oracle.ref_colnormsq_csc(n, jc, x) if here else nsq
+            _pin(f"nsq_p{p}_n{n}", rnsq)
+            assert np.array_equal(nsq, rnsq)
+            assert np.array_equal(rnx2, rnsq)
 
 
 def _load_golden(prefix):
