@@ -340,6 +340,24 @@ uint64_t spkm_record_bytes(uint64_t s, int ir_bits);
 int spkm_mix_sample_rec_dev(spkm_ctx *ctx, uint64_t p, uint64_t p2, uint64_t n, const double *d_x,
                             const double *d_sign, double premul, double postdiv, uint64_t s, uint64_t seed,
                             uint64_t col0, int ir_bits, void *d_rec_out);
+/* The sparsifier for the sketches without a power-of-two transform (p2 = p): kind SPKM_SKETCH_DCT, the orthonormal
+ * DCT-II of DD*X (kmeans_sparsified.m:256-258,283-295; 'auto' picks it when p is not a power of two), or
+ * SPKM_SKETCH_NONE ('SketchType','none').  Rows are drawn exactly as by spkm_mix_sample_dev (same Philox stream, keyed by
+ * (seed, col0 + c), p2 = p); the sketch is evaluated only at them, never as a whole column:
+ *   DCT:  (w(k) * sum_n cos(pi (2n+1) k / (2p)) * ((x_n * premul) * d_sign[n])) / (s/p),  w(0) = sqrt(1/p), else sqrt(2/p)
+ *         (s*p multiply-adds per point; to tolerance against an FFT-based dct)
+ *   none: (x_k * premul) / (s/p), bit for bit what the reference computes at that row.
+ * d_sign: p doubles of +-1, required for the DCT and ignored by none.  spkm_sketch_sample_dev writes CSC (as
+ * spkm_mix_sample_dev), spkm_sketch_sample_rec_dev records (as spkm_mix_sample_rec_dev).
+ * SPKM_ERR_BAD_VALUE for a bad kind, s == 0, s > p, ir_bits not 16 / 32, or 16-bit ids with p > 65536;
+ * SPKM_ERR_UNSUPPORTED for a DCT with p > 16384 (its cosine table, (p + 1) * 8 bytes of LDS, must fit a workgroup). */
+#define SPKM_SKETCH_NONE 0
+#define SPKM_SKETCH_DCT 1
+int spkm_sketch_sample_dev(spkm_ctx *ctx, int kind, uint64_t p, uint64_t n, const double *d_x, const double *d_sign,
+                           double premul, uint64_t s, uint64_t seed, uint64_t col0, void *d_ir_out, int ir_bits,
+                           double *d_x_out);
+int spkm_sketch_sample_rec_dev(spkm_ctx *ctx, int kind, uint64_t p, uint64_t n, const double *d_x, const double *d_sign,
+                               double premul, uint64_t s, uint64_t seed, uint64_t col0, int ir_bits, void *d_rec_out);
 /* A shard over n records of exactly s entries each that the caller holds on the device (and keeps alive): what
  * kmeans_sparsified.m:316-334 produces for one GPU, in the library's own layout.  Everything a CSC shard can do it can do:
  * an entry point that needs CSC arrays re-materialises library-owned ones from the records first.

@@ -779,6 +779,66 @@ extern "C" int spkm_mix_sample_rec_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, u
     return fwht_launch(ctx, p, p2, n, d_x, d_sign, premul, postdiv, (double*)d_rec_out, ir0, ir_bits, (int)s, level, R);
 }
 
+// The sparsifier for the DCT and for no sketch (p2 = p): k_sample_rows draws the rows exactly as for the Hadamard path,
+// k_sketch_gather evaluates the sketch at them.  stride > 0: records (ids at d_out + s*8 + c*stride, values at d_out +
+// c*stride); stride == 0: CSC (ids in d_ir_out, values in d_out).
+static int sketch_sample_launch(spkm_ctx* ctx, int kind, uint64_t p, uint64_t n, const double* d_x, const double* d_sign,
+                                double premul, uint64_t s, uint64_t seed, uint64_t col0, void* d_ir_out, int ir_bits,
+                                double* d_out, long long stride)
+{
+    if (kind != SPKM_SKETCH_NONE && kind != SPKM_SKETCH_DCT) return SPKM_ERR_BAD_VALUE;
+    if (n && kind == SPKM_SKETCH_DCT && !d_sign) return SPKM_ERR_NULL_ARG;
+    if (s == 0 || s > p || (ir_bits != 16 && ir_bits != 32) || (ir_bits == 16 && p > 65536) || p > 0x7fffffffull)
+        return SPKM_ERR_BAD_VALUE;
+    const size_t tab = kind == SPKM_SKETCH_DCT ? (size_t)(p + 1) * 8 : 0;
+    if (kind == SPKM_SKETCH_DCT && (p > 16384 || tab > ctx->lds_max)) return SPKM_ERR_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return SPKM_OK;
+    const unsigned sblocks = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, ctx->num_cus) * 16);
+    // a large table is built once per 16 waves, a small one per 4
+    const int threads = tab > 40960 ? 1024 : 256;
+    const uint64_t waves = (uint64_t)threads / 64;
+    const unsigned gblocks = (unsigned)std::min<uint64_t>((n + waves - 1) / waves,
+                                                          (uint64_t)std::max(1, ctx->num_cus) * (threads == 1024 ? 2 : 8));
+    const double level = (double)s / (double)p;   // SparsityLevel = small_p / p (randsample_fixedNumberEntries.m:30-31)
+    if (ir_bits == 16) {
+        hipLaunchKernelGGL((k_sample_rows<unsigned short>), dim3(sblocks), dim3(256), 0, ctx->stream,
+                           (unsigned long long)seed, (long long)col0, (long long)n, (int)p, (int)s, (unsigned short*)d_ir_out, stride);
+        if (tab) HIP_TRY(hipFuncSetAttribute((const void*)k_sketch_gather<unsigned short>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab));
+        hipLaunchKernelGGL((k_sketch_gather<unsigned short>), dim3(gblocks), dim3(threads), tab, ctx->stream, d_x, (int)p,
+                           (long long)n, (int)s, (const unsigned short*)d_ir_out, d_sign, premul, level, (int)kind, d_out, stride);
+    } else {
+        hipLaunchKernelGGL((k_sample_rows<unsigned int>), dim3(sblocks), dim3(256), 0, ctx->stream,
+                           (unsigned long long)seed, (long long)col0, (long long)n, (int)p, (int)s, (unsigned int*)d_ir_out, stride);
+        if (tab) HIP_TRY(hipFuncSetAttribute((const void*)k_sketch_gather<unsigned int>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab));
+        hipLaunchKernelGGL((k_sketch_gather<unsigned int>), dim3(gblocks), dim3(threads), tab, ctx->stream, d_x, (int)p,
+                           (long long)n, (int)s, (const unsigned int*)d_ir_out, d_sign, premul, level, (int)kind, d_out, stride);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPKM_OK;
+}
+
+extern "C" int spkm_sketch_sample_dev(spkm_ctx* ctx, int kind, uint64_t p, uint64_t n, const double* d_x,
+                                      const double* d_sign, double premul, uint64_t s, uint64_t seed, uint64_t col0,
+                                      void* d_ir_out, int ir_bits, double* d_x_out)
+{
+    if (!ctx || (n && (!d_x || !d_ir_out || !d_x_out))) return SPKM_ERR_NULL_ARG;
+    return sketch_sample_launch(ctx, kind, p, n, d_x, d_sign, premul, s, seed, col0, d_ir_out, ir_bits, d_x_out, 0);
+}
+
+extern "C" int spkm_sketch_sample_rec_dev(spkm_ctx* ctx, int kind, uint64_t p, uint64_t n, const double* d_x,
+                                          const double* d_sign, double premul, uint64_t s, uint64_t seed, uint64_t col0,
+                                          int ir_bits, void* d_rec_out)
+{
+    if (!ctx || (n && (!d_x || !d_rec_out))) return SPKM_ERR_NULL_ARG;
+    if (s == 0 || (ir_bits != 16 && ir_bits != 32)) return SPKM_ERR_BAD_VALUE;
+    const long long R = (long long)spkm_record_bytes(s, ir_bits);
+    return sketch_sample_launch(ctx, kind, p, n, d_x, d_sign, premul, s, seed, col0, (char*)d_rec_out + s * 8, ir_bits,
+                                (double*)d_rec_out, R);
+}
+
 extern "C" int spkm_widen_f64_dev(spkm_ctx* ctx, int kind, uint64_t count, const void* d_src, double* d_dst)
 {
     if (!ctx || (count && (!d_src || !d_dst))) return SPKM_ERR_NULL_ARG;

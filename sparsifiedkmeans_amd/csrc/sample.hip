@@ -85,3 +85,86 @@ __global__ __launch_bounds__(256) void k_widen_f64(const void* __restrict__ src,
         if (two) dst[i + 1] = b;
     }
 }
+
+// Sampled sketch for the kinds without a power-of-two transform: the DCT ('auto' for p not a power of two,
+// kmeans_sparsified.m:226-231,256-258) and no sketch at all.  It runs after k_sample_rows (p2 = p here) and evaluates the
+// mixed column ONLY at the s kept rows, never the whole transform:
+//   dct = 0 (none): y[t] = (x[k_t] * premul) / level -- the host's two roundings in its order, bit for bit
+//   dct = 1:        y[t] = (w(k_t) * sum_n cos(pi (2n+1) k_t / (2p)) * ((x_n * premul) * sign_n)) / level,
+//                   w(0) = sqrt(1/p), w(k>0) = sqrt(2/p): MATLAB's orthonormal dct of DD*X at row k_t; s*p FMAs per point
+//                   instead of the p^2 of a dense transform
+// with level = s/p.  One wave per column, one lane per sampled row (columns longer than 64 in groups of 64).  x_n is
+// wave-uniform: a lane loads x[n0 + lane] coalesced and the inner loop broadcasts it with v_readlane (no LDS traffic).
+// The cosines come from an LDS quarter-wave table tab[j] = cos(pi j / (2p)), j = 0..p ((p+1) * 8 bytes, 131 KB at
+// p = 16384), indexed by (2n+1) k mod 4p, which each lane advances by 2k per n.
+// stride_bytes > 0: column c's ids start that many BYTES after column c - 1's, and so do its values (the record layout).
+template <typename IR>
+__global__ __launch_bounds__(1024) void k_sketch_gather(const double* __restrict__ x, int p, long long n, int s,
+                                                        const IR* __restrict__ ir, const double* __restrict__ dsign,
+                                                        double premul, double level, int dct, double* __restrict__ y,
+                                                        long long stride_bytes)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* tab = reinterpret_cast<double*>(smem);
+    if (dct) {
+        const double inv = 1.0 / (2.0 * (double)p);
+        for (int j = threadIdx.x; j <= p; j += blockDim.x) tab[j] = cospi((double)j * inv);
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int waves = blockDim.x >> 6;
+    const double w0 = sqrt(1.0 / (double)p), w1 = sqrt(2.0 / (double)p);
+    for (long long c = (long long)blockIdx.x * waves + (threadIdx.x >> 6); c < n; c += (long long)gridDim.x * waves) {
+        const IR* irc = stride_bytes > 0 ? reinterpret_cast<const IR*>(reinterpret_cast<const char*>(ir) + (size_t)c * (size_t)stride_bytes)
+                                         : ir + (size_t)c * s;
+        double* yc = stride_bytes > 0 ? reinterpret_cast<double*>(reinterpret_cast<char*>(y) + (size_t)c * (size_t)stride_bytes)
+                                      : y + (size_t)c * s;
+        const double* xc = x + (size_t)c * p;
+        if (!dct) {
+            for (int t = lane; t < s; t += 64) {
+                double v = xc[(int)irc[t]];
+                if (premul != 1.0) v = v * premul;
+                yc[t] = v / level;
+            }
+            continue;
+        }
+        for (int t0 = 0; t0 < s; t0 += 64) {
+            const int t = t0 + lane;
+            const bool on = t < s;
+            const int k = on ? (int)irc[t] : 0;
+            const int two_p = 2 * p, four_p = 4 * p, step = 2 * k;   // 2k < 4p: one wrap per step at most
+            int idx = k;                                               // (2n+1) k mod 4p at n = 0
+            double acc = 0.0;
+            for (int n0 = 0; n0 < p; n0 += 64) {
+                double v = 0.0;
+                if (n0 + lane < p) {
+                    v = xc[n0 + lane];
+                    if (premul != 1.0) v = v * premul;
+                    v = v * dsign[n0 + lane];
+                }
+                const long long vb = __double_as_longlong(v);
+                const int lo = (int)vb, hi = (int)(vb >> 32);
+                // groups of 8 (v_readlane is convergent: a loop of run-time length would not be unrolled); lanes past p
+                // hold zeros, so a group that runs past p adds nothing
+                const int cnt = p - n0 < 64 ? p - n0 : 64;
+                for (int q0 = 0; q0 < cnt; q0 += 8)
+#pragma unroll
+                for (int q = q0; q < q0 + 8; q++) {
+                    const unsigned xl = (unsigned)__builtin_amdgcn_readlane(lo, q);
+                    const unsigned xh = (unsigned)__builtin_amdgcn_readlane(hi, q);
+                    const double xn = __longlong_as_double((long long)(((unsigned long long)xh << 32) | xl));
+                    // cos(pi idx / (2p)) from the quarter wave: [0,p] +, (p,2p) -, [2p,3p] -, (3p,4p) +
+                    int a = idx;
+                    bool neg = false;
+                    if (a >= two_p) { a -= two_p; neg = true; }
+                    if (a > p) { a = two_p - a; neg = !neg; }
+                    const double cv = tab[a];
+                    acc = fma(xn, neg ? -cv : cv, acc);
+                    idx += step;
+                    if (idx >= four_p) idx -= four_p;
+                }
+            }
+            if (on) yc[t] = ((k == 0 ? w0 : w1) * acc) / level;
+        }
+    }
+}

@@ -448,6 +448,35 @@ def mix_sample_records_device(ctx: Context, x: torch.Tensor, p2: int, sign: torc
                                                   int(col0), int(ir_bits), _p(rec_out)), "spkm_mix_sample_rec_dev")
 
 
+SKETCH_KIND = {"none": 0, "dct": 1}   # SPKM_SKETCH_NONE, SPKM_SKETCH_DCT
+
+
+def sketch_sample_device(ctx: Context, kind: str, x: torch.Tensor, sign: torch.Tensor | None, premul: float, s: int,
+                         seed: int, col0: int, ir_out: torch.Tensor, x_out: torch.Tensor):
+    """The sparsifier for kind "dct" / "none" (p2 = p) on a dense device chunk [n, p] (spkm_sketch_sample_dev): the rows
+    of mix_sample_device's generator, the values dct(DD*(x*premul))[row] / (s/p) or (x[row]*premul) / (s/p)."""
+    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2
+    n, p = x.shape
+    assert ir_out.numel() >= n * s and x_out.numel() >= n * s and x_out.dtype == torch.float64
+    bits = ir_out.element_size() * 8
+    _lib.check(_lib.lib().spkm_sketch_sample_dev(ctx.handle, SKETCH_KIND[kind], p, n, _p(x),
+                                                 _p(sign) if sign is not None else None, float(premul), int(s),
+                                                 int(seed) & (2**64 - 1), int(col0), _p(ir_out), bits, _p(x_out)),
+               "spkm_sketch_sample_dev")
+
+
+def sketch_sample_records_device(ctx: Context, kind: str, x: torch.Tensor, sign: torch.Tensor | None, premul: float,
+                                 s: int, seed: int, col0: int, rec_out: torch.Tensor, ir_bits: int = 16):
+    """sketch_sample_device writing RECORDS (spkm_sketch_sample_rec_dev; layout as mix_sample_records_device)."""
+    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2
+    n, p = x.shape
+    assert rec_out.dtype == torch.uint8 and rec_out.is_contiguous() and rec_out.numel() >= n * record_bytes(s, ir_bits)
+    _lib.check(_lib.lib().spkm_sketch_sample_rec_dev(ctx.handle, SKETCH_KIND[kind], p, n, _p(x),
+                                                     _p(sign) if sign is not None else None, float(premul), int(s),
+                                                     int(seed) & (2**64 - 1), int(col0), int(ir_bits), _p(rec_out)),
+               "spkm_sketch_sample_rec_dev")
+
+
 def dense_assign_device(ctx: Context, x: torch.Tensor, centers: torch.Tensor):
     """[assignments, distances] = findClusterAssignments(full(X), centers), dense branch / expanded quadratic
     (private/findClusterAssignments.m:157-171) for a dense device chunk ``x`` [n, p] and ``centers`` [K, p].
@@ -513,7 +542,11 @@ class StreamingSparsifier:
     """One-pass ingest of a dense dataset that never fits in HBM at once: chunk -> X*(1+2eps) -> mix ->
     sample -> append to the resident sparse shard (private/sampleAndMixFromLargeFile.m:79-129).  Only the
     sparse form (10 B per kept entry) stays on the device; the dense intermediate of a chunk lives in one
-    reusable buffer and the mixed chunk never leaves LDS.
+    reusable buffer and the mixed chunk never reaches HBM.
+
+    ``kind``: "hadamard" (the FWHT of the zero-padded column, p2 = next power of two; the mixed column stays in LDS),
+    "dct" or "none" (p2 = p; the sketch is evaluated at the sampled rows only, spkm_sketch_sample_dev).  The rows are
+    drawn by the same generator for every kind.  Without ``kind``, ``sketch=True`` means "hadamard", False "none".
 
     Chunks may arrive as float64 / float32 / uint8 / int16 / int32 (a 1e9-point dataset is not stored as doubles);
     narrower types cross PCIe as they are and are widened on the device (spkm_widen_f64_dev, exact).  Host chunks go
@@ -525,11 +558,12 @@ class StreamingSparsifier:
     (seed, global index) only, so any chunking / sharding yields the same dataset)."""
 
     def __init__(self, ctx: Context, p: int, n_local: int, s: int, seed: int, sign: torch.Tensor | None,
-                 first: int = 0, sketch: bool = True, layout: str = "csc"):
+                 first: int = 0, sketch: bool = True, layout: str = "csc", kind: str | None = None):
         self.ctx, self.p, self.n, self.s, self.seed, self.first = ctx, int(p), int(n_local), int(s), int(seed), int(first)
-        self.p2 = (1 << max(1, int(np.ceil(np.log2(p))))) if sketch else int(p)
-        if not sketch:
-            raise NotImplementedError("the fused sampler sits behind the Hadamard sketch (power-of-two row count)")
+        self.kind = kind if kind is not None else ("hadamard" if sketch else "none")
+        if self.kind not in ("hadamard", "dct", "none"):
+            raise ValueError(f"unknown sketch kind {self.kind!r}")
+        self.p2 = (1 << max(1, int(np.ceil(np.log2(p))))) if self.kind == "hadamard" else int(p)
         dev = torch.device("cuda", ctx.device)
         self.sign = sign
         # layout = "records": the chunks are appended in the library's record layout (Shard.from_records; columns of at most
@@ -623,12 +657,20 @@ class StreamingSparsifier:
                        "spkm_widen_f64_dev")
             fin = buf
         o = self.filled * self.s
-        if self.records:
-            mix_sample_records_device(self.ctx, fin, self.p2, self.sign, 1.0 + 2.0 * float(np.finfo(np.float64).eps),
+        premul = 1.0 + 2.0 * float(np.finfo(np.float64).eps)
+        if self.kind != "hadamard":
+            if self.records:
+                sketch_sample_records_device(self.ctx, self.kind, fin, self.sign, premul, self.s, self.seed,
+                                             self.first + self.filled, self.rec[self.filled * self.R:], self.ir_bits)
+            else:
+                sketch_sample_device(self.ctx, self.kind, fin, self.sign, premul, self.s, self.seed,
+                                     self.first + self.filled, self.ir[o:], self.x[o:])
+        elif self.records:
+            mix_sample_records_device(self.ctx, fin, self.p2, self.sign, premul,
                                       float(np.sqrt(np.float64(self.p2))), self.s, self.seed, self.first + self.filled,
                                       self.rec[self.filled * self.R:], self.ir_bits)
         else:
-            mix_sample_device(self.ctx, fin, self.p2, self.sign, 1.0 + 2.0 * float(np.finfo(np.float64).eps),
+            mix_sample_device(self.ctx, fin, self.p2, self.sign, premul,
                               float(np.sqrt(np.float64(self.p2))), self.s, self.seed, self.first + self.filled,
                               self.ir[o:], self.x[o:])
         if not t.is_cuda:

@@ -5,8 +5,11 @@ the MI355X through libspkm.so.
 Scope: the sparsified path -- 'Sparsify',true with the Hadamard sketch or no
 sketch -- including the two-pass outputs (nargout 6..9).  What the reference does with MATLAB toolboxes
 outside that path (matfile containers, function-handle sketches) raises NotImplementedError naming the option,
-rather than silently doing something else.  The DCT sketch ('auto' picks it when p is not a power of two) is a
-p x p orthonormal matrix applied with a library GEMM.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
+rather than silently doing something else.  Data is sparsified on the device for the Hadamard sketch (16 <= p2 <= 16384),
+the DCT sketch ('auto' picks it when p is not a power of two; p <= 16384) and no sketch: chunks cross PCIe in their own
+dtype, rows are drawn by one counter-based generator keyed by (seed, global index), and the sketch is applied in HIP
+(the DCT evaluated at the sampled rows only).  Unmixing the K centres of the DCT is a p x p GEMM; a Hadamard sketch
+outside that p2 range samples on the host.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
 dense kernels of the two-pass outputs (one GPU, data resident in HBM).  'MLcorrection',false (plain means of the sparse columns,
 kmeans_sparsified.m:449-451) runs on the same accumulation with a different final division.
 
@@ -190,7 +193,7 @@ def kmeans_sparsified(X, K, **options):
         X = np.asarray(X)
         # float32 / uint8 / int16 data stays as it is on the host (it crosses PCIe narrow and is widened on the device,
         # exactly); everything else becomes float64 as in MATLAB
-        keep_narrow = X.dtype in (np.float32, np.uint8, np.int16) and str(o["SketchType"]).lower() in ("auto", "hadamard")
+        keep_narrow = X.dtype in (np.float32, np.uint8, np.int16)
         if not keep_narrow:
             X = np.asarray(X, np.float64)
         if not o["ColumnSamples"]:
@@ -234,11 +237,12 @@ def kmeans_sparsified(X, K, **options):
     gamma = small_p / p                                                          # :329 (divides by p, not p2)
     sample_seed = int(rng.integers(0, 2**63 - 1))
     Y = None
-    if sk == "hadamard" and 16 <= p2 <= 16384:
+    if (sk == "hadamard" and 16 <= p2 <= 16384) or sketch.kind in ("dct", "none"):
         # device sparsifier: chunk -> X*(1+2eps) -> mix -> sample -> resident CSC (kmeans_sparsified.m:292-334;
-        # for 'DataFile': sampleAndMixFromLargeFile.m:100-129).  The dense mixed data never reaches HBM.
+        # for 'DataFile': sampleAndMixFromLargeFile.m:100-129).  The dense mixed data never reaches HBM: the Hadamard
+        # transform stays in LDS, the DCT is evaluated at the sampled rows only, no sketch gathers them.
         t1 = time.time()
-        sp_ = StreamingSparsifier(ctx, p, n, small_p, sample_seed, sketch.sign, first=first)
+        sp_ = StreamingSparsifier(ctx, p, n, small_p, sample_seed, sketch.sign, first=first, kind=sketch.kind)
         nn = max(1, min(n, int(o["MB_limit"] * 2**20 // (8 * p))))               # sampleAndMixFromLargeFile.m:82-84
         if LoadFromDisk and o["DataFileVerbose"]:
             print(f"Splitting {p} x {n} matrix into {-(-n // nn)} {p} x {nn} chunks")
@@ -250,10 +254,10 @@ def kmeans_sparsified(X, K, **options):
             sp_.append(np.ascontiguousarray(blk))
         shard = sp_.finish()
         vals_ = sp_.x[: n * small_p]
-        # one Inf / NaN entry makes its whole mixed column non-finite (every output of the transform is a signed sum
-        # of all inputs), so the sampled values tell.  The reference has no such check: its run ends in
-        # error('Found NaN in centers') (:480-484) a few iterations later; here the data is refused up front, because
-        # the argmin kernels are specified for finite distances only.
+        # with a sketch, one Inf / NaN entry makes its whole mixed column non-finite (every output of the transform is a
+        # signed sum of all inputs), so the sampled values tell (without one, the sampled entries themselves).  The
+        # reference has no such check: its run ends in error('Found NaN in centers') (:480-484) a few iterations later;
+        # here the data is refused up front, because the argmin kernels are specified for finite distances only.
         if not bool(torch.isfinite(vals_).all().item()):
             raise ValueError("X must be finite (Inf / NaN entries found)")
         nnz = n * small_p
@@ -275,7 +279,7 @@ def kmeans_sparsified(X, K, **options):
         torch.cuda.synchronize()
         OUTPUT["TimeToSketch"] = OUTPUT["TimeToSample"] = time.time() - t1       # fused: one number for both
     else:
-        # DCT / no sketch: mix on the device (a GEMM or nothing), sample on the host (randsample_fixedNumberEntries,
+        # Hadamard with p2 < 16 or p2 > 16384: mix on the device, sample on the host (randsample_fixedNumberEntries,
         # :334), MB_limit columns at a time -- the same generator runs through all chunks, so a 'DataFile' run
         # draws exactly the samples of the in-memory run (sampleAndMixFromLargeFile.m:100-129)
         nn = max(1, min(n, int(o["MB_limit"] * 2**20 // (8 * p)))) if LoadFromDisk else n
