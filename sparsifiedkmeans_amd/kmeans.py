@@ -75,6 +75,32 @@ def _nextpow2(p: int) -> int:
     return 1 << max(0, int(np.ceil(np.log2(p)))) if p > 1 else 1
 
 
+def dct_matrix(p: int, device, rows=None) -> torch.Tensor:
+    """The orthonormal DCT-II as MATLAB's dct() applies it, as a matrix: M[k, n] = w(k) cos(pi (2n+1) k / (2p)) with
+    w(0) = sqrt(1/p), w(k>0) = sqrt(2/p) (0-based); idct is its transpose.  ``rows``: only those k (default all).
+    The angle is reduced exactly in integers, m = (2n+1) k mod 4p, as k_sketch_gather does (sample.hip), and folded onto
+    [0, pi/4] (the cosine below, the sine of the complement above): the start and the centres live in the coordinates
+    of the values that kernel samples.  The cosine of the float64 product pi (2n+1) k / (2p) instead carries the rounding
+    of an argument of up to ~p pi rad (relative entry errors up to ~1e-11 at p = 16383)."""
+    k = torch.arange(p, dtype=torch.int64, device=device) if rows is None else torch.as_tensor(rows, dtype=torch.int64,
+                                                                                                device=device)
+    n = torch.arange(p, dtype=torch.int64, device=device)
+    m = torch.remainder((2 * n[None, :] + 1) * k[:, None], 4 * p)                 # < 4p; (2n+1) k < 2 p^2 fits int64
+    neg = m >= 2 * p                                                               # cos(a + pi) = -cos(a)
+    m = torch.where(neg, m - 2 * p, m)
+    back = m > p                                                                   # cos(pi - a) = -cos(a)
+    m = torch.where(back, 2 * p - m, m)
+    hi = 2 * m > p                                                                 # cos(a) = sin(pi/2 - a) above pi/4
+    a = torch.where(hi, p - m, m).to(torch.float64) * (np.pi / (2.0 * p))          # in [0, pi/4]
+    M = torch.where(hi, torch.sin(a), torch.cos(a))
+    del a, hi, m
+    M = torch.where(neg ^ back, -M, M)
+    del neg, back
+    w = torch.where(k == 0, torch.tensor(np.sqrt(1.0 / p), dtype=torch.float64, device=device),
+                    torch.tensor(np.sqrt(2.0 / p), dtype=torch.float64, device=device))
+    return M * w[:, None]
+
+
 class _Sketch:
     """mix / unmix of kmeans_sparsified.m:238-296 on device tensors laid out [n, p]."""
 
@@ -83,14 +109,10 @@ class _Sketch:
         self.p2 = _nextpow2(p) if kind == "hadamard" else p
         self.sign = None if sign is None else torch.tensor(sign, dtype=torch.float64, device=f"cuda:{ctx.device}")
         if kind == "dct":
-            # orthonormal DCT-II as MATLAB's dct(): y(k) = w(k) sum_n x(n) cos(pi (2n-1)(k-1) / (2N)), w(1) = 1/sqrt(N),
-            # w(k>1) = sqrt(2/N); idct is its transpose (kmeans_sparsified.m:256-258).  A p x p matrix applied with a
-            # library GEMM: one pass over the data, and the reference's own dct is a toolbox FFT whose rounding is
-            # not specified either (tolerance parity).
-            k = torch.arange(p, dtype=torch.float64, device=f"cuda:{ctx.device}")[:, None]
-            nn_ = torch.arange(p, dtype=torch.float64, device=f"cuda:{ctx.device}")[None, :]
-            M = torch.cos(np.pi * (2.0 * nn_ + 1.0) * k / (2.0 * p)) * np.sqrt(2.0 / p)
-            M[0] = M[0] / np.sqrt(2.0)
+            # orthonormal DCT-II as MATLAB's dct() applied with a library GEMM (kmeans_sparsified.m:256-258): one pass over
+            # the data, and the reference's own dct is a toolbox FFT whose rounding is not specified either (tolerance
+            # parity).  The matrix is built as the sampling kernel evaluates it (dct_matrix).
+            M = dct_matrix(p, f"cuda:{ctx.device}")
             self.M = M                                                            # [p, p]: y = M x
 
     def mix(self, x: torch.Tensor, premul: float = 1.0) -> torch.Tensor:

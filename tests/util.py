@@ -148,3 +148,134 @@ def mnist_like_pixels(n=60000, K=10, seed=3):
         px = 255.0 * gain * im + 12.0 * rng.standard_normal((m, 28, 28)) * (im > 0.05)
         X[c0:c0 + m] = np.clip(np.round(px), 0, 255).astype(np.uint8).reshape(m, 784)
     return X, labels
+
+
+# ---- high-precision host replay of the DCT / no-sketch sparsifier (k_sketch_gather, _Sketch, kmeans_sparsified) ----
+PREMUL = 1.0 + 2.0 * np.finfo(np.float64).eps          # X*(1+2eps) (kmeans_sparsified.m:292)
+PI_LD = np.longdouble("3.14159265358979323846264338327950288")   # np.pi is only a double
+_LD_BLOCK = 1 << 21                                   # long-double entries per block of the references below
+
+
+def _dct_cos_table_ld(p):
+    """tab[m] = cos(pi m / (2p)), m = 0 .. 4p-1, in long double: m is folded onto [0, p] (quarter wave, exact in
+    integers) before the cosine, so the zeros and +-1 of the table are exact"""
+    m = np.arange(4 * p, dtype=np.int64)
+    neg = m >= 2 * p
+    a = np.where(neg, m - 2 * p, m)
+    back = a > p
+    a = np.where(back, 2 * p - a, a)
+    tab = np.cos(PI_LD * a.astype(np.longdouble) / np.longdouble(2 * p))
+    tab[a == p] = 0
+    return np.where(neg ^ back, -tab, tab)
+
+
+def _dct_weights_ld(p):
+    w = np.full(p, np.sqrt(np.longdouble(2) / np.longdouble(p)))
+    w[0] = np.sqrt(np.longdouble(1) / np.longdouble(p))
+    return w
+
+
+def dct_rows_ld(X, sign, rows, premul):
+    """MATLAB's orthonormal dct of DD*(X*premul) at the given rows, in long double.  X: [n, p] points as rows; sign: [p]
+    (None: no DD); rows: [n, s] 0-based rows k.  X*premul is rounded to float64 first, as the product is in the
+    reference (kmeans_sparsified.m:292) and in the kernel; after that everything is long double: the angle reduced
+    exactly in integers, m = (2n+1) k mod 4p, a long-double pi, w(0) = sqrt(1/p), w(k>0) = sqrt(2/p).
+    Returns [n, s] long double (not divided by the sparsity level)."""
+    X = np.asarray(X, np.float64)
+    n, p = X.shape
+    rows = np.asarray(rows, np.int64).reshape(n, -1)
+    V = X * premul if premul != 1.0 else X.copy()
+    if sign is not None:
+        V = V * np.asarray(sign, np.float64)
+    tab, w = _dct_cos_table_ld(p), _dct_weights_ld(p)
+    odd = 2 * np.arange(p, dtype=np.int64) + 1
+    pi_, pk = np.nonzero(np.ones(rows.shape, bool))
+    pk = rows[pi_, pk]
+    out = np.empty(pi_.size, np.longdouble)
+    g = max(1, _LD_BLOCK // max(p, 1))
+    for j0 in range(0, pi_.size, g):
+        k, i = pk[j0:j0 + g], pi_[j0:j0 + g]
+        out[j0:j0 + g] = w[k] * np.einsum("ij,ij->i", tab[(odd[None, :] * k[:, None]) % (4 * p)],
+                                            V[i].astype(np.longdouble))
+    return out.reshape(rows.shape)
+
+
+def dct_matrix_ld(p):
+    """[p, p] long double: M[k, n] = w(k) cos(pi (2n+1) k / (2p)) (the start mix is M @ (d .* S'))"""
+    k = np.arange(p, dtype=np.int64)
+    return _dct_weights_ld(p)[:, None] * _dct_cos_table_ld(p)[((2 * k[None, :] + 1) * k[:, None]) % (4 * p)]
+
+
+def dct_ld(X, sign):
+    """full orthonormal dct of DD*X, rows = points: [n, p] -> [n, p] long double (the start mix; no premul).  A second,
+    independent long-double route to dct_rows_ld's numbers, for whole transforms (the direct sum is O(p^2) per point):
+    with u[2n+1] = x_n in an otherwise zero sequence of length 4p, fft(u)[k] = sum_n x_n exp(-i pi (2n+1) k / (2p)),
+    so y_k = w(k) Re fft(u)[k].  numpy's FFT runs in long double for long-double input."""
+    X = np.asarray(X, np.float64)
+    n, p = X.shape
+    u = np.zeros((n, 4 * p), np.longdouble)
+    u[:, 1:2 * p:2] = X if sign is None else X * np.asarray(sign, np.float64)
+    return _dct_weights_ld(p)[None, :] * np.fft.fft(u, axis=1)[:, :p].real
+
+
+def idct_ld(Y, sign):
+    """DD*idct(Y) (kmeans_sparsified.m:296) in long double, rows = points: Y [K, p] -> [K, p].  x_n = sum_k w(k) y_k
+    cos(pi (2n+1) k / (2p)) = Re fft(v)[2n+1] with v[k] = w(k) y_k (k < p) in a zero sequence of length 4p."""
+    Y = np.asarray(Y).astype(np.longdouble)
+    K, p = Y.shape
+    v = np.zeros((K, 4 * p), np.longdouble)
+    v[:, :p] = Y * _dct_weights_ld(p)[None, :]
+    x = np.fft.fft(v, axis=1)[:, 1:2 * p:2].real
+    return x if sign is None else x * np.asarray(sign, np.float64)[None, :]
+
+
+def dct_value_bound(X, rows, premul, level, want, cols=None):
+    """Bound on |kernel - exact| for the sampled DCT values of k_sketch_gather (X [n, p] rows = points, rows [n, s],
+    want: the exact values, already divided by level).  The kernel forms acc = sum_n fma(v_n, c_n, acc) over p terms,
+    v_n = fl(x_n premul) sign_n, c_n its LDS table entry cospi(fl(fl(1/(2p)) j)):
+      - the p fma roundings: |acc - sum v_n c_n| <= (p - 1) u sum |v_n c_n| <= (p - 1) u sum |v_n|
+      - each table entry: the argument carries two roundings (relative u each, so <= (pi/2) 2u absolute in radians,
+        and |d cos| <= |d arg|) plus cospi's own error of <= 2 ulp: |c_n - cos| <= (pi + 2) u <= 6u, i.e. 6u sum |v_n|
+    so |acc - exact| <= (p + 5) u sum |v_n|; the weight w(k) (u relative, from sqrt) multiplies it, and the product
+    w acc and the division by level are two more roundings of the answer (2u |want|).  With u = 2^-53:
+      bound = (p + 6) u w(k) sum_n |fl(x_n premul)| / level + 2u |want|     (first order; the long-double reference
+    itself is ~1e-19 relative).  cols: rows / want are flat entries of those points (a ragged CSC) instead of [n, s]."""
+    X = np.asarray(X, np.float64)
+    n, p = X.shape
+    u = np.finfo(np.float64).eps / 2
+    V = X * premul if premul != 1.0 else X
+    w = np.where(np.asarray(rows) == 0, np.sqrt(1.0 / p), np.sqrt(2.0 / p))
+    sa = np.abs(V).sum(axis=1)
+    sa = sa[:, None] if cols is None else sa[np.asarray(cols)]
+    return (p + 6) * u * w * sa / level + 2 * u * np.abs(np.asarray(want, np.float64))
+
+
+def replay_sketch_products(X, kind, gamma_opt, seed, first=0):
+    """The random products kmeans_sparsified(X.T, K, Sparsify=True, SketchType='DCT' | 'none', rng=seed) draws, replayed
+    on the host: rng = default_rng(seed); for the DCT only d = sign(standard_normal(p)), d[d == 0] = 1; then
+    sample_seed = rng.integers(0, 2**63 - 1); the rows of sample_rows_reference(sample_seed, first, n, p, s); the
+    values dct(DD*(X*premul)) (long double, dct_rows_ld) or X*premul at those rows, divided by s/p; exact zeros
+    dropped as sparse() drops them.  X: p x n (points as columns).  Returns (Y scipy CSC p x n, d or None, s, gamma)
+    -- gamma = s/p, the driver's."""
+    from sparsifiedkmeans_amd import synth
+
+    X = np.asarray(X, np.float64)
+    p, n = X.shape
+    rng = np.random.default_rng(seed)
+    d = None
+    if kind == "dct":
+        d = np.sign(rng.standard_normal(p))
+        d[d == 0] = 1
+    elif kind != "none":
+        raise ValueError(kind)
+    sample_seed = int(rng.integers(0, 2**63 - 1))
+    s = synth.small_p_of(gamma_opt, p)
+    rows = sample_rows_reference(sample_seed, first, n, p, s)
+    level = np.float64(s) / np.float64(p)
+    if kind == "dct":
+        vals = (dct_rows_ld(X.T, d, rows, PREMUL) / np.longdouble(level)).astype(np.float64)
+    else:
+        vals = (X.T * PREMUL)[np.arange(n)[:, None], rows] / level          # the host formula's two roundings
+    Y = sp.csc_matrix((vals.ravel(), rows.ravel(), np.arange(0, (n + 1) * s, s)), shape=(p, n))
+    Y.eliminate_zeros()                                                      # randsample_fixedNumberEntries.m:62
+    return Y, d, s, s / p
