@@ -358,6 +358,26 @@ int spkm_sketch_sample_dev(spkm_ctx *ctx, int kind, uint64_t p, uint64_t n, cons
                            double *d_x_out);
 int spkm_sketch_sample_rec_dev(spkm_ctx *ctx, int kind, uint64_t p, uint64_t n, const double *d_x, const double *d_sign,
                                double premul, uint64_t s, uint64_t seed, uint64_t col0, int ir_bits, void *d_rec_out);
+/* The DCT sketch at any 1 <= p <= SPKM_DCT_MAX_P, with a cosine table of O(sqrt(p)) bytes: the values and rows of
+ * spkm_sketch_sample_dev(SPKM_SKETCH_DCT, ...) -- the rows bit for bit (same generator), the values to within
+ * 81 u w(k) sum_n |x_n premul| / (s/p) + 3u |value| (u = 2^-53), a bound that does not grow with p (sample.hip,
+ * k_dct_gather).  d_sign is required.  spkm_dct_sample_dev writes CSC, spkm_dct_sample_rec_dev records.
+ * SPKM_ERR_BAD_VALUE for s == 0, s > p, ir_bits not 16 / 32, or 16-bit ids with p > 65536;
+ * SPKM_ERR_UNSUPPORTED for p > SPKM_DCT_MAX_P. */
+#define SPKM_DCT_MAX_P 131072
+int spkm_dct_sample_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, const double *d_x, const double *d_sign, double premul,
+                        uint64_t s, uint64_t seed, uint64_t col0, void *d_ir_out, int ir_bits, double *d_out);
+int spkm_dct_sample_rec_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, const double *d_x, const double *d_sign,
+                            double premul, uint64_t s, uint64_t seed, uint64_t col0, int ir_bits, void *d_rec_out);
+/* Whole orthonormal DCTs of nvec vectors (rows of d_in / d_out, [nvec, p] row-major, d_out distinct from d_in), never a
+ * p x p matrix (M[k, n] = w(k) cos(pi (2n+1) k / (2p)), MATLAB's dct):
+ *   inverse = 0:  d_out = M (d_sign .* d_in)        the start mix (kmeans_sparsified.m:406)
+ *   inverse = 1:  d_out = d_sign .* (M' d_in)       the centre unmix, DD*idct(Y) (:296, :523)
+ * p^2 multiply-adds per vector; error per entry <= 81 u w(k) sum_n |x_n| + 3u |y_k| (forward) and
+ * 84 u sum_k w(k) |y_k| (inverse).  SPKM_ERR_BAD_VALUE for p == 0 or inverse not 0 / 1; SPKM_ERR_UNSUPPORTED for
+ * p > SPKM_DCT_MAX_P. */
+int spkm_dct_apply_dev(spkm_ctx *ctx, uint64_t p, uint64_t nvec, const double *d_in, const double *d_sign, int inverse,
+                       double *d_out);
 /* A shard over n records of exactly s entries each that the caller holds on the device (and keeps alive): what
  * kmeans_sparsified.m:316-334 produces for one GPU, in the library's own layout.  Everything a CSC shard can do it can do:
  * an entry point that needs CSC arrays re-materialises library-owned ones from the records first.

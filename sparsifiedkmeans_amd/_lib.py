@@ -128,6 +128,9 @@ def lib():
     L.spkm_mix_sample_rec_dev.argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _dbl, _dbl, _u64, _u64, _u64, C.c_int, _vp]
     L.spkm_sketch_sample_dev.argtypes = [_vp, C.c_int, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, _vp, C.c_int, _vp]
     L.spkm_sketch_sample_rec_dev.argtypes = [_vp, C.c_int, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, C.c_int, _vp]
+    L.spkm_dct_sample_dev.argtypes = [_vp, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, _vp, C.c_int, _vp]
+    L.spkm_dct_sample_rec_dev.argtypes = [_vp, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, C.c_int, _vp]
+    L.spkm_dct_apply_dev.argtypes = [_vp, _u64, _u64, _vp, _vp, C.c_int, _vp]
     L.spkm_shard_create_rec_dev.argtypes = [_vp, _u64, _u64, _u64, C.c_int, _vp, C.POINTER(_vp)]
     L.spkm_last_screen_rounds.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_screen_mode.argtypes = [_vp, C.POINTER(C.c_int64)]

@@ -839,6 +839,76 @@ extern "C" int spkm_sketch_sample_rec_dev(spkm_ctx* ctx, int kind, uint64_t p, u
                                 (double*)d_rec_out, R);
 }
 
+// The DCT sketch at any p <= SPKM_DCT_MAX_P: k_sample_rows (unchanged: the rows of spkm_sketch_sample_dev) and
+// k_dct_gather, whose LDS table is O(sqrt(p)).  stride > 0: records, as sketch_sample_launch.
+static int dct_sample_launch(spkm_ctx* ctx, uint64_t p, uint64_t n, const double* d_x, const double* d_sign,
+                             double premul, uint64_t s, uint64_t seed, uint64_t col0, void* d_ir_out, int ir_bits,
+                             double* d_out, long long stride)
+{
+    if (s == 0 || s > p || (ir_bits != 16 && ir_bits != 32) || (ir_bits == 16 && p > 65536)) return SPKM_ERR_BAD_VALUE;
+    if (p > SPKM_DCT_MAX_P) return SPKM_ERR_UNSUPPORTED;
+    const int lf = dct_fine_log2((int)p);
+    const size_t tab = (size_t)dct_table_entries((int)p) * 16;
+    if (tab > ctx->lds_max) return SPKM_ERR_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return SPKM_OK;
+    const unsigned sblocks = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, ctx->num_cus) * 16);
+    const uint64_t items = n * ((s + 63) / 64);     // one wave per (column, 64 sampled rows)
+    const unsigned gblocks = (unsigned)std::min<uint64_t>((items + 3) / 4, (uint64_t)std::max(1, ctx->num_cus) * 8);
+    const double level = (double)s / (double)p;   // SparsityLevel = small_p / p (randsample_fixedNumberEntries.m:30-31)
+    if (ir_bits == 16) {
+        hipLaunchKernelGGL((k_sample_rows<unsigned short>), dim3(sblocks), dim3(256), 0, ctx->stream,
+                           (unsigned long long)seed, (long long)col0, (long long)n, (int)p, (int)s, (unsigned short*)d_ir_out, stride);
+        hipLaunchKernelGGL((k_dct_gather<unsigned short>), dim3(gblocks), dim3(256), tab, ctx->stream, d_x, (int)p, lf,
+                           (long long)n, (int)s, (const unsigned short*)d_ir_out, d_sign, premul, level, d_out, stride);
+    } else {
+        hipLaunchKernelGGL((k_sample_rows<unsigned int>), dim3(sblocks), dim3(256), 0, ctx->stream,
+                           (unsigned long long)seed, (long long)col0, (long long)n, (int)p, (int)s, (unsigned int*)d_ir_out, stride);
+        hipLaunchKernelGGL((k_dct_gather<unsigned int>), dim3(gblocks), dim3(256), tab, ctx->stream, d_x, (int)p, lf,
+                           (long long)n, (int)s, (const unsigned int*)d_ir_out, d_sign, premul, level, d_out, stride);
+    }
+    HIP_TRY(hipGetLastError());
+    return SPKM_OK;
+}
+
+extern "C" int spkm_dct_sample_dev(spkm_ctx* ctx, uint64_t p, uint64_t n, const double* d_x, const double* d_sign,
+                                   double premul, uint64_t s, uint64_t seed, uint64_t col0, void* d_ir_out, int ir_bits,
+                                   double* d_out)
+{
+    if (!ctx || (n && (!d_x || !d_sign || !d_ir_out || !d_out))) return SPKM_ERR_NULL_ARG;
+    return dct_sample_launch(ctx, p, n, d_x, d_sign, premul, s, seed, col0, d_ir_out, ir_bits, d_out, 0);
+}
+
+extern "C" int spkm_dct_sample_rec_dev(spkm_ctx* ctx, uint64_t p, uint64_t n, const double* d_x, const double* d_sign,
+                                       double premul, uint64_t s, uint64_t seed, uint64_t col0, int ir_bits,
+                                       void* d_rec_out)
+{
+    if (!ctx || (n && (!d_x || !d_sign || !d_rec_out))) return SPKM_ERR_NULL_ARG;
+    if (s == 0 || (ir_bits != 16 && ir_bits != 32)) return SPKM_ERR_BAD_VALUE;
+    const long long R = (long long)spkm_record_bytes(s, ir_bits);
+    return dct_sample_launch(ctx, p, n, d_x, d_sign, premul, s, seed, col0, (char*)d_rec_out + s * 8, ir_bits,
+                             (double*)d_rec_out, R);
+}
+
+extern "C" int spkm_dct_apply_dev(spkm_ctx* ctx, uint64_t p, uint64_t nvec, const double* d_in, const double* d_sign,
+                                  int inverse, double* d_out)
+{
+    if (!ctx || (nvec && (!d_in || !d_sign || !d_out))) return SPKM_ERR_NULL_ARG;
+    if (p == 0 || (inverse != 0 && inverse != 1)) return SPKM_ERR_BAD_VALUE;
+    if (p > SPKM_DCT_MAX_P) return SPKM_ERR_UNSUPPORTED;
+    const int lf = dct_fine_log2((int)p);
+    const size_t tab = (size_t)dct_table_entries((int)p) * 16;
+    if (tab > ctx->lds_max) return SPKM_ERR_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (nvec == 0) return SPKM_OK;
+    const uint64_t items = nvec * ((p + 63) / 64);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((items + 3) / 4, (uint64_t)std::max(1, ctx->num_cus) * 8);
+    hipLaunchKernelGGL(k_dct_apply, dim3(blocks), dim3(256), tab, ctx->stream, d_in, (int)p, lf, (long long)nvec, d_sign,
+                       inverse, d_out);
+    HIP_TRY(hipGetLastError());
+    return SPKM_OK;
+}
+
 extern "C" int spkm_widen_f64_dev(spkm_ctx* ctx, int kind, uint64_t count, const void* d_src, double* d_dst)
 {
     if (!ctx || (count && (!d_src || !d_dst))) return SPKM_ERR_NULL_ARG;

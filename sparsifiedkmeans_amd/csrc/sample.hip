@@ -168,3 +168,203 @@ __global__ __launch_bounds__(1024) void k_sketch_gather(const double* __restrict
         }
     }
 }
+
+// ---- the DCT without a p-sized table: k_dct_gather (sampled rows, any p <= SPKM_DCT_MAX_P) and k_dct_apply (whole
+// transforms of a few vectors: the start mix and the centre unmix, kmeans_sparsified.m:296,406,523) ----
+//
+// Both evaluate, per lane, one cosine sum  S = sum_i v_i cos(pi m_i / (2p)),  m_i = m0 + i * step  (mod 4p, exact in
+// integers), with v_i wave-uniform (loaded coalesced, broadcast by v_readlane as in k_sketch_gather):
+//   DCT-II at row k (k_dct_gather, k_dct_apply forward):  v_n = fl(x_n premul) sign_n,  m0 = k,  step = 2k
+//   DCT-III at entry n (k_dct_apply inverse):             v_k = fl(w(k) y_k),           m0 = 0,  step = 2n + 1
+// The sum runs in blocks of Q = DCT_Q consecutive terms.  A lane holds r_q = e^{i pi (q step) / (2p)}, q < Q, in
+// registers; per block it fetches e^{i theta_b} (theta_b = pi m_{bQ} / (2p)) once, and the block adds
+//   P_b = Re(e^{i theta_b} sum_q v_q r_q) = cos(theta_b) A_b - sin(theta_b) B_b,  A_b = sum_q v_q Re r_q,  B_b = sum_q v_q Im r_q,
+// two FMA chains of Q terms (two FMAs per term, no LDS read per term).  The P_b are summed with Neumaier's compensated
+// summation, so the error does not grow with the number of blocks.
+// e^{i pi m / (2p)}, m in [0, 4p): the quadrant is split off exactly (m = j p + r, a factor i^j), and e^{i pi r / (2p)},
+// r in [0, p), is the product of two LDS entries, coarse[r >> lf] e^{i pi (r >> lf) L / (2p)} and fine[r & (L-1)]
+// e^{i pi (r & (L-1)) / (2p)}, L = 2^lf >= sqrt(p): (L + ceil(p / L)) * 16 bytes, at most 12 KB at p = 131072.
+//
+// A-priori error bound, first order in u = 2^-53, for |S - sum_i v_i cos(pi m_i / (2p))| (exact cosine), with
+// Sv = sum_i |v_i|:
+//   - a table entry: sincospi of fl(j / (2p)) (one rounding of an argument <= 1/2: <= (pi/2) u in radians) plus <= 2
+//     ulp of the function: <= 4u per component.  The product of two entries (fma(a, b, -fl(c d))): the entries'
+//     errors times |.| + |.| <= sqrt(2), twice, plus <= 3 roundings: eps_T <= 2 sqrt(2) 4u + 3u <= 15u per component
+//     (exact quarter-wave factor i^j).
+//   - the effective cosine of a term, cos(theta_b) Re r_q - sin(theta_b) Im r_q, from four such values:
+//     <= 2 sqrt(2) eps_T <= 43u, i.e. 43u Sv in all.
+//   - the chains A_b, B_b: <= 2Q roundings each (Q with FMA; 2Q if multiply and add round apart), weighted by
+//     |cos theta_b| |Re r_q| + |sin theta_b| |Im r_q| <= 1:  2Q u Sv.
+//   - P_b from A_b, B_b: <= 3 roundings of terms each <= sqrt(2) sum_block |v|: 3.5u Sv (taken as 4u).
+//   - Neumaier's sum of the P_b: <= 2u |S| + O(#blocks u^2) sum |P_b| <= 2u Sv (+ second order).
+//   =>  |S - exact| <= (2Q + 49) u Sv = 81 u Sv for Q = 16  (DCT_ACC_ROUNDINGS), independent of p.
+// The entry written is then fl(fl(w S) / level) (sampled), fl(w S) (forward) or sign_n S (inverse); w = sqrt(fl(c/p))
+// carries <= 1.5u:  bound = 81 u w Sv / level + 3u |want|  (sampled, forward with level = 1) and, for the inverse,
+// (81 + 3) u sum_k w(k) |y_k| (the input product w(k) y_k adds 2.5u per term).  k_sketch_gather's chain gives
+// (p + 6) u w Sv instead (tests/util.py: dct_value_bound).
+constexpr int DCT_Q = 16;
+
+__host__ __device__ inline int dct_fine_log2(int p)
+{
+    int lf = 0;
+    while ((1ll << (2 * lf)) < (long long)p) lf++;         // L = 2^lf >= sqrt(p)
+    return lf;
+}
+
+__host__ __device__ inline int dct_table_entries(int p)
+{
+    const int lf = dct_fine_log2(p);
+    return (1 << lf) + ((p - 1) >> lf) + 1;
+}
+
+// tab[0, L): fine, tab[L, L + ceil(p / L)): coarse; (cos, sin)(pi j / (2p)) from sincospi of one correctly rounded quotient
+__device__ inline void dct_build_table(double2* tab, int p, int lf)
+{
+    const int L = 1 << lf, total = L + ((p - 1) >> lf) + 1;
+    for (int j = threadIdx.x; j < total; j += blockDim.x) {
+        const int r = j < L ? j : (j - L) << lf;
+        double sv, cv;
+        sincospi((double)r / (2.0 * (double)p), &sv, &cv);
+        tab[j] = make_double2(cv, sv);
+    }
+    __syncthreads();
+}
+
+// (cos, sin)(pi m / (2p)), m in [0, 4p)
+__device__ inline void dct_trig(const double2* __restrict__ tab, int p, int lf, int m, double& c, double& s)
+{
+    const bool neg = m >= 2 * p;
+    if (neg) m -= 2 * p;
+    const bool rot = m >= p;
+    if (rot) m -= p;
+    const double2 f = tab[m & ((1 << lf) - 1)], g = tab[(1 << lf) + (m >> lf)];
+    const double re = fma(g.x, f.x, -(g.y * f.y));
+    const double im = fma(g.x, f.y, g.y * f.x);
+    double cc = rot ? -im : re, ss = rot ? re : im;   // e^{i pi/2} (re + i im) = -im + i re
+    c = neg ? -cc : cc;
+    s = neg ? -ss : ss;
+}
+
+// S = sum_i v_i cos(pi (m0 + i step) / (2p)) for the lane's (m0, step); v_i = in(i) is loaded by lane i mod 64.
+// INV = false: v_i = fl(xc[i] premul) sign[i];  INV = true: v_i = fl(w(i) xc[i]).
+template <bool INV>
+__device__ inline double dct_lane_sum(const double* __restrict__ xc, const double* __restrict__ dsign, double premul,
+                                      double w0, double w1, int p, int lf, const double2* __restrict__ tab, int m0,
+                                      int step, int lane)
+{
+    const int four_p = 4 * p;
+    double rc[DCT_Q], rs[DCT_Q];
+    int mq = 0;
+#pragma unroll
+    for (int q = 0; q < DCT_Q; q++) {
+        dct_trig(tab, p, lf, mq, rc[q], rs[q]);
+        mq += step;
+        if (mq >= four_p) mq -= four_p;
+    }
+    const int bstep = (int)(((long long)DCT_Q * step) % four_p);
+    int mb = m0;
+    double S = 0.0, comp = 0.0;
+    for (int n0 = 0; n0 < p; n0 += 64) {
+        double v = 0.0;
+        const int i = n0 + lane;
+        if (i < p) {
+            if (INV) {
+                v = (i == 0 ? w0 : w1) * xc[i];
+            } else {
+                v = xc[i];
+                if (premul != 1.0) v = v * premul;
+                v = v * dsign[i];
+            }
+        }
+        const long long vb = __double_as_longlong(v);
+        const int lo = (int)vb, hi = (int)(vb >> 32);
+        const int cnt = p - n0 < 64 ? p - n0 : 64;
+        // lanes past p hold zeros: a block that runs past p adds nothing
+        for (int b0 = 0; b0 < cnt; b0 += DCT_Q) {
+            double cb, sb;
+            dct_trig(tab, p, lf, mb, cb, sb);
+            double A = 0.0, B = 0.0;
+#pragma unroll
+            for (int q = 0; q < DCT_Q; q++) {
+                const unsigned xl = (unsigned)__builtin_amdgcn_readlane(lo, b0 + q);
+                const unsigned xh = (unsigned)__builtin_amdgcn_readlane(hi, b0 + q);
+                const double xn = __longlong_as_double((long long)(((unsigned long long)xh << 32) | xl));
+                A = fma(xn, rc[q], A);
+                B = fma(xn, rs[q], B);
+            }
+            const double P = fma(cb, A, -(sb * B));
+            const double T = S + P;                                   // Neumaier
+            comp += fabs(S) >= fabs(P) ? (S - T) + P : (P - T) + S;
+            S = T;
+            mb += bstep;
+            if (mb >= four_p) mb -= four_p;
+        }
+    }
+    return S + comp;
+}
+
+// The sampled DCT-II of k_sketch_gather (dct = 1) without its p-sized table: y[t] = (w(k_t) S(k_t)) / level at the rows
+// k_sample_rows drew.  One wave per (column, group of 64 sampled rows), one lane per row, so that a few wide columns
+// still fill the device.  stride_bytes > 0: records.
+template <typename IR>
+__global__ __launch_bounds__(256) void k_dct_gather(const double* __restrict__ x, int p, int lf, long long n, int s,
+                                                    const IR* __restrict__ ir, const double* __restrict__ dsign,
+                                                    double premul, double level, double* __restrict__ y,
+                                                    long long stride_bytes)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double2* tab = reinterpret_cast<double2*>(smem);
+    dct_build_table(tab, p, lf);
+    const int lane = threadIdx.x & 63;
+    const int waves = blockDim.x >> 6;
+    const double w0 = sqrt(1.0 / (double)p), w1 = sqrt(2.0 / (double)p);
+    const long long groups = (s + 63) / 64;
+    for (long long wi = (long long)blockIdx.x * waves + (threadIdx.x >> 6); wi < n * groups;
+         wi += (long long)gridDim.x * waves) {
+        const long long c = wi / groups;
+        const IR* irc = stride_bytes > 0 ? reinterpret_cast<const IR*>(reinterpret_cast<const char*>(ir) + (size_t)c * (size_t)stride_bytes)
+                                         : ir + (size_t)c * s;
+        double* yc = stride_bytes > 0 ? reinterpret_cast<double*>(reinterpret_cast<char*>(y) + (size_t)c * (size_t)stride_bytes)
+                                      : y + (size_t)c * s;
+        const double* xc = x + (size_t)c * p;
+        const int t = (int)(wi - c * groups) * 64 + lane;
+        const bool on = t < s;
+        const int k = on ? (int)irc[t] : 0;
+        const double acc = dct_lane_sum<false>(xc, dsign, premul, w0, w1, p, lf, tab, k, 2 * k, lane);
+        if (on) yc[t] = ((k == 0 ? w0 : w1) * acc) / level;
+    }
+}
+
+// Whole transforms of nvec vectors of length p (rows of in / out), never a p x p matrix:
+//   inverse = 0:  out[v][k] = w(k) sum_n cos(pi (2n+1) k / (2p)) (in[v][n] sign[n])          y = M (d .* x)
+//   inverse = 1:  out[v][n] = sign[n] sum_k cos(pi (2n+1) k / (2p)) (w(k) in[v][k])          x = d .* (M' y)
+// One wave per (vector, 64 outputs), one lane per output.
+__global__ __launch_bounds__(256) void k_dct_apply(const double* __restrict__ in, int p, int lf, long long nvec,
+                                                   const double* __restrict__ dsign, int inverse,
+                                                   double* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double2* tab = reinterpret_cast<double2*>(smem);
+    dct_build_table(tab, p, lf);
+    const int lane = threadIdx.x & 63;
+    const int waves = blockDim.x >> 6;
+    const double w0 = sqrt(1.0 / (double)p), w1 = sqrt(2.0 / (double)p);
+    const long long groups = (p + 63) / 64;
+    for (long long wi = (long long)blockIdx.x * waves + (threadIdx.x >> 6); wi < nvec * groups;
+         wi += (long long)gridDim.x * waves) {
+        const long long vec = wi / groups;
+        const int t = (int)(wi - vec * groups) * 64 + lane;
+        const bool on = t < p;
+        const int j = on ? t : 0;
+        const double* xc = in + (size_t)vec * p;
+        double r;
+        if (inverse) {
+            r = dct_lane_sum<true>(xc, dsign, 1.0, w0, w1, p, lf, tab, 0, 2 * j + 1, lane);
+            r = r * dsign[j];
+        } else {
+            r = dct_lane_sum<false>(xc, dsign, 1.0, w0, w1, p, lf, tab, j, 2 * j, lane);
+            r = (j == 0 ? w0 : w1) * r;
+        }
+        if (on) out[(size_t)vec * p + t] = r;
+    }
+}

@@ -477,6 +477,45 @@ def sketch_sample_records_device(ctx: Context, kind: str, x: torch.Tensor, sign:
                "spkm_sketch_sample_rec_dev")
 
 
+DCT_TABLE_MAX_P = 16384     # spkm_sketch_sample_dev's DCT: a (p + 1) * 8-byte cosine table in LDS
+DCT_MAX_P = 131072          # SPKM_DCT_MAX_P: spkm_dct_sample_dev / spkm_dct_apply_dev (a table of O(sqrt(p)) bytes)
+
+
+def dct_sample_device(ctx: Context, x: torch.Tensor, sign: torch.Tensor, premul: float, s: int, seed: int, col0: int,
+                      ir_out: torch.Tensor, x_out: torch.Tensor):
+    """sketch_sample_device(kind="dct") for any p <= DCT_MAX_P (spkm_dct_sample_dev): the same rows bit for bit, the
+    values dct(DD*(x*premul))[row] / (s/p) to within a bound that does not grow with p."""
+    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2 and sign is not None
+    n, p = x.shape
+    assert ir_out.numel() >= n * s and x_out.numel() >= n * s and x_out.dtype == torch.float64
+    bits = ir_out.element_size() * 8
+    _lib.check(_lib.lib().spkm_dct_sample_dev(ctx.handle, p, n, _p(x), _p(sign), float(premul), int(s),
+                                              int(seed) & (2**64 - 1), int(col0), _p(ir_out), bits, _p(x_out)),
+               "spkm_dct_sample_dev")
+
+
+def dct_sample_records_device(ctx: Context, x: torch.Tensor, sign: torch.Tensor, premul: float, s: int, seed: int,
+                              col0: int, rec_out: torch.Tensor, ir_bits: int = 16):
+    """dct_sample_device writing RECORDS (spkm_dct_sample_rec_dev; layout as mix_sample_records_device)."""
+    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2 and sign is not None
+    n, p = x.shape
+    assert rec_out.dtype == torch.uint8 and rec_out.is_contiguous() and rec_out.numel() >= n * record_bytes(s, ir_bits)
+    _lib.check(_lib.lib().spkm_dct_sample_rec_dev(ctx.handle, p, n, _p(x), _p(sign), float(premul), int(s),
+                                                  int(seed) & (2**64 - 1), int(col0), int(ir_bits), _p(rec_out)),
+               "spkm_dct_sample_rec_dev")
+
+
+def dct_apply_device(ctx: Context, x: torch.Tensor, sign: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+    """Whole orthonormal DCTs of the rows of ``x`` [nvec, p] without a p x p matrix (spkm_dct_apply_dev): M (d .* x) for
+    inverse=False (the start mix), d .* (M' x) for inverse=True (the centre unmix, DD*idct)."""
+    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2 and sign is not None
+    nvec, p = x.shape
+    y = torch.empty((nvec, p), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().spkm_dct_apply_dev(ctx.handle, p, nvec, _p(x), _p(sign), int(bool(inverse)), _p(y)),
+               "spkm_dct_apply_dev")
+    return y
+
+
 def dense_assign_device(ctx: Context, x: torch.Tensor, centers: torch.Tensor):
     """[assignments, distances] = findClusterAssignments(full(X), centers), dense branch / expanded quadratic
     (private/findClusterAssignments.m:157-171) for a dense device chunk ``x`` [n, p] and ``centers`` [K, p].
@@ -545,7 +584,8 @@ class StreamingSparsifier:
     reusable buffer and the mixed chunk never reaches HBM.
 
     ``kind``: "hadamard" (the FWHT of the zero-padded column, p2 = next power of two; the mixed column stays in LDS),
-    "dct" or "none" (p2 = p; the sketch is evaluated at the sampled rows only, spkm_sketch_sample_dev).  The rows are
+    "dct" or "none" (p2 = p; the sketch is evaluated at the sampled rows only: spkm_sketch_sample_dev, and for a DCT with
+    p > DCT_TABLE_MAX_P = 16384, up to DCT_MAX_P = 131072, spkm_dct_sample_dev with the same rows).  The rows are
     drawn by the same generator for every kind.  Without ``kind``, ``sketch=True`` means "hadamard", False "none".
 
     Chunks may arrive as float64 / float32 / uint8 / int16 / int32 (a 1e9-point dataset is not stored as doubles);
@@ -658,7 +698,14 @@ class StreamingSparsifier:
             fin = buf
         o = self.filled * self.s
         premul = 1.0 + 2.0 * float(np.finfo(np.float64).eps)
-        if self.kind != "hadamard":
+        if self.kind == "dct" and self.p > DCT_TABLE_MAX_P:
+            if self.records:
+                dct_sample_records_device(self.ctx, fin, self.sign, premul, self.s, self.seed, self.first + self.filled,
+                                          self.rec[self.filled * self.R:], self.ir_bits)
+            else:
+                dct_sample_device(self.ctx, fin, self.sign, premul, self.s, self.seed, self.first + self.filled,
+                                  self.ir[o:], self.x[o:])
+        elif self.kind != "hadamard":
             if self.records:
                 sketch_sample_records_device(self.ctx, self.kind, fin, self.sign, premul, self.s, self.seed,
                                              self.first + self.filled, self.rec[self.filled * self.R:], self.ir_bits)

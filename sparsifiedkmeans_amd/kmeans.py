@@ -6,10 +6,10 @@ Scope: the sparsified path -- 'Sparsify',true with the Hadamard 
 sketch -- including the two-pass outputs (nargout 6..9).  What the reference does with MATLAB toolboxes
 outside that path (matfile containers, function-handle sketches) raises NotImplementedError naming the option,
 rather than silently doing something else.  Data is sparsified on the device for the Hadamard sketch (16 <= p2 <= 16384),
-the DCT sketch ('auto' picks it when p is not a power of two; p <= 16384) and no sketch: chunks cross PCIe in their own
+the DCT sketch ('auto' picks it when p is not a power of two; p <= 131072) and no sketch: chunks cross PCIe in their own
 dtype, rows are drawn by one counter-based generator keyed by (seed, global index), and the sketch is applied in HIP
-(the DCT evaluated at the sampled rows only).  Unmixing the K centres of the DCT is a p x p GEMM; a Hadamard sketch
-outside that p2 range samples on the host.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
+(the DCT evaluated at the sampled rows only).  Mixing the start and unmixing the K centres of the DCT is a p x p GEMM
+up to p = 16384 and a matrix-free HIP transform above; a Hadamard sketch outside that p2 range samples on the host.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
 dense kernels of the two-pass outputs (one GPU, data resident in HBM).  'MLcorrection',false (plain means of the sparse columns,
 kmeans_sparsified.m:449-451) runs on the same accumulation with a different final division.
 
@@ -39,8 +39,8 @@ import torch
 from . import _lib
 from . import distributed as D_
 from . import synth
-from .engine import (LloydEngine, Shard, StreamingSparsifier, dense_accumulate_device, dense_assign_device, mix_device,
-                     torch_context)
+from .engine import (DCT_MAX_P, DCT_TABLE_MAX_P, LloydEngine, Shard, StreamingSparsifier, dct_apply_device,
+                     dense_accumulate_device, dense_assign_device, mix_device, torch_context)
 
 EPS = np.finfo(np.float64).eps
 
@@ -108,16 +108,22 @@ class _Sketch:
         self.ctx, self.kind, self.p = ctx, kind, p
         self.p2 = _nextpow2(p) if kind == "hadamard" else p
         self.sign = None if sign is None else torch.tensor(sign, dtype=torch.float64, device=f"cuda:{ctx.device}")
-        if kind == "dct":
+        self.M = None
+        if kind == "dct" and p <= DCT_TABLE_MAX_P:
             # orthonormal DCT-II as MATLAB's dct() applied with a library GEMM (kmeans_sparsified.m:256-258): one pass over
             # the data, and the reference's own dct is a toolbox FFT whose rounding is not specified either (tolerance
             # parity).  The matrix is built as the sampling kernel evaluates it (dct_matrix).
             M = dct_matrix(p, f"cuda:{ctx.device}")
             self.M = M                                                            # [p, p]: y = M x
+        # above that the p x p matrix (8 p^2 bytes, 20 GB at p = 50000) is never built: mix / unmix run the matrix-free
+        # transform (spkm_dct_apply_dev), p^2 multiply-adds per vector for the K start / centre vectors only
 
     def mix(self, x: torch.Tensor, premul: float = 1.0) -> torch.Tensor:
         if self.kind == "none":
             return x * premul if premul != 1.0 else x
+        if self.kind == "dct" and self.M is None:
+            xs = x if premul == 1.0 else x * premul
+            return dct_apply_device(self.ctx, xs.contiguous(), self.sign)        # M (DD*X), no matrix
         if self.kind == "dct":
             xs = x * self.sign if premul == 1.0 else (x * premul) * self.sign     # DD*X (:283-291), rows = points
             return (xs @ self.M.T).contiguous()
@@ -127,6 +133,8 @@ class _Sketch:
     def unmix(self, y: torch.Tensor) -> torch.Tensor:
         if self.kind == "none":
             return y
+        if self.kind == "dct" and self.M is None:
+            return dct_apply_device(self.ctx, y.contiguous(), self.sign, inverse=True)   # DD*idct(Y), no matrix
         if self.kind == "dct":
             return ((y @ self.M) * self.sign).contiguous()                        # DD*idct(Y) (:296)
         # downsample(DD*Ht(y)), Ht = H (:255,296)
@@ -240,8 +248,8 @@ def kmeans_sparsified(X, K, **options):
     if sk == "dct":
         d = np.sign(rng.random(p)) if o["FORCE_BUG"] else np.sign(rng.standard_normal(p))   # :283-287 (p2 = p here)
         d[d == 0] = 1.0
-        if p > 16384:
-            raise NotImplementedError("the DCT sketch is applied as a p x p matrix; p is too large for that")
+        if p > DCT_MAX_P:
+            raise NotImplementedError(f"the DCT sketch supports p <= {DCT_MAX_P} (its cost is ~s*p per point); p = {p}")
         sketch = _Sketch(ctx, "dct", p, d)
     elif sk in ("nothing", "none"):
         sketch = _Sketch(ctx, "none", p, None)
