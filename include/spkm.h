@@ -326,7 +326,19 @@ int spkm_mix_dev(spkm_ctx *ctx, uint64_t p, uint64_t p2, uint64_t n, const doubl
  * uniform without replacement (Philox4x32-10 keyed by (seed, col0 + c): independent of chunking and of
  * the number of GPUs), ascending, into d_ir_out[c*s .. c*s+s) (uint16 / uint32 by ir_bits) and the values
  * (mix(x)[row] ) / (s/p2) into d_x_out[c*s ..).  The dense mixed column never reaches HBM.
- * premul / postdiv / d_sign as in spkm_mix_dev.  Needs 16 <= p2 <= 16384. */
+ * premul / postdiv / d_sign as in spkm_mix_dev.  Needs 2 <= p2 <= SPKM_MIX_MAX_P2 (2^24).
+ * 16 <= p2 <= 16384: one kernel, the mixed column stays in LDS.  Other widths: the mixed columns go through a device
+ * scratch buffer that the context owns and grows on demand, at most SPKM_MIX_SCRATCH_BYTES (256 MiB): the library cuts the
+ * call into internal passes of max(1, SPKM_MIX_SCRATCH_BYTES / (8 p2)) columns (p2 = 2^24: 2 columns, 128 MiB each).  Above
+ * 16384 the transform runs as slices of 16384 rows in LDS, then log2(p2 / 16384) further stages, up to 4 per pass over the
+ * scratch; the values are the same bits at every width (the stages are the reference's add/sub butterflies in its order,
+ * hadamard.c:66-77, however they are grouped).  MI355X, p = 65536 float32 through the driver: 22.5 GB/s of input against
+ * 57 GB/s PCIe; the row draw (k_sample_rows, one lane per column) takes 8.9 ms of each 1000-column chunk, the transform
+ * and gather 0.26 ms.
+ * SPKM_ERR_BAD_VALUE for s == 0, s > p2, ir_bits not 16 / 32, 16-bit ids with p2 > 65536, or p > p2;
+ * SPKM_ERR_LEN_LE_1 for p2 <= 1, SPKM_ERR_NOT_POW2, SPKM_ERR_UNSUPPORTED for p2 > SPKM_MIX_MAX_P2. */
+#define SPKM_MIX_MAX_P2 (1ull << 24)
+#define SPKM_MIX_SCRATCH_BYTES (256ull << 20)
 int spkm_mix_sample_dev(spkm_ctx *ctx, uint64_t p, uint64_t p2, uint64_t n, const double *d_x,
                         const double *d_sign, double premul, double postdiv, uint64_t s, uint64_t seed,
                         uint64_t col0, void *d_ir_out, int ir_bits, double *d_x_out);

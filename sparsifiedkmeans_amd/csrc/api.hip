@@ -140,7 +140,7 @@ extern "C" void spkm_ctx_destroy(spkm_ctx* ctx)
                      &ctx->nk, &ctx->stats, &ctx->perm, &ctx->offs, &ctx->cursor, &ctx->items, &ctx->nitems,
                      &ctx->bmap, &ctx->blk_dff, &ctx->ct, &ctx->tmp_assign, &ctx->tmp_mind, &ctx->mscr, &ctx->dbg, &ctx->t32, &ctx->scr_m1, &ctx->scr_m2,
                      &ctx->scr_k, &ctx->cmax, &ctx->list, &ctx->nlist, &ctx->dn_x, &ctx->dn_c, &ctx->dn_nk, &ctx->bmapq, &ctx->todo, &ctx->bstat, &ctx->nk_ev, &ctx->fin_ticket, &ctx->wgstat, &ctx->offs2, &ctx->cursor2, &ctx->hist2,
-                     &ctx->items2, &ctx->perm_o};
+                     &ctx->items2, &ctx->perm_o, &ctx->mix_scr};
     for (devbuf* b : all) release(*b);
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
     for (auto& pr : ctx->tlog) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -690,9 +690,9 @@ static int fwht_launch(spkm_ctx* ctx, uint64_t p_in, uint64_t m, uint64_t n, con
         const int threads = std::max(T, 256);
         const int cpb = threads / T;
         const size_t lds = (size_t)cpb * (m + m / 8) * 8;
-        HIP_TRY(hipFuncSetAttribute((const void*)k_fwht_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_fwht_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const uint64_t want = (n + cpb - 1) / cpb;
-        hipLaunchKernelGGL(k_fwht_lds, dim3((unsigned)std::min<uint64_t>(want, (uint64_t)blocks_cap)), dim3(threads),
+        hipLaunchKernelGGL(k_fwht_lds<false>, dim3((unsigned)std::min<uint64_t>(want, (uint64_t)blocks_cap)), dim3(threads),
                            lds, ctx->stream, d_x, d_y, (int)m, logm, (long long)n, (int)p_in, d_sign, premul,
                            postdiv, cpb, gather_ir, gather_bits, gather_s, gather_level, gather_stride);
     } else {
@@ -721,6 +721,85 @@ extern "C" int spkm_mix_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint64_t n, 
     return fwht_launch(ctx, p, p2, n, d_x, d_sign, premul, postdiv, d_y);
 }
 
+// The Hadamard sparsifier where the whole column does not fit the LDS (16384 < p2 <= SPKM_MIX_MAX_P2) or is shorter than
+// k_fwht_lds's 16 rows (p2 in {2, 4, 8}).  Runs after k_sample_rows, over passes of at most SPKM_MIX_SCRATCH_BYTES of
+// mixed columns in ctx->mix_scr:
+//   p2 > 16384:  k_fwht_lds<true> (slices of B rows: the fused input ops and stages bit = 1 .. B/2) -> k_fwht_high (stages
+//                bit = B .. p2/2, up to 4 per pass over the scratch; the last one divides by postdiv)
+//   p2 < 16:     k_fwht_small (all stages and postdiv)
+// then k_sketch_gather (none, premul 1) writes (Y[row] * 1) / level at the rows already drawn: bit for bit the fused path's
+// (Y / postdiv) / level, since the stages are the reference's butterflies in its order however they are grouped.
+// stride > 0: records (ids at ir + c * stride, values at out + c * stride); stride == 0: CSC.
+static int mix_blocked_fits(const spkm_ctx* ctx, uint64_t p2, int* logB)
+{
+    if (p2 < 16) return 1;
+    int lb = 14;                                           // B = 16384: 147 KB of LDS, one workgroup per CU
+    while (lb >= 4 && ((1ull << lb) + (1ull << lb) / 8) * 8 > ctx->lds_max) lb--;
+    if (logB) *logB = lb;
+    return lb >= 4;
+}
+
+template <typename IR>
+static int mix_sample_blocked(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint64_t n, const double* d_x,
+                              const double* d_sign, double premul, double postdiv, uint64_t s, double level,
+                              const char* ir, char* out, long long stride)
+{
+    int logm = 0;
+    while ((1ull << logm) < p2) logm++;
+    int logB = 0;
+    if (!mix_blocked_fits(ctx, p2, &logB)) return SPKM_ERR_UNSUPPORTED;
+    const uint64_t per_pass = std::min<uint64_t>(n, std::max<uint64_t>(1, SPKM_MIX_SCRATCH_BYTES / (p2 * 8)));
+    int rc = ensure(ctx, ctx->mix_scr, per_pass * p2 * 8);
+    if (rc) return rc;
+    double* scr = (double*)ctx->mix_scr.p;
+    const int ncu = std::max(1, ctx->num_cus);
+    const size_t ir_col = stride > 0 ? (size_t)stride : (size_t)s * sizeof(IR);
+    const size_t out_col = stride > 0 ? (size_t)stride : (size_t)s * 8;
+    if (p2 > 16384) {
+        const int B = 1 << logB, T = B / 16, threads = std::max(T, 256), cpb = threads / T;
+        const size_t lds = (size_t)cpb * (B + B / 8) * 8;
+        HIP_TRY(hipFuncSetAttribute((const void*)k_fwht_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    for (uint64_t c0 = 0; c0 < n; c0 += per_pass) {
+        const uint64_t cols = std::min<uint64_t>(per_pass, n - c0);
+        const double* xc = d_x + c0 * p;
+        if (p2 < 16) {
+            hipLaunchKernelGGL(k_fwht_small, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, ctx->stream, xc, scr,
+                               (int)p2, (long long)cols, (int)p, d_sign, premul, postdiv);
+        } else {
+            const int B = 1 << logB, T = B / 16, threads = std::max(T, 256), cpb = threads / T;
+            const size_t lds = (size_t)cpb * (B + B / 8) * 8;
+            const int sl = logm - logB;
+            const uint64_t nv = cols << sl;                   // slices
+            hipLaunchKernelGGL(k_fwht_lds<true>, dim3((unsigned)std::min<uint64_t>((nv + cpb - 1) / cpb, (uint64_t)ncu * 16)),
+                               dim3(threads), lds, ctx->stream, xc, scr, B, logB, (long long)nv, (int)p, d_sign, premul,
+                               0.0, cpb, nullptr, 0, 0, 1.0, 0ll, sl);
+            for (int b = logB; b < logm; b += 4) {
+                const int nb = std::min(4, logm - b);
+                const double pd = b + nb == logm ? postdiv : 0.0;
+                const unsigned g = (unsigned)std::min<uint64_t>(((cols << (logm - nb)) + 255) / 256, (uint64_t)ncu * 32);
+                switch (nb) {
+                case 4: hipLaunchKernelGGL(k_fwht_high<4>, dim3(g), dim3(256), 0, ctx->stream, scr, logm, (long long)cols, b, pd); break;
+                case 3: hipLaunchKernelGGL(k_fwht_high<3>, dim3(g), dim3(256), 0, ctx->stream, scr, logm, (long long)cols, b, pd); break;
+                case 2: hipLaunchKernelGGL(k_fwht_high<2>, dim3(g), dim3(256), 0, ctx->stream, scr, logm, (long long)cols, b, pd); break;
+                default: hipLaunchKernelGGL(k_fwht_high<1>, dim3(g), dim3(256), 0, ctx->stream, scr, logm, (long long)cols, b, pd); break;
+                }
+            }
+        }
+        const unsigned gb = (unsigned)std::min<uint64_t>((cols + 3) / 4, (uint64_t)ncu * 8);
+        hipLaunchKernelGGL((k_sketch_gather<IR>), dim3(gb), dim3(256), 0, ctx->stream, (const double*)scr, (int)p2,
+                           (long long)cols, (int)s, (const IR*)(ir + c0 * ir_col), (const double*)nullptr, 1.0, level,
+                           0, (double*)(out + c0 * out_col), stride);
+        HIP_TRY(hipGetLastError());
+    }
+    return SPKM_OK;
+}
+
+static bool mix_in_lds(const spkm_ctx* ctx, uint64_t p2)
+{
+    return p2 >= 16 && p2 <= 16384 && (p2 + p2 / 8) * 8 <= ctx->lds_max;
+}
+
 extern "C" int spkm_mix_sample_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint64_t n, const double* d_x,
                                    const double* d_sign, double premul, double postdiv, uint64_t s, uint64_t seed,
                                    uint64_t col0, void* d_ir_out, int ir_bits, double* d_x_out)
@@ -729,6 +808,11 @@ extern "C" int spkm_mix_sample_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint6
     if (s == 0 || s > p2 || (ir_bits != 16 && ir_bits != 32) || (ir_bits == 16 && p2 > 65536)) return SPKM_ERR_BAD_VALUE;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return SPKM_OK;
+    int rc = check_pow2(p2);
+    if (rc) return rc;
+    if (p > p2) return SPKM_ERR_BAD_VALUE;
+    const bool lds = mix_in_lds(ctx, p2);
+    if (!lds && (p2 > SPKM_MIX_MAX_P2 || !mix_blocked_fits(ctx, p2, nullptr))) return SPKM_ERR_UNSUPPORTED;
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, ctx->num_cus) * 16);
     if (ir_bits == 16)
         hipLaunchKernelGGL((k_sample_rows<unsigned short>), dim3(blocks), dim3(256), 0, ctx->stream,
@@ -741,6 +825,13 @@ extern "C" int spkm_mix_sample_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint6
     HIP_TRY(hipGetLastError());
     // SparsityLevel = small_p / p with p the row count of the mixed matrix (randsample_fixedNumberEntries.m:30-31)
     const double level = (double)s / (double)p2;
+    if (!lds) {
+        if (ir_bits == 16)
+            return mix_sample_blocked<unsigned short>(ctx, p, p2, n, d_x, d_sign, premul, postdiv, s, level,
+                                                      (const char*)d_ir_out, (char*)d_x_out, 0);
+        return mix_sample_blocked<unsigned int>(ctx, p, p2, n, d_x, d_sign, premul, postdiv, s, level,
+                                                (const char*)d_ir_out, (char*)d_x_out, 0);
+    }
     return fwht_launch(ctx, p, p2, n, d_x, d_sign, premul, postdiv, d_x_out, d_ir_out, ir_bits, (int)s, level);
 }
 
@@ -760,6 +851,11 @@ extern "C" int spkm_mix_sample_rec_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, u
     if (s == 0 || s > p2 || (ir_bits != 16 && ir_bits != 32) || (ir_bits == 16 && p2 > 65536)) return SPKM_ERR_BAD_VALUE;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return SPKM_OK;
+    int rc = check_pow2(p2);
+    if (rc) return rc;
+    const bool lds = mix_in_lds(ctx, p2);
+    if (!lds && (p2 > SPKM_MIX_MAX_P2 || !mix_blocked_fits(ctx, p2, nullptr))) return SPKM_ERR_UNSUPPORTED;
+    if (p > p2) return SPKM_ERR_BAD_VALUE;
     const long long R = (long long)spkm_record_bytes(s, ir_bits);
     char* ir0 = (char*)d_rec_out + s * 8;
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, ctx->num_cus) * 16);
@@ -772,9 +868,13 @@ extern "C" int spkm_mix_sample_rec_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, u
     HIP_TRY(hipGetLastError());
     const double level = (double)s / (double)p2;
     // (the gather reads column c's ids at ir0 + c R and writes its values at d_rec_out + c R)
-    int rc = check_pow2(p2);
-    if (rc) return rc;
-    if (!(p2 >= 16 && p2 <= 16384 && (p2 + p2 / 8) * 8 <= ctx->lds_max)) return SPKM_ERR_UNSUPPORTED;
+    if (!lds) {
+        if (ir_bits == 16)
+            return mix_sample_blocked<unsigned short>(ctx, p, p2, n, d_x, d_sign, premul, postdiv, s, level, ir0,
+                                                      (char*)d_rec_out, R);
+        return mix_sample_blocked<unsigned int>(ctx, p, p2, n, d_x, d_sign, premul, postdiv, s, level, ir0,
+                                                (char*)d_rec_out, R);
+    }
     // fwht_launch's gather takes ONE base for ids and ONE for values: the values' base is d_rec_out, the ids' ir0
     return fwht_launch(ctx, p, p2, n, d_x, d_sign, premul, postdiv, (double*)d_rec_out, ir0, ir_bits, (int)s, level, R);
 }

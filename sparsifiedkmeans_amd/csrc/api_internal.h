@@ -62,6 +62,7 @@ struct spkm_ctx {
     // grow-only device scratch
     devbuf tiles, part_acc, part_k, blk_obj, blk_max, blk_imax, nk, stats, perm, offs, cursor, items, nitems,
         bmap, blk_dff, ct, tmp_assign, tmp_mind, mscr, dbg, t32, scr_m1, scr_m2, scr_k, cmax, list, nlist, dn_x, dn_c, dn_nk, bmapq, todo, bstat, nk_ev, fin_ticket, wgstat, offs2, cursor2, hist2, items2, perm_o;
+    devbuf mix_scr; // mixed columns of the wide / short Hadamard sparsifier (at most SPKM_MIX_SCRATCH_BYTES)
     // results of an iteration handed to the host without a copy or a stream synchronisation (spkm_lloyd_iter_host): pinned host
     // memory the device maps -- [sequence number | dff^2 | obj^2 | cluster sizes], written by k_finalize_centers' last workgroup
     double* h_res = nullptr;

@@ -54,12 +54,18 @@ __device__ __forceinline__ void fwht_round(double* __restrict__ col, int tau, in
     for (int q = 0; q < 16; q++) col[padidx(idx(q))] = a[q];
 }
 
+// SLICED (the low stages of a column longer than the LDS, p2 = m << slice_log2): "column" v of this kernel is slice
+// j = v mod 2^slice_log2 of input column c = v >> slice_log2, i.e. rows j*m .. j*m + m - 1 of the zero-padded p2-vector
+// (x column stride p_in; rows >= p_in read as 0; sign d[j*m + i]).  Its stages bit = 1 .. m/2 land at y + v*m = the
+// slice's place in the p2 x n result.  Callers pass postdiv = 0 and no gather: k_fwht_high applies the rest.
+template <bool SLICED>
 __global__ __launch_bounds__(1024) void k_fwht_lds(const double* __restrict__ x, double* __restrict__ y, int m,
                                                    int logm, long long n, int p_in,
                                                    const double* __restrict__ dsign, double premul,
                                                    double postdiv, int cols_per_block,
                                                    const void* __restrict__ gather_ir, int gather_bits, int gather_s,
-                                                   double gather_level, long long gather_stride = 0)
+                                                   double gather_level, long long gather_stride = 0,
+                                                   int slice_log2 = 0)
 {
     // gather epilogue (sample.hip): when gather_ir != null the transformed column stays in LDS and only
     // its gather_s sampled rows are written, y[c*gather_s + t] = (Y[row_t] / postdiv) / gather_level.
@@ -102,21 +108,26 @@ __global__ __launch_bounds__(1024) void k_fwht_lds(const double* __restrict__ x,
             const bool have = csub < ncols;
             // unconditional loads on clamped indices (a predicated load would be waited for before the next
             // one is issued); out-of-range rows / columns are zeroed afterwards
-            const double* xc = x + (size_t)(cbase + (have ? csub : 0)) * p_in;
+            const long long vc = cbase + (have ? csub : 0);
+            // SLICED: off = the slice's first row; lim = rows of it that exist in x (may be <= 0: an all-padding slice,
+            // whose clamped index lim - 1 still is the column's last element)
+            const int off = SLICED ? (int)(vc & ((1 << slice_log2) - 1)) << logm : 0;
+            const int lim = p_in - off;
+            const double* xc = SLICED ? x + (size_t)(vc >> slice_log2) * p_in + off : x + (size_t)vc * p_in;
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 const int r = tau + T * i;
-                v[i] = xc[r < p_in ? r : p_in - 1];
+                v[i] = xc[r < lim ? r : lim - 1];
             }
             if (dsign) {
 #pragma unroll
-                for (int i = 0; i < 16; i++) sg[i] = dsign[tau + T * i];
+                for (int i = 0; i < 16; i++) sg[i] = dsign[off + tau + T * i];
             }
             if (have) {
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
                     const int r = tau + T * i;
-                    double w = (r < p_in) ? v[i] : 0.0;
+                    double w = (r < lim) ? v[i] : 0.0;
                     if (premul != 1.0) w = w * premul;
                     if (dsign) w = sg[i] * w;
                     col[padidx(r)] = w;
@@ -191,6 +202,44 @@ __global__ void k_fwht_small(const double* __restrict__ x, double* __restrict__ 
         for (int j = 0; j < m; j++)
             if ((j & bit) == 0) { const double u = a[j], w = a[j | bit]; a[j] = u + w; a[j | bit] = u - w; }
     for (int r = 0; r < m; r++) y[(size_t)c * m + r] = (postdiv > 0.0) ? a[r] / postdiv : a[r];
+}
+
+// The high stages of columns longer than the LDS: stages bit = 2^b .. 2^(b+NB-1) (b >= the slice length's log2) of each
+// m = 2^logm column of y, in place.  A thread owns 2^NB elements e(q) = (H << (b+NB)) | (q << b) | L (tau = (H << b) | L:
+// consecutive lanes read consecutive L, coalesced) and applies the NB stages in ascending bit order in registers -- the
+// same disjoint add/sub butterflies as the reference, so any grouping of stages into passes gives the same bits.  One
+// read and one write of y per pass; postdiv > 0 (the last pass) divides every output once.
+template <int NB>
+__global__ __launch_bounds__(256) void k_fwht_high(double* __restrict__ y, int logm, long long n, int b, double postdiv)
+{
+    const int lt = logm - NB;                                   // log2(threads per column)
+    const long long total = n << lt;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        const int tau = (int)(t & ((1ll << lt) - 1));
+        double* col = y + ((t >> lt) << logm);
+        const int base = ((tau >> b) << (b + NB)) | (tau & ((1 << b) - 1));
+        double a[1 << NB];
+#pragma unroll
+        for (int q = 0; q < (1 << NB); q++) a[q] = col[base | (q << b)];
+#pragma unroll
+        for (int st = 0; st < NB; st++) {
+#pragma unroll
+            for (int q = 0; q < (1 << NB); q++) {
+                if ((q & (1 << st)) == 0) {
+                    const double u = a[q], w = a[q | (1 << st)];
+                    a[q] = u + w;
+                    a[q | (1 << st)] = u - w;
+                }
+            }
+        }
+        if (postdiv > 0.0) {
+#pragma unroll
+            for (int q = 0; q < (1 << NB); q++) a[q] = a[q] / postdiv;
+        }
+#pragma unroll
+        for (int q = 0; q < (1 << NB); q++) col[base | (q << b)] = a[q];
+    }
 }
 
 // m > 16384: stage-by-stage in global memory (one launch per stage; rare).

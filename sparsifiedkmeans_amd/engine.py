@@ -479,6 +479,7 @@ def sketch_sample_records_device(ctx: Context, kind: str, x: torch.Tensor, sign:
 
 DCT_TABLE_MAX_P = 16384     # spkm_sketch_sample_dev's DCT: a (p + 1) * 8-byte cosine table in LDS
 DCT_MAX_P = 131072          # SPKM_DCT_MAX_P: spkm_dct_sample_dev / spkm_dct_apply_dev (a table of O(sqrt(p)) bytes)
+MIX_MAX_P2 = 1 << 24        # SPKM_MIX_MAX_P2: spkm_mix_sample_dev / _rec_dev (Hadamard sketch, 2 <= p2 <= 2^24)
 
 
 def dct_sample_device(ctx: Context, x: torch.Tensor, sign: torch.Tensor, premul: float, s: int, seed: int, col0: int,
@@ -583,7 +584,9 @@ class StreamingSparsifier:
     sparse form (10 B per kept entry) stays on the device; the dense intermediate of a chunk lives in one
     reusable buffer and the mixed chunk never reaches HBM.
 
-    ``kind``: "hadamard" (the FWHT of the zero-padded column, p2 = next power of two; the mixed column stays in LDS),
+    ``kind``: "hadamard" (the FWHT of the zero-padded column, p2 = next power of two, 2 <= p2 <= MIX_MAX_P2 = 2^24; for
+    16 <= p2 <= 16384 the mixed column stays in LDS, at other widths it goes through a library scratch buffer of at most
+    256 MiB),
     "dct" or "none" (p2 = p; the sketch is evaluated at the sampled rows only: spkm_sketch_sample_dev, and for a DCT with
     p > DCT_TABLE_MAX_P = 16384, up to DCT_MAX_P = 131072, spkm_dct_sample_dev with the same rows).  The rows are
     drawn by the same generator for every kind.  Without ``kind``, ``sketch=True`` means "hadamard", False "none".

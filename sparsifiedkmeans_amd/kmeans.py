@@ -5,11 +5,11 @@ the MI355X through libspkm.so.
 Scope: the sparsified path -- 'Sparsify',true with the Hadamard sketch or no
 sketch -- including the two-pass outputs (nargout 6..9).  What the reference does with MATLAB toolboxes
 outside that path (matfile containers, function-handle sketches) raises NotImplementedError naming the option,
-rather than silently doing something else.  Data is sparsified on the device for the Hadamard sketch (16 <= p2 <= 16384),
+rather than silently doing something else.  Data is sparsified on the device for the Hadamard sketch (2 <= p2 <= 2^24),
 the DCT sketch ('auto' picks it when p is not a power of two; p <= 131072) and no sketch: chunks cross PCIe in their own
 dtype, rows are drawn by one counter-based generator keyed by (seed, global index), and the sketch is applied in HIP
 (the DCT evaluated at the sampled rows only).  Mixing the start and unmixing the K centres of the DCT is a p x p GEMM
-up to p = 16384 and a matrix-free HIP transform above; a Hadamard sketch outside that p2 range samples on the host.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
+up to p = 16384 and a matrix-free HIP transform above; a Hadamard sketch with p2 > 2^24 samples on the host.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
 dense kernels of the two-pass outputs (one GPU, data resident in HBM).  'MLcorrection',false (plain means of the sparse columns,
 kmeans_sparsified.m:449-451) runs on the same accumulation with a different final division.
 
@@ -39,7 +39,7 @@ import torch
 from . import _lib
 from . import distributed as D_
 from . import synth
-from .engine import (DCT_MAX_P, DCT_TABLE_MAX_P, LloydEngine, Shard, StreamingSparsifier, dct_apply_device,
+from .engine import (DCT_MAX_P, DCT_TABLE_MAX_P, MIX_MAX_P2, LloydEngine, Shard, StreamingSparsifier, dct_apply_device,
                      dense_accumulate_device, dense_assign_device, mix_device, torch_context)
 
 EPS = np.finfo(np.float64).eps
@@ -267,7 +267,7 @@ def kmeans_sparsified(X, K, **options):
     gamma = small_p / p                                                          # :329 (divides by p, not p2)
     sample_seed = int(rng.integers(0, 2**63 - 1))
     Y = None
-    if (sk == "hadamard" and 16 <= p2 <= 16384) or sketch.kind in ("dct", "none"):
+    if (sk == "hadamard" and 2 <= p2 <= MIX_MAX_P2) or sketch.kind in ("dct", "none"):
         # device sparsifier: chunk -> X*(1+2eps) -> mix -> sample -> resident CSC (kmeans_sparsified.m:292-334;
         # for 'DataFile': sampleAndMixFromLargeFile.m:100-129).  The dense mixed data never reaches HBM: the Hadamard
         # transform stays in LDS, the DCT is evaluated at the sampled rows only, no sketch gathers them.
@@ -309,7 +309,8 @@ def kmeans_sparsified(X, K, **options):
         torch.cuda.synchronize()
         OUTPUT["TimeToSketch"] = OUTPUT["TimeToSample"] = time.time() - t1       # fused: one number for both
     else:
-        # Hadamard with p2 < 16 or p2 > 16384: mix on the device, sample on the host (randsample_fixedNumberEntries,
+        # Hadamard with p = 1 (mix_device refuses it as hadamard.c:100-102 does) or p2 > MIX_MAX_P2: mix on the device,
+        # sample on the host (randsample_fixedNumberEntries,
         # :334), MB_limit columns at a time -- the same generator runs through all chunks, so a 'DataFile' run
         # draws exactly the samples of the in-memory run (sampleAndMixFromLargeFile.m:100-129)
         nn = max(1, min(n, int(o["MB_limit"] * 2**20 // (8 * p)))) if LoadFromDisk else n
