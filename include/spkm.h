@@ -55,7 +55,14 @@ void spkm_ctx_destroy(spkm_ctx *ctx);
 int spkm_ctx_sync(spkm_ctx *ctx); /* block until everything enqueued on the context's stream is done */
 /* The library's A/B switches (environment variables SPKM_NO_SCREEN, SPKM_NO_BOUNDS, ...: DESIGN.md section 6.1; none
  * changes an output) are read ONCE, by spkm_ctx_create.  This re-reads them: for tests and A/B tools that toggle a
- * switch inside one process. */
+ * switch inside one process.
+ * Test aids (tests/test_gpu_screen_forms.py; they change no default and no output): SPKM_FORCE_FORM=1|2|3 makes every fused
+ * screen call take the plain form (1), the unconditional two-phase form (2) or the hinted two-phase form (3) whatever the
+ * policy would choose, and SPKM_FORCE_POINT_LIST=1 makes the carried-bounds test list points instead of 16-point steps.
+ * Each applies only where the call's state allows it: a hinted call needs the bounds carried from this shard's previous
+ * screen call, a point list needs the carried-bounds test (not SPKM_NO_BOUNDS), a two-phase form a compiled split below
+ * the round count; elsewhere the call falls back to what it may run.  Early or late split: as the policy says
+ * (SPKM_NO_LATE_SPLIT=1: early). */
 int spkm_ctx_reload_switches(spkm_ctx *ctx);
 /* device facts used by the host driver / bench: [0]=CU count, [1]=LDS bytes per workgroup,
  * [2]=device memory bytes, [3]=wavefront size */

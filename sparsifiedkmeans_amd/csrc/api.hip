@@ -34,6 +34,8 @@ static spkm_switches read_switches()
     w.force_pair_events = on("SPKM_FORCE_PAIR_EVENTS");
     w.check_assign = on("SPKM_CHECK_ASSIGN");
     w.no_regroup = on("SPKM_NO_REGROUP");
+    w.force_point_list = on("SPKM_FORCE_POINT_LIST");
+    if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
     if (const char* v = getenv("SPKM_X_HINT_CHUNK")) w.x_hint_chunk = atoi(v);   // points per chunk in the two-phase screen launches (default 256)
     if (const char* v = getenv("SPKM_X_PLAIN_CHUNK")) w.x_plain_chunk = atoi(v); // ... in the plain launch (default: n / (8 x teams), at most 4096)
     return w;

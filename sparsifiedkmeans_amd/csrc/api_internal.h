@@ -51,6 +51,8 @@ struct spkm_switches {
     bool no_teams = false;        // SPKM_NO_TEAMS: screen workgroups split over the tiles by cost (tiles drift apart) instead of teams
     bool no_regroup = false;      // SPKM_NO_REGROUP: the library's order of the points stays the caller's whatever their steps look like
     bool check_assign = false;    // SPKM_CHECK_ASSIGN: before blocks are skipped, verify the lazy contract on d_assign (debug aid; syncs)
+    int force_form = 0;           // SPKM_FORCE_FORM=1|2|3: plain / unconditional two-phase / hinted screen, where legal (test aid, spkm.h)
+    bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
 };
 struct spkm_ctx {
     int device = 0;

@@ -224,7 +224,7 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
         const bool skip_enabled = bounds_ok && !ctx->sw.no_bounds;
         // point-granular list (screen.hip, k_bounds_steps): once the previous call's test passed >= 60 % of the points
         // (counters read back one call late); SPKM_NO_POINT_LIST=1: always 16-point steps (A/B switch)
-        pt_mode = skip_enabled && sm->pol.pt_next && !ctx->sw.no_point_list;
+        pt_mode = skip_enabled && (sm->pol.pt_next || ctx->sw.force_point_list) && !ctx->sw.no_point_list;
         // the two-phase forms' compiled splits (policy.h): the step-major copy lists a point's entries by |x| descending and
         // stops earlier than the point-list kernels, whose entries may come from the records in storage order
         // (the UNCONDITIONAL two-phase form takes the later of the ordered copy's splits, a quarter of the rounds: it finishes
@@ -811,7 +811,12 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
             sm->regroup_wanted = true;
         sm->pol.observe(c, (double)s->n, (int)((K64 + SCREEN_KT - 1) / SCREEN_KT), (s->fixed_s + 3) / 4);
     }
-    const spkm_policy::choice ch = sm->pol.next(ctx->sw.no_prune, ctx->sw.no_hint, screen_use_quad(ctx, s));
+    spkm_policy::choice ch = sm->pol.next(ctx->sw.no_prune, ctx->sw.no_hint, screen_use_quad(ctx, s));
+    if (ctx->sw.force_form) { // SPKM_FORCE_FORM (test aid, spkm.h): run_screen still checks what the call's state allows
+        ch.exact = false;
+        ch.prune_a = ctx->sw.force_form == 2 ? 1 : 0; // (any positive value: run_screen takes the compiled split)
+        ch.want_hint = ctx->sw.force_form == 3 && screen_use_quad(ctx, s);
+    }
     const bool cooling = ch.exact;
     if (s->n > 0 && !cooling && screen_eligible(ctx, s, (int)K64)) {
         ctx->ev_valid = false;

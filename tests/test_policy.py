@@ -327,3 +327,30 @@ def test_movers_are_credited_to_the_call_that_was_observed(pol):
     assert pol.pol_refresh_due(w2.p, N) == 0                 # 6 N + a fresh summation: the count starts over
     w2.call(sums="events"); w2.seen(movers=2.0 * N)
     assert pol.pol_refresh_due(w2.p, N) == 0
+
+
+def test_launch_kind_helper_matches_the_compiled_splits(pol):
+    """tests/screen_forms.py lists the launch kinds of k_screen_quad that tests/test_gpu_screen_forms.py must reach; its
+    splits are policy.h's, round count by round count, and so are the counts: 55 kinds over 16-point steps, 51 over point
+    lists (106 per row-id width), run by 78 compiled kernels."""
+    import screen_forms as F
+
+    for nr in range(1, F.NR_MAX + 1):
+        assert F.split_early(nr) == pol.pol_quad_split(nr), nr
+        assert F.split_late(nr) == pol.pol_quad_split_late(nr), nr
+        assert F.split_early(nr, True) == pol.pol_quad_split_pts(nr), nr
+        assert F.split_late(nr, True) == pol.pol_quad_split_late_pts(nr), nr
+        for pts in (False, True):
+            kinds = F.expected_kinds(nr, pts)
+            # the unconditional form as run_screen converts the policy's choice; hinted splits as take_hinted_split allows
+            late = pol.pol_quad_split_late_pts(nr) if pts else pol.pol_quad_split_late(nr)
+            early = pol.pol_quad_split_pts(nr) if pts else pol.pol_quad_split(nr)
+            uncond = late if (not pts and late > 0) else early
+            assert kinds["plain"] == (pts, nr, nr, False)
+            assert kinds.get("two-phase") == ((pts, nr, uncond, False) if uncond < nr else None), (nr, pts)
+            assert kinds.get("hinted-early") == ((pts, nr, early, True) if early < nr else None), (nr, pts)
+            assert kinds.get("hinted-late") == ((pts, nr, late, True) if early < nr and late > early else None), (nr, pts)
+    kinds = F.all_kinds()
+    assert len(kinds) == 106 and sum(1 for k in kinds if not k[0]) == 55
+    assert len(F.all_kernels()) == 78
+    assert [F.last_tile_body(K) for K in (40, 44, 64, 66, 100)] == [1, 2, 4, 5, 5]
