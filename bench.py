@@ -15,9 +15,14 @@ own loop -- runs from the start centres until norm(centersOld-centers,'fro') < T
 Tol = 1e-6, MaxIter = 100), the host reading dff after every iteration as the driver does; when a run has
 converged the next one starts from the same start centres with the library's carried state dropped
 (spkm_shard_reset_policy: what a new replicate does).  The W warm-up steps run the same loop and are followed by
-such a reset, so the K timed steps always begin with a cold first iteration.  `regimes` reports one complete run
-iteration by iteration (cold first iteration / mean over the run / converged) on this dataset and on the same
-mixture in shuffled point order.
+such a reset, so the K timed steps always begin with a cold first iteration.
+
+A plain run does what the headline figure needs: it generates the dataset, warms up, times the K steps, writes
+--dump-outputs if asked and prints the line.  --full adds the measurements that take time of their own: `regimes` (one
+complete run iteration by iteration -- cold first iteration / mean over the run / converged -- on this dataset, on the
+same mixture in the other point order and with overlapping clusters), the CPU baseline, the HBM traffic of the
+assignment kernel from counter passes of this invocation, the preconditioner's rates, one all-reduce timed by itself
+and the objective after the timed steps.
 
 Prints ONE JSON line on rank 0.
 """
@@ -55,8 +60,8 @@ def main():
     ap.add_argument("--gen-chunk", type=int, default=131072)
     ap.add_argument("--order", choices=["block", "shuffled"], default="block",
                     help="point order of the dataset the headline value is measured on: cluster-contiguous blocks "
-                         "(example_sparseKMeans.m:19-22, SURVEY 8(d)) or arbitrary order; the other one is reported "
-                         "under `regimes` unless --no-regimes")
+                         "(example_sparseKMeans.m:19-22, SURVEY 8(d)) or arbitrary order; with --full the other one is "
+                         "reported under `regimes` unless --no-regimes")
     ap.add_argument("--start", choices=["sample", "planted"], default="sample",
                     help="initial centres: K mixture points drawn with replacement (default: duplicate and uncovered "
                          "clusters, a run needs many iterations) or the K planted means + noise (converges at once)")
@@ -70,6 +75,10 @@ def main():
                          "as it is (the entries exist once: peak = resident), or CSC arrays (the reference's format; the "
                          "library builds its layouts from them on the first call and the arrays are released afterwards: the "
                          "entries exist twice for a moment)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (regimes, CPU baseline, live PMC traffic, "
+                         "preconditioner rates, the all-reduce alone, the final objective); --no-regimes, --no-pmc and "
+                         "--cpu-sample 0 leave parts of it out")
     ap.add_argument("--no-regimes", action="store_true", help="skip the traced runs to convergence (quick experiments)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not measure roofline.traffic in this invocation (two short child runs of this script under "
@@ -148,7 +157,7 @@ def main():
     # roofline.traffic, measured in THIS invocation: HBM bytes of the full-work launch of the assignment kernel from two
     # counter passes (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE do not fit one pass; --pmc only, no trace domain)
     live_pmc = None
-    if rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child and args.workload != "config5":
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child and args.workload != "config5":
         live_pmc = pmc_passes(args)
     first = rank * n_total // world
     n_local = (rank + 1) * n_total // world - first
@@ -190,7 +199,7 @@ def main():
 
     # the one-off preconditioner, reported separately: dense mix() and the fused mix+sample on one chunk
     fw = None
-    if rank == 0:
+    if args.full and rank == 0:
         mcols = min(131072, n_local)
         xd = torch.randn((mcols, p), device="cuda", dtype=torch.float64)
         irt = torch.zeros(mcols * s + 16, dtype=torch.int16 if p2 <= 65536 else torch.int32, device="cuda")
@@ -308,7 +317,7 @@ def main():
 
     # host copies for the CPU legs are taken now: the shard's CSC arrays are about to be released
     cpu_data = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload != "config5":
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload != "config5":
         cpu_data = cpu_sample_arrays(data, centers0, s, min(max(args.cpu_sample, 4_000_000), n_local))
     loop = Loop(shard, centers0)
     # (at least two calls: the first builds the shard's record layout and screen copy, the second is where a shard in
@@ -355,7 +364,7 @@ def main():
     c_n, c_r = comm_info(ctx)
     exchange = {"library_comm_nranks": c_n, "library_comm_rank": c_r, "world_size": world, "reduce_buffer_bytes": int(eng.reduce.numel() * 8),
                 "allreduce_ms": None}
-    if world > 1:
+    if args.full and world > 1:
         keep = eng.reduce.clone()
         sync_all()
         ta = time.perf_counter()
@@ -420,8 +429,9 @@ def main():
     else:
         t, ratio, which = pmc_traffic(scr_name, n_local, K, p2, args.start)
         rl_full["traffic"], rl_full["traffic_over_algorithmic"] = t, ratio
+        why = ("no --full" if not args.full else "--no-pmc" if args.no_pmc else "not a single-GPU screen run")
         rl_full["traffic_source"] = {"source": "committed profile" if t else "none", "record": which, "file": "profiles/pmc_latest.json",
-                                     "why": (live_pmc or {}).get("error", "--no-pmc" if args.no_pmc else "not a single-GPU screen run")}
+                                     "why": (live_pmc or {}).get("error", why)}
     for rl in (rl_screen, rl_acc):
         if rl:   # (by_kernel: the committed passes' figures for the window's kernels, each marked as such)
             t, ratio, which = pmc_traffic(rl["kernel"], n_local, K, p2, args.start)
@@ -470,7 +480,7 @@ def main():
     roofline["exact_pass_points_share"] = acc_share
     free_b, total_b = torch.cuda.mem_get_info()
     ops = 3.0 * nnz_local * K
-    final_obj = loop.objective_now() if loop.it > 0 else float("nan")   # (after the timed region; every rank calls it)
+    final_obj = loop.objective_now() if args.full and loop.it > 0 else float("nan")   # (after the timed region; every rank calls it)
 
     result = {
         "metric": "Lloyd iters/sec + achieved HBM GB/s, N=1e8 d=1024 K=100" if args.workload == "headline"
@@ -531,10 +541,10 @@ def main():
                                       "source": f"uint8 points in pinned host memory ({data['pool_points']} distinct, cycled), "
                                                 f"{args.gen_chunk}-point chunks, copy stream + two staging buffers -> "
                                                 "spkm_widen_f64_dev -> spkm_mix_sample_dev -> resident sparse shard"}
-    if not args.no_regimes and args.workload == "config5":
+    if args.full and not args.no_regimes and args.workload == "config5":
         regimes = {args.order: traced_run(loop, L, ctx, _lib, read_tlog, world, dist, torch, b_iter, b_acc, scr_name, b_screen)}
         result["regimes"] = regimes
-    elif not args.no_regimes:
+    elif args.full and not args.no_regimes:
         regimes = {args.order: traced_run(loop, L, ctx, _lib, read_tlog, world, dist, torch, b_iter, b_acc, scr_name, b_screen)}
         del loop, eng
         shard.close()

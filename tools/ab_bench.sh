@@ -7,7 +7,7 @@ out=$root/gpurun_out/ab_$tag; mkdir -p $out
 for i in $(seq 1 ${PAIRS:-2}); do
   for v in A B; do
     if [ $v = A ]; then export SPKM_AB_LIB=$root/$A; else unset SPKM_AB_LIB; fi
-    timeout 600 python $root/bench.py --no-pmc --cpu-sample 0 "$@" --detail-out $out/detail_${v}_$i.json > $out/line_${v}_$i.json 2> $out/err_${v}_$i.txt
+    timeout 600 python $root/bench.py --full --no-pmc --cpu-sample 0 "$@" --detail-out $out/detail_${v}_$i.json > $out/line_${v}_$i.json 2> $out/err_${v}_$i.txt
     python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ cd $root
 for i in $(seq 1 $pairs); do
   for v in "$a" "$b"; do
     export $var=$v
-    timeout 400 python bench.py --no-pmc --cpu-sample 0 --detail-out /tmp/ab_env_detail.json "$@" > /tmp/ab_env_line.json 2> /tmp/ab_env_err.txt
+    timeout 400 python bench.py --full --no-pmc --cpu-sample 0 --detail-out /tmp/ab_env_detail.json "$@" > /tmp/ab_env_line.json 2> /tmp/ab_env_err.txt
     python - <<PY
 import json
 d=json.load(open("/tmp/ab_env_detail.json"))

@@ -6,7 +6,7 @@ cd $root
 out=$root/gpurun_out/sweep_r6; mkdir -p $out
 run() {
   tag=$1; shift
-  timeout 900 python bench.py --steps 20 --warmup 5 --no-pmc --cpu-sample 0 --detail-out $out/$tag.json "$@" > $out/$tag.line 2> $out/$tag.err
+  timeout 900 python bench.py --full --steps 20 --warmup 5 --no-pmc --cpu-sample 0 --detail-out $out/$tag.json "$@" > $out/$tag.line 2> $out/$tag.err
   python - <<PY
 import json
 try:
