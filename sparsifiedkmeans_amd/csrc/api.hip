@@ -325,7 +325,6 @@ extern "C" int spkm_shard_reset_policy(spkm_shard* s)
     s->hb_valid = false;
     s->sp_clean = false;
     s->assign_synced = false;
-    s->regroup_wanted = false;
     s->regroup_done = false; // (the order a previous run left stays; a new run may ask once more)
     s->pend_full = false;
     return SPKM_OK;

@@ -180,8 +180,7 @@ struct spkm_shard {
     // the library's own order of the points (regroup_shard): point i of the screen copy / of every per-point array the
     // library keeps is the caller's point map[i] (null: the caller's order).  The records stay in the caller's order.
     int* map = nullptr;
-    bool regroup_wanted = false;   // the last call over all points found most 16-point steps mixing clusters
-    bool regroup_done = false;     // ... and it has been acted on since the last spkm_shard_reset_policy
+    bool regroup_done = false;     // the shard has been regrouped (spkm_policy::regroup_wanted) since the last spkm_shard_reset_policy
     bool pend_full = false;        // the call whose counters are pending screened every point in plain order (its step statistics count)
     int* ev_o = nullptr;         // pair events (K <= 128): the mover's old cluster (-1: none); n + 4096 of them
     size_t ev_o_cap = 0;

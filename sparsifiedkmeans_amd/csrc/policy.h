@@ -49,6 +49,8 @@ SPKM_HD constexpr int quad_split(int nr, bool pts = false)
 struct spkm_policy_counters {
     double listed = 0, ambig = 0, early = 0, skipped = 0, kept = 0, movers = 0;
     bool full_opened = false; // a call that queued both accumulation forms: the device opened the full pass (k_pick_form)
+    double one_cluster_steps = 0; // 16-point steps whose points all sit in one cluster (counted by a call over every point)
+    bool may_regroup = false;     // that call screened every point of a lazy shard not yet regrouped (pend_full, lazy, !regroup_done)
 };
 
 struct spkm_policy {
@@ -74,6 +76,7 @@ struct spkm_policy {
     bool crowded = false;           // the latest plain call over ALL points found >= 90 % of them with a runner-up within
                                     // 2.25x of the winner: clusters that overlap -- no partial sum clears a hint there
                                     // (hinted calls only cost: 32.3 against 31.0 ms at N = 1e8), so none is issued
+    bool regroup_wanted = false;    // the next call regroups the shard by cluster first (run_screen, regroup_shard)
     bool movers_known = false;      // last_movers is a count (not before a run's second screen call has been read back)
     unsigned long long last_movers = 0;
     // incremental sums are a running add / subtract: their rounding error is relative to everything a table entry has
@@ -100,6 +103,11 @@ struct spkm_policy {
     void observe(const spkm_policy_counters& c, double n, int tiles, int nr)
     {
         if (mov_pending_valid) { last_movers = (unsigned long long)c.movers; movers_known = true; }
+        // data in arbitrary order: a call over every point found fewer than one in eight of its 16-point steps in one
+        // cluster -- the next call regroups the shard first (run_screen).  Not while clusters overlap (nine points in ten
+        // ambiguous: steps mixed whatever the order).  Regrouping cluster-contiguous data by its first cells was measured: 37
+        // ms spent, nothing gained cold, 0.53 against 0.32 ms per converged iteration at N = 1e8.
+        if (c.may_regroup && n >= 4096 && c.one_cluster_steps < 0.125 * std::ceil(n / 16.0) && c.ambig < 0.9 * n) regroup_wanted = true;
         if (!hint_pending && prune_pending_a == 0 && !skip_pending) crowded = c.ambig >= 0.9 * n; // (a plain call that screened every point)
         if (ev_latched && dual_latched && c.full_opened) { ev_calls = 0; ev_cum_movers = 0; } // (the sums are fresh after all)
         else if (ev_latched && mov_pending_valid) ev_cum_movers += (unsigned long long)c.movers;
@@ -224,3 +232,152 @@ struct spkm_policy {
     bool refresh_due(double n) const { return ev_calls >= 256 || (double)ev_cum_movers > 8.0 * n; }
     static unsigned long long event_cap(unsigned long long n, bool pair_events = false) { return pair_events ? n / 2ull : 2ull * (n / 3ull); }
 };
+
+// One fused call's plan: what run_screen (api_lloyd_fused.inc) decides for the call it issues, from the call's shapes, the
+// device's limits, the switches and the shard's state.  Pure but for take_hinted_split (a hinted call's bookkeeping).
+// Device outcomes are fed back: the event buffers (lose_events), the pair plan's LDS and the pair buffer (lose_pair)
+// before the screen, the record layout (spkm_plan_sums) after it.  Constants of the kernels sized here: checked against
+// SCREEN_KT, BOUNDS_SPAN[_PT] and SEG_POINTS in api_lloyd_fused.inc.
+constexpr int spkm_plan_kt = 32, spkm_plan_span = 16384, spkm_plan_span_pt = 4096, spkm_plan_seg = 2048;
+struct spkm_call_in {
+    long long n = 0;
+    int p = 0, K = 0, fixed_s = 0;
+    bool quad = false;          // the 4-lanes-per-point screen (s <= 64)
+    size_t lds_max = 0;
+    int num_cus = 0, teams = 1; // teams: chunk divisor of the screen launch (quad ? bmapq_blocks / 4 : bmap_streams)
+    bool no_bounds = false, no_point_list = false, force_point_list = false, no_late_split = false, no_incremental = false,
+         no_pair_events = false, force_pair_events = false, no_block_skip = false, no_cluster_skip = false,
+         no_sums_only = false, no_dual = false, no_direct_events = false; // the switches (spkm_switches) that matter here
+    int x_hint_chunk = 0, x_plain_chunk = 0;
+    // the shard: bounds_valid = hb describes its previous screen call, same K and gamma; want_dist = the caller asked for
+    // the distances; has_map = regrouped; sp_clean / sp_blocks: the block summaries describe the previous call, over this
+    // many blocks; same_assign = d_assign is that call's buffer; sort_kept = the context's cluster sizes are this shard's
+    // previous call's, sort_reusable = ... and its sort buffers too
+    bool bounds_valid = false, lazy = false, want_dist = false, has_map = false, cl_valid = false, cl_stats_valid = false,
+         sp_clean = false;
+    long long sp_blocks = 0;
+    bool same_assign = false, assign_synced = false, sort_kept = false, sort_reusable = false;
+    int prune_a = 0; bool want_hint = false; // the caller's choice (spkm_policy::next)
+};
+struct spkm_call_plan {
+    // tiles of G x 32 centroids; pl_last = centroid pairs per lane of the last one (1, 2, 4; 5: its <= 4 centroids ride on
+    // the tile before); Gs = tiles with workgroups / result slots; nr = rounds of 4 entries per column
+    int G = 0, pl_last = 4, Gs = 0, nr = 0;
+    bool bounds_ok = false, kept = false, ev_possible = false, pair_capable = false, ev_path = false, pair_ev = false;
+    bool skip_enabled = false, pt_mode = false, hinted = false, late = false;
+    int prune_a = 0, rounds_all = 0; // the compiled split of a two-phase form (0: plain); rounds for all centroids
+    bool drift = false, erode = false, sp_on = false, sp_reset = true, trusted = false; // drift: the bounds test runs
+    long long npad = 0, span = 0, chunk = 0;
+    int bgrid = 0;
+    bool use_rec = false, pipe = false, cl_on = false, cl_skip = false, sums_only = false, lazy_ub = false, dual = false,
+         reuse = false, nk_incr = false, direct = false; // (spkm_plan_sums)
+    unsigned ev_cap = 0xffffffffu;
+    int seg_ev = spkm_plan_seg;
+    void lose_events() { ev_possible = ev_path = pair_ev = false; } // (no room for the event buffers: the full pass)
+    void lose_pair() { pair_ev = false; }                           // (no pair plan LDS / pair buffer: two events per mover)
+};
+// The screen's tiles.  The last tile: <= 4 centroids ride on the tile before as one extra centroid per lane (pl 5; needs
+// (p+1) x 16 B more LDS); <= 16: a narrow tile with 1 or 2 centroid pairs per lane instead of 4.
+inline void spkm_plan_tiles(spkm_call_plan& pl, const spkm_call_in& in)
+{
+    pl.G = (in.K + spkm_plan_kt - 1) / spkm_plan_kt;
+    const int k_last = in.K - (pl.G - 1) * spkm_plan_kt;
+    pl.pl_last = !in.quad ? 4 : (k_last <= 8 ? 1 : (k_last <= 16 ? 2 : 4));
+    if (in.quad && pl.G >= 2 && k_last <= 4 && (size_t)(in.p + 1) * (spkm_plan_kt * 4 + 16) + 16 <= in.lds_max) pl.pl_last = 5;
+    pl.Gs = pl.pl_last == 5 ? pl.G - 1 : pl.G;
+    pl.nr = (in.fixed_s + 3) / 4;
+    pl.npad = (in.n + 63) / 64 * 64;
+}
+// Everything decided before the screen launches, every device resource assumed granted (after spkm_plan_tiles).
+inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_policy& pol)
+{
+    const long long n = in.n;
+    const int K = in.K, nr = pl.nr;
+    int prune_a = in.prune_a;
+    if (in.quad) {
+        pl.bounds_ok = in.bounds_valid;
+        pl.kept = pl.bounds_ok && in.sort_kept;
+        // Incremental call (spkm_shard_set_lazy_stats; SPKM_NO_INCREMENTAL=1: A/B switch): the sums move by the events of
+        // the points that change cluster.  Needs lazy statistics without distances, the library's previous assignment and
+        // sums (kept, cl_valid) and few movers.  The first lazy call allocates what later ones need.
+        pl.ev_possible = in.lazy && !in.no_incremental && (size_t)in.p * 12 <= 64 * 1024;
+        // PAIR events (K <= 128; SPKM_NO_PAIR_EVENTS=1: A/B switch): one event per mover, its record read once.  Only while a
+        // pair's run pays for its slab and the second sort level -- >= 256 movers per pair expected (n / 3 with no count) --
+        // and while that level's plan fits the LDS: K (K + 1) counters beside 8 KB of static arrays (a 64-KB part: K < 120)
+        const unsigned long long est_movers = pol.movers_known ? pol.last_movers : (unsigned long long)n / 3ull;
+        pl.pair_capable = K <= 128 && !in.no_pair_events && (size_t)K * (size_t)(K + 1) * 4 + 8192 <= in.lds_max &&
+                          (est_movers >= 256ull * (unsigned long long)K * (unsigned long long)(K + 1) || in.force_pair_events);
+        pl.ev_path = pl.ev_possible && !in.want_dist && pl.kept && in.cl_valid && pol.few_movers((double)n, pl.pair_capable) &&
+                     !pol.refresh_due((double)n);
+        pl.pair_ev = pl.ev_path && pl.pair_capable;
+        pl.skip_enabled = pl.bounds_ok && !in.no_bounds;
+        // point-granular list (k_bounds_steps): see pt_next; SPKM_NO_POINT_LIST=1: always 16-point steps (A/B switch)
+        pl.pt_mode = pl.skip_enabled && (pol.pt_next || in.force_point_list) && !in.no_point_list;
+        // the UNCONDITIONAL two-phase form takes the later of the ordered copy's splits, a quarter of the rounds: it finishes
+        // every step on its partial sums, and with the early split's 4 entries their scatter sends 5 % of a moderately
+        // separated shard to the exact list (the hinted form checks before it stops); point lists: their early split
+        if (prune_a > 0)
+            prune_a = (!pl.pt_mode && quad_split_late(nr, false) > 0) ? quad_split_late(nr, false) : quad_split(nr, pl.pt_mode);
+        // hinted two-phase form: needs the carried bounds (the hints are ub + drift) and a split that saves rounds
+        pl.hinted = in.want_hint && pl.bounds_ok && prune_a == 0 && quad_split(nr, pl.pt_mode) < nr;
+        if (pl.hinted) {
+            pl.late = pol.take_hinted_split(nr, in.no_late_split) && quad_split_late(nr, pl.pt_mode) > quad_split(nr, pl.pt_mode);
+            prune_a = pl.late ? quad_split_late(nr, pl.pt_mode) : quad_split(nr, pl.pt_mode);
+        }
+        pl.drift = pl.skip_enabled || pl.hinted;
+        if (pl.drift) {
+            // (small shards: shorter spans, so that the launch still has >= 8 workgroups per CU)
+            pl.span = pl.pt_mode ? spkm_plan_span_pt : spkm_plan_span;
+            pl.bgrid = 4 * std::max(1, in.num_cus); // (8, 16, 32 per CU measured within noise of 4)
+            while (pl.span > 1024 && (pl.npad + pl.span - 1) / pl.span < 4LL * pl.bgrid) pl.span /= 2;
+            // erode: every lazy call without distances -- no fresh upper bound for a point that passes, so its bound
+            // takes its centroid's drift here
+            pl.erode = in.lazy && !in.want_dist;
+            // block summaries (lazy calls only): a settled block's part of the caller's buffer goes unvisited while it is
+            // the buffer of the previous call (the lazy contract, spkm.h)
+            pl.sp_on = pl.erode && pl.skip_enabled && K <= 128 && pol.blocks_next && !in.no_block_skip;
+            pl.sp_reset = !(pl.sp_on && in.sp_clean && in.sp_blocks == pl.npad / 1024 + 1 && in.same_assign);
+            // trusted: a REGROUPED shard's buffer of the previous call holds the library's copy, not read nor restored by the
+            // test -- while the claim stands (assign_synced; otherwise it may be a new buffer at an old address)
+            pl.trusted = in.has_map && in.lazy && !in.want_dist && in.same_assign && in.assign_synced;
+        }
+    }
+    pl.prune_a = prune_a;
+    pl.rounds_all = in.quad && prune_a > 0 && prune_a < nr ? prune_a : nr;
+    // chunk = n / (8 x teams), 256 ..= 4096 points; two-phase launches take 256 (finer grains for workgroups that run at
+    // their own pace: 82.8 -> 84.9 it/s, profiles/r06_exp_hint_chunk.txt); SPKM_X_HINT_CHUNK / SPKM_X_PLAIN_CHUNK: others
+    const long long sweep = 16 * 16;
+    long long chunk = std::max<long long>(sweep, std::min<long long>(n / ((long long)in.teams * 8), 16 * sweep)) / sweep * sweep;
+    if (in.quad && prune_a > 0) chunk = std::min<long long>(chunk, in.x_hint_chunk >= sweep ? in.x_hint_chunk : sweep);
+    if (in.quad && prune_a == 0 && in.x_plain_chunk >= sweep) chunk = std::min<long long>(chunk, in.x_plain_chunk);
+    if (in.quad) { long long c2 = sweep; while (c2 * 2 <= chunk) c2 *= 2; chunk = c2; } // (a power of two: screen_quad.hip's step arithmetic)
+    pl.chunk = chunk;
+}
+// ... and what is decided once the record layout is known (build_records runs after the screen).  rec: the shard has it.
+inline void spkm_plan_sums(spkm_call_plan& pl, const spkm_call_in& in, const spkm_policy& pol, bool rec)
+{
+    pl.use_rec = rec;
+    // software-pipelined record kernel (k_exact_accumulate_rec): 16 waves x 16 points, columns of up to 64 entries
+    pl.pipe = rec && in.fixed_s <= 64 && (size_t)in.p * 20 + 16 + (size_t)16 * 16 * (in.fixed_s | 1) * 8 + 1024 <= in.lds_max;
+    // Unchanged-cluster shortcut (k_cluster_need; SPKM_NO_CLUSTER_SKIP=1: A/B switch): a cluster whose centroid is bitwise
+    // the previous call's and that no point left or entered is not streamed again (needs the pipelined kernel)
+    pl.cl_on = in.quad && pl.pipe;
+    pl.cl_skip = pl.cl_on && pl.bounds_ok && pl.drift && in.cl_valid && in.cl_stats_valid && !in.want_dist && !in.no_cluster_skip &&
+                 !pl.ev_path;
+    // Sums-only full pass (SPKM_NO_SUMS_ONLY=1: A/B switch): a LAZY call off the event path adds up every member, no distances
+    pl.sums_only = pl.cl_on && in.lazy && !in.want_dist && !pl.ev_path && !pl.cl_skip && !in.no_sums_only;
+    // the certificate writes the upper bounds -- also for a regrouped shard, whose exact pass walks the caller's order
+    pl.lazy_ub = pl.ev_path || pl.sums_only || in.has_map;
+    // Form chosen on the device (SPKM_NO_DUAL=1: A/B switch): an incremental call issued without a mover count queues the
+    // sums-only pass as well, and k_pick_form opens one of the two from the number of events (form_on_device, event_cap)
+    pl.dual = pl.ev_path && pol.form_on_device() && pl.cl_on && !in.no_dual && !in.no_sums_only;
+    pl.ev_cap = pl.dual ? (unsigned)std::min<unsigned long long>(spkm_policy::event_cap((unsigned long long)in.n, pl.pair_ev), 0xfffffff0ull)
+                        : 0xffffffffu;
+    // the kept sort is used again (its kernels return at once when no assignment changed); the cluster sizes move by the movers
+    pl.reuse = pl.kept && in.sort_reusable;
+    pl.nk_incr = pl.kept;
+    // few movers known (a settled run): the events are applied where they were appended, no counting sort
+    // (k_events_direct; SPKM_NO_DIRECT_EVENTS=1: A/B switch); few events: short segments, spread over more workgroups
+    pl.direct = pl.ev_path && !pl.dual && pol.events_direct() && !in.no_direct_events;
+    pl.seg_ev = (pol.movers_known && pol.last_movers < 100000) ? 256 : spkm_plan_seg;
+}

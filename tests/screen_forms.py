@@ -1,5 +1,5 @@
 """The launch kinds of the 4-lanes-per-point screen (k_screen_quad, csrc/screen_quad.hip) that the fused call can reach,
-as the host code selects them (csrc/api_lloyd_fused.inc, run_screen).  A plain helper for the tests, not a conftest:
+as the host code selects them (csrc/policy.h, spkm_plan_call).  A plain helper for the tests, not a conftest:
 tests/test_policy.py pins it against the compiled policy.h, tests/test_gpu_screen_forms.py checks that a case reaches
 every kind it lists.
 
@@ -30,7 +30,7 @@ def split_late(nr: int, pts: bool = False) -> int:
 
 
 def unconditional_split(nr: int, pts: bool) -> int:
-    """rounds for all centroids of the unconditional two-phase form (run_screen): the late split of the step-major copy
+    """rounds for all centroids of the unconditional two-phase form (policy.h, spkm_plan_call): the late split of the step-major copy
     where it has one, else the early one; the point-list kernels take their early split"""
     if not pts and split_late(nr) > 0:
         return split_late(nr)
@@ -70,7 +70,7 @@ def all_kernels() -> set:
 
 
 def last_tile_body(K: int, p: int = 256, lds_max: int = 160 * 1024) -> int:
-    """pl of the last centroid tile (run_screen): 1 / 2 centroid pairs per lane for a narrow tile of <= 8 / <= 16,
+    """pl of the last centroid tile (policy.h, spkm_plan_tiles): 1 / 2 centroid pairs per lane for a narrow tile of <= 8 / <= 16,
     4 for a full one, 5 when <= 4 centroids are carried by the tile before"""
     G = (K + 31) // 32
     k_last = K - (G - 1) * 32

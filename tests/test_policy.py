@@ -39,7 +39,40 @@ def pol(tmp_path_factory):
     L.pol_event_cap.restype = C.c_uint64
     L.pol_event_cap_pair.argtypes = [C.c_uint64]
     L.pol_event_cap_pair.restype = C.c_uint64
+    L.plan_call.argtypes = [C.POINTER(CallIn), C.c_void_p, C.POINTER(Plan)]
+    L.plan_lose_events.argtypes = L.plan_lose_pair.argtypes = [C.POINTER(Plan)]
+    L.plan_sums.argtypes = [C.POINTER(Plan), C.POINTER(CallIn), C.c_void_p, C.c_int]
+    L.pol_set.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int]
+    L.pol_regroup_wanted.argtypes = [C.c_void_p]
+    L.pol_observe_regroup.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double]
+    sizes = (C.c_int * 2)()
+    L.plan_sizes(sizes)
+    assert (sizes[0], sizes[1]) == (C.sizeof(CallIn), C.sizeof(Plan)), "the ctypes mirror of policy.h's plan structs is stale"
+    L.plan_in_offset.argtypes = L.plan_offset.argtypes = [C.c_char_p]
+    for S, off in ((CallIn, L.plan_in_offset), (Plan, L.plan_offset)):          # ... field by field
+        for f, _ in S._fields_:
+            assert off(f.encode()) == getattr(S, f).offset, (S.__name__, f)
     return L
+
+
+def _struct(name, spec):
+    """a ctypes mirror of a policy.h struct: spec = [(ctype, "field field ..."), ...] in declaration order"""
+    return type(name, (C.Structure,), {"_fields_": [(f, t) for t, names in spec for f in names.split()]})
+
+
+B = C.c_bool
+CallIn = _struct("CallIn", [(C.c_longlong, "n"), (C.c_int, "p K fixed_s"), (B, "quad"), (C.c_size_t, "lds_max"),
+                            (C.c_int, "num_cus teams"),
+                            (B, "no_bounds no_point_list force_point_list no_late_split no_incremental no_pair_events "
+                                "force_pair_events no_block_skip no_cluster_skip no_sums_only no_dual no_direct_events"),
+                            (C.c_int, "x_hint_chunk x_plain_chunk"),
+                            (B, "bounds_valid lazy want_dist has_map cl_valid cl_stats_valid sp_clean"), (C.c_longlong, "sp_blocks"),
+                            (B, "same_assign assign_synced sort_kept sort_reusable"), (C.c_int, "prune_a"), (B, "want_hint")])
+Plan = _struct("Plan", [(C.c_int, "G pl_last Gs nr"),
+                        (B, "bounds_ok kept ev_possible pair_capable ev_path pair_ev skip_enabled pt_mode hinted late"),
+                        (C.c_int, "prune_a rounds_all"), (B, "drift erode sp_on sp_reset trusted"), (C.c_longlong, "npad span chunk"),
+                        (C.c_int, "bgrid"), (B, "use_rec pipe cl_on cl_skip sums_only lazy_ub dual reuse nk_incr direct"),
+                        (C.c_uint, "ev_cap"), (C.c_int, "seg_ev")])
 
 
 class Walk:
@@ -345,7 +378,7 @@ def test_launch_kind_helper_matches_the_compiled_splits(pol):
             # the unconditional form as run_screen converts the policy's choice; hinted splits as take_hinted_split allows
             late = pol.pol_quad_split_late_pts(nr) if pts else pol.pol_quad_split_late(nr)
             early = pol.pol_quad_split_pts(nr) if pts else pol.pol_quad_split(nr)
-            uncond = late if (not pts and late > 0) else early
+            uncond = Call(pol, fixed_s=4 * nr, prune_a=1, force_point_list=pts, want_hint=False).plan().prune_a
             assert kinds["plain"] == (pts, nr, nr, False)
             assert kinds.get("two-phase") == ((pts, nr, uncond, False) if uncond < nr else None), (nr, pts)
             assert kinds.get("hinted-early") == ((pts, nr, early, True) if early < nr else None), (nr, pts)
@@ -354,3 +387,225 @@ def test_launch_kind_helper_matches_the_compiled_splits(pol):
     assert len(kinds) == 106 and sum(1 for k in kinds if not k[0]) == 55
     assert len(F.all_kernels()) == 78
     assert [F.last_tile_body(K) for K in (40, 44, 64, 66, 100)] == [1, 2, 4, 5, 5]
+
+
+# ---- the per-call plan (spkm_plan_call / spkm_plan_sums): what run_screen decides for the call it issues ----
+
+class Call:
+    """one fused call's input: by default a settled lazy call on the headline shape -- n = 1e6, p = 1024, K = 100, s = 51
+    (13 rounds), the previous call's bounds, sort, cluster cache and block summaries all held, few movers known"""
+
+    def __init__(self, L, movers=1000, pt_next=False, blocks_next=True, ev_calls=0, known=True, **kw):
+        self.L, self.pol = L, C.c_void_p(L.pol_new())
+        L.pol_set(self.pol, int(known), int(movers), int(pt_next), int(blocks_next), ev_calls)
+        n = kw.get("n", 1_000_000)
+        self.inp = CallIn(n=n, p=1024, K=100, fixed_s=51, quad=True, lds_max=160 * 1024, num_cus=256, teams=192,
+                          bounds_valid=True, lazy=True, cl_valid=True, cl_stats_valid=True, sp_clean=True,
+                          sp_blocks=(n + 63) // 64 * 64 // 1024 + 1, same_assign=True, assign_synced=True, sort_kept=True,
+                          sort_reusable=True, want_hint=True)
+        for k, v in kw.items():
+            setattr(self.inp, k, v)
+
+    def plan(self, rec=True, lose=()):
+        """spkm_plan_call, the device's refusals in run_screen's order, then spkm_plan_sums"""
+        pl = Plan()
+        self.L.plan_call(C.byref(self.inp), self.pol, C.byref(pl))
+        if "events" in lose and pl.ev_possible:
+            self.L.plan_lose_events(C.byref(pl))
+        if ("pair_lds" in lose or "ev_o" in lose) and pl.pair_ev:
+            self.L.plan_lose_pair(C.byref(pl))
+        self.L.plan_sums(C.byref(pl), C.byref(self.inp), self.pol, int(rec))
+        return pl
+
+
+def test_plan_takes_the_events_only_where_the_call_allows_them(pol):
+    assert Call(pol).plan().ev_path
+    for kw in (dict(lazy=False), dict(want_dist=True), dict(sort_kept=False), dict(bounds_valid=False), dict(cl_valid=False),
+               dict(no_incremental=True), dict(quad=False), dict(p=6000)):
+        assert not Call(pol, **kw).plan().ev_path, kw
+    assert not Call(pol, movers=400_000).plan().ev_path                 # more than a third of the points moved
+    assert Call(pol, movers=300_000).plan().ev_path
+    assert not Call(pol, ev_calls=256).plan().ev_path                   # a refresh is due: the full pass
+    assert Call(pol, known=False).plan().ev_path                        # no count yet: taken as few
+    assert Call(pol, lazy=True, want_dist=True).plan().ev_possible      # (buffers for a later call are still sized)
+    assert not Call(pol, lazy=False).plan().ev_possible
+
+
+def test_plan_pair_events_bars(pol):
+    big = dict(movers=10_000_000, n=100_000_000)                         # 1e7 movers known: 980 per pair at K = 100
+    assert Call(pol, known=False, n=100_000_000).plan().pair_capable    # n / 3 expected: >= 256 per pair
+    assert not Call(pol, known=False).plan().pair_capable               # 1e6 points: 33 per pair
+    assert Call(pol, **big).plan().pair_ev
+    assert Call(pol, movers=4_300_000, n=100_000_000, K=128).plan().pair_capable
+    assert not Call(pol, movers=40_000_000, n=100_000_000, K=129).plan().pair_capable
+    # K (K + 1) x 4 B + 8 KB of LDS: a 64-KB part fits K = 119, not 120
+    assert Call(pol, K=119, lds_max=64 * 1024, force_pair_events=True).plan().pair_capable
+    assert not Call(pol, K=120, lds_max=64 * 1024, force_pair_events=True).plan().pair_capable
+    assert not Call(pol, **big, no_pair_events=True).plan().pair_capable
+    assert Call(pol, force_pair_events=True).plan().pair_capable        # SPKM_FORCE_PAIR_EVENTS: whatever is expected
+    # 256 K (K + 1) expected movers, exactly
+    assert Call(pol, movers=256 * 100 * 101, n=100_000_000).plan().pair_capable
+    assert not Call(pol, movers=256 * 100 * 101 - 1, n=100_000_000).plan().pair_capable
+    # pair events pay up to half the points moving, two events per mover up to a third
+    assert Call(pol, movers=45_000_000, n=100_000_000).plan().pair_ev
+    assert not Call(pol, movers=45_000_000, n=100_000_000, no_pair_events=True).plan().ev_path
+
+
+def test_plan_point_lists(pol):
+    assert not Call(pol).plan().pt_mode
+    assert Call(pol, pt_next=True).plan().pt_mode
+    assert Call(pol, force_point_list=True).plan().pt_mode
+    for kw in (dict(no_point_list=True), dict(no_bounds=True), dict(bounds_valid=False)):
+        assert not Call(pol, pt_next=True, force_point_list=True, **kw).plan().pt_mode, kw
+    pl = Call(pol, no_bounds=True).plan()
+    assert not pl.skip_enabled and pl.hinted and pl.drift               # hints still need the drift and the bounds test
+
+
+def test_plan_hinted_split_early_late_and_the_unconditional_conversion(pol):
+    import screen_forms as F
+
+    c2 = Call(pol)
+    seq = [c2.plan() for _ in range(5)]                                  # take_hinted_split: the run's first three are late
+    assert [(p.hinted, p.late, p.prune_a) for p in seq] == [(True, True, 3)] * 3 + [(True, False, 1)] * 2
+    pl = Call(pol, no_late_split=True).plan()
+    assert (pl.hinted, pl.late, pl.prune_a, pl.rounds_all) == (True, False, 1, 1)
+    pl = Call(pol, pt_next=True).plan()                                  # point lists: their own splits (3 / 7 of 13)
+    assert (pl.hinted, pl.late, pl.prune_a) == (True, True, 7)
+    for kw in (dict(want_hint=False), dict(bounds_valid=False), dict(prune_a=1), dict(fixed_s=8)):
+        assert not Call(pol, **kw).plan().hinted, kw                     # (2 rounds: no split saves one)
+    # no hinted call, no late-split bookkeeping
+    c3 = Call(pol, want_hint=False)
+    assert not any(c3.plan().hinted for _ in range(3))
+    c3.inp.want_hint = True
+    assert c3.plan().late
+    # the unconditional form's compiled split, as tests/screen_forms.py restates it
+    for nr in range(1, F.NR_MAX + 1):
+        for pts in (False, True):
+            pl = Call(pol, fixed_s=4 * nr, prune_a=1, force_point_list=pts).plan()
+            assert pl.nr == nr and not pl.hinted
+            assert pl.prune_a == F.unconditional_split(nr, pts), (nr, pts)
+            assert pl.rounds_all == (pl.prune_a if pl.prune_a < nr else nr)
+    assert Call(pol, prune_a=1, quad=False).plan().prune_a == 1          # (the 16-lanes-per-point screen: no conversion)
+
+
+def test_plan_block_summaries_and_the_trusted_buffer(pol):
+    pl = Call(pol).plan()
+    assert pl.erode and pl.sp_on and not pl.sp_reset and not pl.trusted
+    for kw in (dict(lazy=False), dict(want_dist=True), dict(no_bounds=True), dict(K=129), dict(no_block_skip=True)):
+        assert not Call(pol, **kw).plan().sp_on, kw
+    assert not Call(pol, blocks_next=False).plan().sp_on
+    for kw in (dict(sp_clean=False), dict(same_assign=False), dict(sp_blocks=7)):
+        pl = Call(pol, **kw).plan()
+        assert pl.sp_on and pl.sp_reset, kw                              # kept, but started over
+    assert Call(pol, has_map=True).plan().trusted
+    for kw in (dict(lazy=False), dict(want_dist=True), dict(same_assign=False), dict(assign_synced=False)):
+        assert not Call(pol, has_map=True, **kw).plan().trusted, kw
+    assert not Call(pol, has_map=True, want_hint=False, bounds_valid=False).plan().trusted   # (no bounds test at all)
+
+
+def test_plan_accumulation_flags(pol):
+    pl = Call(pol).plan()                                                # settled, few movers: events, one by one
+    assert pl.ev_path and pl.direct and not pl.dual and not pl.cl_skip and not pl.sums_only and pl.lazy_ub
+    assert pl.ev_cap == 0xFFFFFFFF and pl.reuse and pl.nk_incr and pl.seg_ev == 256
+    assert not Call(pol, movers=5000).plan().direct and Call(pol, movers=5000, no_direct_events=True).plan().ev_path
+    assert not Call(pol, movers=1000, no_direct_events=True).plan().direct
+    assert Call(pol, movers=200_000).plan().seg_ev == 2048
+    pl = Call(pol, known=False).plan()                                   # no count yet: both forms, the device picks
+    assert pl.dual and pl.ev_cap == 2 * (1_000_000 // 3) and not pl.direct
+    assert Call(pol, known=False, force_pair_events=True).plan().ev_cap == 500_000
+    for kw in (dict(no_dual=True), dict(no_sums_only=True)):
+        assert not Call(pol, known=False, **kw).plan().dual, kw
+    assert not Call(pol, known=False).plan(rec=False).dual               # (no records: no pipelined pass, no shortcut)
+    pl = Call(pol, lazy=False, want_dist=True).plan()                    # distances asked for: the full pass with its statistics
+    assert pl.cl_on and not pl.cl_skip and not pl.sums_only and not pl.lazy_ub
+    pl = Call(pol, lazy=False).plan()                                    # not lazy, no distances: the shortcut
+    assert pl.cl_skip and not pl.sums_only
+    for kw in (dict(cl_stats_valid=False), dict(no_cluster_skip=True), dict(want_hint=False, no_bounds=True)):
+        pl = Call(pol, lazy=False, **kw).plan()
+        assert not pl.cl_skip, kw
+    pl = Call(pol, movers=400_000).plan()                                # too many movers, nothing changed: the shortcut
+    assert (pl.ev_path, pl.cl_skip, pl.sums_only, pl.lazy_ub) == (False, True, False, False)
+    pl = Call(pol, movers=400_000, cl_stats_valid=False).plan()          # ... after an incremental call: a sums-only pass
+    assert (pl.ev_path, pl.cl_skip, pl.sums_only, pl.lazy_ub) == (False, False, True, True)
+    assert not Call(pol, movers=400_000, cl_stats_valid=False, no_sums_only=True).plan().sums_only
+    assert Call(pol, lazy=False, want_dist=True, has_map=True).plan().lazy_ub    # a regrouped shard: the certificate writes them
+    pl = Call(pol).plan(rec=False)
+    assert not pl.use_rec and not pl.pipe and not pl.cl_on
+    assert not Call(pol, fixed_s=65, quad=False).plan().pipe             # columns of more than 64 entries
+    assert not Call(pol, sort_reusable=False).plan().reuse and not Call(pol, sort_kept=False).plan().nk_incr
+
+
+def test_plan_last_tile(pol):
+    bodies = []
+    for K in (40, 44, 64, 66, 100):
+        pl = Call(pol, K=K, p=256).plan()
+        bodies.append(pl.pl_last)
+        assert pl.G == (K + 31) // 32 and pl.Gs == (pl.G - 1 if pl.pl_last == 5 else pl.G)
+    assert bodies == [1, 2, 4, 5, 5]
+    import screen_forms as F
+    assert bodies == [F.last_tile_body(K) for K in (40, 44, 64, 66, 100)]
+    assert Call(pol, K=100, p=1024, lds_max=64 * 1024).plan().pl_last == 1      # no room for the carried centroids
+    assert Call(pol, K=40, quad=False).plan().pl_last == 4                      # the 16-lanes-per-point screen: full tiles
+
+
+def test_plan_chunk(pol):
+    def chunk(**kw):
+        return Call(pol, **kw).plan().chunk
+
+    assert chunk(want_hint=False) == 512                                  # plain: n / (8 x 192 teams) = 651 -> 512
+    assert chunk(n=100_000_000, want_hint=False) == 4096                  # (at most 16 sweeps)
+    assert chunk(n=1000, want_hint=False) == 256                          # (at least one)
+    assert chunk() == 256 and chunk(prune_a=1, want_hint=False) == 256    # the two-phase forms: 256 by default
+    assert chunk(n=100_000_000, x_hint_chunk=4096) == 4096 and chunk(n=100_000_000, x_hint_chunk=1000) == 512
+    assert chunk(n=100_000_000, x_hint_chunk=100) == 256                  # (below a sweep: the default)
+    assert chunk(n=100_000_000, want_hint=False, x_plain_chunk=1024) == 1024 and chunk(x_plain_chunk=1024) == 256
+    assert chunk(n=100_000_000, quad=False, want_hint=False) == 4096 and chunk(n=3_000_000, quad=False) == 1792
+    for n in (1000, 54321, 10**6, 3 * 10**7, 10**8):
+        for kw in (dict(), dict(want_hint=False), dict(prune_a=1, want_hint=False, x_hint_chunk=3000)):
+            c = chunk(n=n, **kw)
+            assert c >= 256 and c & (c - 1) == 0, (n, kw, c)
+
+
+def test_plan_bounds_span(pol):
+    def span(n, **kw):
+        return Call(pol, n=n, **kw).plan().span
+
+    assert span(100_000_000) == 16384 and span(100_000_000, pt_next=True) == 4096
+    assert span(1_000_000) == 1024 and span(10_000_000) == 2048           # halved until 4 x 4 workgroups per CU
+    assert span(30_000_000) == 4096 and span(4096) == 1024
+    assert span(10_000_000, num_cus=0) == 16384                           # (an unknown CU count: one)
+
+
+def test_plan_device_fallbacks(pol):
+    big = dict(movers=10_000_000, n=100_000_000)
+    pl = Call(pol, cl_stats_valid=False).plan(lose=("events",))          # no room for the event buffers: the full pass
+    assert not pl.ev_possible and not pl.ev_path and not pl.pair_ev and pl.sums_only and not pl.direct
+    pl = Call(pol, known=False, cl_stats_valid=False).plan(lose=("events",))
+    assert not pl.dual and pl.ev_cap == 0xFFFFFFFF and pl.sums_only
+    for lose in ("pair_lds", "ev_o"):                                    # no pair plan / pair buffer: two events per mover
+        pl = Call(pol, **big).plan(lose=(lose,))
+        assert pl.ev_path and not pl.pair_ev and pl.pair_capable and not pl.sums_only
+    pl = Call(pol, known=False, force_pair_events=True).plan(lose=("ev_o",))
+    assert pl.dual and pl.ev_cap == 2 * (1_000_000 // 3)                 # (the device's bar follows the form)
+
+
+def test_regroup_is_wanted_after_a_full_call_over_mixed_steps(pol):
+    """spkm_policy::observe: a call over every point of a lazy shard not yet regrouped found fewer than one in eight of its
+    16-point steps in one cluster, and fewer than nine points in ten ambiguous"""
+    steps = N / 16
+
+    def wanted(ambig=0.3 * N, one=0.1 * steps, may=1, n=N):
+        p = C.c_void_p(pol.pol_new())
+        pol.pol_observe_regroup(p, ambig, one, may, n)
+        return pol.pol_regroup_wanted(p)
+
+    assert wanted() == 1
+    assert wanted(one=0.125 * steps) == 0 and wanted(one=0.124 * steps) == 1
+    assert wanted(ambig=0.9 * N) == 0 and wanted(may=0) == 0
+    assert wanted(n=4095, one=0, ambig=0) == 0 and wanted(n=4096, one=0, ambig=0) == 1
+    p = C.c_void_p(pol.pol_new())
+    pol.pol_observe_regroup(p, 0.3 * N, 0.0, 1, N)
+    pol.pol_observe_regroup(p, 0.3 * N, steps, 1, N)                     # (a later report does not take it back)
+    assert pol.pol_regroup_wanted(p) == 1
+    pol.pol_reset(p)
+    assert pol.pol_regroup_wanted(p) == 0

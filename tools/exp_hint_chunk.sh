@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/exp_hint_chunk; mkdir -p $out
 cd $root
-for c in 0 1024 512 256; do
+for c in 4096 1024 512 256; do
   export SPKM_X_HINT_CHUNK=$c
   for rep in 1 2; do
     SPKM_BENCH_DUMP=1 timeout 300 python bench.py --steps 20 --warmup 5 --no-pmc --no-regimes --cpu-sample 0 --detail-out /dev/null > $out/line_${c}_$rep.json 2> $out/err_${c}_$rep.txt
