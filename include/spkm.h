@@ -279,6 +279,16 @@ int spkm_last_screen_mode(spkm_ctx *ctx, int64_t info[8]);
  * old one's together (K <= 128; SPKM_NO_PAIR_EVENTS=1: A/B switch) -- 0 if two events per mover, each applied on its
  * own (kmeans_sparsified.m:447-448's S and Cnt either way).  Does not block. */
 int spkm_last_events_form(spkm_ctx *ctx, int64_t info[2]);
+/* Launch shapes the library chose last from the LDS size of the device (debug aid; stored values, changes no path, does
+ * not block): info[0] = tile width of the last spkm_assign_dev -- also the one a fused call on the all-exact kernels
+ * issued -- 64, 32 or 16 centroids, 0 = the generic kernel or the K = 1 stream; info[1] = its number of tiles;
+ * info[2] = last-tile body of the last fused call's screen plan: 1, 2 or 4 centroid pairs per lane, 5 = a last tile of
+ * <= 4 centroids rode on the tile before it (0: that call did not take the screen); info[3] = points staged per wave by
+ * the last exact pass: 8 .. 64 (fused call: k_exact_accumulate; 16 .. 64 for the K = 1 stream of spkm_assign_dev), 16 for
+ * the pipelined record kernel, 0 when the last call ran none (tiles, generic kernel, incremental sums); info[4] = kernel
+ * of the last spkm_accumulate_dev: 1 = LDS slab over a counting sort, 2 = global atomics (rows beyond a 64-KB slab),
+ * 0 = none; info[5] = kernel of the last spkm_distances[_stats]_dev: 1 = streaming record kernel, 2 = generic, 0 = none. */
+int spkm_last_assign_tile(spkm_ctx *ctx, int64_t info[6]);
 
 /* Unchanged-cluster shortcut of the fused call's exact pass.  A cluster (i) whose centroid is BITWISE the one the
  * previous fused call on this shard was given and (ii) that no point left or entered is not streamed again: every

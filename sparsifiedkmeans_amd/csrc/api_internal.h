@@ -89,6 +89,10 @@ struct spkm_ctx {
     long long sort_n = 0;
     bool tlog_both = false; // fused screen path: log the exact accumulation kernel too (pairs alternate)
     int assign_KT = 0, assign_G = 0; // of the last assign call
+    int last_pl_last = 0;            // the last screen call's plan: centroid pairs per lane of its last tile (5: carried)
+    int last_exact_pts = 0;          // points staged per wave by the last exact pass / K = 1 stream (16: the pipelined kernel)
+    int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics
+    int last_dist_form = 0;          // the last distances call: 1 streaming record kernel, 2 generic kernel
     int last_path = 0;               // 0 = exact tiled/generic, 1 = f32 screen + exact confirmation
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
     bool last_hint_late = false; // the last hinted call used the late split

@@ -523,6 +523,7 @@ extern "C" int spkm_assign_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64,
             HIP_TRY(hipGetLastError());
             ctx->assign_KT = 0;
             ctx->assign_G = 1;
+            ctx->last_exact_pts = pts;
             if (d_stats) HIP_TRY(hipMemcpyAsync(d_stats, ctx->stats.p, 3 * 8, hipMemcpyDeviceToDevice, ctx->stream));
             if (d_nk_u64) HIP_TRY(hipMemcpyAsync(d_nk_u64, ctx->nk.p, 8, hipMemcpyDeviceToDevice, ctx->stream));
             return SPKM_OK;
@@ -584,6 +585,7 @@ extern "C" int spkm_assign_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64,
     }
     ctx->assign_KT = KT;
     ctx->assign_G = G;
+    ctx->last_exact_pts = 0; // (no staged pass: tiles or the generic kernel)
     return combine_partials(ctx, n, G, K, d_assign, d_mind, d_stats, d_nk_u64);
 }
 
@@ -684,8 +686,10 @@ extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t 
     if (!ctx->nk.p || !ctx->stats.p) return SPKM_ERR_BAD_VALUE; // spkm_assign_dev must come first
     int rc;
     const size_t slab = (size_t)p * 12;
+    ctx->last_acc_form = 0;
     if (n > 0 && s->nnz > 0) {
         if (slab <= ctx->lds_max && slab <= 64 * 1024) {
+            ctx->last_acc_form = 1;
             const int max_items = (int)(n / SEG_POINTS) + K + 1;
             if ((rc = ensure(ctx, ctx->perm, (size_t)n * 4))) return rc;
             if ((rc = ensure(ctx, ctx->offs, (size_t)(K + 1) * 8))) return rc;
@@ -710,6 +714,7 @@ extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t 
                                    (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
                                    (const int*)ctx->nitems.p, p, s->fixed_s, sums, counts);
         } else {
+            ctx->last_acc_form = 2;
             const int blocks = std::max(1, ctx->num_cus) * 8;
             if (s->ir_bits == 16)
                 hipLaunchKernelGGL((k_accumulate_atomic<unsigned short>), dim3(blocks), dim3(256), 0, ctx->stream,
@@ -748,6 +753,7 @@ static int run_distances(spkm_ctx* ctx, const spkm_shard* s, int K, const double
     const size_t fixed_lds = (size_t)p * 20 + 16;
     const bool stream_ok = s->rec && s->fixed_s > 0 && s->fixed_s <= 64 && K <= 16384 &&
                            fixed_lds + (size_t)nw * 16 * per_pt + 1024 <= ctx->lds_max;
+    ctx->last_dist_form = stream_ok ? 1 : 2;
     if (stream_ok) {
         bool have_sort = ctx->sort_owner == (const void*)s && ctx->sort_perm_valid && ctx->sort_K == K && ctx->sort_n == n &&
                          s->hb && s->hb_valid && s->hb_npad == npad;
@@ -933,6 +939,21 @@ extern "C" int spkm_last_events_form(spkm_ctx* ctx, int64_t info[2])
     const bool inc = ctx->last_path == 1 && ctx->last_incremental;
     info[0] = inc ? (ctx->last_direct_events ? 2 : 1) : 0;
     info[1] = (inc && ctx->last_pair_events) ? 1 : 0;
+    return SPKM_OK;
+}
+
+// Launch shapes the host chose last (stored values; does not block): tile width and tile count of the last spkm_assign_dev,
+// the last-tile body of the last screen call's plan, points staged per wave by the last exact pass, the kernels of the last
+// spkm_accumulate_dev and of the last distances call.
+extern "C" int spkm_last_assign_tile(spkm_ctx* ctx, int64_t info[6])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    info[0] = ctx->assign_KT;
+    info[1] = ctx->assign_G;
+    info[2] = ctx->last_path == 1 ? ctx->last_pl_last : 0;
+    info[3] = ctx->last_exact_pts;
+    info[4] = ctx->last_acc_form;
+    info[5] = ctx->last_dist_form;
     return SPKM_OK;
 }
 

@@ -281,6 +281,7 @@ struct screen_call : spkm_call_in {
                            (unsigned long long*)ctx->cmax.p, pl.pl_last, quad ? 1 : 0, (double*)ctx->ct.p,
                            quad ? sm->hb_centers : (double*)nullptr);
         ctx->last_sums_only = false;
+        ctx->last_pl_last = pl.pl_last;
         const size_t lds = (size_t)(p + 1) * (SCREEN_KT * 4 + (pl.pl_last == 5 ? 16 : 0)) + 16;
         const void* kern = quad ? screen_quad_kernel<IR>(pl.nr, pl.prune_a > 0 ? pl.prune_a : pl.nr, pl.pt_mode) : (const void*)k_screen_tile<IR>;
         HIP_TRY(allow_lds(ctx, kern, lds));
@@ -385,6 +386,7 @@ struct screen_call : spkm_call_in {
             hipLaunchKernelGGL(k_pick_form, dim3(1), dim3(1), 0, ctx->stream, (unsigned*)ctx->nlist.p, pl.ev_cap, (int*)ctx->nitems.p);
         double *cache_s = sm->cl_cache, *cache_c = cache_s + pk;
         ctx->last_direct_events = pl.direct;
+        ctx->last_exact_pts = 0; // (no exact pass; a dual call's queued full pass is the pipelined kernel's)
         const int* perm = (const int*)ctx->perm.p;
         const long long* offs = (const long long*)ctx->offs.p;
         const int4* items = (const int4*)ctx->items.p;
@@ -517,6 +519,7 @@ struct screen_call : spkm_call_in {
         if ((rc = ensure_blk_stats(ctx, (size_t)std::max(ab, max_items)))) return rc;
         if (ctx->tlog_both) HIP_TRY(timing_begin(ctx));
         float* ub = (quad && sm->map == nullptr) ? sm->hb : (float*)nullptr; // (a regrouped shard: the certificate wrote them)
+        ctx->last_exact_pts = pl.pipe ? 16 : pts;
         if (pl.pipe) {
             if ((rc = exact_rec<IR>(!pl.sums_only, mind, ub, ab))) return rc;
         } else {

@@ -346,6 +346,15 @@ class LloydEngine:
         _lib.check(_lib.lib().spkm_last_events_form(self.ctx.handle, a))
         return int(a[0]), int(a[1])
 
+    def last_assign_tile(self) -> tuple[int, ...]:
+        """(tile width of the last assign call: 64 / 32 / 16, 0 = generic kernel or K = 1 stream; its tiles; last-tile body
+        of the last screen plan, 5 = carried, 0 = no screen; points staged per wave by the last exact pass, 0 = none;
+        kernel of the last accumulate_step: 1 slab / 2 atomics; kernel of the last distances(): 1 streaming / 2 generic)
+        -- spkm_last_assign_tile."""
+        a = (C.c_int64 * 6)()
+        _lib.check(_lib.lib().spkm_last_assign_tile(self.ctx.handle, a))
+        return tuple(int(v) for v in a)
+
     def iterate(self, centers: torch.Tensor, want_mind: bool = True):
         """One full Lloyd iteration in place on ``centers``; returns the device tensor
         [dff^2, obj^2] (no host sync).  One library call (spkm_lloyd_iter: fused assignment + accumulation, the

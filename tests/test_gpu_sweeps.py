@@ -18,9 +18,22 @@ _SW = max(1, int(_os.environ.get("SPKM_SWEEP", "1")))
 @pytest.mark.parametrize("seed", range(24 * _SW))
 def test_assign_step_random_shapes(gpu_ctx, oracle, seed):
     """spkm_assign_dev (exact kernels): ragged or fixed columns, any K, gamma present or empty."""
+    _assign_step_random_shape(gpu_ctx, oracle, seed)
+
+
+@pytest.mark.parametrize("p", [1279, 5462, 8191])
+@pytest.mark.parametrize("seed", [100, 101, 102, 103])
+def test_assign_step_random_shapes_past_the_lds_limits(gpu_ctx, oracle, seed, p):
+    """the same draws at rows past what a 16-centroid tile holds (1279: the generic kernel), past the 64-KB accumulation
+    slab (5462: atomics) and between the widths the other tests visit (8191); tests/test_gpu_lds_edges.py sits ON the limits"""
+    _assign_step_random_shape(gpu_ctx, oracle, seed, p)
+
+
+def _assign_step_random_shape(gpu_ctx, oracle, seed, p_fixed=None):
     from sparsifiedkmeans_amd.engine import LloydEngine, Shard
     rng = np.random.default_rng(2000 + seed)
     p = int(rng.choice([3, 17, 64, 100, 255, 256, 777, 1024, 1500, 3000]))
+    p = p_fixed or p
     K = int(rng.integers(1, 90))
     n = int(rng.integers(1, 3001))
     s = int(rng.integers(1, min(p, 70) + 1))
@@ -204,9 +217,20 @@ def test_driver_random_options(gpu_ctx, seed):
 def test_screen_equals_exact_kernels_midsize(gpu_ctx, seed, monkeypatch):
     """1e5 .. 6e5 points (many chunks per workgroup, ragged last chunk, every tile / round variant by chance):
     the screen path against the all-exact kernels, every point, bit for bit.  No CPU oracle at this size."""
+    _screen_equals_exact_midsize(gpu_ctx, seed, monkeypatch)
+
+
+@pytest.mark.parametrize("seed", [100, 101, 102])
+def test_screen_equals_exact_kernels_midsize_at_the_widest_screen_tile(gpu_ctx, seed, monkeypatch):
+    """the same at p = 1278, the last row count whose f32 tile fits 160 KB of LDS"""
+    _screen_equals_exact_midsize(gpu_ctx, seed, monkeypatch, 1278)
+
+
+def _screen_equals_exact_midsize(gpu_ctx, seed, monkeypatch, p_fixed=None):
     from sparsifiedkmeans_amd.engine import LloydEngine, Shard
     rng = np.random.default_rng(9000 + seed)
     p = int(rng.choice([64, 128, 256, 512, 1000, 1024]))
+    p = p_fixed or p
     s = int(rng.integers(1, min(64, p) + 1))
     K = int(rng.integers(2, 200))
     n = int(rng.integers(100_000, 600_001))
@@ -297,9 +321,20 @@ def test_lloyd_runs_random_shapes_equal_oracle_every_iteration(gpu_ctx, oracle, 
     """Short Lloyd runs on drawn shapes (n not a multiple of 16 or 64, K with narrow / carried remainders, 1..64
     entries per column): every iteration's assignments and min-distances equal the oracle's for the centres that went
     in, while the library moves through its forms (plain / two-phase / hinted screen, carried bounds) on its own."""
+    _lloyd_run_random_shape(gpu_ctx, oracle, seed)
+
+
+@pytest.mark.parametrize("seed", [100, 101, 102])
+def test_lloyd_runs_at_the_widest_screen_tile_equal_oracle_every_iteration(gpu_ctx, oracle, seed, monkeypatch):
+    """the same at p = 1278, the last row count whose f32 tile fits 160 KB of LDS"""
+    _lloyd_run_random_shape(gpu_ctx, oracle, seed, 1278)
+
+
+def _lloyd_run_random_shape(gpu_ctx, oracle, seed, p_fixed=None):
     from sparsifiedkmeans_amd.engine import LloydEngine, Shard
     rng = np.random.default_rng(9000 + seed)
     p = int(rng.choice([64, 128, 256, 500, 1024]))
+    p = p_fixed or p
     s_ = int(rng.integers(1, min(p, 64) + 1))
     K = int(rng.choice([2, 3, 17, 33, 36, 40, 64, 68, 100]))
     n = int(rng.integers(200, 3000))

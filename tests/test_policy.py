@@ -548,6 +548,44 @@ def test_plan_last_tile(pol):
     assert Call(pol, K=40, quad=False).plan().pl_last == 4                      # the 16-lanes-per-point screen: full tiles
 
 
+@pytest.mark.parametrize("lds", [64 * 1024, 160 * 1024, 144 * 1000 + 8])    # (the last: a size at which the + 16 of the tile formula decides)
+def test_plan_lds_limits_hold_exactly_and_no_launch_asks_for_more_than_the_device_has(pol, lds):
+    """The two LDS comparisons of policy.h, p swept across each limit (and coarsely over 1 .. 9000): pl_last == 5 exactly
+    when the f32 tile with 16 B per row more fits, pipe exactly when centroid + slab + 16 x 16 staged points + 1 KB fit.  The
+    launches those decisions lead to are sized in api_lloyd_fused.inc (`lds =` of the screen, `lds3 =` of the pipelined
+    record kernel, `lds2 =` of k_exact_accumulate), restated here: none asks for more than lds_max -- the exact pass's
+    with the 1 KB its static arrays and alignment are given."""
+    def screen_ok(p, s):                                                  # screen_eligible's two LDS conditions
+        return (p + 1) * 32 * 4 + 16 <= lds and p * 20 + 1024 + 16 * 8 * (s | 1) * 8 <= lds
+
+    lim = (lds - 16) // 144 - 1
+    assert (lim + 1) * 144 + 16 <= lds < (lim + 2) * 144 + 16
+    for p in sorted(set(range(lim - 4, lim + 5)) | set(range(1, 9000, 61))):
+        for K in (66, 100):
+            pl = Call(pol, K=K, p=p, lds_max=lds).plan()
+            assert (pl.pl_last == 5) == ((p + 1) * 144 + 16 <= lds), (p, K)
+            assert pl.pl_last in (1, 5) and pl.Gs == (pl.G - 1 if pl.pl_last == 5 else pl.G)
+            if screen_ok(p, 51):
+                assert (p + 1) * (32 * 4 + (16 if pl.pl_last == 5 else 0)) + 16 <= lds, (p, K)       # `lds =`
+    swept = 0
+    for s in (1, 4, 26, 51, 63, 64):
+        per_pt = (s | 1) * 8
+        lim = (lds - 16 - 1024 - 256 * per_pt) // 20                     # (negative: the 16 x 16 points never fit)
+        for p in sorted(set(range(max(1, lim - 4), max(1, lim) + 5)) | set(range(1, 9000, 61))):
+            pl = Call(pol, p=p, fixed_s=s, lds_max=lds).plan()
+            fits = p * 20 + 16 + 256 * per_pt + 1024 <= lds
+            assert pl.pipe == fits and pl.cl_on == fits, (p, s)
+            assert not Call(pol, p=p, fixed_s=s, lds_max=lds).plan(rec=False).pipe
+            swept += fits and p == lim
+            if pl.pipe:
+                assert p * 20 + 16 + 16 * 16 * per_pt + 1024 <= lds, (p, s)                             # `lds3 =`
+            elif screen_ok(p, s):
+                pts = max(8, min(64, (lds - (p * 20 + 16) - 1024) // 16 // per_pt) & ~7)
+                assert p * 20 + 16 + 16 * pts * per_pt <= lds - 1024 + 16, (p, s, pts)                 # `lds2 =`
+    assert swept >= (5 if lds > 64 * 1024 else 3)                        # (the limit itself was met where there is one)
+    assert not Call(pol, p=64, fixed_s=65, quad=False, lds_max=lds).plan().pipe                      # columns of > 64 entries
+
+
 def test_plan_chunk(pol):
     def chunk(**kw):
         return Call(pol, **kw).plan().chunk
