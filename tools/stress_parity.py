@@ -1,6 +1,10 @@
 """GPU box: randomized parity stress of the fused iteration (screen + carried bounds + point lists + cluster shortcut +
 in-place assignment copy) against the CPU oracle: random shapes, block-ordered and shuffled data, 'sample' starts, every
-iteration's assignment compared bit for bit, distances on demand and centroids at the end.
+iteration's assignment compared bit for bit, distances on demand and centroids at the end.  About one case in four has a
+near-tie ramp (tests/near_ties.py) spliced in between two of its start centres.  (That decision draws from the
+case generator in every case: a seed's sequence of cases is not the one it gave before the ramps were added.  Only the
+ramp's two centroids lie in its value range; the other start centres set Cmax, so a ramp here realises less of the
+screen's error bound than in tests/test_gpu_near_ties.py.)
     python tools/stress_parity.py [seconds] [seed]"""
 import os, sys, time
 import numpy as np, torch
@@ -11,6 +15,7 @@ from oracle import oracle as O
 from sparsifiedkmeans_amd import synth
 from sparsifiedkmeans_amd.engine import LloydEngine, Shard, torch_context
 from util import parts
+import near_ties
 
 O.build()
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -46,9 +51,22 @@ while time.time() < t_end:
     d = np.sign(rng.standard_normal(p)); d[d == 0] = 1
     Y = synth.sparsify_dense(O.mix(X, d, p), s, rng)
     gam = s / p
+    C0 = O.mix(X[:, rng.choice(n, K, replace=True)], d, p) + 1e-3 * rng.standard_normal((p, K))
+    if rng.random() < 0.25 and s >= 2:
+        # about one case in four: a near-tie ramp (tests/near_ties.py: points through the place where two centroids are equally
+        # far, centroid values whose f32 roundings all push one way) between two of the start centres, on its own support,
+        # at the data's scale (a power of two, so that the f32 alignment survives), somewhere among the columns
+        ka, kb = (int(v) for v in rng.choice(K, 2, replace=False))
+        r = near_ties.ramp(p, s, 8, float(rng.choice([0.02, 0.005])), int(rng.integers(1 << 30)), ka, kb, True, K=K,
+                           mirrored=bool(rng.integers(0, 2)))
+        sc = 2.0 ** np.round(np.log2(max(np.median(np.abs(Y.data)), 1e-300) / 1.5))
+        C0[r["rows"], ka], C0[r["rows"], kb] = r["C"][r["rows"], ka] * sc, r["C"][r["rows"], kb] * sc
+        at = int(rng.integers(0, n + 1))
+        Y = sp.hstack([Y[:, :at], r["Y"] * sc, Y[:, at:]]).tocsc()
+        Y.sort_indices()
+        n = Y.shape[1]
     Yones = Y.copy(); Yones.data[:] = 1.0                     # spones(X) (kmeans_sparsified.m:352-355)
     shard = Shard.from_scipy(ctx, Y)
-    C0 = O.mix(X[:, rng.choice(n, K, replace=True)], d, p) + 1e-3 * rng.standard_normal((p, K))
     eng = LloydEngine(shard, K, gam)
     c = torch.tensor(np.ascontiguousarray(C0.T), device="cuda")
     want_mind = bool(rng.integers(0, 2))
