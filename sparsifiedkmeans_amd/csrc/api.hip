@@ -38,6 +38,7 @@ static spkm_switches read_switches()
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
     if (const char* v = getenv("SPKM_X_HINT_CHUNK")) w.x_hint_chunk = atoi(v);   // points per chunk in the two-phase screen launches (default 256)
     if (const char* v = getenv("SPKM_X_PLAIN_CHUNK")) w.x_plain_chunk = atoi(v); // ... in the plain launch (default: n / (8 x teams), at most 4096)
+    if (const char* v = getenv("SPKM_X_CERTIFY_GRID")) w.x_certify_grid = atoi(v); // workgroups of the certification launch (default: one per 256 points, at most 4096)
     return w;
 }
 

@@ -39,6 +39,7 @@ struct spkm_switches {
     bool no_cluster_skip = false; // SPKM_NO_CLUSTER_SKIP: every cluster is planned, placed and streamed in every call
     int x_hint_chunk = 0;         // SPKM_X_HINT_CHUNK: chunk size of the two-phase screen launches (0: the default, 256 points)
     int x_plain_chunk = 0;        // SPKM_X_PLAIN_CHUNK: ... of the plain launch (0: the default)
+    int x_certify_grid = 0;       // SPKM_X_CERTIFY_GRID: at most this many workgroups in k_combine_screen's launch (0: the default, up to 4096)
     bool no_late_split = false;   // SPKM_NO_LATE_SPLIT: the hinted screen always asks after a quarter of the rounds
     bool no_incremental = false;  // SPKM_NO_INCREMENTAL: per-cluster sums are always re-accumulated over every member
     bool no_support_drift = false; // SPKM_NO_SUPPORT_DRIFT: centroid drift by its full 2-norm, not its s largest entries

@@ -326,12 +326,17 @@ struct screen_call : spkm_call_in {
         unsigned long long* nk = pl.nk_incr ? (unsigned long long*)ctx->nk.p : (unsigned long long*)nullptr;
         int *ev_pt = pl.ev_path ? sm->ev_pt : nullptr, *ev_k = pl.ev_path ? sm->ev_k : nullptr, *ev_o = pl.pair_ev ? sm->ev_o : nullptr;
         unsigned long long* nk_ev = pl.ev_path ? (unsigned long long*)ctx->nk_ev.p : (unsigned long long*)nullptr;
-        const int cb = (int)std::min<long long>(4096, (n + 255) / 256); // (8192+: the cold pass gains 6 %, the short lists of a converged run lose 70 %)
-        hipLaunchKernelGGL(k_combine_screen, dim3(cb), dim3(256), ((pl.nk_incr ? (size_t)K : 0) + (pl.ev_path ? (size_t)2 * K : 0)) * 4,
+        // (8192+: the cold pass gains 6 %, the short lists of a converged run lose 70 %; SPKM_X_CERTIFY_GRID: fewer, so that a
+        //  small shard gives a workgroup several trips -- experiments, and the tests of the event stage's flushes)
+        int cb = (int)std::min<long long>(4096, (n + 255) / 256); // (a workgroup of the 4-points-per-thread form beyond the work returns at once)
+        if (ctx->sw.x_certify_grid > 0) cb = std::min(cb, ctx->sw.x_certify_grid);
+        // (4 consecutive points per thread where a trip's points are contiguous)
+        hipLaunchKernelGGL(pl.pt_mode ? k_combine_screen<1> : k_combine_screen<4>, dim3(cb), dim3(256),
+                           ((pl.nk_incr ? (size_t)K : 0) + (pl.ev_path ? (size_t)2 * K : 0)) * 4,
                            ctx->stream, (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, pl.Gs,
                            (const float*)sm->xnr, sm->fixed_s, (const unsigned long long*)ctx->cmax.p, (int*)assign,
                            (int*)ctx->list.p, (unsigned int*)ctx->nlist.p, quad ? sm->hb : (float*)nullptr, pl.npad,
-                           pl.skip_enabled ? 1 : 0, (const int*)ctx->todo.p, pl.pt_mode ? 1 : 0,
+                           pl.skip_enabled ? 1 : 0, (const int*)ctx->todo.p,
                            quad ? (const double*)(sm->hb_cum + sm->cum_par) : (const double*)nullptr, pl.bounds_ok ? 1 : 0,
                            touched, K, nk, pl.lazy_ub ? 1 : 0, ev_pt, ev_k, nk_ev, pl.ev_cap, (unsigned*)ctx->wgstat.p, ev_o,
                            (const int*)sm->map, (pl.trusted && pl.bounds_ok) ? 1 : 0);

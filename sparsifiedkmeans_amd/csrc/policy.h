@@ -345,7 +345,8 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
     pl.prune_a = prune_a;
     pl.rounds_all = in.quad && prune_a > 0 && prune_a < nr ? prune_a : nr;
     // chunk = n / (8 x teams), 256 ..= 4096 points; two-phase launches take 256 (finer grains for workgroups that run at
-    // their own pace: 82.8 -> 84.9 it/s, profiles/r06_exp_hint_chunk.txt); SPKM_X_HINT_CHUNK / SPKM_X_PLAIN_CHUNK: others
+    // their own pace: 82.8 -> 84.9 it/s against SPKM_X_HINT_CHUNK=4096, the size before -- 0 or unset is the 256 of today,
+    // profiles/r06_exp_hint_chunk.txt); SPKM_X_HINT_CHUNK / SPKM_X_PLAIN_CHUNK: others
     const long long sweep = 16 * 16;
     long long chunk = std::max<long long>(sweep, std::min<long long>(n / ((long long)in.teams * 8), 16 * sweep)) / sweep * sweep;
     if (in.quad && prune_a > 0) chunk = std::min<long long>(chunk, in.x_hint_chunk >= sweep ? in.x_hint_chunk : sweep);

@@ -655,12 +655,48 @@ __global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__
     }
 }
 
-// One thread per point, 16-lane groups = the screen's steps.  A step whose points all pass the carried-bounds
+// PPT consecutive points of one array, per thread: ONE 16-byte access where the caller knows that all four exist and that
+// the address is aligned (wide: the same for every lane of the wave, so the branch is a scalar one), else one by one.
+template <int PPT, typename T>
+__device__ __forceinline__ void ld_points(const T* __restrict__ p, size_t at, bool wide, const bool (&in)[PPT], T fill,
+                                          T (&out)[PPT])
+{
+    if constexpr (PPT == 4) {
+        if (wide) {
+            typedef T v4 __attribute__((ext_vector_type(4)));
+            const v4 v = *reinterpret_cast<const v4*>(p + at);
+            out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < PPT; c++) out[c] = in[c] ? p[at + c] : fill;
+}
+// ... and stored: one 16-byte store where all four are written (m), else the ones that are
+template <int PPT, typename T>
+__device__ __forceinline__ void st_points(T* __restrict__ p, size_t at, bool wide, const bool (&m)[PPT], const T (&v)[PPT])
+{
+    if constexpr (PPT == 4) {
+        if (wide && m[0] && m[1] && m[2] && m[3]) {
+            typedef T v4 __attribute__((ext_vector_type(4)));
+            v4 w; w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3];
+            *reinterpret_cast<v4*>(p + at) = w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < PPT; c++) if (m[c]) p[at + c] = v[c];
+}
+
+// 4 consecutive points per thread (16-byte loads of the two bounds and the assignment), 4-lane groups = the screen's
+// steps; a workgroup's trip is a block of 1024 points, and the next block's loads are in flight while this one is tested.
+// A step whose points all pass the carried-bounds
 // test (k_center_drift's comment) is settled here: assignment = the previous one, lower bound moved by the largest
 // drift.  Every other step is appended to todo[] (its index; order within the list does not matter) -- the list
 // the screen kernel and k_combine_screen iterate; counters[4] = length, counters[3] = steps skipped.
 #define BOUNDS_SPAN 16384   // points per workgroup of k_bounds_steps (1024 steps)
 #define BOUNDS_SPAN_PT 4096 // ... when it lists points
+#define BOUNDS_KTAB 1024    // centroids whose drift tables k_bounds_steps keeps in LDS
 // pt_mode: the bounds are applied POINT BY POINT -- a point that passes keeps its assignment (and gets its lower
 // bound moved) whatever its 15 neighbours do, the others are listed one by one, and k_screen_quad / k_combine_screen
 // run over the listed points only.  With the points of a cluster scattered over the shard (data in arbitrary order)
@@ -732,7 +768,18 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     unsigned nskip = 0, nkept = 0;
     if (threadIdx.x == 0) { s_cnt = 0; s_skip = 0; s_kept = 0; }
     __syncthreads();
-    constexpr int UN = 4; // rounds whose (dependent) loads are in flight together
+    constexpr int UN = 4; // consecutive points per thread
+    // delta[k] and hterm[k], gathered by every point's assignment: from LDS (K <= BOUNDS_KTAB), else from global memory
+    __shared__ float s_dk[BOUNDS_KTAB], s_hk[BOUNDS_KTAB];
+    const bool tab = K <= BOUNDS_KTAB;
+    if (tab)
+        for (int k = threadIdx.x; k < K; k += blockDim.x) { s_dk[k] = bnd[3 * npad + k]; s_hk[k] = bnd[3 * npad + HB_HTERM + k]; }
+    __syncthreads();
+    const bool have_cur = skip_enabled && (!MAPPED || assign != nullptr); // the caller's buffer is read (and repaired)
+    // which arrays may take 16-byte accesses at a point index that is a multiple of 4
+    const bool al_bnd = (npad & 3) == 0 && ((reinterpret_cast<size_t>(bnd) | reinterpret_cast<size_t>(hintu)) & 15) == 0;
+    const bool al_as = (reinterpret_cast<size_t>(assign) & 15) == 0;
+    const bool al_map = (reinterpret_cast<size_t>(map) & 15) == 0;
     // a workgroup takes several spans: its list is flushed per span (one global atomic, none for a span that lists
     // nothing), its statistics once at the end (at one span per workgroup the 3-4 same-address atomics of 24000
     // workgroups took longer than the test itself)
@@ -779,102 +826,150 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
         }
     }
     bool span_read = false; // some block of this span took the per-point path (uniform): only then is there a list to flush
-    for (int it0 = 0; it0 < span / 256; it0 += UN) {
-        if (span0 + it0 * 256 >= npad) break; // npad: whole waves
+    // a 1024-point block of the span: 0 = past the end, 1 = passes as a block (nothing of it is read), 2 = point by point
+    // (the same answer for every thread of the workgroup: uniform branches)
+    auto blk_state = [&](int it0) -> int {
+        if (it0 >= span / 256 || span0 + (long long)it0 * 256 >= npad) return 0; // npad: whole waves
+        if (sp_on && !sp_reset) {
+            const int slot = span_i * nbs + (it0 >> 2);
+            if (slot < 256 ? s_pass[slot] : block_passes((span0 + (long long)it0 * 256) >> 10)) return 1;
+        }
+        return 2;
+    };
+    // a thread's 4 consecutive points of a block: upper bound, stored lower bound, assignment and what the caller's buffer
+    // holds now (fetched with the rest: behind the test it would be a second memory round trip; a point that keeps its
+    // assignment is stored only if the buffer differs) -- four 16-byte loads where all 64 lanes have their four points
+    auto fetch = [&](int it0, float (&ub)[UN], float (&lb)[UN], int (&ap)[UN], int (&cur)[UN]) {
+        const long long i0 = span0 + (long long)it0 * 256 + UN * (long long)threadIdx.x;
+        bool in[UN], inc[UN];
+#pragma unroll
+        for (int c = 0; c < UN; c++) { in[c] = i0 + c < n; inc[c] = in[c] && have_cur; }
+        const bool wide = al_bnd && __all(i0 + (UN - 1) < n);
+        ld_points<UN>((const float*)bnd, (size_t)i0, wide, in, 0.f, ub);
+        ld_points<UN>((const float*)bnd + npad, (size_t)i0, wide, in, 0.f, lb);
+        ld_points<UN>(reinterpret_cast<const int*>(bnd) + 2 * npad, (size_t)i0, wide, in, 0, ap);
+        if (MAPPED) {
+            int mp[UN];
+            ld_points<UN>(map, (size_t)i0, wide && al_map && have_cur, inc, 0, mp);
+#pragma unroll
+            for (int c = 0; c < UN; c++) cur[c] = inc[c] ? assign[mp[c]] : 0;
+        } else
+            ld_points<UN>((const int*)assign, (size_t)i0, wide && al_as && have_cur, inc, 0, cur);
+    };
+    float ubn_[UN], lbn_[UN];
+    int apn_[UN], curn_[UN]; // the next block to read, in flight while this one is tested
+    int st = blk_state(0);
+    if (st == 2) fetch(0, ubn_, lbn_, apn_, curn_);
+    for (int it0 = 0; st != 0; it0 += UN) {
         const long long blk0 = span0 + (long long)it0 * 256;
         const long long bsp = blk0 >> 10;
-        if (sp_on && !sp_reset) { // (the same word for every thread of the workgroup: a uniform branch)
-            const int slot = span_i * nbs + (it0 >> 2);
-            if (slot < 256 ? s_pass[slot] : block_passes(bsp)) { // every point of the block passes
-                if (blk0 + 1024 <= n) { // (a whole block: every wave has 4 x 64 points, 4 x 4 steps of it -- a uniform, scalar test:
-                    nkept += 256u;      //  per-lane 64-bit arithmetic here was 70 of the kernel's 100 us at N = 1e8)
-                    nskip += 16u;
-                } else {
-#pragma unroll
-                    for (int u = 0; u < UN; u++) {
-                        const long long live = n - (blk0 + u * 256 + (long long)(threadIdx.x & ~63)); // points of this wave's 64 that exist
-                        nkept += (unsigned)(live <= 0 ? 0 : (live >= 64 ? 64 : live));
-                        nskip += (unsigned)(live <= 0 ? 0 : (live >= 64 ? 4 : (live + 15) / 16));
-                    }
-                }
-                continue;
+        const int st_now = st;
+        st = blk_state(it0 + UN);
+        if (st_now == 1) { // every point of the block passes
+            if (blk0 + 1024 <= n) { // (a whole block: every wave has 4 x 64 points, 4 x 4 steps of it -- a uniform, scalar test:
+                nkept += 256u;      //  per-lane 64-bit arithmetic here was 70 of the kernel's 100 us at N = 1e8)
+                nskip += 16u;
+            } else {
+                const long long live = n - (blk0 + UN * (long long)(threadIdx.x & ~63)); // points of this wave's 256 that exist
+                nkept += (unsigned)(live <= 0 ? 0 : (live >= 64 * UN ? 64 * UN : live));
+                nskip += (unsigned)(live <= 0 ? 0 : (live >= 64 * UN ? 4 * UN : (live + 15) / 16));
             }
+            if (st == 2) fetch(it0 + UN, ubn_, lbn_, apn_, curn_);
+            continue;
         }
         span_read = true;
         float ubv[UN], lbv[UN], dav[UN];
         int apv[UN], curv[UN];
+#pragma unroll
+        for (int c = 0; c < UN; c++) { ubv[c] = ubn_[c]; lbv[c] = lbn_[c]; apv[c] = apn_[c]; curv[c] = curn_[c]; }
+        if (st == 2) fetch(it0 + UN, ubn_, lbn_, apn_, curn_);
+        const long long i0 = blk0 + UN * (long long)threadIdx.x;
+        bool in[UN];
+#pragma unroll
+        for (int c = 0; c < UN; c++) in[c] = i0 + c < n;
+        const bool wide = al_bnd && __all(i0 + (UN - 1) < n);
         bool blk_kept = true;          // sp_on: every point of the block passed
         float tmin = __builtin_inff(); // ... and the smallest slack among them
         unsigned bm0 = 0u, bm1 = 0u, bm2 = 0u, bm3 = 0u;
 #pragma unroll
-        for (int u = 0; u < UN; u++) {
-            const long long i = span0 + (it0 + u) * 256 + threadIdx.x;
-            const bool in = i < n;
-            ubv[u] = in ? bnd[i] : 0.f;
-            lbv[u] = in ? bnd[npad + i] : 0.f;
-            apv[u] = in ? reinterpret_cast<const int*>(bnd)[2 * npad + i] : 0;
-            // what the caller's buffer holds now, fetched with the rest (behind the test it would be a second memory
-            // round trip per group): a point that keeps its assignment is stored only if the buffer differs
-            if (MAPPED) curv[u] = (in && skip_enabled && assign != nullptr) ? assign[map[i]] : apv[u];
-            else curv[u] = (in && skip_enabled) ? assign[i] : 0;
-        }
+        // (the stored assignment of EVERY point indexes the tables, not only of the listed ones: it lies in [0, K) whenever
+        //  this kernel runs -- the bounds are valid only after a call that wrote the library's copy for every point; 0 past n)
+        for (int c = 0; c < UN; c++) dav[c] = tab ? s_dk[apv[c]] : bnd[3 * npad + apv[c]];
+        float hv[UN] = {0.f, 0.f, 0.f, 0.f}; // the hints (where one is written)
+        if (hintu != nullptr) {
 #pragma unroll
-        for (int u = 0; u < UN; u++) dav[u] = bnd[3 * npad + apv[u]];
-        if (hintu != nullptr && !skip_enabled) { // (with the test on, only the points that stay on the screen get a hint: below)
-#pragma unroll
-            for (int u = 0; u < UN; u++) {
-                const long long i = span0 + (it0 + u) * 256 + threadIdx.x;
-                if (i < n) hintu[i] = sqrtf(ubv[u] * ubv[u] + bnd[3 * npad + HB_HTERM + apv[u]]);
-            }
+            for (int c = 0; c < UN; c++) hv[c] = sqrtf(ubv[c] * ubv[c] + (tab ? s_hk[apv[c]] : bnd[3 * npad + HB_HTERM + apv[c]]));
         }
+        if (hintu != nullptr && !skip_enabled) // (with the test on, only the points that stay on the screen get a hint: below)
+            st_points<UN>(hintu, (size_t)i0, wide, in, hv);
         if (!skip_enabled) continue;
+        bool keep[UN], st_er[UN];
+        float ubn[UN];
+        unsigned long long b[UN];
 #pragma unroll
-        for (int u = 0; u < UN; u++) {
-            const long long i = span0 + (it0 + u) * 256 + threadIdx.x;
-            if (span0 + (it0 + u) * 256 >= npad) break;
-            const bool keep = !(i < n) || (double)(ubv[u] + dav[u]) * 1.000001 < ((double)lbv[u] - cum_now) * 0.999999; // false for NaN
-            const unsigned long long b = __ballot(keep);
-            nkept += (unsigned)__popcll(__ballot(keep && i < n));
-            const float ubn = (erode && dav[u] > 0.f) ? __double2float_ru((double)ubv[u] + (double)dav[u]) : ubv[u]; // Hamerly's update
-            if (erode && keep && i < n && dav[u] > 0.f) bnd[i] = ubn;
-            if (sp_on && i < n) {
-                blk_kept = blk_kept && keep;
-                tmin = fminf(tmin, __double2float_rd((double)lbv[u] * 0.999999 - (double)ubn * 1.000001));
-                const unsigned bit = 1u << (apv[u] & 31);
-                const int w = apv[u] >> 5;
+        for (int c = 0; c < UN; c++) {
+            keep[c] = !in[c] || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_now) * 0.999999; // false for NaN
+            b[c] = __ballot(keep[c]);
+            nkept += (unsigned)__popcll(__ballot(keep[c] && in[c]));
+            ubn[c] = (erode && dav[c] > 0.f) ? __double2float_ru((double)ubv[c] + (double)dav[c]) : ubv[c]; // Hamerly's update
+            st_er[c] = erode && keep[c] && in[c] && dav[c] > 0.f;
+            if (sp_on && in[c]) {
+                blk_kept = blk_kept && keep[c];
+                tmin = fminf(tmin, __double2float_rd((double)lbv[c] * 0.999999 - (double)ubn[c] * 1.000001));
+                const unsigned bit = 1u << (apv[c] & 31);
+                const int w = apv[c] >> 5;
                 bm0 |= w == 0 ? bit : 0u; bm1 |= w == 1 ? bit : 0u; bm2 |= w == 2 ? bit : 0u; bm3 |= w == 3 ? bit : 0u;
             }
-            if (pt_mode) {
-                if (keep && i < n && curv[u] != apv[u]) assign[MAPPED ? (long long)map[i] : i] = apv[u]; // (see the step mode below)
-                if (!keep && hintu != nullptr) hintu[i] = sqrtf(ubv[u] * ubv[u] + bnd[3 * npad + HB_HTERM + apv[u]]);
-                const unsigned long long lm = ~b; // (lanes past n count as kept)
-                if (lm) {
-                    unsigned basepos = 0;
-                    if (lane == 0) basepos = atomicAdd(&s_cnt, (unsigned)__popcll(lm));
-                    basepos = __builtin_amdgcn_readfirstlane(basepos);
-                    if (!keep) s_todo[basepos + __popcll(lm & ((1ull << lane) - 1ull))] = (int)i;
-                }
-                // (statistics in the same unit as the other mode: steps whose 16 points all passed)
-                const bool whole = ((unsigned)(b >> (lane & 48)) & 0xffffu) == 0xffffu;
-                nskip += (unsigned)__popcll(__ballot((lane & 15) == 0 && (i - (lane & 15)) < n && whole));
-                continue;
+        }
+        if (erode) st_points<UN>(bnd, (size_t)i0, wide, st_er, ubn);
+        // a step is 16 / UN neighbouring lanes
+        constexpr int LPS = 16 / UN;
+        const unsigned long long bq = __ballot(keep[0] && keep[1] && keep[2] && keep[3]);
+        const bool whole = ((unsigned)(bq >> (lane & ~(LPS - 1))) & ((1u << LPS) - 1u)) == (1u << LPS) - 1u; // all 16 points of the step pass
+        const bool live_step = (i0 - UN * (lane & (LPS - 1))) < n; // the step has at least one point
+        const bool lead_lane = (lane & (LPS - 1)) == 0 && live_step;
+        if (pt_mode) {
+            unsigned long long lm[UN];
+            unsigned tot = 0;
+#pragma unroll
+            for (int c = 0; c < UN; c++) {
+                if (keep[c] && in[c] && have_cur && curv[c] != apv[c]) assign[MAPPED ? (long long)map[i0 + c] : i0 + c] = apv[c]; // (see the step mode below)
+                if (!keep[c] && hintu != nullptr) hintu[i0 + c] = hv[c];
+                lm[c] = ~b[c]; // (lanes past n count as kept)
+                tot += (unsigned)__popcll(lm[c]);
             }
-            const unsigned grp = (unsigned)(b >> (lane & 48)) & 0xffffu;
-            const bool skip = grp == 0xffffu;
-            const bool live_step = (i - (lane & 15)) < n; // the step has at least one point
-            // a caller that passes the same buffer call after call already holds this value: a 4-B read instead of a
-            // 4-B store (a gigabyte of stores costs as much as several of loads here)
-            if (skip && i < n && curv[u] != apv[u]) assign[MAPPED ? (long long)map[i] : i] = apv[u];
-            if (!skip && i < n && hintu != nullptr) hintu[i] = sqrtf(ubv[u] * ubv[u] + bnd[3 * npad + HB_HTERM + apv[u]]);
-            const bool lead = (lane & 15) == 0 && live_step && !skip;
+            if (tot) {
+                unsigned basepos = 0;
+                if (lane == 0) basepos = atomicAdd(&s_cnt, tot);
+                basepos = __builtin_amdgcn_readfirstlane(basepos);
+#pragma unroll
+                for (int c = 0; c < UN; c++) {
+                    if (!keep[c]) s_todo[basepos + __popcll(lm[c] & ((1ull << lane) - 1ull))] = (int)(i0 + c);
+                    basepos += (unsigned)__popcll(lm[c]);
+                }
+            }
+            // (statistics in the same unit as the other mode: steps whose 16 points all passed)
+            nskip += (unsigned)__popcll(__ballot(lead_lane && whole));
+        } else {
+            const bool skip = whole;
+            bool st_h[UN];
+#pragma unroll
+            for (int c = 0; c < UN; c++) {
+                // a caller that passes the same buffer call after call already holds this value: a 4-B read instead of a
+                // 4-B store (a gigabyte of stores costs as much as several of loads here)
+                if (skip && in[c] && have_cur && curv[c] != apv[c]) assign[MAPPED ? (long long)map[i0 + c] : i0 + c] = apv[c];
+                st_h[c] = !skip && in[c] && hintu != nullptr;
+            }
+            if (hintu != nullptr) st_points<UN>(hintu, (size_t)i0, wide, st_h, hv);
+            const bool lead = lead_lane && !skip;
             const unsigned long long lm = __ballot(lead);
             if (lm) {
                 unsigned basepos = 0;
                 if (lane == 0) basepos = atomicAdd(&s_cnt, (unsigned)__popcll(lm));
                 basepos = __builtin_amdgcn_readfirstlane(basepos);
-                if (lead) s_todo[basepos + __popcll(lm & ((1ull << lane) - 1ull))] = (int)(i >> 4);
+                if (lead) s_todo[basepos + __popcll(lm & ((1ull << lane) - 1ull))] = (int)(i0 >> 4);
             }
-            nskip += (unsigned)__popcll(__ballot((lane & 15) == 0 && live_step && skip));
+            nskip += (unsigned)__popcll(__ballot(lead_lane && skip));
         }
         if (sp_on) { // the block's new summary (every thread of the workgroup is here: the trip counts are uniform)
             for (int off = 32; off > 0; off >>= 1) {
@@ -1098,6 +1193,14 @@ __global__ void k_zero_u64_gated(unsigned long long* __restrict__ dst, int n, co
 // Per point: best / second-best estimate over the G tiles, certification, candidate assignment.
 // Uncertified points are appended to list[] (count in *nlist); a tile that reports "no candidate"
 // (+inf, +inf, -1) can never certify.
+// PPT = 4 (calls over all points and step lists: the points of a thread's trip are contiguous): a thread takes 4 CONSECUTIVE
+// points -- a quarter of a listed step -- and fetches each result plane, xnr and the library's assignment with one 16-byte load
+// apiece, all of them issued before the first is used; a wave's trip is 16 steps.  The planes lie n floats apart, so they take
+// the wide loads when n is a multiple of 4 (and the caller's buffer when it is 16-byte aligned); any other shard, and the
+// last points of a shard, go one point at a time through the same code.  PPT = 1 (point lists): one point per lane, its
+// planes by list slot, everything else through the list.  A regrouped shard (map) keeps the wide loads of the library's
+// arrays; what it writes to the caller's buffer is scattered point by point.
+template <int PPT>
 __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict__ scr_m1,
                                                         const float* __restrict__ scr_m2,
                                                         const int* __restrict__ scr_k, long long n, int G,
@@ -1106,7 +1209,7 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
                                                         int* __restrict__ assign, int* __restrict__ list,
                                                         unsigned int* __restrict__ nlist,
                                                         float* __restrict__ bnd, long long npad, int skipping,
-                                                        const int* __restrict__ todo, int pt_mode,
+                                                        const int* __restrict__ todo,
                                                         const double* __restrict__ cum, int lib_valid,
                                                         int* __restrict__ touched, int K,
                                                         unsigned long long* __restrict__ nk,
@@ -1141,9 +1244,15 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     // one global atomic per ~1500 (half the points move in a run's first iterations: an atomic per wave on one address
     // would take tens of milliseconds).  nlist[14] counts the movers in every mode, nlist[16] the events.
     constexpr int EVCAP = 2048;
+    // a wave stages at most 64 lanes x PPT points x 2 events per trip: all four waves' reservations fit the empty stage, so a
+    // wave that retries after a flush cannot fail for ever
+    static_assert(4 * 64 * PPT * 2 <= EVCAP, "the four waves' events of one trip must fit the empty stage");
     __shared__ int s_evp[EVCAP], s_evk[EVCAP];
     const bool pair = ev_o != nullptr; // (staged as new | (old + 1) << 16 in s_evk: pair events are for K <= 128)
-    __shared__ unsigned s_evn, s_evbase, s_mov, s_over; // s_over: the running event count has passed ev_cap -- this workgroup stops collecting events
+    // s_evn: slots of the stage handed out; s_valid: the first slot NOT filled (the start of the first reservation that did
+    // not fit); s_done: waves past their last trip; s_over: the running event count has passed ev_cap -- this workgroup stops
+    // collecting events
+    __shared__ unsigned s_evn, s_evbase, s_mov, s_over, s_valid, s_done;
     const double cum_now = cum ? *cum : 0.0; // lower bounds are stored relative to the accumulated drift (k_bounds_steps)
     // The library's own copy of the assignment (bnd + 2 npad) is kept up to date here and in k_assign_list -- the only
     // two places an assignment can change: a CERTIFIED point's new cluster is written at once; an uncertified one keeps
@@ -1168,121 +1277,221 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     const double nu = 0x1p-45;
     unsigned nambig = 0;
     // skipping: k_bounds_steps has settled the skipped steps; only the listed ones (nlist[4] of them) are looked at
-    const long long total = skipping ? (pt_mode ? (long long)nlist[4] : (long long)nlist[4] * 16) : n;
+    // PPT = 1 IS the point-list form (the template argument alone says how todo[] is read: no second flag to disagree with it)
+    const bool by_slot = PPT == 1 && skipping;
+    const long long total = skipping ? (by_slot ? (long long)nlist[4] : (long long)nlist[4] * 16) : n;
+    constexpr int WGP = 256 * PPT; // points of a workgroup's trip
     __shared__ unsigned s_amb, s_chg, s_hom;
-    if ((long long)blockIdx.x * blockDim.x >= total) { // (whole workgroup)
+    if ((long long)blockIdx.x * WGP >= total) { // (whole workgroup)
         if (threadIdx.x == 0) { wgstat[4 * blockIdx.x] = 0u; wgstat[4 * blockIdx.x + 1] = 0u; wgstat[4 * blockIdx.x + 2] = 0u; wgstat[4 * blockIdx.x + 3] = 0u; }
         return;
     }
-    if (threadIdx.x == 0) { s_amb = 0u; s_chg = 0u; s_evn = 0u; s_mov = 0u; s_over = 0u; s_hom = 0u; }
+    if (threadIdx.x == 0) { s_amb = 0u; s_chg = 0u; s_evn = 0u; s_mov = 0u; s_over = 0u; s_hom = 0u; s_valid = 0xffffffffu; s_done = 0u; }
     if (nk) for (int k = threadIdx.x; k < K; k += blockDim.x) delta[k] = 0;
     if (ev_pt) for (int k = threadIdx.x; k < (pair ? K : 2 * K); k += blockDim.x) evc[k] = 0u;
     __syncthreads();
     unsigned nmov = 0, nhomog = 0;
-    auto flush_events = [&]() { // (whole workgroup)
-        if (threadIdx.x == 0) { s_evbase = atomicAdd(nlist + 16, s_evn); if (s_evbase > ev_cap) s_over = 1u; }
+    const int ln = threadIdx.x & 63;
+    const unsigned long long lt = (1ull << ln) - 1ull; // the lanes below this one
+    // which arrays may take 16-byte accesses at a point index that is a multiple of 4
+    const bool al_pl = PPT == 4 && (n & 3) == 0 &&
+                       ((reinterpret_cast<size_t>(scr_m1) | reinterpret_cast<size_t>(scr_m2) | reinterpret_cast<size_t>(scr_k)) & 15) == 0;
+    const bool al_lib = PPT == 4 && (npad & 3) == 0 && ((reinterpret_cast<size_t>(bnd) | reinterpret_cast<size_t>(xnr)) & 15) == 0;
+    const bool al_as = PPT == 4 && map == nullptr && (reinterpret_cast<size_t>(assign) & 15) == 0;
+    const bool al_map = PPT == 4 && (reinterpret_cast<size_t>(map) & 15) == 0;
+    // The events of a workgroup are staged in LDS WITHOUT a barrier per trip: a wave reserves the slots of its movers with one
+    // LDS atomic (slot within the wave: ballot + popcount) and fills them.  A reservation that does not fit is void: the wave
+    // notes where it began (s_valid: every slot below the first void reservation is filled or being filled by a wave on its
+    // way here) and calls the workgroup together.  The others learn of it from their own next reservation -- every wave makes
+    // one per trip, of 0 slots when nothing moved, and s_evn stays past the capacity until the flush resets it -- and a wave
+    // past its last trip waits in the same place (flush_events below), so the barriers pair up whatever trip a wave is in:
+    // every barrier of this kernel between the start and the closing one is one of the four in flush_events, and a wave enters flush_events only
+    // (a) on a void reservation or (b) after its last trip, again and again until all four waves have counted themselves done.
+    // One global atomic per flush; the order of the events in the global arrays is arbitrary, no result depends on it.
+    // Returns bit 0: s_over (the same for every wave: it changes only here, between barriers); bit 1: every wave is done.
+    auto flush_events = [&]() -> unsigned { // (whole workgroup)
+        __syncthreads(); // nobody stages from here to the last barrier; every filled slot is visible
+        const unsigned nst = min(s_evn, s_valid);
+        const unsigned done = s_done;
+        if (threadIdx.x == 0 && nst) { s_evbase = atomicAdd(nlist + 16, nst); if (s_evbase > ev_cap) s_over = 1u; }
         __syncthreads();
-        if (s_evbase <= ev_cap)
-            for (unsigned j = threadIdx.x; j < s_evn; j += blockDim.x) {
+        if (nst && s_evbase <= ev_cap)
+            for (unsigned j = threadIdx.x; j < nst; j += blockDim.x) {
                 ev_pt[s_evbase + j] = s_evp[j];
                 const int kv = s_evk[j];
                 ev_k[s_evbase + j] = pair ? (kv & 0xffff) : kv;
                 if (pair) ev_o[s_evbase + j] = (kv >> 16) - 1;
             }
+        const unsigned ov = s_over;
         __syncthreads();
-        if (threadIdx.x == 0) s_evn = 0u;
+        if (threadIdx.x == 0) { s_evn = 0u; s_valid = 0xffffffffu; }
         __syncthreads();
+        return (ov ? 1u : 0u) | (done == blockDim.x / 64 ? 2u : 0u);
     };
-    for (long long q0 = (long long)blockIdx.x * blockDim.x; q0 < total; q0 += (long long)gridDim.x * blockDim.x) {
-      const long long q = q0 + threadIdx.x;
-      bool mover = false;
-      int mv_old = -1, mv_new = 0, mine_k = -1;
-      long long i = n;
-      if (q < total) i = skipping ? (pt_mode ? (long long)todo[q] : (long long)todo[q >> 4] * 16 + (q & 15)) : q;
-      if (i < n) {
-        float b1 = __builtin_inff(), b2 = __builtin_inff();
-        int bk = -1;
-        for (int g = 0; g < G; g++) {
-            const size_t at = (size_t)g * n + (size_t)((skipping && pt_mode) ? q : i); // (point lists: stored by list slot)
-            const float m1 = scr_m1[at], m2 = scr_m2[at];
-            const int k = scr_k[at];
-            // m1 = estimate of the tile's leader, m2 = a LOWER bound of every other centroid of the tile (the
-            // second smallest estimate, or with the two-phase screen the second smallest partial sum -- which
-            // can lie below m1): every m2 and every m1 but the best one bound the competition from below
-            if (m1 < b1) { b2 = fminf(b2, b1); b1 = m1; bk = k; }
-            else { b2 = fminf(b2, m1); }
-            b2 = fminf(b2, m2);
-        }
-        const double E = eu * ((double)xnr[i] + sqrt_s * cmax) * (1.0 + 1e-9) * (1.0 + 1e-9); // eu sqrt(W), W as in the header
+    bool over = false; // s_over, as of this wave's last flush
+    // EVERY wave must reach the reservation at the end of the trip in EVERY trip while !over (no early `continue`, no
+    // wave-dependent exit): it is how a wave learns that the workgroup has to flush, and a wave that skipped it would leave
+    // the others waiting at flush_events' first barrier.  `over` changes only on return from flush_events, for all four waves.
+    for (long long q0 = (long long)blockIdx.x * WGP; q0 < total; q0 += (long long)gridDim.x * WGP) {
+      const long long q = q0 + (long long)threadIdx.x * PPT;
+      long long i0 = n; // this thread's first point
+      if (q < total) i0 = skipping ? (by_slot ? (long long)todo[q] : (long long)todo[q >> 4] * 16 + (q & 15)) : q;
+      bool in[PPT];
+#pragma unroll
+      for (int c = 0; c < PPT; c++) in[c] = i0 + c < n;
+      // (all 64 lanes have their four points: the loads of this trip are 16-byte ones where the array allows it)
+      const bool wide = PPT == 4 && __all(i0 + 3 < n);
+      const size_t pat = (size_t)(by_slot ? q : i0); // (point lists: stored by list slot)
+      float xn[PPT];
+      int old[PPT], mp[PPT];
+      ld_points<PPT>(xnr, (size_t)i0, wide && al_lib, in, 0.f, xn);
+      bool in_old[PPT], in_map[PPT];
+#pragma unroll
+      for (int c = 0; c < PPT; c++) { in_old[c] = in[c] && alib && lib_valid; in_map[c] = in[c] && map != nullptr; }
+      ld_points<PPT>((const int*)alib, (size_t)i0, wide && al_lib && alib && lib_valid, in_old, -1, old);
+      ld_points<PPT>(map, (size_t)i0, wide && al_map && map != nullptr, in_map, 0, mp);
+      float b1[PPT], b2[PPT];
+      int bk[PPT];
+#pragma unroll
+      for (int c = 0; c < PPT; c++) { b1[c] = __builtin_inff(); b2[c] = __builtin_inff(); bk[c] = -1; }
+      for (int g0 = 0; g0 < G; g0 += 4) { // (four planes' loads in flight together: all of them at K <= 128)
+          float m1[4][PPT], m2[4][PPT];
+          int kk[4][PPT];
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+              if (g0 + j < G) {
+                  const size_t at = (size_t)(g0 + j) * n + pat;
+                  ld_points<PPT>(scr_m1, at, wide && al_pl, in, 0.f, m1[j]);
+                  ld_points<PPT>(scr_m2, at, wide && al_pl, in, 0.f, m2[j]);
+                  ld_points<PPT>(scr_k, at, wide && al_pl, in, 0, kk[j]);
+              }
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+              if (g0 + j < G) {
+#pragma unroll
+                  for (int c = 0; c < PPT; c++) {
+                      // m1 = estimate of the tile's leader, m2 = a LOWER bound of every other centroid of the tile (the
+                      // second smallest estimate, or with the two-phase screen the second smallest partial sum -- which
+                      // can lie below m1): every m2 and every m1 but the best one bound the competition from below
+                      if (m1[j][c] < b1[c]) { b2[c] = fminf(b2[c], b1[c]); b1[c] = m1[j][c]; bk[c] = kk[j][c]; }
+                      else { b2[c] = fminf(b2[c], m1[j][c]); }
+                      b2[c] = fminf(b2[c], m2[j][c]);
+                  }
+              }
+      }
+      bool mover[PPT], unc[PPT], st_as[PPT], st_al[PPT], st_ub[PPT], st_lb[PPT];
+      int mv_old[PPT], newk[PPT];
+      float ubn[PPT], lbn[PPT];
+#pragma unroll
+      for (int c = 0; c < PPT; c++) {
+        mover[c] = false; unc[c] = false; mv_old[c] = -1; newk[c] = -1;
+        st_as[c] = st_al[c] = st_ub[c] = st_lb[c] = false;
+        ubn[c] = 0.f; lbn[c] = 0.f;
+        if (in[c]) {
+          const double E = eu * ((double)xn[c] + sqrt_s * cmax) * (1.0 + 1e-9) * (1.0 + 1e-9); // eu sqrt(W), W as in the header
 
-        const double r1 = sqrt((double)b1), r2 = sqrt((double)b2);
-        const double e1 = E + gacc * r1 + 1e-20, e2 = E + gacc * r2 + 1e-20;
-        const bool certified = (bk >= 0) && ((r1 + e1) * (1.0 + nu) < (r2 - e2) * (1.0 - nu));
-        const int newk = bk >= 0 ? bk : 0;
-        const long long ic = map != nullptr ? (long long)map[i] : i; // the caller's index of this point
-        const int old = (alib && lib_valid) ? alib[i] : -1;
-        if (!(trusted && lib_valid) || old != newk) assign[ic] = newk; // (the caller's buffer; tentative for an uncertified point)
-        mine_k = newk;
-        if (alib && certified) {
-            if (old != newk) {
-                alib[i] = newk;
-                if (lib_valid) {
-                    changed = true;
-                    const bool vo = (unsigned)old < (unsigned)K;
-                    if (touched) { if (vo) touched[old] = 1; touched[newk] = 1; }
-                    if (nk) { if (vo) atomicAdd(&delta[old], -1); atomicAdd(&delta[newk], 1); }
-                    mover = true; mv_old = vo ? old : -1; mv_new = newk;
-                    nmov++;
-                }
-            }
+          const double r1 = sqrt((double)b1[c]), r2 = sqrt((double)b2[c]);
+          const double e1 = E + gacc * r1 + 1e-20, e2 = E + gacc * r2 + 1e-20;
+          const bool certified = (bk[c] >= 0) && ((r1 + e1) * (1.0 + nu) < (r2 - e2) * (1.0 - nu));
+          newk[c] = bk[c] >= 0 ? bk[c] : 0;
+          st_as[c] = !(trusted && lib_valid) || old[c] != newk[c]; // (the caller's buffer; tentative for an uncertified point)
+          if (alib && certified) {
+              if (old[c] != newk[c]) {
+                  st_al[c] = true;
+                  if (lib_valid) {
+                      changed = true;
+                      const bool vo = (unsigned)old[c] < (unsigned)K;
+                      if (touched) { if (vo) touched[old[c]] = 1; touched[newk[c]] = 1; }
+                      if (nk) { if (vo) atomicAdd(&delta[old[c]], -1); atomicAdd(&delta[newk[c]], 1); }
+                      mover[c] = true; mv_old[c] = vo ? old[c] : -1;
+                      nmov++;
+                  }
+              }
+          }
+          if (lazy && certified && bnd) { st_ub[c] = true; ubn[c] = __double2float_ru((r1 + e1) * (1.0 + nu) * (1.0 + 1e-12)); }
+          if (lbv) { st_lb[c] = true; lbn[c] = __double2float_rd((certified ? fmax(0.0, (r2 - e2) * (1.0 - nu)) : 0.0) + cum_now); }
+          unc[c] = !certified;
+          // nlist[1]: points whose runner-up is within 2.25x of the winner -- the ones a partial-sum lower bound (a
+          // quarter of the rounds: 5x in the squares leaves a margin)
+          // could not separate; the host decides from this count whether the next call may use the two-phase screen
+          if (!(r2 >= 2.25 * r1)) nambig++;
         }
-        if (lazy && certified && bnd) bnd[i] = __double2float_ru((r1 + e1) * (1.0 + nu) * (1.0 + 1e-12));
-        if (lbv) lbv[i] = __double2float_rd((certified ? fmax(0.0, (r2 - e2) * (1.0 - nu)) : 0.0) + cum_now);
-        if (!certified) {
-            // one atomic per wave, not per point: atomics on one address are served one after the other (~12 ns each --
-            // 30 000 uncertified points of a cold iteration cost more than the rest of this kernel)
-            const unsigned long long um = __ballot(1);
-            const int ln = threadIdx.x & 63;
-            unsigned at = 0;
-            if (ln == __builtin_ctzll(um)) at = atomicAdd(nlist, (unsigned)__popcll(um));
-            at = (unsigned)__builtin_amdgcn_readlane((int)at, __builtin_ctzll(um));
-            list[at + __popcll(um & ((1ull << ln) - 1ull))] = (int)i;
+      }
+      if (map != nullptr) { // the caller's index of each point: scattered
+#pragma unroll
+          for (int c = 0; c < PPT; c++) if (st_as[c]) assign[mp[c]] = newk[c];
+      } else
+          st_points<PPT>(assign, (size_t)i0, wide && al_as, st_as, newk);
+      if (alib) st_points<PPT>(alib, (size_t)i0, wide && al_lib, st_al, newk);
+      if (bnd) st_points<PPT>(bnd, (size_t)i0, wide && al_lib, st_ub, ubn);
+      if (lbv) st_points<PPT>(lbv, (size_t)i0, wide && al_lib, st_lb, lbn);
+      { // uncertified points: one global atomic per wave and trip, not per point -- atomics on one address are served one
+        // after the other (~12 ns each: 30 000 uncertified points of a cold iteration cost more than the rest of this kernel)
+          unsigned long long um[PPT];
+          unsigned tot = 0;
+#pragma unroll
+          for (int c = 0; c < PPT; c++) { um[c] = __ballot(unc[c]); tot += (unsigned)__popcll(um[c]); }
+          if (tot) {
+              unsigned at = 0;
+              if (ln == 0) at = atomicAdd(nlist, tot);
+              at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
+#pragma unroll
+              for (int c = 0; c < PPT; c++) {
+                  if (unc[c]) list[at + __popcll(um[c] & lt)] = (int)(i0 + c);
+                  at += (unsigned)__popcll(um[c]);
+              }
+          }
+      }
+      if (!skipping) { // (q = i: a 16-point step is 16 / PPT neighbouring lanes)
+          constexpr int LPS = 16 / PPT;
+          const int kf = __shfl(newk[0], ln & ~(LPS - 1));
+          bool same_k = true;
+#pragma unroll
+          for (int c = 0; c < PPT; c++) same_k = same_k && in[c] && newk[c] == kf;
+          const unsigned long long eq = __ballot(same_k);
+          const unsigned full_step = (1u << LPS) - 1u;
+          if ((ln & (LPS - 1)) == 0 && in[0] && ((unsigned)(eq >> (ln & ~(LPS - 1))) & full_step) == full_step) nhomog++;
+      }
+      // (over: the full pass will run whatever else moves, k_pick_form -- no event of this workgroup is needed any more)
+      if (ev_pt && !over) {
+        unsigned long long bm[PPT], bo[PPT]; // movers; movers that leave a cluster, when that is an event of its own
+        unsigned wtot = 0;
+#pragma unroll
+        for (int c = 0; c < PPT; c++) {
+            bm[c] = __ballot(mover[c]);
+            bo[c] = pair ? 0ull : __ballot(mover[c] && mv_old[c] >= 0);
+            wtot += (unsigned)(__popcll(bm[c]) + __popcll(bo[c]));
         }
-        // nlist[1]: points whose runner-up is within 2.25x of the winner -- the ones a partial-sum lower bound (a
-        // quarter of the rounds: 5x in the squares leaves a margin) 
-        // could not separate; the host decides from this count whether the next call may use the two-phase screen
-        if (!(r2 >= 2.25 * r1)) nambig++;
-      }
-      if (!skipping) { // (q = i: the wave's lanes are four whole 16-point steps)
-          const int kf = __shfl(mine_k, threadIdx.x & 48);
-          const unsigned long long eq = __ballot(mine_k == kf && i < n);
-          if ((threadIdx.x & 15) == 0 && i < n && (unsigned)((eq >> (threadIdx.x & 48)) & 0xffffull) == 0xffffu) nhomog++;
-      }
-      // (s_over: the full pass will run whatever else moves, k_pick_form -- no event of this workgroup is needed any more;
-      //  the flag changes only inside flush_events, between barriers: the same for every thread of a trip)
-      if (ev_pt && !s_over && __syncthreads_or(mover ? 1 : 0)) { // (every thread of the workgroup gets here in every trip; no mover: nothing to stage)
-        const int cnt = mover ? ((mv_old >= 0 && !pair) ? 2 : 1) : 0;
-        // exclusive prefix of cnt inside the wave, one LDS atomic per wave for its total
-        int incl = cnt;
-        for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if ((int)(threadIdx.x & 63) >= off) incl += t; }
-        const int wtot = __shfl(incl, 63);
-        unsigned wbase = 0;
-        if (wtot) {
-            if ((threadIdx.x & 63) == 0) wbase = atomicAdd(&s_evn, (unsigned)wtot);
+        for (;;) { // (wtot <= 128 PPT: a reservation on the empty stage always fits)
+            unsigned wbase = 0;
+            if (ln == 0) wbase = atomicAdd(&s_evn, wtot);
             wbase = (unsigned)__builtin_amdgcn_readfirstlane((int)wbase);
+            if (wbase + wtot <= (unsigned)EVCAP) {
+                if (wtot) {
+#pragma unroll
+                    for (int c = 0; c < PPT; c++) {
+                        if (mover[c]) {
+                            unsigned at = wbase + (unsigned)(__popcll(bm[c] & lt) + __popcll(bo[c] & lt));
+                            const int ie = map != nullptr ? mp[c] : (int)(i0 + c); // (the records the events are applied from are in the caller's order)
+                            if (!pair && mv_old[c] >= 0) { s_evp[at] = ie; s_evk[at] = K + mv_old[c]; at++; atomicAdd(&evc[K + mv_old[c]], 1u); }
+                            s_evp[at] = ie; s_evk[at] = pair ? (newk[c] | ((mv_old[c] + 1) << 16)) : newk[c];
+                            atomicAdd(&evc[newk[c]], 1u);
+                        }
+                        wbase += (unsigned)(__popcll(bm[c]) + __popcll(bo[c]));
+                    }
+                }
+                break;
+            }
+            if (ln == 0) atomicMin(&s_valid, wbase);
+            over = (flush_events() & 1u) != 0u;
+            if (over) break;
         }
-        if (mover) {
-            unsigned at = wbase + (unsigned)(incl - cnt);
-            const int ie = map != nullptr ? map[i] : (int)i; // (the records the events are applied from are in the caller's order)
-            if (!pair && mv_old >= 0) { s_evp[at] = ie; s_evk[at] = K + mv_old; at++; atomicAdd(&evc[K + mv_old], 1u); }
-            s_evp[at] = ie; s_evk[at] = pair ? (mv_new | ((mv_old + 1) << 16)) : mv_new;
-            atomicAdd(&evc[mv_new], 1u);
-        }
-        __syncthreads();
-        if (s_evn + 2u * 256u > (unsigned)EVCAP) flush_events();
       }
     }
-    if (ev_pt) { __syncthreads(); if (s_evn) flush_events(); }
+    if (ev_pt) { // what is left on the stage, once every wave is past its last trip (and any flush another wave still needs)
+        if (ln == 0) atomicAdd(&s_done, 1u);
+        while (!(flush_events() & 2u)) {}
+    }
     for (int off = 32; off > 0; off >>= 1) nmov += __shfl_down(nmov, off);
     if ((threadIdx.x & 63) == 0 && nmov) atomicAdd(&s_mov, nmov);
     // per workgroup: with a short list nearly every wave holds an ambiguous point (the listed points ARE the ones near a

@@ -7,7 +7,10 @@ out=$root/gpurun_out/ab_$tag; mkdir -p $out
 for i in $(seq 1 ${PAIRS:-2}); do
   for v in A B; do
     if [ $v = A ]; then export SPKM_AB_LIB=$root/$A; else unset SPKM_AB_LIB; fi
-    timeout 600 python $root/bench.py --full --no-pmc --cpu-sample 0 "$@" --detail-out $out/detail_${v}_$i.json > $out/line_${v}_$i.json 2> $out/err_${v}_$i.txt
+    timeout -k 10 600 python $root/bench.py --full --no-pmc --cpu-sample 0 "$@" --detail-out $out/detail_${v}_$i.json > $out/line_${v}_$i.json 2> $out/err_${v}_$i.txt
+    rc=$?
+    # a run that failed or ran out of time ends the A/B: nothing more is started on a device that may have faulted
+    if [ $rc -ne 0 ]; then echo "$v$i: bench.py exit status $rc (see $out/err_${v}_$i.txt); stopping" >&2; tail -5 $out/err_${v}_$i.txt >&2; exit 1; fi
     python - <<PY
 import json
 try:
