@@ -140,6 +140,16 @@ int spkm_shard_reset_policy(spkm_shard *s);
  * visited at all, their part of d_assign included (SPKM_NO_BLOCK_SKIP=1: every point is looked at, as without lazy
  * statistics).  A different buffer is noticed and filled completely. */
 int spkm_shard_set_lazy_stats(spkm_shard *s, int on);
+/* Wide rows (on != 0; default off).  The certified f32 screen of spkm_assign_accumulate_dev keeps a tile of 32 centroids, p + 1
+ * rows of 128 bytes, in the workgroup's LDS; one row past what fits (p = 1278 with 160 KB) a fused call runs the all-exact
+ * kernels -- and, since the exact tiles stop at the same p, the generic one.  A shard that opts in is screened beyond that p
+ * on NARROWER tiles, 16 centroids (p <= 2558 with 160 KB) or 8 (p <= 5118), by a kernel of its own (csrc/screen_wide.hip)
+ * in front of the same certificate, exact list and exact accumulation pass: every output is what the all-exact kernels
+ * give, bit for bit where they are reproducible.  The plain screen only: no hints, carried bounds or incremental sums at
+ * these widths -- every call screens every point and runs a full accumulation pass.  Below the 32-wide limit the setting
+ * changes nothing.  Turning it on or off forgets the shard's policy state, like spkm_shard_reset_policy.
+ * SPKM_WIDE_SCREEN=1 opts every shard of a context in (read with the other switches: spkm_ctx_reload_switches). */
+int spkm_shard_set_wide_screen(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by
@@ -219,7 +229,11 @@ int spkm_accumulate_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, const in
  * proves for most points of a converging run that their centroid is unchanged; 16-point steps of such points
  * skip the screen.  The exact pass still recomputes every point's distance to its centroid and all sums, so the
  * outputs are the same bit for bit.  Nothing here depends on buffers the caller owns.  SPKM_NO_BOUNDS=1 disables
- * the skipping; spkm_shard_reset_policy forgets the bounds. */
+ * the skipping; spkm_shard_reset_policy forgets the bounds.
+ * Wide rows: the screen needs its 32-centroid f32 tile in LDS, (p + 1) * 128 + 16 bytes.  Past that p a call takes the
+ * all-exact kernels unless the shard (spkm_shard_set_wide_screen) or the context (SPKM_WIDE_SCREEN=1) opted in to the
+ * narrow-tile screen -- 16 or 8 centroids per tile, K >= 2, any number of entries per column that the exact pass can
+ * stage, the plain form without hints, carried bounds or incremental sums; spkm_last_screen_tile says which width ran. */
 int spkm_assign_accumulate_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, const double *d_centers,
                                double gamma, int32_t *d_assign, double *d_mind, double *d_stats,
                                uint64_t *d_nk_u64, double *d_reduce);
@@ -289,6 +303,10 @@ int spkm_last_events_form(spkm_ctx *ctx, int64_t info[2]);
  * of the last spkm_accumulate_dev: 1 = LDS slab over a counting sort, 2 = global atomics (rows beyond a 64-KB slab),
  * 0 = none; info[5] = kernel of the last spkm_distances[_stats]_dev: 1 = streaming record kernel, 2 = generic, 0 = none. */
 int spkm_last_assign_tile(spkm_ctx *ctx, int64_t info[6]);
+/* The screen of the last fused call (stored values; does not block): info[0] = centroids per tile -- 32 (the 4- and
+ * 16-lanes-per-point kernels), 16 or 8 (the narrow tiles of a shard that opted in, spkm_shard_set_wide_screen), 0 = that
+ * call took no screen; info[1] = its number of tiles (result slots per point). */
+int spkm_last_screen_tile(spkm_ctx *ctx, int64_t info[2]);
 
 /* Unchanged-cluster shortcut of the fused call's exact pass.  A cluster (i) whose centroid is BITWISE the one the
  * previous fused call on this shard was given and (ii) that no point left or entered is not streamed again: every

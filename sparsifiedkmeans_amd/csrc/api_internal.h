@@ -53,6 +53,7 @@ struct spkm_switches {
     bool no_regroup = false;      // SPKM_NO_REGROUP: the library's order of the points stays the caller's whatever their steps look like
     bool check_assign = false;    // SPKM_CHECK_ASSIGN: before blocks are skipped, verify the lazy contract on d_assign (debug aid; syncs)
     int force_form = 0;           // SPKM_FORCE_FORM=1|2|3: plain / unconditional two-phase / hinted screen, where legal (test aid, spkm.h)
+    bool wide_screen = false;     // SPKM_WIDE_SCREEN: every shard of the context takes the narrow-tile screen (k_screen_wide) past the 32-wide tile, as if opted in
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
 };
 struct spkm_ctx {
@@ -90,6 +91,7 @@ struct spkm_ctx {
     long long sort_n = 0;
     bool tlog_both = false; // fused screen path: log the exact accumulation kernel too (pairs alternate)
     int assign_KT = 0, assign_G = 0; // of the last assign call
+    int last_screen_kt = 0, last_screen_tiles = 0; // centroids per tile and tiles of the last fused call's screen (0: it took none)
     int last_pl_last = 0;            // the last screen call's plan: centroid pairs per lane of its last tile (5: carried)
     int last_exact_pts = 0;          // points staged per wave by the last exact pass / K = 1 stream (16: the pipelined kernel)
     int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics
@@ -126,6 +128,7 @@ struct spkm_shard {
     bool owned_csc = false; // ir / x are the library's
     int fixed_s = 0;   // > 0: every column has exactly this many entries
     uint64_t slack = 0; // entries readable past nnz in ir / x
+    bool wide = false; // spkm_shard_set_wide_screen: past the 32-wide tile this shard's fused calls take the narrow-tile screen
     float* xfs = nullptr;  // screen copy for the 4-lanes-per-point kernel: f32 values, columns partitioned by row parity
     void* irs = nullptr;   // ... and their row ids
     bool norms_done = false, xf_done = false;

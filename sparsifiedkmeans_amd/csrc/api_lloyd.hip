@@ -4,6 +4,7 @@
 #include "assign.hip"
 #include "update.hip"
 #include "screen.hip"
+#include "screen_wide.hip"
 #include "dense.hip"
 
 #include "api_internal.h"
@@ -954,6 +955,15 @@ extern "C" int spkm_last_assign_tile(spkm_ctx* ctx, int64_t info[6])
     info[3] = ctx->last_exact_pts;
     info[4] = ctx->last_acc_form;
     info[5] = ctx->last_dist_form;
+    return SPKM_OK;
+}
+
+// The last fused call's screen: centroids per tile (32, 16, 8; 0: it took no screen) and tiles.  Stored values; does not block.
+extern "C" int spkm_last_screen_tile(spkm_ctx* ctx, int64_t info[2])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    info[0] = ctx->last_path == 1 ? ctx->last_screen_kt : 0;
+    info[1] = ctx->last_path == 1 ? ctx->last_screen_tiles : 0;
     return SPKM_OK;
 }
 

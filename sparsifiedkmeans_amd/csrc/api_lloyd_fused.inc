@@ -4,30 +4,25 @@
 // ------------------------------------------------------------------------------------------
 // fused iteration front half: assignment + accumulation (everything before the all-reduce)
 // ------------------------------------------------------------------------------------------
-// The 4-lanes-per-point screen keeps a point's entries in registers (up to 64); longer columns use the
-// first-generation 16-lanes-per-point kernel.
+// Centroids per tile of the screen this shard's rows take on this device, whatever K is: 32 while that tile fits the LDS;
+// beyond it 16 or 8 (k_screen_wide) for a shard or a context that opted in (spkm_shard_set_wide_screen,
+// SPKM_WIDE_SCREEN=1); 0: no screen.
+static int screen_tile_kt(const spkm_ctx* ctx, const spkm_shard* s)
+{
+    if ((s->p + 1) * (uint64_t)SCREEN_KT * 4 + 16 <= ctx->lds_max) return SCREEN_KT;
+    return (s->wide || ctx->sw.wide_screen) ? spkm_wide_kt((long long)s->p, ctx->lds_max) : 0;
+}
+// The 4-lanes-per-point screen keeps a point's entries in registers (up to 64) and works on 32-centroid tiles; longer
+// columns use the first-generation 16-lanes-per-point kernel, longer rows the narrow tiles of k_screen_wide.
 static bool screen_use_quad(const spkm_ctx* ctx, const spkm_shard* s)
 {
-    return s->fixed_s <= 64;
+    return spkm_screen_quad(screen_tile_kt(ctx, s), s->fixed_s);
 }
-
-static bool screen_eligible(const spkm_ctx* ctx, const spkm_shard* s, int K)
+// The screen a fused call with K centroids takes (policy.h, spkm_screen_width): 32, 16, 8 centroids per tile, 0 = none.
+static int screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
 {
-    if (ctx->sw.no_screen) return false;
-    if (s->fixed_s <= 0 || s->slack < 48 || s->nnz == 0) return false; // the screen reads up to 33 entries past a column
-    // K <= 16 fits one exact tile that streams X once; the 4-lanes-per-point screen (one narrow tile) + exact
-    // confirmation is still ~13 % faster per iteration there (K = 10, N = 2e7: 4.6 vs 5.2 ms).  K = 1 has nothing to screen.
-    if (K < 2 || (K <= 16 && !screen_use_quad(ctx, s))) return false;
-    if ((s->p + 1) * (uint64_t)SCREEN_KT * 4 + 16 > ctx->lds_max) return false;
-    const int nb = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    const int tiles = (K + SCREEN_KT - 1) / SCREEN_KT;
-    if (tiles > nb) return false;
-    // the 4-lanes-per-point kernel gives every tile at least one workgroup per XCD
-    if (screen_use_quad(ctx, s) && tiles > ((nb % 8 == 0) ? nb / 8 : nb)) return false;
-    // phase 2 needs the centroid column + slab + at least 8 staged points per wave
-    const size_t per_pt = (size_t)(s->fixed_s | 1) * 8;
-    if (s->p * 20 + 1024 + 16 * 8 * per_pt > ctx->lds_max) return false;
-    return true;
+    return spkm_screen_width((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
+                             s->wide || ctx->sw.wide_screen);
 }
 
 
@@ -64,6 +59,7 @@ struct screen_call : spkm_call_in {
     size_t pk;
     spkm_call_plan pl;
     spkm_zero_jobs zj;
+    int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
     int bstat_n = 0, seg = 0, max_items = 0; // bstat_n: workgroups of k_bounds_steps whose statistics wait in ctx->bstat
     // everything this call needs zeroed, in one launch (flushed in front of the first kernel)
     void zero_later(void* q, size_t bytes) { zj.p[zj.n] = (unsigned*)q; zj.words[zj.n] = bytes / 4; zj.n++; }
@@ -101,7 +97,7 @@ struct screen_call : spkm_call_in {
         if (quad) rc = build_blockmap_quad(ctx, Gs, pl.pl_last, pl.nr);
         else rc = build_blockmap(ctx, pl.G);
         if (rc) return rc;
-        if ((rc = ensure(ctx, ctx->t32, (size_t)pl.G * (p + 1) * SCREEN_KT * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
+        if ((rc = ensure(ctx, ctx->t32, (size_t)pl.G * (p + 1) * kt * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
             (rc = ensure(ctx, ctx->scr_m1, (size_t)Gs * n * 4)) || (rc = ensure(ctx, ctx->scr_m2, (size_t)Gs * n * 4)) ||
             (rc = ensure(ctx, ctx->scr_k, (size_t)Gs * n * 4)) || (rc = ensure(ctx, ctx->list, (size_t)n * 4)))
             return rc;
@@ -270,20 +266,29 @@ struct screen_call : spkm_call_in {
         sm->hb_valid = false;     // until this call has gone through
         return SPKM_OK;
     }
-    // The screen: f32 tiles of the centroids, then the 4-lanes-per-point (or 16-lanes-per-point) screen launch.
+    // The screen: f32 tiles of the centroids, then the 4-lanes-per-point (or 16-lanes-per-point, or narrow-tile) screen launch.
     template <typename IR> int screen()
     {
         zero_flush();
         // (one launch: the f32 tiles, the row-major f64 centres of the exact list, the library's copy for the next call's drift)
-        const size_t tile_floats = (size_t)pl.G * (p + 1) * SCREEN_KT;
-        hipLaunchKernelGGL(k_prep_tiles_f32, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
-                           0, ctx->stream, C, p, K, pl.G, gamma, (float*)ctx->t32.p,
-                           (unsigned long long*)ctx->cmax.p, pl.pl_last, quad ? 1 : 0, (double*)ctx->ct.p,
-                           quad ? sm->hb_centers : (double*)nullptr);
+        const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
+        if (kt == SCREEN_KT)
+            hipLaunchKernelGGL(k_prep_tiles_f32, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
+                               0, ctx->stream, C, p, K, pl.G, gamma, (float*)ctx->t32.p,
+                               (unsigned long long*)ctx->cmax.p, pl.pl_last, quad ? 1 : 0, (double*)ctx->ct.p,
+                               quad ? sm->hb_centers : (double*)nullptr);
+        else
+            hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
+                               0, ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p,
+                               (unsigned long long*)ctx->cmax.p, (double*)ctx->ct.p);
         ctx->last_sums_only = false;
         ctx->last_pl_last = pl.pl_last;
-        const size_t lds = (size_t)(p + 1) * (SCREEN_KT * 4 + (pl.pl_last == 5 ? 16 : 0)) + 16;
-        const void* kern = quad ? screen_quad_kernel<IR>(pl.nr, pl.prune_a > 0 ? pl.prune_a : pl.nr, pl.pt_mode) : (const void*)k_screen_tile<IR>;
+        ctx->last_screen_kt = kt;
+        ctx->last_screen_tiles = pl.Gs;
+        const size_t lds = (size_t)(p + 1) * (kt * 4 + (pl.pl_last == 5 ? 16 : 0)) + 16;
+        const void* kern = quad ? screen_quad_kernel<IR>(pl.nr, pl.prune_a > 0 ? pl.prune_a : pl.nr, pl.pt_mode)
+                                : (kt == SCREEN_KT ? (const void*)k_screen_tile<IR>
+                                                   : (kt == 16 ? (const void*)k_screen_wide<IR, 16> : (const void*)k_screen_wide<IR, 8>));
         HIP_TRY(allow_lds(ctx, kern, lds));
         HIP_TRY(timing_begin(ctx));
         const IR* a_ir = quad ? (const IR*)sm->irs : (const IR*)sm->ir;
@@ -597,15 +602,16 @@ struct screen_call : spkm_call_in {
 template <typename IR>
 static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_centers, double gamma,
                       int32_t* d_assign, double* d_mind, double* d_reduce, int prune_a, bool want_hint,
-                      double* d_stats, uint64_t* d_nk_u64)
+                      double* d_stats, uint64_t* d_nk_u64, int kt)
 {
     screen_call c;
+    c.kt = kt;
     c.ctx = ctx; c.sm = const_cast<spkm_shard*>(s); c.C = d_centers; c.gamma = gamma; c.assign = d_assign; c.mind = d_mind;
-    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = screen_use_quad(ctx, s);
+    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = spkm_screen_quad(kt, s->fixed_s);
     c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
     c.zj.n = 0;
     c.seg = seg_points(c.n, ctx->num_cus); c.max_items = (int)(c.n / c.seg) + K + 1;
-    spkm_plan_tiles(c.pl, c);
+    spkm_plan_tiles(c.pl, c, kt);
     int rc;
     if ((rc = c.buffers<IR>())) return rc;
     c.plan_input(prune_a, want_hint);
@@ -659,7 +665,8 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         c.full_opened = sm->h_nlist[19] != 0u;
         c.one_cluster_steps = sm->h_nlist[21];
         c.may_regroup = sm->pend_full && sm->lazy && !sm->regroup_done;
-        sm->pol.observe(c, (double)s->n, (int)((K64 + SCREEN_KT - 1) / SCREEN_KT), (s->fixed_s + 3) / 4);
+        const int kt_seen = std::max(8, screen_tile_kt(ctx, s)); // (a shard's screen calls share one width while its opt-in stands)
+        sm->pol.observe(c, (double)s->n, (int)((K64 + kt_seen - 1) / kt_seen), (s->fixed_s + 3) / 4);
     }
     spkm_policy::choice ch = sm->pol.next(ctx->sw.no_prune, ctx->sw.no_hint, screen_use_quad(ctx, s));
     if (ctx->sw.force_form) { // SPKM_FORCE_FORM (test aid, spkm.h): run_screen still checks what the call's state allows
@@ -668,15 +675,16 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         ch.want_hint = ctx->sw.force_form == 3 && screen_use_quad(ctx, s);
     }
     const bool cooling = ch.exact;
-    if (s->n > 0 && !cooling && screen_eligible(ctx, s, (int)K64)) {
+    const int kt = screen_width(ctx, s, (int)K64);
+    if (s->n > 0 && !cooling && kt > 0) {
         ctx->ev_valid = false;
         // Hinted two-phase screen: when the unconditional two-phase form is not chosen and hints are not paused, the
         // screen compares the competition's partial sums with per-point upper bounds taken from the carried bounds
         // (run_screen / k_bounds_steps); needs this shard's previous call to have been a screen call.
         const int prune_a = ch.prune_a;
         const bool want_hint = ch.want_hint;
-        rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64)
-                                : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64);
+        rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt)
+                                : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt);
         if (rc) return rc;
         ctx->last_mode = ctx->last_hinted ? 2 : (ctx->last_rounds_all < ctx->last_rounds ? 1 : 0);
         if (!sm->nlist_pending) { // (run_screen's k_call_tail was told to report under the number nlist_seq + 1)
@@ -689,6 +697,7 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         return SPKM_OK; // (statistics and cluster sizes were handed over by run_screen's last kernel)
     }
     ctx->last_path = 0;
+    ctx->last_screen_kt = ctx->last_screen_tiles = 0;
     ctx->last_dual = false;
     sm->sp_clean = false;
     sm->assign_synced = false;

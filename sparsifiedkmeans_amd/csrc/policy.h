@@ -239,6 +239,45 @@ struct spkm_policy {
 // before the screen, the record layout (spkm_plan_sums) after it.  Constants of the kernels sized here: checked against
 // SCREEN_KT, BOUNDS_SPAN[_PT] and SEG_POINTS in api_lloyd_fused.inc.
 constexpr int spkm_plan_kt = 32, spkm_plan_span = 16384, spkm_plan_span_pt = 4096, spkm_plan_seg = 2048;
+// Narrow tiles of the screen (screen_wide.hip, k_screen_wide) for rows whose 32-centroid f32 tile no longer fits the LDS:
+// the widest of 16 and 8 centroids whose tile -- p + 1 rows of kt floats and the work ticket -- fits; 0: neither.  (160 KB:
+// 16 up to p = 2558, 8 up to 5118; the exact pass behind the screen stops before a 4-centroid tile would be needed.)
+inline int spkm_wide_kt(long long p, size_t lds_max)
+{
+    for (int kt : {16, 8})
+        if ((unsigned long long)(p + 1) * (unsigned)kt * 4ull + 16ull <= (unsigned long long)lds_max) return kt;
+    return 0;
+}
+// Which screen a fused call on a shard takes, from its shapes, the device and the opt-ins alone -- centroids per tile:
+// 32 (k_screen_quad for columns of up to 64 entries, spkm_screen_quad; k_screen_tile beyond), 16 or 8 (k_screen_wide: only
+// where the 32-wide tile does not fit and the shard -- spkm_shard_set_wide_screen -- or the context -- SPKM_WIDE_SCREEN=1
+// -- asked for it), 0: none, the all-exact kernels.  The policy's cool-down is the caller's to add.
+//  * fixed stride, 48 entries of slack (the 32-wide kernels read up to 33 entries past a column), a non-empty shard;
+//  * K >= 2; at 32: K <= 16 fits one exact tile that streams X once -- the 4-lanes-per-point screen (one narrow tile) + exact
+//    confirmation is still ~13 % faster per iteration there (K = 10, N = 2e7: 4.6 vs 5.2 ms), the 16-lanes-per-point one is
+//    not; beyond the 32-wide tile no exact tile fits either (they stop at the same p) and K = 2 is screened like any other;
+//  * a workgroup per tile at least; the 4-lanes-per-point kernel gives every tile one per XCD;
+//  * phase 2 needs the centroid column + slab + at least 8 staged points per wave.
+inline bool spkm_screen_quad(int kt, int fixed_s) { return kt == spkm_plan_kt && fixed_s <= 64; }
+inline int spkm_screen_width(long long p, int K, int fixed_s, unsigned long long slack, unsigned long long nnz, size_t lds_max,
+                             int num_cus, bool no_screen, bool wide)
+{
+    if (no_screen) return 0;
+    if (fixed_s <= 0 || slack < 48 || nnz == 0) return 0;
+    int kt = spkm_plan_kt;
+    if ((unsigned long long)(p + 1) * (unsigned)spkm_plan_kt * 4ull + 16ull > (unsigned long long)lds_max)
+        kt = wide ? spkm_wide_kt(p, lds_max) : 0;
+    if (kt == 0) return 0;
+    const bool quad = spkm_screen_quad(kt, fixed_s);
+    if (K < 2 || (kt == spkm_plan_kt && K <= 16 && !quad)) return 0;
+    const int nb = num_cus > 0 ? num_cus : 256;
+    const int tiles = (K + kt - 1) / kt;
+    if (tiles > nb) return 0;
+    if (quad && tiles > ((nb % 8 == 0) ? nb / 8 : nb)) return 0;
+    const size_t per_pt = (size_t)(fixed_s | 1) * 8;
+    if ((size_t)p * 20 + 1024 + 16 * 8 * per_pt > lds_max) return 0;
+    return kt;
+}
 struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;
@@ -260,7 +299,7 @@ struct spkm_call_in {
     int prune_a = 0; bool want_hint = false; // the caller's choice (spkm_policy::next)
 };
 struct spkm_call_plan {
-    // tiles of G x 32 centroids; pl_last = centroid pairs per lane of the last one (1, 2, 4; 5: its <= 4 centroids ride on
+    // tiles of G x 32 centroids (G x 16 / G x 8: the narrow tiles of k_screen_wide, pl_last 4); pl_last = centroid pairs per lane of the last one (1, 2, 4; 5: its <= 4 centroids ride on
     // the tile before); Gs = tiles with workgroups / result slots; nr = rounds of 4 entries per column
     int G = 0, pl_last = 4, Gs = 0, nr = 0;
     bool bounds_ok = false, kept = false, ev_possible = false, pair_capable = false, ev_path = false, pair_ev = false;
@@ -278,10 +317,11 @@ struct spkm_call_plan {
 };
 // The screen's tiles.  The last tile: <= 4 centroids ride on the tile before as one extra centroid per lane (pl 5; needs
 // (p+1) x 16 B more LDS); <= 16: a narrow tile with 1 or 2 centroid pairs per lane instead of 4.
-inline void spkm_plan_tiles(spkm_call_plan& pl, const spkm_call_in& in)
+// kt: centroids per tile (spkm_screen_width); the narrow tiles always come with !in.quad.
+inline void spkm_plan_tiles(spkm_call_plan& pl, const spkm_call_in& in, int kt = spkm_plan_kt)
 {
-    pl.G = (in.K + spkm_plan_kt - 1) / spkm_plan_kt;
-    const int k_last = in.K - (pl.G - 1) * spkm_plan_kt;
+    pl.G = (in.K + kt - 1) / kt;
+    const int k_last = in.K - (pl.G - 1) * kt;
     pl.pl_last = !in.quad ? 4 : (k_last <= 8 ? 1 : (k_last <= 16 ? 2 : 4));
     if (in.quad && pl.G >= 2 && k_last <= 4 && (size_t)(in.p + 1) * (spkm_plan_kt * 4 + 16) + 16 <= in.lds_max) pl.pl_last = 5;
     pl.Gs = pl.pl_last == 5 ? pl.G - 1 : pl.G;

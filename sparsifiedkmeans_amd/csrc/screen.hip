@@ -2,7 +2,9 @@
 // for K >= 2 (gfx950).  RESULTS ARE IDENTICAL to the exact kernel of assign.hip -- assignments
 // bit-for-bit, min-distances bit-for-bit -- because nothing computed in f32 is ever output:
 //
-//   1. k_screen_quad     (columns of up to 64 entries; k_screen_tile, the 16-lanes-per-point kernel, beyond)
+//   1. k_screen_quad     (columns of up to 64 entries; k_screen_tile, the 16-lanes-per-point kernel, beyond; rows
+//                        too long for the 32-centroid tile: k_screen_wide, screen_wide.hip, on tiles of 16 or 8
+//                        centroids for shards that opted in -- the plain form of this step, same estimates)
 //                        for every point and centroid, an f32 estimate of the squared distance, 32 centroids
 //                        per LDS tile; per (point, tile): the leader's estimate m1, its centroid, and m2, a
 //                        LOWER BOUND of the estimate of every other centroid of the tile (the second smallest

@@ -1,0 +1,198 @@
+// The certified f32 screen for rows beyond the 32-centroid tile: k_screen_wide<IR, KT> on NARROW tiles of KT = 16 or 8
+// centroids (64- or 32-byte rows), for p up to (LDS - 16) / (4 KT) - 1 -- 2558 / 5118 with 160 KB.  Textually part of
+// api_lloyd.hip, behind screen.hip (whose header carries the certificate's proof and whose k_combine_screen, k_assign_list
+// and exact pass take it from here: the pipeline of the 16-lanes-per-point kernel, k_screen_tile).  Plain form only: no
+// hints, no carried bounds, no point lists, no events -- every call screens every point and runs a full accumulation pass.
+//
+// Arithmetic, as the proof assumes: t = fl32(x~ + T) with T = -fl32(c), acc = fmaf(t, t, acc), one accumulator per
+// (point, centroid), over the column's s entries in storage order: s roundings of the FMA, none anywhere else.  A slot
+// past the column's end is x = 0 on row p (all zero): fmaf(0, 0, acc) = acc exactly.
+
+// Twt[g][r][kk] = -fl32(C[(g*kt+kk)*p + r] / gamma), row p zero, rows of kt floats; cmax_bits = max |C/gamma| (f64 bits,
+// atomicMax) and Cs[r*K + k] = C[k*p + r] / gamma (row-major f64 for k_assign_list) in the same launch, as
+// k_prep_tiles_f32 produces them for the 32-wide tile.
+__global__ __launch_bounds__(256) void k_prep_tiles_wide(const double* __restrict__ C, int p, int K, int G, int kt, double gamma,
+                                                         float* __restrict__ Twt, unsigned long long* __restrict__ cmax_bits,
+                                                         double* __restrict__ Cs)
+{
+    if (Cs != nullptr) {
+        const size_t pkk = (size_t)p * K;
+        for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < pkk; t += (size_t)gridDim.x * blockDim.x) {
+            const int k = (int)(t % K);
+            const size_t r = t / K;
+            double v = C[(size_t)k * p + r];
+            if (gamma > 0.0) v = v / gamma;
+            Cs[t] = v;
+        }
+    }
+    const size_t total = (size_t)G * (p + 1) * kt;
+    double mx = 0.0;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int kk = (int)(t % kt);
+        const size_t rest = t / kt;
+        const int r = (int)(rest % (p + 1));
+        const int k = (int)(rest / (p + 1)) * kt + kk;
+        float v = 0.f;
+        if (r < p && k < K) {
+            double c = C[(size_t)k * p + r];
+            if (gamma > 0.0) c = c / gamma;
+            mx = fmax(mx, fabs(c));
+            v = -(float)c;
+        }
+        Twt[t] = v;
+    }
+    __shared__ double s_mx[4];
+    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_down(mx, off));
+    if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); w++) mx = fmax(mx, s_mx[w]);
+        if (mx > 0.0) atomicMax(cmax_bits, __builtin_bit_cast(unsigned long long, mx));
+    }
+}
+
+typedef float wide_f2 __attribute__((ext_vector_type(2)));
+
+// lane Q of every group of LG lanes (LG = 4: the quad; LG = 2: each half of it), in every lane of the group
+template <int LG, int Q> __device__ __forceinline__ int wide_bcast(int v)
+{
+    constexpr int ctrl = LG == 4 ? Q * 0x55 : (Q | (Q << 2) | ((2 + Q) << 4) | ((2 + Q) << 6)); // quad_perm
+    return __builtin_amdgcn_update_dpp(0, v, ctrl, 0xf, 0xf, false);
+}
+
+// One stored entry (value x, LDS byte offset of its row) against this lane's 4 centroids
+__device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xbits, int rowoff, wide_f2& a01, wide_f2& a23)
+{
+    const float4 T = *reinterpret_cast<const float4*>(tile + rowoff); // ds_read_b128
+    const float x = __builtin_bit_cast(float, xbits);
+    const wide_f2 xx = {x, x};
+    const wide_f2 t01 = xx + wide_f2{T.x, T.y}, t23 = xx + wide_f2{T.z, T.w};
+    a01 = __builtin_elementwise_fma(t01, t01, a01); // (explicit: the build runs with -ffp-contract=off)
+    a23 = __builtin_elementwise_fma(t23, t23, a23);
+}
+
+// LG = KT / 4 lanes per point, each owning 4 consecutive centroids of the tile; 64 / LG points per wave (16 / 32).  The
+// workgroup keeps one tile in LDS and its waves draw steps of 64 / LG points from an LDS ticket, over the chunks of the
+// blockmap's stream (build_blockmap: the workgroups of the G tiles that stream the same chunks share an XCD's L2), as
+// k_screen_tile does.  The LG lanes of a point fetch LG consecutive entries of its column per round (value and row id,
+// 4 + sizeof(IR) bytes per lane) and hand them round inside the quad by DPP; four rounds are fetched ahead of their use.
+// Nothing past a column's own s entries is read: a slot beyond the end takes x = 0 and row p without a load, and a point
+// past n reads point n - 1 and stores nothing.
+// LDS banks.  A ds_read_b128 is served in four groups of 16 lanes, bank = (address / 4) % 64.  The LG lanes of a point
+// read the 16 * LG contiguous bytes of ONE row, so a 16-lane group holds 16 / LG points (4 at KT = 16, 8 at KT = 8) on
+// rows the DATA chooses: a 256-byte bank line holds 256 / (4 KT) rows (4 / 8), and two points of a group collide when
+// their rows differ and agree modulo that number.  No layout of the tile moves that: any fixed map of rows to bank
+// offsets leaves rows drawn at random by the sampler colliding at the same rate (the 32-wide kernel lowers it by
+// reordering each point's ENTRIES by row parity in its own copy of the shard, k_screen_reorder; this kernel streams
+// the shard's plain f32 copy).  With uniform rows the largest of 4 points' counts on 4 offsets averages 2.1, of 8 on 8
+// 2.7: the read is that many passes instead of one -- the price of the plain layout, kept because the rows stay
+// 16-byte aligned 64-/32-byte runs that one b128 per lane covers.  Slots on the zero row all read one address (a broadcast).
+template <typename IR, int KT>
+__global__ __launch_bounds__(1024) void k_screen_wide(
+    const IR* __restrict__ ir, const float* __restrict__ xval, const float* __restrict__ Twt, int p, int n,
+    int fixed_s, int K, const spkm_blockmap* __restrict__ bmap, int chunk_points, float* __restrict__ scr_m1,
+    float* __restrict__ scr_m2, int* __restrict__ scr_k)
+{
+    static_assert(KT == 16 || KT == 8, "tiles of 16 or 8 centroids");
+    constexpr int LG = KT / 4, PPW = 64 / LG, ROWB = KT * 4, UN = 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const spkm_blockmap bm = bmap[blockIdx.x];
+    if (bm.tile < 0) return;
+    const int g = bm.tile;
+    const int tid = threadIdx.x;
+    const size_t tile_bytes = (size_t)(p + 1) * ROWB;
+    {
+        const float4* src = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(Twt) + (size_t)g * tile_bytes);
+        float4* dst = reinterpret_cast<float4*>(smem);
+        for (size_t t = tid; t < tile_bytes / 16; t += blockDim.x) dst[t] = src[t];
+        if (tid == 0) *reinterpret_cast<unsigned*>(smem + tile_bytes) = 0u;
+    }
+    __syncthreads();
+
+    const int lane = tid & 63;
+    const int sub = lane & (LG - 1), ps = lane / LG;
+    const char* mytile = smem + sub * 16;
+    const int s = fixed_s;
+    const int nr = (s + LG - 1) / LG; // rounds of LG entries
+    const int zero_off = p * ROWB;
+    const int nchunks = (n + chunk_points - 1) / chunk_points;
+    const int R = chunk_points / PPW;
+    const int my_chunks = (nchunks > bm.stream) ? (nchunks - bm.stream + bm.nstreams - 1) / bm.nstreams : 0;
+    const int T = my_chunks * R;
+    float* m1o = scr_m1 + (size_t)g * n;
+    float* m2o = scr_m2 + (size_t)g * n;
+    int* ko = scr_k + (size_t)g * n;
+    const int kfirst = g * KT + sub * 4; // this lane's centroids: kfirst .. kfirst + 3
+    const bool ragged_tile = g * KT + KT > K; // (block-uniform: only the last tile has slots k >= K)
+    unsigned* ticket = reinterpret_cast<unsigned*>(smem + tile_bytes);
+    auto draw = [&]() {
+        unsigned v = 0;
+        if (lane == 0) v = atomicAdd(ticket, 1u);
+        return (int)__builtin_amdgcn_readfirstlane(v);
+    };
+    for (int u = draw(); u < T; u = draw()) {
+        const int ci = u / R;
+        const int base = (bm.stream + ci * bm.nstreams) * chunk_points + (u - ci * R) * PPW;
+        if (base >= n) continue; // (the last chunk's steps past the shard)
+        const int i = base + ps;
+        const size_t col = (size_t)(i < n ? i : n - 1) * (size_t)s;
+        const float* xp = xval + col;
+        const IR* rp = ir + col;
+        int xv[UN], ro[UN];
+        auto fetch = [&](int r0, int (&xo)[UN], int (&oo)[UN]) {
+#pragma unroll
+            for (int c = 0; c < UN; c++) {
+                const int e = (r0 + c) * LG + sub;
+                const bool in = e < s;
+                xo[c] = in ? __builtin_bit_cast(int, xp[e]) : 0;
+                oo[c] = in ? (int)rp[e] * ROWB : zero_off;
+            }
+        };
+        fetch(0, xv, ro);
+        wide_f2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
+        for (int r0 = 0; r0 < nr; r0 += UN) {
+            int xn[UN], rn[UN];
+            fetch(r0 + UN, xn, rn); // (past the column: no loads, zero slots)
+#pragma unroll
+            for (int c = 0; c < UN; c++) {
+                wide_entry(mytile, wide_bcast<LG, 0>(xv[c]), wide_bcast<LG, 0>(ro[c]), a01, a23);
+                wide_entry(mytile, wide_bcast<LG, 1>(xv[c]), wide_bcast<LG, 1>(ro[c]), a01, a23);
+                if (LG == 4) {
+                    wide_entry(mytile, wide_bcast<LG, 2 % LG>(xv[c]), wide_bcast<LG, 2 % LG>(ro[c]), a01, a23);
+                    wide_entry(mytile, wide_bcast<LG, 3 % LG>(xv[c]), wide_bcast<LG, 3 % LG>(ro[c]), a01, a23);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < UN; c++) { xv[c] = xn[c]; ro[c] = rn[c]; }
+        }
+        // the point's smallest estimate, its centroid and the second smallest over the tile (store_screen_winner's
+        // conventions: NaN estimates compare equal to nothing -- all of them NaN: m1 = m2 = +inf, k = -1; a tie names either)
+        float a[4] = {a01.x, a01.y, a23.x, a23.y};
+        if (ragged_tile) {
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                if (kfirst + c >= K) a[c] = __builtin_inff();
+        }
+        const float lo = fminf(fminf(a[0], a[1]), fminf(a[2], a[3]));
+        const int li = a[0] == lo ? 0 : (a[1] == lo ? 1 : (a[2] == lo ? 2 : (a[3] == lo ? 3 : -1)));
+        float lo2 = __builtin_inff(); // this lane's second smallest
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (c != li) lo2 = fminf(lo2, a[c]);
+        float m1 = lo;
+#pragma unroll
+        for (int o = 1; o < LG; o <<= 1) m1 = fminf(m1, __shfl_xor(m1, o));
+        int first = (li >= 0 && lo == m1) ? sub : LG; // the first lane of the group that holds the smallest
+#pragma unroll
+        for (int o = 1; o < LG; o <<= 1) first = min(first, __shfl_xor(first, o));
+        float m2 = sub == first ? lo2 : lo;
+#pragma unroll
+        for (int o = 1; o < LG; o <<= 1) m2 = fminf(m2, __shfl_xor(m2, o));
+        const bool none = first == LG;
+        if (sub == (none ? 0 : first) && i < n) {
+            m1o[i] = none ? __builtin_inff() : m1;
+            m2o[i] = none ? __builtin_inff() : m2;
+            ko[i] = none ? -1 : kfirst + li;
+        }
+    }
+}

@@ -80,6 +80,13 @@ class Shard:
         delivers them for the iteration that needs them."""
         _lib.check(_lib.lib().spkm_shard_set_lazy_stats(self.handle, 1 if on else 0), "spkm_shard_set_lazy_stats")
 
+    def set_wide_screen(self, on: bool = True):
+        """Let fused calls on this shard take the certified screen on narrow tiles (16 or 8 centroids) where its rows are
+        too long for the 32-centroid tile -- p > 1278 with 160 KB of LDS -- instead of the all-exact kernels
+        (spkm_shard_set_wide_screen; off by default at the C interface).  Outputs never depend on it; the shard's policy
+        state is forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_wide_screen(self.handle, 1 if on else 0), "spkm_shard_set_wide_screen")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""
@@ -354,6 +361,13 @@ class LloydEngine:
         a = (C.c_int64 * 6)()
         _lib.check(_lib.lib().spkm_last_assign_tile(self.ctx.handle, a))
         return tuple(int(v) for v in a)
+
+    def last_screen_tile(self) -> tuple[int, int]:
+        """(centroids per tile of the last fused call's screen: 32, or 16 / 8 on a shard with set_wide_screen(); 0 = it
+        took no screen, its number of tiles) -- spkm_last_screen_tile."""
+        a = (C.c_int64 * 2)()
+        _lib.check(_lib.lib().spkm_last_screen_tile(self.ctx.handle, a))
+        return int(a[0]), int(a[1])
 
     def iterate(self, centers: torch.Tensor, want_mind: bool = True):
         """One full Lloyd iteration in place on ``centers``; returns the device tensor

@@ -50,7 +50,9 @@ _DEFAULTS = dict(
     SparsityLevel=0.01, SketchType="auto", EmptyAction="singleton", ColumnSamples=False, MLcorrection=True,
     DataFile=None, MB_limit=500, DataFileVerbose=False, SparsityIgnoreUpsampling=False, FORCE_BUG=False,
     tryBuiltinMex=True, unbiasedDistance=True, unbiasedInitialization=True, denseCenters=False)
-_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None)  # Python-side additions (not reference options)
+# Python-side additions (not reference options).  wideScreen: rows too long for the screen's 32-centroid tile (p2 > 1278 with
+# 160 KB of LDS) are screened on narrow tiles instead of running the all-exact kernels (Shard.set_wide_screen); False: off
+_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True)
 
 
 def _parse(opts: dict) -> dict:
@@ -163,7 +165,9 @@ def findClusterAssignments(X, centers, tryBuiltinMex=None, gamma=None, ctx=None)
     if centers.shape[0] != p:
         raise ValueError("Array of centers not of correct size")  # :55
     K = centers.shape[1]
-    eng = LloydEngine(Shard.from_scipy(ctx, X), K, gamma if gamma else 1.0, unbiased=bool(gamma))
+    shard = Shard.from_scipy(ctx, X)
+    shard.set_wide_screen(True)
+    eng = LloydEngine(shard, K, gamma if gamma else 1.0, unbiased=bool(gamma))
     dev = f"cuda:{ctx.device}"
     if sp.issparse(centers):
         Cd = np.ascontiguousarray(centers.toarray().T)
@@ -344,6 +348,7 @@ def kmeans_sparsified(X, K, **options):
     # together with the distances (spkm_shard_set_lazy_stats, LloydEngine.distances)
     lazy_stats = Display != "iter"
     shard.set_lazy_stats(lazy_stats)
+    shard.set_wide_screen(bool(o["wideScreen"]))
     if Display in ("iter", "final"):
         print(f"Randomly mixing of type {sk}")
         print(f"Randomly taking {100 * gamma:.1f}% of the data; actual dataset is {100 * nnz / (p2 * n):.1f}% sparse")
@@ -542,6 +547,7 @@ def kmeans_sparsified(X, K, **options):
             if not np.isfinite(dff2) and bool(torch.isnan(centers).any().item()):
                 raise RuntimeError("Found NaN in centers")                       # :480-484 (a NaN centre makes dff NaN)
         last_path = eng.last_path_info()[0] if fused_iters else 0
+        OUTPUT["screenTile"] = eng.last_screen_tile()[0] if fused_iters else 0   # (not a reference field: 32 / 16 / 8 centroids, 0 = no screen)
         if its > 0 and mind_pending:
             eng_used.distances(centers_used)                                     # `distances` of the last iteration (:420)
             dist_t = eng_used.mind
