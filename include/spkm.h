@@ -145,11 +145,22 @@ int spkm_shard_set_lazy_stats(spkm_shard *s, int on);
  * kernels -- and, since the exact tiles stop at the same p, the generic one.  A shard that opts in is screened beyond that p
  * on NARROWER tiles, 16 centroids (p <= 2558 with 160 KB) or 8 (p <= 5118), by a kernel of its own (csrc/screen_wide.hip)
  * in front of the same certificate, exact list and exact accumulation pass: every output is what the all-exact kernels
- * give, bit for bit where they are reproducible.  The plain screen only: no hints, carried bounds or incremental sums at
- * these widths -- every call screens every point and runs a full accumulation pass.  Below the 32-wide limit the setting
- * changes nothing.  Turning it on or off forgets the shard's policy state, like spkm_shard_reset_policy.
+ * give, bit for bit where they are reproducible.  No hints and no incremental sums at these widths: every call runs a full
+ * accumulation pass and, unless the shard carries bounds (spkm_shard_set_wide_bounds), screens every point.  Below the
+ * 32-wide limit the setting changes nothing.  Turning it on or off forgets the shard's policy state, like spkm_shard_reset_policy.
  * SPKM_WIDE_SCREEN=1 opts every shard of a context in (read with the other switches: spkm_ctx_reload_switches). */
 int spkm_shard_set_wide_screen(spkm_shard *s, int on);
+/* Carried bounds beyond the 4-lanes-per-point screen (on != 0; default off).  Despite the name it covers BOTH shapes that
+ * leave that screen: wide rows (the narrow tiles of spkm_shard_set_wide_screen) and long columns (more than 64 entries per
+ * column, the 16-lanes-per-point kernel).  A shard that opts in keeps the per-point bounds of spkm_assign_accumulate_dev
+ * between its screen calls there too: the next call tests them point by point and screens only the points they do not
+ * settle, by a point-list form of the narrow-tile kernel (32 centroids per tile for long columns).  The certificate, the
+ * exact list and the exact pass stay what they are -- the pass still runs over every point in every call -- so every
+ * output is unchanged.  No hints, step lists, block summaries, regrouping or incremental sums on these shards.  On a shard
+ * that takes the 4-lanes-per-point screen the setting changes nothing.  Turning it on or off forgets the shard's policy
+ * state and its bounds, like spkm_shard_reset_policy.  SPKM_WIDE_BOUNDS=1 opts every shard of a context in (read with the
+ * other switches); SPKM_NO_BOUNDS=1 keeps the bounds but skips nothing on them. */
+int spkm_shard_set_wide_bounds(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by
@@ -233,7 +244,10 @@ int spkm_accumulate_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, const in
  * Wide rows: the screen needs its 32-centroid f32 tile in LDS, (p + 1) * 128 + 16 bytes.  Past that p a call takes the
  * all-exact kernels unless the shard (spkm_shard_set_wide_screen) or the context (SPKM_WIDE_SCREEN=1) opted in to the
  * narrow-tile screen -- 16 or 8 centroids per tile, K >= 2, any number of entries per column that the exact pass can
- * stage, the plain form without hints, carried bounds or incremental sums; spkm_last_screen_tile says which width ran. */
+ * stage, without hints or incremental sums; spkm_last_screen_tile says which width ran.
+ * Beyond the 4-lanes-per-point screen -- these narrow tiles, and columns of more than 64 entries -- the bounds are carried
+ * only by a shard (spkm_shard_set_wide_bounds) or a context (SPKM_WIDE_BOUNDS=1) that opted in, and always point by point:
+ * such a call reports info[7] = 2 in spkm_last_screen_mode, and spkm_last_screen_points says how many points it screened. */
 int spkm_assign_accumulate_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, const double *d_centers,
                                double gamma, int32_t *d_assign, double *d_mind, double *d_stats,
                                uint64_t *d_nk_u64, double *d_reduce);
@@ -307,6 +321,10 @@ int spkm_last_assign_tile(spkm_ctx *ctx, int64_t info[6]);
  * 16-lanes-per-point kernels), 16 or 8 (the narrow tiles of a shard that opted in, spkm_shard_set_wide_screen), 0 = that
  * call took no screen; info[1] = its number of tiles (result slots per point). */
 int spkm_last_screen_tile(spkm_ctx *ctx, int64_t info[2]);
+/* How many points the screen of the last fused call evaluated (any screen kernel): info[0] = n for a call over all points,
+ * the length of the list for a call that skipped on its carried bounds (points; 16 per listed step for a step list), 0
+ * when the call took no screen; info[1] = the running total over the context.  Blocks on the stream. */
+int spkm_last_screen_points(spkm_ctx *ctx, int64_t info[2]);
 
 /* Unchanged-cluster shortcut of the fused call's exact pass.  A cluster (i) whose centroid is BITWISE the one the
  * previous fused call on this shard was given and (ii) that no point left or entered is not streamed again: every

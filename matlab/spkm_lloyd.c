@@ -158,6 +158,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         check(spkm_shard_create_host(ctx, mxGetM(X), mxGetN(X), (const uint64_t *)mxGetJc(X), (const uint64_t *)mxGetIr(X),
                                      mxGetPr(X), &g_shard));
         check(spkm_shard_set_wide_screen(g_shard, 1));           /* rows past the 32-centroid tile: the narrow-tile screen */
+        check(spkm_shard_set_wide_bounds(g_shard, 1));           /* ... and carried bounds there and on columns of more than 64 entries */
         g_p = mxGetM(X);
         g_n = mxGetN(X);
         return;
@@ -213,6 +214,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
             check(spkm_shard_create_dev(ctx, p2, n, n * s, g_jc, g_ir, 16, g_x, n * s + 48, &g_shard));
         }
         check(spkm_shard_set_wide_screen(g_shard, 1));           /* rows past the 32-centroid tile: the narrow-tile screen */
+        check(spkm_shard_set_wide_bounds(g_shard, 1));           /* ... and carried bounds there and on columns of more than 64 entries */
         hipFree(d_chunk);
         hipFree(d_sign);
         g_p = p2; g_n = n; g_s = s;

@@ -138,7 +138,9 @@ def lib():
     L.spkm_last_assign_tile.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_shard_reset_policy.argtypes = [_vp]
     L.spkm_shard_set_wide_screen.argtypes = [_vp, C.c_int]
+    L.spkm_shard_set_wide_bounds.argtypes = [_vp, C.c_int]
     L.spkm_last_screen_tile.argtypes = [_vp, C.POINTER(C.c_int64)]
+    L.spkm_last_screen_points.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_dense_assign_dev.argtypes = [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp]
     L.spkm_dense_accumulate_dev.argtypes = [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp]
     L.spkm_last_assign_kernel_ms.argtypes = [_vp, C.POINTER(_dbl)]

@@ -54,6 +54,7 @@ struct spkm_switches {
     bool check_assign = false;    // SPKM_CHECK_ASSIGN: before blocks are skipped, verify the lazy contract on d_assign (debug aid; syncs)
     int force_form = 0;           // SPKM_FORCE_FORM=1|2|3: plain / unconditional two-phase / hinted screen, where legal (test aid, spkm.h)
     bool wide_screen = false;     // SPKM_WIDE_SCREEN: every shard of the context takes the narrow-tile screen (k_screen_wide) past the 32-wide tile, as if opted in
+    bool wide_bounds = false;     // SPKM_WIDE_BOUNDS: every shard of the context that takes the narrow-tile or the 16-lanes-per-point screen carries bounds, as if opted in (spkm_shard_set_wide_bounds)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
 };
 struct spkm_ctx {
@@ -111,6 +112,7 @@ struct spkm_ctx {
     bool last_pair_events = false;   // ... recorded one event per mover (pair events)
     bool last_pt_mode = false;       // ... and listed points instead of 16-point steps
     bool last_hinted = false;        // ... used the hinted two-phase form
+    long long last_screen_n = 0;     // points of the last screen call's shard (spkm_last_screen_points: what a call over all points evaluated)
     char errmsg[256] = {0};
     // data-parallel exchange: an RCCL communicator bound to this context's device and stream (Part 3 of spkm.h)
     void* comm = nullptr; // ncclComm_t
@@ -129,6 +131,7 @@ struct spkm_shard {
     int fixed_s = 0;   // > 0: every column has exactly this many entries
     uint64_t slack = 0; // entries readable past nnz in ir / x
     bool wide = false; // spkm_shard_set_wide_screen: past the 32-wide tile this shard's fused calls take the narrow-tile screen
+    bool wide_bounds = false; // spkm_shard_set_wide_bounds: where this shard takes the narrow-tile or the 16-lanes-per-point screen it carries bounds between calls
     float* xfs = nullptr;  // screen copy for the 4-lanes-per-point kernel: f32 values, columns partitioned by row parity
     void* irs = nullptr;   // ... and their row ids
     bool norms_done = false, xf_done = false;

@@ -899,6 +899,23 @@ extern "C" int spkm_screen_work_totals(spkm_ctx* ctx, int64_t info[2])
     return SPKM_OK;
 }
 
+// Points the last fused call's screen evaluated (n for a call over all points, the length of its list otherwise -- 16 per
+// listed step --, 0: it took no screen) and the running total over the context.  Blocks on the stream.
+extern "C" int spkm_last_screen_points(spkm_ctx* ctx, int64_t info[2])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    info[0] = info[1] = 0;
+    if (ctx->nlist.p) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        unsigned v[3] = {0u, 0u, 0u};
+        HIP_TRY(hipMemcpy(v, (const unsigned*)ctx->nlist.p + 38, sizeof(v), hipMemcpyDeviceToHost));
+        info[1] = (int64_t)(((unsigned long long)v[1] << 32) | v[0]);
+        info[0] = ctx->last_path == 1 ? (int64_t)v[2] : 0;
+    }
+    return SPKM_OK;
+}
+
 extern "C" int spkm_last_screen_rounds(spkm_ctx* ctx, int64_t info[2])
 {
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;

@@ -60,6 +60,7 @@ struct screen_call : spkm_call_in {
     spkm_call_plan pl;
     spkm_zero_jobs zj;
     int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
+    bool carry = false; // this shard carries bounds between screen calls: quad, or carry_bounds (spkm_shard_set_wide_bounds)
     int bstat_n = 0, seg = 0, max_items = 0; // bstat_n: workgroups of k_bounds_steps whose statistics wait in ctx->bstat
     // everything this call needs zeroed, in one launch (flushed in front of the first kernel)
     void zero_later(void* q, size_t bytes) { zj.p[zj.n] = (unsigned*)q; zj.words[zj.n] = bytes / 4; zj.n++; }
@@ -113,7 +114,7 @@ struct screen_call : spkm_call_in {
         zero_later(ctx->nlist.p, 32);
         zero_later((char*)ctx->nlist.p + 40, 128 - 40); // (not the running total at [8..9])
         zero_later(sums, (2 * pk + K + 1) * 8);
-        if (!quad) return SPKM_OK;
+        if (!carry) return SPKM_OK;
         // bounds carried from this shard's previous screen call (screen.hip, k_center_drift): steps whose points provably keep
         // their centroids are skipped.  SPKM_NO_BOUNDS=1: A/B switch (bounds are still maintained).
         if (!sm->hb || sm->hb_npad != pl.npad) {
@@ -129,7 +130,7 @@ struct screen_call : spkm_call_in {
         // data in arbitrary order (spkm_policy::observe): the library's order of the points becomes "by cluster" now
         // (regroup_shard; SPKM_NO_REGROUP=1: A/B switch).  Lazy shards only: with the library's order its own, the caller's
         // buffers are reached through a map, which pays while they are written for the points that move and not for all of them.
-        if (sm->pol.regroup_wanted && !sm->regroup_done && bounds_valid && sm->lazy && mind == nullptr && sm->rec != nullptr &&
+        if (quad && sm->pol.regroup_wanted && !sm->regroup_done && bounds_valid && sm->lazy && mind == nullptr && sm->rec != nullptr &&
             sm->xfs != nullptr && !ctx->sw.no_regroup) {
             if ((rc = regroup_shard<IR>(ctx, sm, K))) return rc;
             sm->regroup_done = true;
@@ -139,6 +140,7 @@ struct screen_call : spkm_call_in {
             HIP_TRY(hipMemsetAsync(sm->hb_cum, 0, 16, ctx->stream));
             sm->cum_par = 0;
         }
+        if (!quad) return SPKM_OK; // (no cluster cache or flags: the exact pass streams every cluster in every call)
         // per-cluster cache / flags of the unchanged-cluster shortcut
         if (!sm->cl_cache || sm->cl_pk != pk || sm->cl_K != K) {
             HIP_TRY(regrow(sm->cl_cache, (2 * pk + 3 * (size_t)K) * 8, &sm->cl_valid));
@@ -208,16 +210,18 @@ struct screen_call : spkm_call_in {
     int bounds()
     {
         const long long npad = pl.npad;
-        if (!quad) {
+        if (!carry) {
             sm->hb_valid = sm->assign_synced = false;
             return SPKM_OK;
         }
+        // (a non-quad shard that carries bounds: no cluster flags -- same is null -- and no hints -- hterm is null)
+        int* same = quad ? sm->cl_flags + 2 * K : (int*)nullptr;
         if (pl.drift) {
             zero_later(sm->hb + 3 * npad + K, 4);
             zero_flush();
             hipLaunchKernelGGL(k_center_drift, dim3(K), dim3(256), 0, ctx->stream, (const double*)sm->hb_centers, C, K, p,
-                               gamma, sm->hb + 3 * npad, sm->cl_flags + 2 * K, ctx->sw.no_support_drift ? 0 : sm->fixed_s,
-                               2.0f * (float)sm->fixed_s / (float)p, sm->hb + 3 * npad + HB_HTERM);
+                               gamma, sm->hb + 3 * npad, same, ctx->sw.no_support_drift ? 0 : sm->fixed_s,
+                               2.0f * (float)sm->fixed_s / (float)p, quad ? sm->hb + 3 * npad + HB_HTERM : (float*)nullptr);
             int rc;
             if ((rc = ensure(ctx, ctx->todo, pl.pt_mode ? (size_t)(npad + 64) * 4 : (size_t)(npad / 16 + 1) * 4))) return rc;
             // (its statistics leave per workgroup, bstat, and are added up by the call's last kernel: same-address atomics of
@@ -256,7 +260,7 @@ struct screen_call : spkm_call_in {
                                (unsigned*)ctx->nlist.p, pl.hinted ? sm->hintu : (float*)nullptr, pl.skip_enabled ? 1 : 0,
                                pl.pt_mode ? 1 : 0, (const double*)(sm->hb_cum + sm->cum_par), sm->hb_cum + (sm->cum_par ^ 1),
                                (int)pl.span, (unsigned*)ctx->bstat.p, pl.erode ? 1 : 0, sp_slack, sp_mask, sp_valid, pl.sp_reset ? 1 : 0,
-                               (const int*)(sm->cl_flags + 2 * K), (const int*)sm->map);
+                               (const int*)same, (const int*)sm->map);
             bstat_n = (int)blocks;
             if (pl.skip_enabled) sm->cum_par ^= 1; // the drift has been added
         }
@@ -276,19 +280,23 @@ struct screen_call : spkm_call_in {
             hipLaunchKernelGGL(k_prep_tiles_f32, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
                                0, ctx->stream, C, p, K, pl.G, gamma, (float*)ctx->t32.p,
                                (unsigned long long*)ctx->cmax.p, pl.pl_last, quad ? 1 : 0, (double*)ctx->ct.p,
-                               quad ? sm->hb_centers : (double*)nullptr);
+                               carry ? sm->hb_centers : (double*)nullptr);
         else
             hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
                                0, ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p,
-                               (unsigned long long*)ctx->cmax.p, (double*)ctx->ct.p);
+                               (unsigned long long*)ctx->cmax.p, (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
         ctx->last_sums_only = false;
         ctx->last_pl_last = pl.pl_last;
         ctx->last_screen_kt = kt;
         ctx->last_screen_tiles = pl.Gs;
         const size_t lds = (size_t)(p + 1) * (kt * 4 + (pl.pl_last == 5 ? 16 : 0)) + 16;
+        // (a non-quad shard that skips on its bounds: the LIST form of k_screen_wide at its width, over the points of todo[])
+        const bool wlist = !quad && pl.skip_enabled;
         const void* kern = quad ? screen_quad_kernel<IR>(pl.nr, pl.prune_a > 0 ? pl.prune_a : pl.nr, pl.pt_mode)
-                                : (kt == SCREEN_KT ? (const void*)k_screen_tile<IR>
-                                                   : (kt == 16 ? (const void*)k_screen_wide<IR, 16> : (const void*)k_screen_wide<IR, 8>));
+                           : wlist ? (kt == SCREEN_KT ? (const void*)k_screen_wide<IR, 32, true>
+                                                      : (kt == 16 ? (const void*)k_screen_wide<IR, 16, true> : (const void*)k_screen_wide<IR, 8, true>))
+                                   : (kt == SCREEN_KT ? (const void*)k_screen_tile<IR>
+                                                      : (kt == 16 ? (const void*)k_screen_wide<IR, 16> : (const void*)k_screen_wide<IR, 8>));
         HIP_TRY(allow_lds(ctx, kern, lds));
         HIP_TRY(timing_begin(ctx));
         const IR* a_ir = quad ? (const IR*)sm->irs : (const IR*)sm->ir;
@@ -313,7 +321,11 @@ struct screen_call : spkm_call_in {
         const int* a_recmap = sm->map;
         void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_extra,
                         &a_hint, &a_hc, &a_cnt, &a_todo, &a_tp, &a_rec, &a_recR, &a_recmap};
-        HIP_TRY(hipLaunchKernel(kern, dim3(quad ? ctx->bmapq_blocks : ctx->bmap_blocks), dim3(1024), args, lds, ctx->stream));
+        // (k_screen_wide: the first twelve, then the list and the counters)
+        void* args_w[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt};
+        const bool wide_args = !quad && (wlist || kt != SCREEN_KT);
+        HIP_TRY(hipLaunchKernel(kern, dim3(quad ? ctx->bmapq_blocks : ctx->bmap_blocks), dim3(1024), wide_args ? args_w : args, lds,
+                                ctx->stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(timing_end(ctx));
         ctx->last_skipping = pl.skip_enabled;
@@ -340,15 +352,15 @@ struct screen_call : spkm_call_in {
                            ((pl.nk_incr ? (size_t)K : 0) + (pl.ev_path ? (size_t)2 * K : 0)) * 4,
                            ctx->stream, (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, pl.Gs,
                            (const float*)sm->xnr, sm->fixed_s, (const unsigned long long*)ctx->cmax.p, (int*)assign,
-                           (int*)ctx->list.p, (unsigned int*)ctx->nlist.p, quad ? sm->hb : (float*)nullptr, pl.npad,
+                           (int*)ctx->list.p, (unsigned int*)ctx->nlist.p, carry ? sm->hb : (float*)nullptr, pl.npad,
                            pl.skip_enabled ? 1 : 0, (const int*)ctx->todo.p,
-                           quad ? (const double*)(sm->hb_cum + sm->cum_par) : (const double*)nullptr, pl.bounds_ok ? 1 : 0,
+                           carry ? (const double*)(sm->hb_cum + sm->cum_par) : (const double*)nullptr, pl.bounds_ok ? 1 : 0,
                            touched, K, nk, pl.lazy_ub ? 1 : 0, ev_pt, ev_k, nk_ev, pl.ev_cap, (unsigned*)ctx->wgstat.p, ev_o,
                            (const int*)sm->map, (pl.trusted && pl.bounds_ok) ? 1 : 0);
         hipLaunchKernelGGL((k_assign_list<IR>), dim3(std::max(1, ctx->num_cus) * 8), dim3(256), 0, ctx->stream,
                            (const long long*)sm->jc, (const IR*)sm->ir, (const double*)sm->x, (const double*)ctx->ct.p, K,
                            sm->fixed_s, (const int*)ctx->list.p, (const unsigned int*)ctx->nlist.p, (int*)assign,
-                           quad ? (int*)(sm->hb + 2 * pl.npad) : (int*)nullptr, pl.bounds_ok ? 1 : 0, (unsigned*)ctx->nlist.p + 5,
+                           carry ? (int*)(sm->hb + 2 * pl.npad) : (int*)nullptr, pl.bounds_ok ? 1 : 0, (unsigned*)ctx->nlist.p + 5,
                            touched, nk, pl.lazy_ub ? sm->hb : (float*)nullptr, ev_pt, ev_k, (unsigned*)ctx->nlist.p,
                            sm->x == nullptr ? (const char*)sm->rec : (const char*)nullptr, sm->rec_R, nk_ev, pl.ev_cap,
                            (const unsigned*)ctx->wgstat.p, cb, ev_o, (const int*)sm->map);
@@ -528,7 +540,9 @@ struct screen_call : spkm_call_in {
         int rc;
         if ((rc = ensure_blk_stats(ctx, (size_t)std::max(ab, max_items)))) return rc;
         if (ctx->tlog_both) HIP_TRY(timing_begin(ctx));
-        float* ub = (quad && sm->map == nullptr) ? sm->hb : (float*)nullptr; // (a regrouped shard: the certificate wrote them)
+        // (a regrouped shard: the certificate wrote them.  A non-quad shard that carries bounds gets EVERY point's fresh upper
+        //  bound here, in every call -- which is why its bounds test erodes nothing)
+        float* ub = (carry && sm->map == nullptr) ? sm->hb : (float*)nullptr;
         ctx->last_exact_pts = pl.pipe ? 16 : pts;
         if (pl.pipe) {
             if ((rc = exact_rec<IR>(!pl.sums_only, mind, ub, ab))) return rc;
@@ -582,9 +596,10 @@ struct screen_call : spkm_call_in {
                            ev ? (const double*)(sm->cl_cache + pk) : (const double*)nullptr, ev ? pk : (size_t)0,
                            ev ? sums : (double*)nullptr, ev ? counts : (double*)nullptr,
                            sm->nlist_pending ? (unsigned*)nullptr : sm->h_nlist_dev, sm->nlist_seq + 1u,
-                           work_steps, work_tiles, pl.nr, ctx->last_rounds_all, work_flags);
+                           work_steps, work_tiles, pl.nr, ctx->last_rounds_all, work_flags, (unsigned long long)n);
         HIP_TRY(hipGetLastError());
-        if (quad) { // the bounds now describe this call: its centroids are what the next call's drift is measured from
+        ctx->last_screen_n = n;
+        if (carry) { // the bounds now describe this call: its centroids are what the next call's drift is measured from
             sm->hb_K = K; sm->hb_gamma = gamma; sm->hb_valid = true;
         }
         if (ev) {
@@ -608,6 +623,7 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     c.kt = kt;
     c.ctx = ctx; c.sm = const_cast<spkm_shard*>(s); c.C = d_centers; c.gamma = gamma; c.assign = d_assign; c.mind = d_mind;
     c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = spkm_screen_quad(kt, s->fixed_s);
+    c.carry_bounds = !c.quad && (s->wide_bounds || ctx->sw.wide_bounds); c.carry = c.quad || c.carry_bounds;
     c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
     c.zj.n = 0;
     c.seg = seg_points(c.n, ctx->num_cus); c.max_items = (int)(c.n / c.seg) + K + 1;

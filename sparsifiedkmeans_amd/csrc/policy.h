@@ -282,6 +282,7 @@ struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;
     bool quad = false;          // the 4-lanes-per-point screen (s <= 64)
+    bool carry_bounds = false;  // this non-quad shard carries bounds (spkm_shard_set_wide_bounds): point lists only
     size_t lds_max = 0;
     int num_cus = 0, teams = 1; // teams: chunk divisor of the screen launch (quad ? bmapq_blocks / 4 : bmap_streams)
     bool no_bounds = false, no_point_list = false, force_point_list = false, no_late_split = false, no_incremental = false,
@@ -380,6 +381,20 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
             // trusted: a REGROUPED shard's buffer of the previous call holds the library's copy, not read nor restored by the
             // test -- while the claim stands (assign_synced; otherwise it may be a new buffer at an old address)
             pl.trusted = in.has_map && in.lazy && !in.want_dist && in.same_assign && in.assign_synced;
+        }
+    } else if (in.carry_bounds) {
+        // the narrow-tile and long-column screens with carried bounds: the test lists POINTS (a step of 16 means nothing
+        // to kernels whose waves hold 8, 16 or 32 points) and the LIST form of k_screen_wide screens them.  Nothing else:
+        // the exact pass runs over every point in every call and writes every upper bound, so nothing is eroded; no
+        // hints, block summaries, events or cluster shortcut.
+        pl.bounds_ok = in.bounds_valid;
+        pl.skip_enabled = pl.bounds_ok && !in.no_bounds;
+        pl.pt_mode = pl.skip_enabled;
+        pl.drift = pl.skip_enabled;
+        if (pl.drift) {
+            pl.span = spkm_plan_span_pt;
+            pl.bgrid = 4 * std::max(1, in.num_cus);
+            while (pl.span > 1024 && (pl.npad + pl.span - 1) / pl.span < 4LL * pl.bgrid) pl.span /= 2;
         }
     }
     pl.prune_a = prune_a;

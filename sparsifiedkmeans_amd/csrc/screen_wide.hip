@@ -1,8 +1,12 @@
 // The certified f32 screen for rows beyond the 32-centroid tile: k_screen_wide<IR, KT> on NARROW tiles of KT = 16 or 8
 // centroids (64- or 32-byte rows), for p up to (LDS - 16) / (4 KT) - 1 -- 2558 / 5118 with 160 KB.  Textually part of
 // api_lloyd.hip, behind screen.hip (whose header carries the certificate's proof and whose k_combine_screen, k_assign_list
-// and exact pass take it from here: the pipeline of the 16-lanes-per-point kernel, k_screen_tile).  Plain form only: no
-// hints, no carried bounds, no point lists, no events -- every call screens every point and runs a full accumulation pass.
+// and exact pass take it from here: the pipeline of the 16-lanes-per-point kernel, k_screen_tile).  No hints, no events,
+// no step lists, and a full accumulation pass in every call.  Two forms: the PLAIN one screens every point; the LIST one
+// (a shard that carries bounds, spkm_shard_set_wide_bounds: the points that k_bounds_steps could not settle) screens the
+// points of todo[] and writes its result planes BY LIST SLOT, as k_screen_quad's point lists do.  The LIST form also
+// exists at KT = 32, 8 lanes per point, for the columns of more than 64 entries that the 4-lanes-per-point kernel does not
+// take: a call over all their points stays with k_screen_tile.
 //
 // Arithmetic, as the proof assumes: t = fl32(x~ + T) with T = -fl32(c), acc = fmaf(t, t, acc), one accumulator per
 // (point, centroid), over the column's s entries in storage order: s roundings of the FMA, none anywhere else.  A slot
@@ -10,19 +14,23 @@
 
 // Twt[g][r][kk] = -fl32(C[(g*kt+kk)*p + r] / gamma), row p zero, rows of kt floats; cmax_bits = max |C/gamma| (f64 bits,
 // atomicMax) and Cs[r*K + k] = C[k*p + r] / gamma (row-major f64 for k_assign_list) in the same launch, as
-// k_prep_tiles_f32 produces them for the 32-wide tile.
+// k_prep_tiles_f32 produces them for the 32-wide tile; keep = C itself, the library's copy that the next call's drift is
+// measured from (a shard that carries bounds; k_center_drift has read the previous copy by now).
 __global__ __launch_bounds__(256) void k_prep_tiles_wide(const double* __restrict__ C, int p, int K, int G, int kt, double gamma,
                                                          float* __restrict__ Twt, unsigned long long* __restrict__ cmax_bits,
-                                                         double* __restrict__ Cs)
+                                                         double* __restrict__ Cs, double* __restrict__ keep = nullptr)
 {
-    if (Cs != nullptr) {
+    if (Cs != nullptr || keep != nullptr) {
         const size_t pkk = (size_t)p * K;
         for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < pkk; t += (size_t)gridDim.x * blockDim.x) {
-            const int k = (int)(t % K);
-            const size_t r = t / K;
-            double v = C[(size_t)k * p + r];
-            if (gamma > 0.0) v = v / gamma;
-            Cs[t] = v;
+            if (keep != nullptr) keep[t] = C[t];
+            if (Cs != nullptr) {
+                const int k = (int)(t % K);
+                const size_t r = t / K;
+                double v = C[(size_t)k * p + r];
+                if (gamma > 0.0) v = v / gamma;
+                Cs[t] = v;
+            }
         }
     }
     const size_t total = (size_t)G * (p + 1) * kt;
@@ -71,33 +79,52 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
     a23 = __builtin_elementwise_fma(t23, t23, a23);
 }
 
-// LG = KT / 4 lanes per point, each owning 4 consecutive centroids of the tile; 64 / LG points per wave (16 / 32).  The
+// LG = KT / 4 lanes per point, each owning 4 consecutive centroids of the tile; 64 / LG points per wave (8 / 16 / 32).  The
 // workgroup keeps one tile in LDS and its waves draw steps of 64 / LG points from an LDS ticket, over the chunks of the
 // blockmap's stream (build_blockmap: the workgroups of the G tiles that stream the same chunks share an XCD's L2), as
-// k_screen_tile does.  The LG lanes of a point fetch LG consecutive entries of its column per round (value and row id,
-// 4 + sizeof(IR) bytes per lane) and hand them round inside the quad by DPP; four rounds are fetched ahead of their use.
+// k_screen_tile does.  The lanes of a point fetch EPR = min(LG, 4) consecutive entries of its column per round (value and
+// row id, 4 + sizeof(IR) bytes per lane) and hand them round inside the quad by DPP; four rounds are fetched ahead of their
+// use.  KT = 32: a point is TWO quads, and both fetch the same 4 entries, e = 4 r + (sub & 3) -- the second quad's loads hit
+// the lines the first one brought, the hand-round stays the quad_perm DPP, and nothing but the ds_read_b128 stream that
+// bounds this kernel goes through the LDS pipe (a ds_swizzle / ds_bpermute broadcast over 8 lanes would compete with it).
 // Nothing past a column's own s entries is read: a slot beyond the end takes x = 0 and row p without a load, and a point
 // past n reads point n - 1 and stores nothing.
+// LIST: the points are todo[0 .. counters[4]) (k_bounds_steps in point mode; the length is read on the device, no host
+// sync).  An empty list returns before the tile is loaded.  Slot q is point todo[q]; its results go to plane g at
+// scr_*[g * n + q] (k_combine_screen<1> reads them by slot); a slot past the length computes on the last listed point and
+// stores nothing.  The slots are dealt to a tile's workgroups in chunks sized from the length, so that every workgroup gets
+// several even for a short list (k_screen_quad sizes chunk_v the same way).  Entries come from the same plain copy.
+// Resources (-Rpass-analysis=kernel-resource-usage, 16- / 32-bit row ids): plain <16> 100 / 96 and <8> 72 / 72 VGPRs, as
+// before the LIST form existed; LIST <32> 98 / 98, <16> 100 / 96, <8> 72 / 72 VGPRs; 65 / 60 SGPRs and no scratch in all.
 // LDS banks.  A ds_read_b128 is served in four groups of 16 lanes, bank = (address / 4) % 64.  The LG lanes of a point
-// read the 16 * LG contiguous bytes of ONE row, so a 16-lane group holds 16 / LG points (4 at KT = 16, 8 at KT = 8) on
-// rows the DATA chooses: a 256-byte bank line holds 256 / (4 KT) rows (4 / 8), and two points of a group collide when
+// read the 16 * LG contiguous bytes of ONE row, so a 16-lane group holds 16 / LG points (2 at KT = 32, 4 at 16, 8 at 8) on
+// rows the DATA chooses: a 256-byte bank line holds 256 / (4 KT) rows (2 / 4 / 8), and two points of a group collide when
 // their rows differ and agree modulo that number.  No layout of the tile moves that: any fixed map of rows to bank
 // offsets leaves rows drawn at random by the sampler colliding at the same rate (the 32-wide kernel lowers it by
 // reordering each point's ENTRIES by row parity in its own copy of the shard, k_screen_reorder; this kernel streams
 // the shard's plain f32 copy).  With uniform rows the largest of 4 points' counts on 4 offsets averages 2.1, of 8 on 8
-// 2.7: the read is that many passes instead of one -- the price of the plain layout, kept because the rows stay
-// 16-byte aligned 64-/32-byte runs that one b128 per lane covers.  Slots on the zero row all read one address (a broadcast).
-template <typename IR, int KT>
+// 2.7 (of 2 on 2: 1.5): the read is that many passes instead of one -- the price of the plain layout, kept because the rows
+// stay 16-byte aligned 128- / 64- / 32-byte runs that one b128 per lane covers.  Slots on the zero row all read one address
+// (a broadcast).
+template <typename IR, int KT, bool LIST = false>
 __global__ __launch_bounds__(1024) void k_screen_wide(
     const IR* __restrict__ ir, const float* __restrict__ xval, const float* __restrict__ Twt, int p, int n,
     int fixed_s, int K, const spkm_blockmap* __restrict__ bmap, int chunk_points, float* __restrict__ scr_m1,
-    float* __restrict__ scr_m2, int* __restrict__ scr_k)
+    float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo = nullptr,
+    const unsigned* __restrict__ counters = nullptr)
 {
-    static_assert(KT == 16 || KT == 8, "tiles of 16 or 8 centroids");
+    static_assert(KT == 16 || KT == 8 || (KT == 32 && LIST), "tiles of 16 or 8 centroids; 32 for lists only");
     constexpr int LG = KT / 4, PPW = 64 / LG, ROWB = KT * 4, UN = 4;
+    constexpr int EPR = LG < 4 ? LG : 4; // entries per round: the lanes of a quad that belong to one point
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const spkm_blockmap bm = bmap[blockIdx.x];
     if (bm.tile < 0) return;
+    int tp = 0; // LIST: the list's length
+    if constexpr (LIST) {
+        tp = (int)counters[4];
+        if (tp <= 0) return; // an empty list: not even the tile is loaded
+        if (tp > n) tp = n;
+    }
     const int g = bm.tile;
     const int tid = threadIdx.x;
     const size_t tile_bytes = (size_t)(p + 1) * ROWB;
@@ -111,12 +138,16 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
 
     const int lane = tid & 63;
     const int sub = lane & (LG - 1), ps = lane / LG;
+    const int esub = sub & (EPR - 1);
     const char* mytile = smem + sub * 16;
     const int s = fixed_s;
-    const int nr = (s + LG - 1) / LG; // rounds of LG entries
+    const int nr = (s + EPR - 1) / EPR; // rounds of EPR entries
     const int zero_off = p * ROWB;
-    const int nchunks = (n + chunk_points - 1) / chunk_points;
-    const int R = chunk_points / PPW;
+    // (LIST: chunks small enough that every workgroup of the tile gets several, whatever the length)
+    const int nv = LIST ? tp : n;
+    const int chunk_v = LIST ? max(256, min(chunk_points, (nv / (bm.nstreams * 2)) & ~255)) : chunk_points;
+    const int nchunks = (nv + chunk_v - 1) / chunk_v;
+    const int R = chunk_v / PPW;
     const int my_chunks = (nchunks > bm.stream) ? (nchunks - bm.stream + bm.nstreams - 1) / bm.nstreams : 0;
     const int T = my_chunks * R;
     float* m1o = scr_m1 + (size_t)g * n;
@@ -132,17 +163,18 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
     };
     for (int u = draw(); u < T; u = draw()) {
         const int ci = u / R;
-        const int base = (bm.stream + ci * bm.nstreams) * chunk_points + (u - ci * R) * PPW;
-        if (base >= n) continue; // (the last chunk's steps past the shard)
-        const int i = base + ps;
-        const size_t col = (size_t)(i < n ? i : n - 1) * (size_t)s;
+        const int base = (bm.stream + ci * bm.nstreams) * chunk_v + (u - ci * R) * PPW;
+        if (base >= nv) continue; // (the last chunk's steps past the shard / the list)
+        const int i = base + ps;  // the point; LIST: the list slot
+        const int pt = LIST ? todo[i < nv ? i : nv - 1] : (i < n ? i : n - 1);
+        const size_t col = (size_t)pt * (size_t)s;
         const float* xp = xval + col;
         const IR* rp = ir + col;
         int xv[UN], ro[UN];
         auto fetch = [&](int r0, int (&xo)[UN], int (&oo)[UN]) {
 #pragma unroll
             for (int c = 0; c < UN; c++) {
-                const int e = (r0 + c) * LG + sub;
+                const int e = (r0 + c) * EPR + esub;
                 const bool in = e < s;
                 xo[c] = in ? __builtin_bit_cast(int, xp[e]) : 0;
                 oo[c] = in ? (int)rp[e] * ROWB : zero_off;
@@ -155,11 +187,11 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
             fetch(r0 + UN, xn, rn); // (past the column: no loads, zero slots)
 #pragma unroll
             for (int c = 0; c < UN; c++) {
-                wide_entry(mytile, wide_bcast<LG, 0>(xv[c]), wide_bcast<LG, 0>(ro[c]), a01, a23);
-                wide_entry(mytile, wide_bcast<LG, 1>(xv[c]), wide_bcast<LG, 1>(ro[c]), a01, a23);
-                if (LG == 4) {
-                    wide_entry(mytile, wide_bcast<LG, 2 % LG>(xv[c]), wide_bcast<LG, 2 % LG>(ro[c]), a01, a23);
-                    wide_entry(mytile, wide_bcast<LG, 3 % LG>(xv[c]), wide_bcast<LG, 3 % LG>(ro[c]), a01, a23);
+                wide_entry(mytile, wide_bcast<EPR, 0>(xv[c]), wide_bcast<EPR, 0>(ro[c]), a01, a23);
+                wide_entry(mytile, wide_bcast<EPR, 1>(xv[c]), wide_bcast<EPR, 1>(ro[c]), a01, a23);
+                if (EPR == 4) {
+                    wide_entry(mytile, wide_bcast<EPR, 2 % EPR>(xv[c]), wide_bcast<EPR, 2 % EPR>(ro[c]), a01, a23);
+                    wide_entry(mytile, wide_bcast<EPR, 3 % EPR>(xv[c]), wide_bcast<EPR, 3 % EPR>(ro[c]), a01, a23);
                 }
             }
 #pragma unroll
@@ -189,7 +221,7 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
 #pragma unroll
         for (int o = 1; o < LG; o <<= 1) m2 = fminf(m2, __shfl_xor(m2, o));
         const bool none = first == LG;
-        if (sub == (none ? 0 : first) && i < n) {
+        if (sub == (none ? 0 : first) && i < nv) {
             m1o[i] = none ? __builtin_inff() : m1;
             m2o[i] = none ? __builtin_inff() : m2;
             ko[i] = none ? -1 : kfirst + li;

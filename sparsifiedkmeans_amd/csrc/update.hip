@@ -875,8 +875,18 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
                             const double* __restrict__ cache_c = nullptr, size_t pk = 0, double* __restrict__ sums = nullptr,
                             double* __restrict__ counts = nullptr, unsigned* __restrict__ host_out = nullptr, unsigned seq = 0u,
                             unsigned long long work_steps = 0ull, int work_tiles = 0, int work_nr = 0, int work_a = 0,
-                            int work_flags = 0)
+                            int work_flags = 0, unsigned long long screen_n = 0ull)
 {
+    // screen_n: the shard's points -- what this call's screen evaluated: all of them, or (work_flags & 2) the points of its
+    // list, 16 per listed step -- into counters[40], and added to the running total at counters[38..39]
+    // (spkm_last_screen_points)
+    if (screen_n > 0ull && blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned long long v = screen_n;
+        if (work_flags & 2) v = (work_flags & 4) ? (unsigned long long)counters[4] : (unsigned long long)counters[4] * 16ull;
+        if (v > screen_n) v = screen_n;
+        counters[40] = (unsigned)v;
+        *reinterpret_cast<unsigned long long*>(counters + 38) += v;
+    }
     // work_*: what this call's 4-lanes-per-point screen launch did, in ROUNDS (4 stored entries of 16 points against the
     // centroids of one tile) -- counters[34..35] += rounds executed for all centroids of a tile, counters[36..37] += rounds of
     // a launch that does all the work (work_steps = ceil(n / 16) steps x work_tiles x work_nr); running totals, read by

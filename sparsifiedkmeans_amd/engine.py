@@ -87,6 +87,13 @@ class Shard:
         state is forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_wide_screen(self.handle, 1 if on else 0), "spkm_shard_set_wide_screen")
 
+    def set_wide_bounds(self, on: bool = True):
+        """Let this shard carry its per-point distance bounds between fused calls also where it leaves the
+        4-lanes-per-point screen -- the narrow tiles of set_wide_screen() AND columns of more than 64 entries -- so that a
+        call screens only the points the bounds do not settle (spkm_shard_set_wide_bounds; off by default at the C
+        interface).  Outputs never depend on it; the shard's policy state and bounds are forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_wide_bounds(self.handle, 1 if on else 0), "spkm_shard_set_wide_bounds")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""
@@ -367,6 +374,14 @@ class LloydEngine:
         took no screen, its number of tiles) -- spkm_last_screen_tile."""
         a = (C.c_int64 * 2)()
         _lib.check(_lib.lib().spkm_last_screen_tile(self.ctx.handle, a))
+        return int(a[0]), int(a[1])
+
+    def last_screen_points(self) -> tuple[int, int]:
+        """(points the last fused call's screen evaluated: n for a call over all points, the length of its list when it
+        skipped on the carried bounds, 0 = it took no screen; the running total on this context; blocks) --
+        spkm_last_screen_points."""
+        a = (C.c_int64 * 2)()
+        _lib.check(_lib.lib().spkm_last_screen_points(self.ctx.handle, a))
         return int(a[0]), int(a[1])
 
     def iterate(self, centers: torch.Tensor, want_mind: bool = True):

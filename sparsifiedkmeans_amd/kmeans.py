@@ -51,8 +51,10 @@ _DEFAULTS = dict(
     DataFile=None, MB_limit=500, DataFileVerbose=False, SparsityIgnoreUpsampling=False, FORCE_BUG=False,
     tryBuiltinMex=True, unbiasedDistance=True, unbiasedInitialization=True, denseCenters=False)
 # Python-side additions (not reference options).  wideScreen: rows too long for the screen's 32-centroid tile (p2 > 1278 with
-# 160 KB of LDS) are screened on narrow tiles instead of running the all-exact kernels (Shard.set_wide_screen); False: off
-_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True)
+# 160 KB of LDS) are screened on narrow tiles instead of running the all-exact kernels (Shard.set_wide_screen); False: off.
+# wideBounds: on those tiles, and with more than 64 entries per column, the shard carries its distance bounds between
+# iterations and a call screens only the points they do not settle (Shard.set_wide_bounds); False: every call screens all
+_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True)
 
 
 def _parse(opts: dict) -> dict:
@@ -349,6 +351,7 @@ def kmeans_sparsified(X, K, **options):
     lazy_stats = Display != "iter"
     shard.set_lazy_stats(lazy_stats)
     shard.set_wide_screen(bool(o["wideScreen"]))
+    shard.set_wide_bounds(bool(o["wideBounds"]))
     if Display in ("iter", "final"):
         print(f"Randomly mixing of type {sk}")
         print(f"Randomly taking {100 * gamma:.1f}% of the data; actual dataset is {100 * nnz / (p2 * n):.1f}% sparse")
@@ -437,6 +440,7 @@ def kmeans_sparsified(X, K, **options):
         dist_t = eng.mind                     # min-distances of the latest iteration (survives a 'drop' re-build of eng)
         mind_pending, eng_used, centers_used = False, eng, centers
         fused_iters = 0
+        screened0 = eng.last_screen_points()[1]   # (the context's running total: this replicate's share is the difference)
         for its in range(1, int(o["MaxIter"]) + 1):
             # [assignments,distances] = findClusters(X,centers) (:420) and the per-cluster sums of :430-453
             host_res = None
@@ -561,6 +565,8 @@ def kmeans_sparsified(X, K, **options):
         # (not reference fields) how many iterations went through the fused call, and which path the library took for
         # the last of them: 1 = certified screen + exact confirmation, 0 = all-exact kernels
         OUTPUT.setdefault("fusedIterations", np.zeros(Replicates, int))[trial] = fused_iters
+        # ... and how many points their screens evaluated in all: fusedIterations x n unless carried bounds settled some
+        OUTPUT.setdefault("screenedPoints", np.zeros(Replicates, np.int64))[trial] = eng.last_screen_points()[1] - screened0
         OUTPUT.setdefault("lastPath", np.zeros(Replicates, int))[trial] = last_path
         distances = dist_t.cpu().numpy()
         if obj < best["obj"]:                                                    # :493-503
