@@ -213,14 +213,12 @@ def _drift_for_kept_share(run, shard, Cm, rng, moving, share=0.75):
     return out
 
 
-@pytest.mark.parametrize("nr,s,bits,order,K", CASES, ids=[f"nr{c[0]}-s{c[1]}-ir{c[2]}-{c[3]}-K{c[4]}" for c in CASES])
-def test_every_launch_kind_of_the_quad_screen_equals_the_oracle(gpu_ctx, oracle, monkeypatch, nr, s, bits, order, K):
+def script(run, gpu_ctx, Y, gam, base, bits):
+    """the scripted sequence of fused calls of one case (run: a Run, or a subclass that asserts more after every call);
+    returns whether the regrouped sub-case regrouped its shard (None: no such sub-case)"""
     from sparsifiedkmeans_amd.engine import LloydEngine
 
-    assert (s + 3) // 4 == nr
-    lazy = order == "arbitrary"
-    Y, gam, base = _data(oracle, nr, s, K, order, seed=1000 * nr + 10 * K + bits)
-    run = Run(oracle, gpu_ctx, monkeypatch, Y, gam, K, nr, s, lazy)
+    K, nr, s, lazy = run.K, run.nr, run.s, run.lazy
     run.switch("SPKM_NO_REGROUP", True)
     sh = _shard(gpu_ctx, Y, bits)
     if lazy:
@@ -294,6 +292,17 @@ def test_every_launch_kind_of_the_quad_screen_equals_the_oracle(gpu_ctx, oracle,
         sh.set_lazy_stats(False)
         if s >= 8 and not regrouped:
             run.bad("the regrouped sub-case did not regroup the shard")
+
+    return regrouped
+
+
+@pytest.mark.parametrize("nr,s,bits,order,K", CASES, ids=[f"nr{c[0]}-s{c[1]}-ir{c[2]}-{c[3]}-K{c[4]}" for c in CASES])
+def test_every_launch_kind_of_the_quad_screen_equals_the_oracle(gpu_ctx, oracle, monkeypatch, nr, s, bits, order, K):
+    assert (s + 3) // 4 == nr
+    lazy = order == "arbitrary"
+    Y, gam, base = _data(oracle, nr, s, K, order, seed=1000 * nr + 10 * K + bits)
+    run = Run(oracle, gpu_ctx, monkeypatch, Y, gam, K, nr, s, lazy)
+    regrouped = script(run, gpu_ctx, Y, gam, base, bits)
 
     want = set(F.expected_kinds(nr, False).values())
     if lazy:
