@@ -269,7 +269,7 @@ extern "C" int spkm_shard_create_dev(spkm_ctx* ctx, uint64_t p, uint64_t n, uint
     s->jc = (long long*)d_jc; s->ir = (void*)d_ir; s->x = (double*)d_x; s->owned = false; s->owned_csc = false;
     s->slack = capacity - nnz;
     if (n > 0 && nnz > 0 && nnz % n == 0 && nnz / n <= 0x7fffffffull) {
-        int rc = ensure(ctx, ctx->nitems, 64);
+        int rc = ensure(ctx, ctx->nitems, NI_WORDS * 4);
         if (rc) { delete s; return rc; }
         int one = 1, flag = 0;
         hipError_t e = hipMemcpyAsync(ctx->nitems.p, &one, 4, hipMemcpyHostToDevice, ctx->stream);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/spkm.h"
+#include "layout.h"
 #include "policy.h"
 
 #include <dlfcn.h>
@@ -57,6 +58,27 @@ struct spkm_switches {
     bool wide_bounds = false;     // SPKM_WIDE_BOUNDS: every shard of the context that takes the narrow-tile or the 16-lanes-per-point screen carries bounds, as if opted in (spkm_shard_set_wide_bounds)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
 };
+// What one fused call did on the screen path: written by the stages of that call (screen_call, api_lloyd_fused.inc), read
+// by its tail and by the policy's bookkeeping, then stored in the context for the spkm_last_* accessors -- after a
+// successful screen call; a call that takes the exact path stores a default-constructed one (path 0: every accessor's
+// "no screen" answer).  After a FAILED call the context's report is unspecified (the previous call's, or the exact path's).
+struct spkm_screen_report {
+    int path = 0;                 // 0 = exact tiled/generic, 1 = f32 screen + exact confirmation
+    int kt = 0, tiles = 0;        // centroids per tile and tiles of the screen
+    int pl_last = 0;              // the plan: centroid pairs per lane of its last tile (5: carried)
+    int rounds_all = 0, rounds = 0; // rounds for all centroids / total rounds of a 4-lanes-per-point screen
+    int mode = 0;                 // 0 plain screen, 1 two-phase, 2 hinted two-phase
+    bool hinted = false;          // the hinted two-phase form ...
+    bool hint_late = false;       // ... with the late split
+    bool skipping = false;        // the carried-bounds test ran ...
+    bool pt_mode = false;         // ... and listed points instead of 16-point steps
+    bool lib_valid = false;       // the call could compare with the library's previous assignment (movers counted)
+    bool incremental = false;     // the sums were updated by events (no exact pass) ...
+    bool direct_events = false;   // ... applied one by one (k_events_direct)
+    bool pair_events = false;     // ... one event per mover (pair events)
+    bool sums_only = false;       // the full pass left the distances out (lazy statistics)
+    bool dual = false;            // both forms were queued; the device chose (counters[NL_GATE_FULL]: the full pass)
+};
 struct spkm_ctx {
     int device = 0;
     spkm_switches sw;
@@ -92,27 +114,12 @@ struct spkm_ctx {
     long long sort_n = 0;
     bool tlog_both = false; // fused screen path: log the exact accumulation kernel too (pairs alternate)
     int assign_KT = 0, assign_G = 0; // of the last assign call
-    int last_screen_kt = 0, last_screen_tiles = 0; // centroids per tile and tiles of the last fused call's screen (0: it took none)
-    int last_pl_last = 0;            // the last screen call's plan: centroid pairs per lane of its last tile (5: carried)
+    spkm_screen_report last;         // of the last spkm_assign_accumulate_dev
     int last_exact_pts = 0;          // points staged per wave by the last exact pass / K = 1 stream (16: the pipelined kernel)
     int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics
     int last_dist_form = 0;          // the last distances call: 1 streaming record kernel, 2 generic kernel
-    int last_path = 0;               // 0 = exact tiled/generic, 1 = f32 screen + exact confirmation
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
-    bool last_hint_late = false; // the last hinted call used the late split
-    int last_rounds_all = 0, last_rounds = 0; // rounds for all centroids / total rounds of the last 4-lane screen call
     bool sort_perm_valid = false;    // ... and perm / offs / items really hold that call's counting sort (not after an incremental call)
-    bool last_lib_valid = false;     // the last screen call could compare with the library's previous assignment (movers counted)
-    bool last_incremental = false;   // the last screen call updated the sums by events (no exact pass)
-    bool last_sums_only = false;     // the last screen call's full pass left the distances out (lazy statistics)
-    bool last_dual = false;          // the last screen call queued both forms; the device chose (counters[19]: the full pass)
-    int last_mode = 0;               // 0 plain screen, 1 two-phase, 2 hinted two-phase (last screen call)
-    bool last_skipping = false;      // the last screen call ran the carried-bounds test
-    bool last_direct_events = false; // ... applied its events one by one (k_events_direct)
-    bool last_pair_events = false;   // ... recorded one event per mover (pair events)
-    bool last_pt_mode = false;       // ... and listed points instead of 16-point steps
-    bool last_hinted = false;        // ... used the hinted two-phase form
-    long long last_screen_n = 0;     // points of the last screen call's shard (spkm_last_screen_points: what a call over all points evaluated)
     char errmsg[256] = {0};
     // data-parallel exchange: an RCCL communicator bound to this context's device and stream (Part 3 of spkm.h)
     void* comm = nullptr; // ncclComm_t
@@ -143,9 +150,9 @@ struct spkm_shard {
     bool rec_tried = false; // one attempt per shard (no retry every call when memory is short)
     // screen bookkeeping of THIS data set (see spkm_assign_accumulate_dev)
     // the screen call's counters for the host policy, written by the call's last kernel (k_call_tail) straight into pinned,
-    // device-mapped host memory: 16 counters, then the call's sequence number (system-scope release).  The host looks at
+    // device-mapped host memory: SPKM_REPORT_WORDS counters (layout.h), then the call's sequence number (system-scope release).  The host looks at
     // them one call later, and only if the number is the one it is waiting for -- no copy, no event, no wait on the hot
-    // path (the copy and its event cost a settled iteration 10 of its 230 us).  SPKM_REPORT_WORDS counters (update.hip).
+    // path (the copy and its event cost a settled iteration 10 of its 230 us).
     unsigned* h_nlist = nullptr;
     unsigned* h_nlist_dev = nullptr; // the same memory as the device addresses it
     unsigned nlist_seq = 0;          // number of the report the host is waiting for (nlist_pending)
@@ -154,7 +161,7 @@ struct spkm_shard {
     // hinted two-phase screen: the hints (written by k_bounds_steps from the carried bounds)
     float* hintu = nullptr;   // per-point hints of the two-phase screen (k_bounds_steps), npad floats
     long long hintu_len = 0;
-    // bounds carried between screen calls (screen.hip, k_center_drift): ub | lb | assignment | drift table, the
+    // bounds carried between screen calls (screen.hip, k_center_drift; laid out by layout.h, hb_*), the
     // centroids of the call that produced them, and whether they describe this shard's previous call
     float* hb = nullptr;
     double* hb_centers = nullptr;
@@ -163,10 +170,7 @@ struct spkm_shard {
     int hb_K = 0;
     double hb_gamma = 0.0;
     bool hb_valid = false;
-    // unchanged-cluster shortcut of the exact pass (screen.hip, k_cluster_need): per-cluster cache of the LOCAL sums and
-    // counts (2 p K doubles), obj2 / max distance / its index (3 K), flags need | touched | same | ibeg | icnt (5 K ints)
-    // block summaries of the carried bounds (screen.hip, k_bounds_steps): per 1024 points the clusters present (K <= 128
-    // bits), the smallest slack between the bounds, a valid flag -- one allocation of 24 B per block
+    // block summaries of the carried bounds (screen.hip, k_bounds_steps; layout.h, sp_*): one allocation
     char* sp = nullptr;
     long long sp_blocks = 0;
     bool sp_clean = false;            // the last call that wrote bounds maintained the summaries
@@ -175,6 +179,7 @@ struct spkm_shard {
                                       // repaired all of it and nobody -- set_lazy_stats, reset_policy, another entry point -- has ended the claim since
     double* hb_cum = nullptr;  // [2]: drift accumulated since the lower bounds were stored (screen.hip, k_bounds_steps), by call parity
     int cum_par = 0;
+    // unchanged-cluster shortcut of the exact pass (screen.hip, k_cluster_need): per-cluster cache and flags (layout.h, cc_* / CL_*)
     double* cl_cache = nullptr;
     int* cl_flags = nullptr;
     size_t cl_pk = 0;

@@ -178,14 +178,14 @@ static int regroup_shard(spkm_ctx* ctx, spkm_shard* sm, int K)
     if ((e = hipMalloc((void**)&keys, (size_t)n * 4 + 64)) != hipSuccess) return fail(e, "hipMalloc(keys)");
     if ((e = hipMalloc((void**)&perm, (size_t)n * 4 + 64)) != hipSuccess) return fail(e, "hipMalloc(perm)");
     if ((e = hipMalloc((void**)&newmap, (size_t)n * 4 + 64)) != hipSuccess) return fail(e, "hipMalloc(map)");
-    if ((e = hipMalloc((void**)&hb_new, ((size_t)3 * npad + HB_TAIL) * 4)) != hipSuccess) return fail(e, "hipMalloc(bounds)");
+    if ((e = hipMalloc((void**)&hb_new, hb_floats(npad) * 4)) != hipSuccess) return fail(e, "hipMalloc(bounds)");
     int rc;
     if ((rc = ensure(ctx, ctx->hist2, (size_t)K2 * 8))) return rc;
     if ((rc = ensure(ctx, ctx->offs2, (size_t)(K2 + 1) * 8))) return rc;
     if ((rc = ensure(ctx, ctx->cursor2, (size_t)K2 * 8))) return rc;
     constexpr int RG_SEG = 2048; // (the plan's items are not used: only its offsets and cursors)
     if ((rc = ensure(ctx, ctx->items2, (size_t)((n / RG_SEG) + K2 + 1) * 16))) return rc;
-    if ((rc = ensure(ctx, ctx->nitems, 64))) return rc;
+    if ((rc = ensure(ctx, ctx->nitems, NI_WORDS * 4))) return rc;
     const unsigned g1 = (unsigned)std::min<long long>(4096, (n + 255) / 256);
     hipLaunchKernelGGL(k_regroup_keys, dim3(g1), dim3(256), 0, ctx->stream, (const float*)sm->hb, npad, n, K,
                        (const double*)(sm->hb_cum + sm->cum_par), keys);
@@ -193,7 +193,7 @@ static int regroup_shard(spkm_ctx* ctx, spkm_shard* sm, int K)
     hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K2 * 4, ctx->stream,
                        (const int*)keys, n, K2, (unsigned long long*)ctx->hist2.p, (const unsigned*)nullptr);
     hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->hist2.p, K2, RG_SEG,
-                       (long long*)ctx->offs2.p, (unsigned long long*)ctx->cursor2.p, (int4*)ctx->items2.p, (int*)ctx->nitems.p + 4,
+                       (long long*)ctx->offs2.p, (unsigned long long*)ctx->cursor2.p, (int4*)ctx->items2.p, (int*)ctx->nitems.p + NI_REGROUP,
                        (const unsigned*)nullptr);
     {
         const int sb = (int)std::max<long long>(std::min<long long>(1024, (n + 1023) / 1024), std::min<long long>(8192, n / 4096));
@@ -204,7 +204,7 @@ static int regroup_shard(spkm_ctx* ctx, spkm_shard* sm, int K)
     }
     hipLaunchKernelGGL(k_regroup_apply, dim3(g1), dim3(256), 0, ctx->stream, (const int*)perm, (const int*)sm->map, newmap,
                        (const float*)sm->hb, hb_new, npad, n);
-    HIP_TRY(hipMemcpyAsync(hb_new + 3 * npad, sm->hb + 3 * npad, (size_t)HB_TAIL * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hb_new + hb_delta(npad), sm->hb + hb_delta(npad), (size_t)HB_TAIL * 4, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(hipGetLastError());
     // the screen copy and the norms in the new order, over the old ones (their source is the records)
     hipLaunchKernelGGL((k_screen_reorder<IR>), dim3((unsigned)std::min<long long>((n + 15) / 16, 16384)), dim3(256), 0, ctx->stream,
@@ -696,7 +696,7 @@ extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t 
             if ((rc = ensure(ctx, ctx->offs, (size_t)(K + 1) * 8))) return rc;
             if ((rc = ensure(ctx, ctx->cursor, (size_t)K * 8))) return rc;
             if ((rc = ensure(ctx, ctx->items, (size_t)max_items * 16))) return rc;
-            if ((rc = ensure(ctx, ctx->nitems, 64))) return rc;
+            if ((rc = ensure(ctx, ctx->nitems, NI_WORDS * 4))) return rc;
             hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream,
                                (const unsigned long long*)ctx->nk.p, K, SEG_POINTS, (long long*)ctx->offs.p,
                                (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p, (int*)ctx->nitems.p, (const unsigned*)nullptr);
@@ -759,14 +759,8 @@ static int run_distances(spkm_ctx* ctx, const spkm_shard* s, int K, const double
         bool have_sort = ctx->sort_owner == (const void*)s && ctx->sort_perm_valid && ctx->sort_K == K && ctx->sort_n == n &&
                          s->hb && s->hb_valid && s->hb_npad == npad;
         if (have_sort) {
-            if ((rc = ensure(ctx, ctx->nlist, 256))) return rc;
-            unsigned* cnt = (unsigned*)ctx->nlist.p + 20;
-            HIP_TRY(hipMemsetAsync(cnt, 0, 4, ctx->stream));
-            hipLaunchKernelGGL(k_count_diff_i32, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const int*)d_assign, (const int*)(s->hb + 2 * npad), n, cnt, (const int*)s->map);
             unsigned diff = 1;
-            HIP_TRY(hipMemcpyAsync(&diff, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream)); // an end-of-run call, not the hot path
+            if ((rc = ensure(ctx, ctx->nlist, NL_WORDS * 4)) || (rc = count_assign_diff(ctx, s, d_assign, npad, &diff))) return rc;
             have_sort = diff == 0;
         }
         const int seg = have_sort ? ctx->sort_seg : seg_points(n, ctx->num_cus);
@@ -780,7 +774,7 @@ static int run_distances(spkm_ctx* ctx, const spkm_shard* s, int K, const double
             if ((rc = ensure(ctx, ctx->offs, (size_t)(K + 1) * 8))) return rc;
             if ((rc = ensure(ctx, ctx->cursor, (size_t)K * 8))) return rc;
             if ((rc = ensure(ctx, ctx->items, (size_t)max_items * 16))) return rc;
-            if ((rc = ensure(ctx, ctx->nitems, 64))) return rc;
+            if ((rc = ensure(ctx, ctx->nitems, NI_WORDS * 4))) return rc;
             HIP_TRY(hipMemsetAsync(ctx->dn_nk.p, 0, (size_t)K * 8, ctx->stream));
             hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
                                ctx->stream, (const int*)d_assign, n, K, (unsigned long long*)ctx->dn_nk.p, (const unsigned*)nullptr);
@@ -876,10 +870,10 @@ extern "C" int spkm_exact_pass_points(spkm_ctx* ctx, int64_t info[2])
     if (ctx->nlist.p) {
         HIP_TRY(hipSetDevice(ctx->device));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        unsigned v[34] = {0};
+        unsigned v[NL_EXACT_TOTAL + 2] = {0};
         HIP_TRY(hipMemcpy(v, ctx->nlist.p, sizeof(v), hipMemcpyDeviceToHost));
-        info[0] = (int64_t)(((unsigned long long)v[33] << 32) | v[32]);
-        info[1] = v[13];
+        info[0] = (int64_t)(((unsigned long long)v[NL_EXACT_TOTAL + 1] << 32) | v[NL_EXACT_TOTAL]);
+        info[1] = v[NL_EXACT_PTS];
     }
     return SPKM_OK;
 }
@@ -891,8 +885,9 @@ extern "C" int spkm_screen_work_totals(spkm_ctx* ctx, int64_t info[2])
     if (ctx->nlist.p) {
         HIP_TRY(hipSetDevice(ctx->device));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
+        static_assert(NL_ROUNDS_FULL == NL_ROUNDS_DONE + 2, "the two totals are copied together");
         unsigned long long v[2] = {0ull, 0ull};
-        HIP_TRY(hipMemcpy(v, (const unsigned*)ctx->nlist.p + 34, sizeof(v), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v, (const unsigned*)ctx->nlist.p + NL_ROUNDS_DONE, sizeof(v), hipMemcpyDeviceToHost));
         info[0] = (int64_t)v[0];
         info[1] = (int64_t)v[1];
     }
@@ -908,10 +903,11 @@ extern "C" int spkm_last_screen_points(spkm_ctx* ctx, int64_t info[2])
     if (ctx->nlist.p) {
         HIP_TRY(hipSetDevice(ctx->device));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
+        static_assert(NL_SCREENED == NL_SCREENED_TOTAL + 2, "the total and the call's count are copied together");
         unsigned v[3] = {0u, 0u, 0u};
-        HIP_TRY(hipMemcpy(v, (const unsigned*)ctx->nlist.p + 38, sizeof(v), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v, (const unsigned*)ctx->nlist.p + NL_SCREENED_TOTAL, sizeof(v), hipMemcpyDeviceToHost));
         info[1] = (int64_t)(((unsigned long long)v[1] << 32) | v[0]);
-        info[0] = ctx->last_path == 1 ? (int64_t)v[2] : 0;
+        info[0] = ctx->last.path == 1 ? (int64_t)v[2] : 0; // (the slot keeps the last SCREEN call's count)
     }
     return SPKM_OK;
 }
@@ -919,8 +915,8 @@ extern "C" int spkm_last_screen_points(spkm_ctx* ctx, int64_t info[2])
 extern "C" int spkm_last_screen_rounds(spkm_ctx* ctx, int64_t info[2])
 {
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
-    info[0] = ctx->last_path == 1 ? ctx->last_rounds_all : 0;
-    info[1] = ctx->last_path == 1 ? ctx->last_rounds : 0;
+    info[0] = ctx->last.rounds_all;
+    info[1] = ctx->last.rounds;
     return SPKM_OK;
 }
 
@@ -930,23 +926,20 @@ extern "C" int spkm_last_screen_mode(spkm_ctx* ctx, int64_t info[8])
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
     info[0] = -1;
     info[1] = info[2] = info[3] = info[4] = info[5] = info[6] = info[7] = 0;
-    if (ctx->last_path == 1 && ctx->nlist.p) {
+    const spkm_screen_report& r = ctx->last;
+    if (r.path == 1 && ctx->nlist.p) {
         HIP_TRY(hipSetDevice(ctx->device));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        unsigned v[10] = {0};
-        HIP_TRY(hipMemcpy(v, ctx->nlist.p, 40, hipMemcpyDeviceToHost));
-        info[0] = ctx->last_mode;
-        for (int j = 0; j < 4; j++) info[1 + j] = v[j];
-        info[5] = (int64_t)(((unsigned long long)v[9] << 32) | v[8]);
+        unsigned v[SPKM_REPORT_WORDS] = {0};
+        HIP_TRY(hipMemcpy(v, ctx->nlist.p, sizeof(v), hipMemcpyDeviceToHost));
+        info[0] = r.mode;
+        info[1] = v[NL_LISTED]; info[2] = v[NL_AMBIG]; info[3] = v[NL_EARLY]; info[4] = v[NL_SKIPPED];
+        info[5] = (int64_t)(((unsigned long long)v[NL_SKIPPED_TOTAL + 1] << 32) | v[NL_SKIPPED_TOTAL]);
         // how the call got its sums: 0 full pass with every distance, 2 incremental (events),
         // 3 full pass without distances (sums only)
-        info[6] = ctx->last_incremental ? (ctx->last_direct_events ? 4 : 2) : (ctx->last_sums_only ? 3 : 0);
-        if (ctx->last_dual) { // both forms were queued: which one the device opened (k_pick_form)
-            unsigned f[2] = {0, 0};
-            HIP_TRY(hipMemcpy(f, (const unsigned*)ctx->nlist.p + 18, 8, hipMemcpyDeviceToHost));
-            info[6] = f[1] ? 3 : 2;
-        }
-        info[7] = ctx->last_pt_mode ? 2 : 0; // 2: point-granular list
+        info[6] = r.incremental ? (r.direct_events ? 4 : 2) : (r.sums_only ? 3 : 0);
+        if (r.dual) info[6] = v[NL_GATE_FULL] ? 3 : 2; // both forms were queued: which one the device opened (k_pick_form)
+        info[7] = r.pt_mode ? 2 : 0; // 2: point-granular list
     }
     return SPKM_OK;
 }
@@ -954,9 +947,9 @@ extern "C" int spkm_last_screen_mode(spkm_ctx* ctx, int64_t info[8])
 extern "C" int spkm_last_events_form(spkm_ctx* ctx, int64_t info[2])
 {
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
-    const bool inc = ctx->last_path == 1 && ctx->last_incremental;
-    info[0] = inc ? (ctx->last_direct_events ? 2 : 1) : 0;
-    info[1] = (inc && ctx->last_pair_events) ? 1 : 0;
+    const spkm_screen_report& r = ctx->last;
+    info[0] = r.incremental ? (r.direct_events ? 2 : 1) : 0;
+    info[1] = (r.incremental && r.pair_events) ? 1 : 0;
     return SPKM_OK;
 }
 
@@ -968,7 +961,7 @@ extern "C" int spkm_last_assign_tile(spkm_ctx* ctx, int64_t info[6])
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
     info[0] = ctx->assign_KT;
     info[1] = ctx->assign_G;
-    info[2] = ctx->last_path == 1 ? ctx->last_pl_last : 0;
+    info[2] = ctx->last.pl_last;
     info[3] = ctx->last_exact_pts;
     info[4] = ctx->last_acc_form;
     info[5] = ctx->last_dist_form;
@@ -979,8 +972,8 @@ extern "C" int spkm_last_assign_tile(spkm_ctx* ctx, int64_t info[6])
 extern "C" int spkm_last_screen_tile(spkm_ctx* ctx, int64_t info[2])
 {
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
-    info[0] = ctx->last_path == 1 ? ctx->last_screen_kt : 0;
-    info[1] = ctx->last_path == 1 ? ctx->last_screen_tiles : 0;
+    info[0] = ctx->last.kt;
+    info[1] = ctx->last.tiles;
     return SPKM_OK;
 }
 
@@ -1007,12 +1000,12 @@ extern "C" int spkm_debug_shard_bounds(spkm_ctx* ctx, const spkm_shard* s, float
     }
     if (lib_assign) {
         std::vector<int32_t> ta(n);
-        HIP_TRY(hipMemcpy(ta.data(), s->hb + 2 * npad, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ta.data(), s->hb + hb_assign(npad), n * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) lib_assign[at(i)] = ta[i];
     }
     if (lb) {
         double cum = 0.0;
-        HIP_TRY(hipMemcpy(tmp.data(), s->hb + npad, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tmp.data(), s->hb + hb_lb(npad), n * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(&cum, s->hb_cum + s->cum_par, 8, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) lb[at(i)] = (double)tmp[i] - cum;
     }
@@ -1023,12 +1016,12 @@ extern "C" int spkm_last_path_info(spkm_ctx* ctx, int64_t info[2])
 {
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    info[0] = ctx->last_path;
+    info[0] = ctx->last.path;
     info[1] = 0;
-    if (ctx->last_path == 1 && ctx->nlist.p) {
+    if (ctx->last.path == 1 && ctx->nlist.p) {
         unsigned v = 0;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipMemcpy(&v, ctx->nlist.p, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&v, (const unsigned*)ctx->nlist.p + NL_LISTED, 4, hipMemcpyDeviceToHost));
         info[1] = v;
     }
     return SPKM_OK;
@@ -1164,7 +1157,7 @@ extern "C" int spkm_dense_accumulate_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n
     if ((rc = ensure(ctx, ctx->offs, (size_t)(K + 1) * 8))) return rc;
     if ((rc = ensure(ctx, ctx->cursor, (size_t)K * 8))) return rc;
     if ((rc = ensure(ctx, ctx->items, (size_t)max_items * 16))) return rc;
-    if ((rc = ensure(ctx, ctx->nitems, 64))) return rc;
+    if ((rc = ensure(ctx, ctx->nitems, NI_WORDS * 4))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->dn_nk.p, 0, (size_t)K * 8, ctx->stream));
     hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
                        ctx->stream, (const int*)d_assign, n, K, (unsigned long long*)ctx->dn_nk.p, (const unsigned*)nullptr);

@@ -48,7 +48,20 @@ static int ensure_blk_stats(spkm_ctx* ctx, size_t items)
     if ((rc = ensure(ctx, ctx->blk_obj, items * 8)) || (rc = ensure(ctx, ctx->blk_max, items * 8))) return rc;
     return ensure(ctx, ctx->blk_imax, items * 8);
 }
-// One screen call: its input (the plan's, policy.h), its plan, the zero jobs of its first launch, and its stages.
+// In how many places the caller's assignment differs from the library's copy of the last screen call's (hb, layout.h).
+// Synchronises the stream: a debug aid and an end-of-run call, not the hot path.
+static int count_assign_diff(spkm_ctx* ctx, const spkm_shard* s, const int32_t* d_assign, long long npad, unsigned* diff)
+{
+    const long long n = (long long)s->n;
+    unsigned* cnt = (unsigned*)ctx->nlist.p + NL_CHECK_DIFF;
+    HIP_TRY(hipMemsetAsync(cnt, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(k_count_diff_i32, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const int*)d_assign, (const int*)(s->hb + hb_assign(npad)), n, cnt, (const int*)s->map);
+    HIP_TRY(hipMemcpyAsync(diff, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SPKM_OK;
+}
+// One screen call: its input (the plan's, policy.h), its plan, its report, the zero jobs of its first launch, and its stages.
 struct screen_call : spkm_call_in {
     spkm_ctx* ctx;
     spkm_shard* sm;
@@ -58,6 +71,7 @@ struct screen_call : spkm_call_in {
     double *mind, *sums, *counts; // sums | counts | nk | obj2: the caller's reduce buffer
     size_t pk;
     spkm_call_plan pl;
+    spkm_screen_report rep; // what this call did, as its stages decide it (stored in the context when the call has gone through)
     spkm_zero_jobs zj;
     int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
     bool carry = false; // this shard carries bounds between screen calls: quad, or carry_bounds (spkm_shard_set_wide_bounds)
@@ -73,7 +87,7 @@ struct screen_call : spkm_call_in {
                            ctx->stream, zj);
         zj.n = 0;
     }
-    int* cl(int i) const { return pl.cl_on ? sm->cl_flags + (size_t)i * K : nullptr; } // need | touched | same | ibeg | icnt
+    int* cl(int row) const { return pl.cl_on ? sm->cl_flags + (size_t)row * K : nullptr; } // row: CL_* (layout.h)
     // Buffers: the screen's inputs and scratch, the shard's carried bounds and cluster cache; a regrouping asked for.
     template <typename IR> int buffers()
     {
@@ -104,21 +118,21 @@ struct screen_call : spkm_call_in {
             return rc;
         {
             const bool fresh = ctx->nlist.p == nullptr;
-            if ((rc = ensure(ctx, ctx->nlist, 256))) return rc;
-            if (fresh) HIP_TRY(hipMemsetAsync(ctx->nlist.p, 0, 256, ctx->stream)); // [8..9]: running total of skipped steps
+            if ((rc = ensure(ctx, ctx->nlist, NL_WORDS * 4))) return rc;
+            if (fresh) HIP_TRY(hipMemsetAsync(ctx->nlist.p, 0, NL_WORDS * 4, ctx->stream)); // (the running totals start here)
         }
         if ((rc = ensure(ctx, ctx->ct, pk * 8)) || (rc = ensure(ctx, ctx->nk, (size_t)K * 8)) || (rc = ensure(ctx, ctx->stats, 4 * 8)))
             return rc;
         // the counters, the largest-drift cell, the touched flags of the cluster shortcut and the caller's reduce buffer
         zero_later(ctx->cmax.p, 16);
-        zero_later(ctx->nlist.p, 32);
-        zero_later((char*)ctx->nlist.p + 40, 128 - 40); // (not the running total at [8..9])
+        zero_later((unsigned*)ctx->nlist.p + NL_ZERO_A, (NL_ZERO_A_END - NL_ZERO_A) * 4);
+        zero_later((unsigned*)ctx->nlist.p + NL_ZERO_B, (NL_ZERO_B_END - NL_ZERO_B) * 4); // (not NL_SKIPPED_TOTAL between them)
         zero_later(sums, (2 * pk + K + 1) * 8);
         if (!carry) return SPKM_OK;
         // bounds carried from this shard's previous screen call (screen.hip, k_center_drift): steps whose points provably keep
         // their centroids are skipped.  SPKM_NO_BOUNDS=1: A/B switch (bounds are still maintained).
         if (!sm->hb || sm->hb_npad != pl.npad) {
-            HIP_TRY(regrow(sm->hb, ((size_t)3 * pl.npad + HB_TAIL) * 4, &sm->hb_valid));
+            HIP_TRY(regrow(sm->hb, hb_floats(pl.npad) * 4, &sm->hb_valid));
             sm->hb_npad = pl.npad;
         }
         if (sm->hb_centers_len < pk) {
@@ -143,11 +157,11 @@ struct screen_call : spkm_call_in {
         if (!quad) return SPKM_OK; // (no cluster cache or flags: the exact pass streams every cluster in every call)
         // per-cluster cache / flags of the unchanged-cluster shortcut
         if (!sm->cl_cache || sm->cl_pk != pk || sm->cl_K != K) {
-            HIP_TRY(regrow(sm->cl_cache, (2 * pk + 3 * (size_t)K) * 8, &sm->cl_valid));
-            HIP_TRY(regrow(sm->cl_flags, (size_t)5 * K * 4));
+            HIP_TRY(regrow(sm->cl_cache, cc_doubles(pk, K) * 8, &sm->cl_valid));
+            HIP_TRY(regrow(sm->cl_flags, (size_t)CL_ROWS * K * 4));
             sm->cl_pk = pk; sm->cl_K = K;
         }
-        zero_later(sm->cl_flags + K, (size_t)K * 4); // touched[] (k_combine_screen / k_assign_list mark, k_cluster_need reads)
+        zero_later(sm->cl_flags + (size_t)CL_TOUCHED * K, (size_t)K * 4); // touched[] (k_combine_screen / k_assign_list mark, k_cluster_need reads)
         return SPKM_OK;
     }
     // The plan's input: this call's shapes, the device, the switches and the shard as the buffer stage left it.
@@ -198,7 +212,7 @@ struct screen_call : spkm_call_in {
             zero_later(ctx->nk_ev.p, (size_t)2 * K * 8);
         }
         if (pl.hinted) {
-            ctx->last_hint_late = pl.late;
+            rep.hint_late = pl.late;
             if (sm->hintu_len < pl.npad) {
                 HIP_TRY(regrow(sm->hintu, (size_t)pl.npad * 4));
                 sm->hintu_len = pl.npad;
@@ -215,37 +229,32 @@ struct screen_call : spkm_call_in {
             return SPKM_OK;
         }
         // (a non-quad shard that carries bounds: no cluster flags -- same is null -- and no hints -- hterm is null)
-        int* same = quad ? sm->cl_flags + 2 * K : (int*)nullptr;
+        int* same = quad ? sm->cl_flags + (size_t)CL_SAME * K : (int*)nullptr;
         if (pl.drift) {
-            zero_later(sm->hb + 3 * npad + K, 4);
+            zero_later(sm->hb + hb_dmax(npad, K), 4);
             zero_flush();
             hipLaunchKernelGGL(k_center_drift, dim3(K), dim3(256), 0, ctx->stream, (const double*)sm->hb_centers, C, K, p,
-                               gamma, sm->hb + 3 * npad, same, ctx->sw.no_support_drift ? 0 : sm->fixed_s,
-                               2.0f * (float)sm->fixed_s / (float)p, quad ? sm->hb + 3 * npad + HB_HTERM : (float*)nullptr);
+                               gamma, sm->hb + hb_delta(npad), same, ctx->sw.no_support_drift ? 0 : sm->fixed_s,
+                               2.0f * (float)sm->fixed_s / (float)p, quad ? sm->hb + hb_hterm(npad) : (float*)nullptr);
             int rc;
             if ((rc = ensure(ctx, ctx->todo, pl.pt_mode ? (size_t)(npad + 64) * 4 : (size_t)(npad / 16 + 1) * 4))) return rc;
             // (its statistics leave per workgroup, bstat, and are added up by the call's last kernel: same-address atomics of
             //  a few thousand workgroups took longer than the test itself on small shards)
-            if ((rc = ensure(ctx, ctx->bstat, (size_t)pl.bgrid * 8))) return rc;
+            if ((rc = ensure(ctx, ctx->bstat, (size_t)pl.bgrid * BS_STRIDE * 4))) return rc;
             const long long nblk = npad / 1024 + 1;
             if (pl.sp_on && sm->sp_blocks != nblk) {
-                HIP_TRY(regrow(sm->sp, (size_t)nblk * 24, &sm->sp_clean));
+                HIP_TRY(regrow(sm->sp, sp_bytes(nblk), &sm->sp_clean));
                 sm->sp_blocks = nblk;
             }
-            unsigned* sp_mask = pl.sp_on ? reinterpret_cast<unsigned*>(sm->sp) : nullptr; // 16 B per block
-            float* sp_slack = pl.sp_on ? reinterpret_cast<float*>(sm->sp + (size_t)nblk * 16) : nullptr;
-            int* sp_valid = pl.sp_on ? reinterpret_cast<int*>(sm->sp + (size_t)nblk * 20) : nullptr;
+            unsigned* sp_mask = pl.sp_on ? reinterpret_cast<unsigned*>(sm->sp) : nullptr;
+            float* sp_slack = pl.sp_on ? reinterpret_cast<float*>(sm->sp + sp_off_slack(nblk)) : nullptr;
+            int* sp_valid = pl.sp_on ? reinterpret_cast<int*>(sm->sp + sp_off_valid(nblk)) : nullptr;
             if (((pl.sp_on && !pl.sp_reset) || pl.trusted) && ctx->sw.check_assign) {
                 // SPKM_CHECK_ASSIGN=1 (debug aid for hosts other than ours): blocks are about to go unvisited on the strength of
                 // the lazy contract (spkm.h: the same buffer, not written to between calls) -- compare the caller's buffer
                 // with the library's copy of the previous call's assignment first and refuse the call if they differ
-                unsigned* cnt = (unsigned*)ctx->nlist.p + 20;
-                HIP_TRY(hipMemsetAsync(cnt, 0, 4, ctx->stream));
-                hipLaunchKernelGGL(k_count_diff_i32, dim3((unsigned)std::min<long long>(4096, (n + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   (const int*)assign, (const int*)(sm->hb + 2 * npad), n, cnt, (const int*)sm->map);
                 unsigned diff = 0;
-                HIP_TRY(hipMemcpyAsync(&diff, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
+                if ((rc = count_assign_diff(ctx, sm, assign, npad, &diff))) return rc;
                 if (diff) {
                     snprintf(ctx->errmsg, sizeof(ctx->errmsg), "SPKM_CHECK_ASSIGN: d_assign differs from the library's copy of the previous "
                              "call's assignment in %u places (lazy statistics: the buffer is the library's to keep between calls)", diff);
@@ -285,10 +294,9 @@ struct screen_call : spkm_call_in {
             hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
                                0, ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p,
                                (unsigned long long*)ctx->cmax.p, (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
-        ctx->last_sums_only = false;
-        ctx->last_pl_last = pl.pl_last;
-        ctx->last_screen_kt = kt;
-        ctx->last_screen_tiles = pl.Gs;
+        rep.pl_last = pl.pl_last;
+        rep.kt = kt;
+        rep.tiles = pl.Gs;
         const size_t lds = (size_t)(p + 1) * (kt * 4 + (pl.pl_last == 5 ? 16 : 0)) + 16;
         // (a non-quad shard that skips on its bounds: the LIST form of k_screen_wide at its width, over the points of todo[])
         const bool wlist = !quad && pl.skip_enabled;
@@ -307,11 +315,12 @@ struct screen_call : spkm_call_in {
         float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
         int* a_k = (int*)ctx->scr_k.p;
         int a_extra = pl.G - 1; // buffer / centroid block of the carried remainder (pl 5)
-        ctx->last_rounds_all = quad ? pl.rounds_all : 0;
-        ctx->last_rounds = quad ? pl.nr : 0;
+        rep.rounds_all = quad ? pl.rounds_all : 0;
+        rep.rounds = quad ? pl.nr : 0;
         const float* a_hint = (pl.hinted && pl.rounds_all < pl.nr) ? sm->hintu : nullptr; // nullptr: every step is finished for the leaders only
         float a_hc = 1.5f; // the other centroids' partial sums must exceed 1.5 x the hinted distance squared
-        ctx->last_hinted = a_hint != nullptr;
+        rep.hinted = a_hint != nullptr;
+        rep.mode = rep.hinted ? 2 : (rep.rounds_all < rep.rounds ? 1 : 0);
         unsigned* a_cnt = (unsigned*)ctx->nlist.p;
         const int* a_todo = pl.skip_enabled ? (const int*)ctx->todo.p : nullptr;
         // point lists: the listed points' entries come from the record layout of the exact pass when this shard has one
@@ -328,18 +337,18 @@ struct screen_call : spkm_call_in {
                                 ctx->stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(timing_end(ctx));
-        ctx->last_skipping = pl.skip_enabled;
-        ctx->last_pt_mode = pl.pt_mode;
+        rep.skipping = pl.skip_enabled;
+        rep.pt_mode = pl.pt_mode;
         return SPKM_OK;
     }
     // Certification (k_combine_screen) and exact evaluation of the uncertified points (k_assign_list).  Only they change an
-    // assignment: they keep the library's copy (hb + 2 npad) up to date in place and, against the previous value, mark the
+    // assignment: they keep the library's copy (hb + hb_assign(npad)) up to date in place and, against the previous value, mark the
     // clusters a point left or entered, move the cluster sizes and record the events.
     template <typename IR> int certify()
     {
         int rc;
-        if ((rc = ensure(ctx, ctx->wgstat, (size_t)4 * 4096 * 4))) return rc; // k_combine_screen's per-workgroup statistics
-        int* touched = pl.cl_skip ? cl(1) : (int*)nullptr;
+        if ((rc = ensure(ctx, ctx->wgstat, (size_t)WG_STRIDE * 4096 * 4))) return rc; // k_combine_screen's per-workgroup statistics
+        int* touched = pl.cl_skip ? cl(CL_TOUCHED) : (int*)nullptr;
         unsigned long long* nk = pl.nk_incr ? (unsigned long long*)ctx->nk.p : (unsigned long long*)nullptr;
         int *ev_pt = pl.ev_path ? sm->ev_pt : nullptr, *ev_k = pl.ev_path ? sm->ev_k : nullptr, *ev_o = pl.pair_ev ? sm->ev_o : nullptr;
         unsigned long long* nk_ev = pl.ev_path ? (unsigned long long*)ctx->nk_ev.p : (unsigned long long*)nullptr;
@@ -360,15 +369,14 @@ struct screen_call : spkm_call_in {
         hipLaunchKernelGGL((k_assign_list<IR>), dim3(std::max(1, ctx->num_cus) * 8), dim3(256), 0, ctx->stream,
                            (const long long*)sm->jc, (const IR*)sm->ir, (const double*)sm->x, (const double*)ctx->ct.p, K,
                            sm->fixed_s, (const int*)ctx->list.p, (const unsigned int*)ctx->nlist.p, (int*)assign,
-                           carry ? (int*)(sm->hb + 2 * pl.npad) : (int*)nullptr, pl.bounds_ok ? 1 : 0, (unsigned*)ctx->nlist.p + 5,
+                           carry ? (int*)(sm->hb + hb_assign(pl.npad)) : (int*)nullptr, pl.bounds_ok ? 1 : 0, (unsigned*)ctx->nlist.p + NL_CHANGED,
                            touched, nk, pl.lazy_ub ? sm->hb : (float*)nullptr, ev_pt, ev_k, (unsigned*)ctx->nlist.p,
                            sm->x == nullptr ? (const char*)sm->rec : (const char*)nullptr, sm->rec_R, nk_ev, pl.ev_cap,
                            (const unsigned*)ctx->wgstat.p, cb, ev_o, (const int*)sm->map);
         ctx->sort_owner = nullptr; // until this call's sort (or its confirmation) has been queued
-        ctx->last_lib_valid = pl.bounds_ok;
-        ctx->last_incremental = pl.ev_path;
-        ctx->last_direct_events = false;
-        ctx->last_pair_events = pl.pair_ev;
+        rep.lib_valid = pl.bounds_ok;
+        rep.incremental = pl.ev_path;
+        rep.pair_events = pl.pair_ev;
         if (pl.ev_path) sm->pol.sums_by_events(); else sm->pol.sums_by_full_pass();
         return SPKM_OK;
     }
@@ -389,7 +397,7 @@ struct screen_call : spkm_call_in {
     template <typename IR> int events()
     {
         const int K2 = 2 * K;
-        const unsigned* ev_n = (const unsigned*)ctx->nlist.p + 16;
+        const unsigned* ev_n = (const unsigned*)ctx->nlist.p + NL_EVENTS;
         const int seg_ev = pl.seg_ev;
         const int max_items_ev = (int)((2 * n) / seg_ev) + K2 + 1;
         int rc;
@@ -400,14 +408,14 @@ struct screen_call : spkm_call_in {
         const long long ev_est = std::max<long long>(4096, (long long)std::min<unsigned long long>(sm->pol.movers_known ? 4 * sm->pol.last_movers + 4096 : (unsigned long long)n, (unsigned long long)2 * n));
         const int hb_ = (int)std::min<long long>(1024, (ev_est + 1023) / 1024);
         // dual: k_pick_form opens the events (gate_ev) or the full pass (gate_full, further down); the events' plan counts
-        // its items in nitems[1], the full pass's in nitems[0] -- whichever does not run leaves an empty work list
-        const unsigned* gate_ev = pl.dual ? (const unsigned*)ctx->nlist.p + 18 : (const unsigned*)nullptr;
-        const unsigned* gate_full = pl.dual ? (const unsigned*)ctx->nlist.p + 19 : (const unsigned*)nullptr;
-        int* nitems_ev = (int*)ctx->nitems.p + (pl.dual ? 1 : 0);
+        // its items in nitems[NI_EVENTS], the full pass's in nitems[NI_FULL] -- whichever does not run leaves an empty work list
+        const unsigned* gate_ev = pl.dual ? (const unsigned*)ctx->nlist.p + NL_GATE_EVENTS : (const unsigned*)nullptr;
+        const unsigned* gate_full = pl.dual ? (const unsigned*)ctx->nlist.p + NL_GATE_FULL : (const unsigned*)nullptr;
+        int* nitems_ev = (int*)ctx->nitems.p + (pl.dual ? NI_EVENTS : NI_FULL);
         if (pl.dual)
             hipLaunchKernelGGL(k_pick_form, dim3(1), dim3(1), 0, ctx->stream, (unsigned*)ctx->nlist.p, pl.ev_cap, (int*)ctx->nitems.p);
-        double *cache_s = sm->cl_cache, *cache_c = cache_s + pk;
-        ctx->last_direct_events = pl.direct;
+        double *cache_s = sm->cl_cache, *cache_c = cache_s + cc_counts(pk);
+        rep.direct_events = pl.direct;
         ctx->last_exact_pts = 0; // (no exact pass; a dual call's queued full pass is the pipelined kernel's)
         const int* perm = (const int*)ctx->perm.p;
         const long long* offs = (const long long*)ctx->offs.p;
@@ -431,7 +439,7 @@ struct screen_call : spkm_call_in {
                 (rc = ensure(ctx, ctx->hist2, (size_t)Kp * 8)) || (rc = ensure(ctx, ctx->items2, (size_t)max_items_acc * 16)) ||
                 (rc = ensure(ctx, ctx->items, (size_t)max_items1 * 16)))
                 return rc;
-            int* nitems1 = (int*)ctx->nitems.p + 2;
+            int* nitems1 = (int*)ctx->nitems.p + NI_PAIR_CHUNKS;
             hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk_ev.p, K,
                                CH, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
                                nitems1, gate_ev, (const int*)nullptr, (int*)nullptr, (int*)nullptr,
@@ -480,26 +488,26 @@ struct screen_call : spkm_call_in {
             // k_pick_form opened gate_full.  Its sums go to the reduce buffer (zeroed at the top of the call), from there
             // into the cache (every cluster is `fresh`), and the tail hands the cache over as it does after the events.
             if ((rc = ensure_blk_stats(ctx, (size_t)max_items))) return rc;
-            hipLaunchKernelGGL(k_cluster_need, dim3(1), dim3(256), 0, ctx->stream, cl(1), (const int*)cl(2), 1, K,
-                               (const unsigned long long*)ctx->nk.p, cl(0), (unsigned*)ctx->nlist.p, gate_full);
+            hipLaunchKernelGGL(k_cluster_need, dim3(1), dim3(256), 0, ctx->stream, cl(CL_TOUCHED), (const int*)cl(CL_SAME), 1, K,
+                               (const unsigned long long*)ctx->nk.p, cl(CL_NEED), (unsigned*)ctx->nlist.p, gate_full);
             hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk.p, K,
                                seg, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
-                               (int*)ctx->nitems.p, gate_full, (const int*)cl(0), cl(3), cl(4));
+                               (int*)ctx->nitems.p, gate_full, (const int*)cl(CL_NEED), cl(CL_IBEG), cl(CL_ICNT));
             const int sb2 = (int)std::max<long long>(std::min<long long>(1024, (n + 1023) / 1024), std::min<long long>(8192, n / 4096));
             launch_scatter(ctx, sb2, (size_t)((K + 1) & ~1) * 4 + (size_t)K * 12, (const int*)assign, n, K, gate_full, (const int*)nullptr);
             if ((rc = exact_rec<IR>(false, nullptr, sm->hb, std::min(max_items, std::max(1, ctx->num_cus))))) return rc;
             hipLaunchKernelGGL(k_cluster_restore, dim3((unsigned)std::min<size_t>((pk + 255) / 256, 2048)), dim3(256), 0, ctx->stream,
-                               (const int*)cl(1), K, p, sums, counts, cache_s, cache_c, gate_full);
+                               (const int*)cl(CL_TOUCHED), K, p, sums, counts, cache_s, cache_c, gate_full);
         }
         if (ctx->tlog_both) HIP_TRY(timing_end(ctx));
         HIP_TRY(hipGetLastError());
         return SPKM_OK;
     }
-    // The full pass: counting sort by cluster (gated: its kernels return at once when the kept sort is reused and nlist[5]
+    // The full pass: counting sort by cluster (gated: its kernels return at once when the kept sort is reused and nlist[NL_CHANGED]
     // counted no change), exact distance + per-cluster accumulation, the cluster shortcut's restore and statistics.
     template <typename IR> int full_pass()
     {
-        const unsigned* gate = pl.reuse ? (const unsigned*)ctx->nlist.p + 5 : (const unsigned*)nullptr;
+        const unsigned* gate = pl.reuse ? (const unsigned*)ctx->nlist.p + NL_CHANGED : (const unsigned*)nullptr;
         if (!pl.nk_incr) {
             hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream,
                                (unsigned long long*)ctx->nk.p, K, gate);
@@ -507,19 +515,19 @@ struct screen_call : spkm_call_in {
                                ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, gate);
         }
         if (pl.cl_on)
-            hipLaunchKernelGGL(k_cluster_need, dim3(1), dim3(256), 0, ctx->stream, cl(1), (const int*)cl(2),
-                               pl.cl_skip ? 0 : 1, K, (const unsigned long long*)ctx->nk.p, cl(0), (unsigned*)ctx->nlist.p);
+            hipLaunchKernelGGL(k_cluster_need, dim3(1), dim3(256), 0, ctx->stream, cl(CL_TOUCHED), (const int*)cl(CL_SAME),
+                               pl.cl_skip ? 0 : 1, K, (const unsigned long long*)ctx->nk.p, cl(CL_NEED), (unsigned*)ctx->nlist.p);
         // (with the shortcut on the plan is never gated: which clusters need work changes even when no assignment does)
         hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk.p, K,
                            seg, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
-                           (int*)ctx->nitems.p, pl.cl_on ? (const unsigned*)nullptr : gate, (const int*)cl(0), cl(3), cl(4));
+                           (int*)ctx->nitems.p, pl.cl_on ? (const unsigned*)nullptr : gate, (const int*)cl(CL_NEED), cl(CL_IBEG), cl(CL_ICNT));
         // (two passes over 4 B per point are latency bound: 8192 workgroups at N = 1e8 -- 0.23 -> 0.12 ms against 1024)
         int sb = (int)std::max<long long>(std::min<long long>(1024, (n + 1023) / 1024), std::min<long long>(8192, n / 4096));
         const size_t sc_lds = (size_t)((K + 1) & ~1) * 4 + (size_t)K * 12;
         // (with the shortcut on the scatter is never gated either -- a cluster may need its part of the permutation again
         //  without any assignment having changed -- and places only the points of clusters that will be streamed)
         launch_scatter(ctx, sb, sc_lds, (const int*)assign, n, K, pl.cl_on ? (const unsigned*)nullptr : gate,
-                       pl.cl_skip ? (const int*)cl(0) : (const int*)nullptr);
+                       pl.cl_skip ? (const int*)cl(CL_NEED) : (const int*)nullptr);
         ctx->sort_partial = pl.cl_skip;
         if (quad) {
             ctx->sort_owner = sm; ctx->sort_K = K; ctx->sort_n = n; ctx->sort_seg = seg;
@@ -555,13 +563,13 @@ struct screen_call : spkm_call_in {
         }
         if (ctx->tlog_both) HIP_TRY(timing_end(ctx));
         if (pl.cl_on) {
-            double *cache_s = sm->cl_cache, *cache_c = cache_s + pk, *cl_obj = cache_c + pk, *cl_max = cl_obj + K;
-            long long* cl_imax = reinterpret_cast<long long*>(cl_max + K);
+            double *cache_s = sm->cl_cache, *cache_c = cache_s + cc_counts(pk), *cl_obj = cache_s + cc_obj(pk), *cl_max = cache_s + cc_max(pk, K);
+            long long* cl_imax = reinterpret_cast<long long*>(cache_s + cc_imax(pk, K));
             hipLaunchKernelGGL(k_cluster_restore, dim3((unsigned)std::min<size_t>((pk + 255) / 256, 2048)), dim3(256), 0, ctx->stream,
-                               (const int*)cl(1) /* = fresh, after k_cluster_need */, K, p, sums, counts, cache_s, cache_c);
+                               (const int*)cl(CL_TOUCHED) /* = fresh, after k_cluster_need */, K, p, sums, counts, cache_s, cache_c);
             if (!pl.sums_only)
-                hipLaunchKernelGGL(k_cluster_stats, dim3(1), dim3(256), 0, ctx->stream, (const int*)cl(0), K, (const int*)cl(3),
-                                   (const int*)cl(4), (const double*)ctx->blk_obj.p, (const double*)ctx->blk_max.p,
+                hipLaunchKernelGGL(k_cluster_stats, dim3(1), dim3(256), 0, ctx->stream, (const int*)cl(CL_NEED), K, (const int*)cl(CL_IBEG),
+                                   (const int*)cl(CL_ICNT), (const double*)ctx->blk_obj.p, (const double*)ctx->blk_max.p,
                                    (const long long*)ctx->blk_imax.p, cl_obj, cl_max, cl_imax, (double*)ctx->stats.p);
             sm->cl_valid = true;
             sm->cl_stats_valid = !pl.sums_only;
@@ -587,18 +595,17 @@ struct screen_call : spkm_call_in {
         // what the screen did, for the running totals of executed rounds (k_call_tail; spkm_screen_work_totals)
         const unsigned long long work_steps = (unsigned long long)((n + 15) / 16);
         const int work_tiles = quad ? pl.Gs : 0;
-        const int work_flags = ((quad && ctx->last_rounds_all < ctx->last_rounds && !ctx->last_hinted) ? 1 : 0) |
+        const int work_flags = ((quad && rep.rounds_all < rep.rounds && !rep.hinted) ? 1 : 0) |
                                (pl.skip_enabled ? 2 : 0) | (pl.pt_mode ? 4 : 0);
         const unsigned grid = ev ? (unsigned)std::max<size_t>((K + 255) / 256, std::min<size_t>((pk + 255) / 256, 1024)) : (unsigned)(K + 255) / 256;
         hipLaunchKernelGGL(k_call_tail, dim3(grid), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk.p, K, nk_f,
                            (const double*)ctx->stats.p, nk_f + K, d_stats, (unsigned long long*)d_nk_u64, (const unsigned*)ctx->bstat.p,
                            bstat_n, (unsigned*)ctx->nlist.p, (ev || pl.sums_only) ? 1 : 0, ev ? sm->cl_cache : (double*)nullptr,
-                           ev ? (const double*)(sm->cl_cache + pk) : (const double*)nullptr, ev ? pk : (size_t)0,
+                           ev ? (const double*)(sm->cl_cache + cc_counts(pk)) : (const double*)nullptr, ev ? pk : (size_t)0,
                            ev ? sums : (double*)nullptr, ev ? counts : (double*)nullptr,
                            sm->nlist_pending ? (unsigned*)nullptr : sm->h_nlist_dev, sm->nlist_seq + 1u,
-                           work_steps, work_tiles, pl.nr, ctx->last_rounds_all, work_flags, (unsigned long long)n);
+                           work_steps, work_tiles, pl.nr, rep.rounds_all, work_flags, (unsigned long long)n);
         HIP_TRY(hipGetLastError());
-        ctx->last_screen_n = n;
         if (carry) { // the bounds now describe this call: its centroids are what the next call's drift is measured from
             sm->hb_K = K; sm->hb_gamma = gamma; sm->hb_valid = true;
         }
@@ -607,7 +614,7 @@ struct screen_call : spkm_call_in {
             ctx->sort_owner = sm;       // (the cluster sizes in ctx->nk stay this shard's; its sort buffers do not)
             ctx->sort_K = K; ctx->sort_n = n; ctx->sort_perm_valid = false; ctx->sort_partial = false;
         }
-        ctx->last_path = 1;
+        rep.path = 1;
         return SPKM_OK;
     }
 };
@@ -617,7 +624,7 @@ struct screen_call : spkm_call_in {
 template <typename IR>
 static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_centers, double gamma,
                       int32_t* d_assign, double* d_mind, double* d_reduce, int prune_a, bool want_hint,
-                      double* d_stats, uint64_t* d_nk_u64, int kt)
+                      double* d_stats, uint64_t* d_nk_u64, int kt, spkm_screen_report* report)
 {
     screen_call c;
     c.kt = kt;
@@ -637,7 +644,7 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     const int ev = c.pl.ev_possible ? 2 : 1, max_items_ev_all = ev == 2 ? (int)((2 * c.n) / 256) + 2 * K + 1 : 0;
     if ((rc = ensure(ctx, ctx->perm, (size_t)ev * c.n * 4)) || (rc = ensure(ctx, ctx->offs, (size_t)(ev * K + 1) * 8)) ||
         (rc = ensure(ctx, ctx->cursor, (size_t)ev * K * 8)) ||
-        (rc = ensure(ctx, ctx->items, (size_t)std::max(c.max_items, max_items_ev_all) * 16)) || (rc = ensure(ctx, ctx->nitems, 64)))
+        (rc = ensure(ctx, ctx->items, (size_t)std::max(c.max_items, max_items_ev_all) * 16)) || (rc = ensure(ctx, ctx->nitems, NI_WORDS * 4)))
         return rc;
     // Record layout of the exact entries (build_records): built once per shard when the device has room for it -- a third
     // off the exact pass on data in arbitrary order, neutral in cluster order.  SPKM_NO_REC=1: the two separate arrays.
@@ -646,10 +653,12 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     // (read only now: an ensure() that replaced a buffer has given the kept sort up)
     c.sort_reusable = ctx->sort_owner == (const void*)s && ctx->sort_perm_valid && ctx->sort_seg == c.seg && !ctx->sort_partial;
     spkm_plan_sums(c.pl, c, c.sm->pol, c.sm->rec != nullptr);
-    ctx->last_sums_only = c.pl.sums_only;
-    ctx->last_dual = c.pl.dual;
+    c.rep.sums_only = c.pl.sums_only;
+    c.rep.dual = c.pl.dual;
     if ((rc = c.certify<IR>()) || (rc = c.pl.ev_path ? c.events<IR>() : c.full_pass<IR>())) return rc;
-    return c.tail(d_stats, d_nk_u64);
+    if ((rc = c.tail(d_stats, d_nk_u64))) return rc;
+    *report = c.rep;
+    return SPKM_OK;
 }
 
 extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, const double* d_centers,
@@ -668,18 +677,19 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
     //    switched on when a plain screen found < 0.2 % of the points with a runner-up within 2.25x of the winner
     //    (converged iterations on separated data), switched off for 16 calls when it listed > 0.5 %.
     if (!sm->h_nlist) {
-        HIP_TRY(hipHostMalloc((void**)&sm->h_nlist, 128, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(sm->h_nlist, 0, 128);
+        HIP_TRY(hipHostMalloc((void**)&sm->h_nlist, SPKM_REPORT_BUF_WORDS * 4, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(sm->h_nlist, 0, SPKM_REPORT_BUF_WORDS * 4);
         HIP_TRY(hipHostGetDevicePointer((void**)&sm->h_nlist_dev, sm->h_nlist, 0));
     }
     if (sm->nlist_pending && __atomic_load_n(sm->h_nlist + SPKM_REPORT_WORDS, __ATOMIC_ACQUIRE) == sm->nlist_seq) {
         sm->nlist_pending = false;
-        ctx->last_listed = sm->h_nlist[0];
+        const unsigned* h = sm->h_nlist;
+        ctx->last_listed = h[NL_LISTED];
         spkm_policy_counters c;
-        c.listed = sm->h_nlist[0]; c.ambig = sm->h_nlist[1]; c.early = sm->h_nlist[2]; c.skipped = sm->h_nlist[3];
-        c.kept = sm->h_nlist[12]; c.movers = sm->h_nlist[14];
-        c.full_opened = sm->h_nlist[19] != 0u;
-        c.one_cluster_steps = sm->h_nlist[21];
+        c.listed = h[NL_LISTED]; c.ambig = h[NL_AMBIG]; c.early = h[NL_EARLY]; c.skipped = h[NL_SKIPPED];
+        c.kept = h[NL_KEPT]; c.movers = h[NL_MOVERS];
+        c.full_opened = h[NL_GATE_FULL] != 0u;
+        c.one_cluster_steps = h[NL_ONE_CLUSTER];
         c.may_regroup = sm->pend_full && sm->lazy && !sm->regroup_done;
         const int kt_seen = std::max(8, screen_tile_kt(ctx, s)); // (a shard's screen calls share one width while its opt-in stands)
         sm->pol.observe(c, (double)s->n, (int)((K64 + kt_seen - 1) / kt_seen), (s->fixed_s + 3) / 4);
@@ -699,22 +709,20 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         // (run_screen / k_bounds_steps); needs this shard's previous call to have been a screen call.
         const int prune_a = ch.prune_a;
         const bool want_hint = ch.want_hint;
-        rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt)
-                                : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt);
+        spkm_screen_report rep;
+        rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep)
+                                : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep);
         if (rc) return rc;
-        ctx->last_mode = ctx->last_hinted ? 2 : (ctx->last_rounds_all < ctx->last_rounds ? 1 : 0);
+        ctx->last = rep;
         if (!sm->nlist_pending) { // (run_screen's k_call_tail was told to report under the number nlist_seq + 1)
             sm->nlist_seq++;
             sm->nlist_pending = true;
-            sm->pol.launched(ctx->last_rounds_all, ctx->last_rounds, ctx->last_hinted, ctx->last_hint_late, ctx->last_skipping,
-                             ctx->last_lib_valid, ctx->last_incremental, ctx->last_dual);
-            sm->pend_full = !ctx->last_skipping && screen_use_quad(ctx, s);
+            sm->pol.launched(rep.rounds_all, rep.rounds, rep.hinted, rep.hint_late, rep.skipping, rep.lib_valid, rep.incremental, rep.dual);
+            sm->pend_full = !rep.skipping && screen_use_quad(ctx, s);
         }
         return SPKM_OK; // (statistics and cluster sizes were handed over by run_screen's last kernel)
     }
-    ctx->last_path = 0;
-    ctx->last_screen_kt = ctx->last_screen_tiles = 0;
-    ctx->last_dual = false;
+    ctx->last = spkm_screen_report(); // (path 0: no screen)
     sm->sp_clean = false;
     sm->assign_synced = false;
     sm->hb_valid = false; // the carried bounds describe the previous SCREEN call only

@@ -26,4 +26,5 @@ struct spkm_blockmap {
 
 #define SCREEN_KT 32 // centroids per tile of the f32 screen (screen.hip, screen_quad.hip)
 
+#include "layout.h" // counter slots and buffer layouts shared by the kernels and the host
 #include "policy.h" // quad_split / quad_split_late (the compile-time splits of the two-phase screen) live with the policy

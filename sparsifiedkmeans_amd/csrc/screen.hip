@@ -38,13 +38,6 @@
 #include "common.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-// tail of a shard's bounds buffer (floats) behind ub[npad] | lb[npad] | assignment[npad]:
-//   delta[K] | dmax              drift of every centroid on a point's support (k_center_drift) and its maximum
-//   hterm[K] at HB_HTERM         hint_w x (full 2-norm drift)^2 per centroid: the hints' estimate, not a bound
-#define HB_KMAX 65536
-#define HB_HTERM (HB_KMAX + 16)
-#define HB_TAIL (2 * HB_KMAX + 32)
-
 // T32[g][r][kk] = -fl32(C[(g*32+kk)*p + r] / gamma), row p zero; cmax_bits = max |C/gamma| (f64 bits, atomicMax).
 // 4-lanes-per-point kernel only:
 //  * pl_last = 1 / 2: the last tile holds <= 16 centroids in floats 0..15 of each row and a second copy of them
@@ -545,7 +538,7 @@ __global__ __launch_bounds__(1024) void k_screen_tile(
 // and (ub + delta_a)(1+nu) < (lb - dmax)(1-nu) proves -- without touching the point -- that the reference's argmin
 // is unchanged (strictly: no tie).  A 16-point step whose points all pass is skipped by the screen; phase 2 still
 // evaluates every point's exact distance to its centroid and the sums, so every output stays exact.
-// Buffer layout (floats): ub[npad] | lb[npad] | a[npad] (int32) | delta[K] | dmax | ... | hterm[K] at HB_HTERM
+// Buffer layout: layout.h (hb_*)
 //
 // delta_k (rounded up, f32) for all k; delta[K] = max (bit pattern atomicMax: the values are >= 0).
 // SUPPORT-AWARE DRIFT (top_s > 0: every point of the shard stores exactly top_s entries).  What the triangle inequality
@@ -695,7 +688,7 @@ __device__ __forceinline__ void st_points(T* __restrict__ p, size_t at, bool wid
 // A step whose points all pass the carried-bounds
 // test (k_center_drift's comment) is settled here: assignment = the previous one, lower bound moved by the largest
 // drift.  Every other step is appended to todo[] (its index; order within the list does not matter) -- the list
-// the screen kernel and k_combine_screen iterate; counters[4] = length, counters[3] = steps skipped.
+// the screen kernel and k_combine_screen iterate; counters[NL_TODO] = length, counters[NL_SKIPPED] = steps skipped.
 #define BOUNDS_SPAN 16384   // points per workgroup of k_bounds_steps (1024 steps)
 #define BOUNDS_SPAN_PT 4096 // ... when it lists points
 #define BOUNDS_KTAB 1024    // centroids whose drift tables k_bounds_steps keeps in LDS
@@ -704,7 +697,7 @@ __device__ __forceinline__ void st_points(T* __restrict__ p, size_t at, bool wid
 // run over the listed points only.  With the points of a cluster scattered over the shard (data in arbitrary order)
 // a 16-point step is settled only if all 16 pass: 98 % certifiable points leave 28 % of the steps on the screen;
 // point by point it is 2 %.  The host selects it from the previous call's counters (both modes count the points that
-// passed, counters[12], and the steps whose 16 points all passed, counters[3]): >= 90 % of the points passed and the
+// passed, counters[NL_KEPT], and the steps whose 16 points all passed, counters[NL_SKIPPED]): >= 90 % of the points passed and the
 // steps left over hold several times as many points as failed (entered at 4x, left below 2.5x).  The screen then fetches 16 B per quad instead of
 // 256 B per wave, which only pays while few points are listed.
 template <bool MAPPED> // MAPPED: a regrouped shard (map != nullptr) -- a compile-time flag: with the choice made at run time the
@@ -744,7 +737,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     // settled clusters (delta_a = 0) are not written.
     // span: points per list flush (<= BOUNDS_SPAN_PT when points are listed, <= 16 BOUNDS_SPAN_PT for steps; a multiple
     // of 1024) -- the host shortens it on small shards so that every CU still gets several workgroups
-    // Lower bounds are stored RELATIVE to the drift accumulated so far: bnd[npad + i] = lb_i + cum at the time lb_i was
+    // Lower bounds are stored RELATIVE to the drift accumulated so far: bnd[hb_lb(npad) + i] = lb_i + cum at the time lb_i was
     // certified (rounded down), cum = sum over the calls since of the largest centroid drift (each rounded up).  The
     // bound that holds now is the stored value minus today's cum -- exactly the "lower bound moved by the largest drift"
     // of every call in between -- so a point that passes needs NO store: the test reads 12 B per point and writes only
@@ -759,7 +752,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     // counted per workgroup (wave-level atomics on one address cost ~8 ms at N = 1e8 when nothing can be skipped)
     __shared__ int s_todo[BOUNDS_SPAN_PT]; // >= BOUNDS_SPAN / 16
     __shared__ unsigned s_cnt, s_pos, s_skip, s_kept;
-    const float dmx = bnd[3 * npad + K];
+    const float dmx = bnd[hb_dmax(npad, K)];
     // rounded UP explicitly: once cum is much larger than dmx the 1e-12 guard on dmx is below the rounding of the addition
     // itself, and cum must stay an upper bound of the total drift.  NaN / inf drift: nothing passes
     // (x + |x| 2^-52 >= the next double above x: one ulp more than the rounded sum can have lost)
@@ -775,7 +768,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     __shared__ float s_dk[BOUNDS_KTAB], s_hk[BOUNDS_KTAB];
     const bool tab = K <= BOUNDS_KTAB;
     if (tab)
-        for (int k = threadIdx.x; k < K; k += blockDim.x) { s_dk[k] = bnd[3 * npad + k]; s_hk[k] = bnd[3 * npad + HB_HTERM + k]; }
+        for (int k = threadIdx.x; k < K; k += blockDim.x) { s_dk[k] = bnd[hb_delta(npad) + k]; s_hk[k] = bnd[hb_hterm(npad) + k]; }
     __syncthreads();
     const bool have_cur = skip_enabled && (!MAPPED || assign != nullptr); // the caller's buffer is read (and repaired)
     // which arrays may take 16-byte accesses at a point index that is a multiple of 4
@@ -801,7 +794,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     __shared__ unsigned long long s_bits[4];
     auto block_passes = [&](long long b) -> int {
         if ((b << 10) >= npad || !sp_valid[b]) return 0;
-        const uint4 mk = *reinterpret_cast<const uint4*>(sp_mask + 4 * b);
+        const uint4 mk = *reinterpret_cast<const uint4*>(sp_mask + SP_MASK_WORDS * b);
         const bool still = ((mk.x & s_moved[0]) | (mk.y & s_moved[1]) | (mk.z & s_moved[2]) | (mk.w & s_moved[3])) == 0u;
         return (still && cum_now * 0.999999 < (double)sp_slack[b]) ? 1 : 0;
     };
@@ -848,8 +841,8 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
         for (int c = 0; c < UN; c++) { in[c] = i0 + c < n; inc[c] = in[c] && have_cur; }
         const bool wide = al_bnd && __all(i0 + (UN - 1) < n);
         ld_points<UN>((const float*)bnd, (size_t)i0, wide, in, 0.f, ub);
-        ld_points<UN>((const float*)bnd + npad, (size_t)i0, wide, in, 0.f, lb);
-        ld_points<UN>(reinterpret_cast<const int*>(bnd) + 2 * npad, (size_t)i0, wide, in, 0, ap);
+        ld_points<UN>((const float*)bnd + hb_lb(npad), (size_t)i0, wide, in, 0.f, lb);
+        ld_points<UN>(reinterpret_cast<const int*>(bnd) + hb_assign(npad), (size_t)i0, wide, in, 0, ap);
         if (MAPPED) {
             int mp[UN];
             ld_points<UN>(map, (size_t)i0, wide && al_map && have_cur, inc, 0, mp);
@@ -896,11 +889,11 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
 #pragma unroll
         // (the stored assignment of EVERY point indexes the tables, not only of the listed ones: it lies in [0, K) whenever
         //  this kernel runs -- the bounds are valid only after a call that wrote the library's copy for every point; 0 past n)
-        for (int c = 0; c < UN; c++) dav[c] = tab ? s_dk[apv[c]] : bnd[3 * npad + apv[c]];
+        for (int c = 0; c < UN; c++) dav[c] = tab ? s_dk[apv[c]] : bnd[hb_delta(npad) + apv[c]];
         float hv[UN] = {0.f, 0.f, 0.f, 0.f}; // the hints (where one is written)
         if (hintu != nullptr) {
 #pragma unroll
-            for (int c = 0; c < UN; c++) hv[c] = sqrtf(ubv[c] * ubv[c] + (tab ? s_hk[apv[c]] : bnd[3 * npad + HB_HTERM + apv[c]]));
+            for (int c = 0; c < UN; c++) hv[c] = sqrtf(ubv[c] * ubv[c] + (tab ? s_hk[apv[c]] : bnd[hb_hterm(npad) + apv[c]]));
         }
         if (hintu != nullptr && !skip_enabled) // (with the test on, only the points that stay on the screen get a hint: below)
             st_points<UN>(hintu, (size_t)i0, wide, in, hv);
@@ -989,7 +982,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
             __syncthreads();
             if (threadIdx.x == 0) {
                 sp_slack[bsp] = fminf(fminf(s_rmin[0], s_rmin[1]), fminf(s_rmin[2], s_rmin[3]));
-                *reinterpret_cast<uint4*>(sp_mask + 4 * bsp) = make_uint4(s_bmask[0], s_bmask[1], s_bmask[2], s_bmask[3]);
+                *reinterpret_cast<uint4*>(sp_mask + SP_MASK_WORDS * bsp) = make_uint4(s_bmask[0], s_bmask[1], s_bmask[2], s_bmask[3]);
                 sp_valid[bsp] = allk;
                 s_bmask[0] = s_bmask[1] = s_bmask[2] = s_bmask[3] = 0u;
             }
@@ -998,7 +991,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     }
     if (span_read) { // (a span whose blocks all passed as blocks listed nothing: four barriers saved, ~100 spans per workgroup)
     __syncthreads();
-    if (threadIdx.x == 0) s_pos = s_cnt ? atomicAdd(counters + 4, s_cnt) : 0u;
+    if (threadIdx.x == 0) s_pos = s_cnt ? atomicAdd(counters + NL_TODO, s_cnt) : 0u;
     __syncthreads();
     for (unsigned j = threadIdx.x; j < s_cnt; j += 256) todo[s_pos + j] = s_todo[j];
     __syncthreads();
@@ -1010,8 +1003,8 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     if (lane == 0 && nkept) atomicAdd(&s_kept, nkept);
     __syncthreads();
     if (threadIdx.x == 0) { // points that passed the test (either mode), steps whose 16 points all passed: k_call_tail adds them up
-        blkstat[2 * blockIdx.x] = s_kept;
-        blkstat[2 * blockIdx.x + 1] = s_skip;
+        blkstat[BS_STRIDE * blockIdx.x + BS_KEPT] = s_kept;
+        blkstat[BS_STRIDE * blockIdx.x + BS_SKIPPED] = s_skip;
     }
 }
 
@@ -1020,7 +1013,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
 // k_combine_screen / k_assign_list): every member's distance to it, the library's upper bounds, the per-cluster sums and counts, obj2
 // and the largest distance are then exactly what the previous call produced, and they are reused (k_cluster_restore,
 // k_cluster_stats) instead of streamed again.  force != 0: everything is processed (first call of a shard, changed K or
-// gamma, distances requested).  need[k] = 1: process.  counters[32..33]: running total of the points processed.
+// gamma, distances requested).  need[k] = 1: process.  counters[NL_EXACT_TOTAL]: running total of the points processed.
 // The sums and counts of a cluster depend on its MEMBERS only: they are taken from the cache whenever no point left or
 // entered (touched[k] == 0), also when the cluster is streamed again because its centroid moved -- what the pass adds up
 // for it then is discarded (k_cluster_restore).  That is what lets a settled cluster's centroid become bitwise stable in
@@ -1045,8 +1038,8 @@ __global__ void k_cluster_need(int* __restrict__ touched, const int* __restrict_
     if (mine) atomicAdd(&s_pts, mine);
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(counters + 32), s_pts);
-        counters[13] = (unsigned)(s_pts > 0xffffffffull ? 0xffffffffull : s_pts); // points the exact pass processes in this call
+        atomicAdd(reinterpret_cast<unsigned long long*>(counters + NL_EXACT_TOTAL), s_pts);
+        counters[NL_EXACT_PTS] = (unsigned)(s_pts > 0xffffffffull ? 0xffffffffull : s_pts); // points the exact pass processes in this call
     }
 }
 
@@ -1111,19 +1104,19 @@ __global__ __launch_bounds__(256) void k_cluster_stats(const int* __restrict__ n
 // know yet -- a run's second call; the counters come back one call late -- queues BOTH forms, the incremental one
 // (k_plan_segments / k_scatter_by_cluster / k_accumulate_events over the events) and the full sums-only pass
 // (k_cluster_need / plan / scatter / k_exact_accumulate_rec<DIST = false> / k_cluster_restore over all points), and this
-// kernel, queued behind k_assign_list -- when every event has been counted, counters[16] -- opens exactly one of them:
-//   counters[18] = 1: the events (at most ev_cap of them: movers <= n / 3, policy.h few_movers)
-//   counters[19] = 1: the full pass
-// The kernels of the other form return at once (their `gate`) or find an empty work list: nitems[0] (full pass) and
-// nitems[1] (events) are zeroed here, and only the plan kernel that runs fills its own.
+// kernel, queued behind k_assign_list -- when every event has been counted, counters[NL_EVENTS] -- opens exactly one of them:
+//   counters[NL_GATE_EVENTS] = 1: the events (at most ev_cap of them: movers <= n / 3, policy.h few_movers)
+//   counters[NL_GATE_FULL] = 1: the full pass
+// The kernels of the other form return at once (their `gate`) or find an empty work list: nitems[NI_FULL] (full pass) and
+// nitems[NI_EVENTS] (events) are zeroed here, and only the plan kernel that runs fills its own.
 __global__ void k_pick_form(unsigned* __restrict__ counters, unsigned ev_cap, int* __restrict__ nitems)
 {
-    const bool full = counters[16] > ev_cap;
-    counters[18] = full ? 0u : 1u;
-    counters[19] = full ? 1u : 0u;
-    nitems[0] = 0;
-    nitems[1] = 0;
-    nitems[2] = 0; // (pair events: the first-level plan's chunk list)
+    const bool full = counters[NL_EVENTS] > ev_cap;
+    counters[NL_GATE_EVENTS] = full ? 0u : 1u;
+    counters[NL_GATE_FULL] = full ? 1u : 0u;
+    nitems[NI_FULL] = 0;
+    nitems[NI_EVENTS] = 0;
+    nitems[NI_PAIR_CHUNKS] = 0; // (pair events: the first-level plan's chunk list)
 }
 
 // REGROUPING a shard whose 16-point steps mix clusters (data in arbitrary order; api_lloyd.hip, regroup_shard): the library's own
@@ -1139,8 +1132,8 @@ __global__ __launch_bounds__(256) void k_regroup_keys(const float* __restrict__ 
     const double cum_now = *cum;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float ub = bnd[i];
-        const double lb = (double)bnd[npad + i] - cum_now;
-        int a = reinterpret_cast<const int*>(bnd)[2 * npad + i];
+        const double lb = (double)bnd[hb_lb(npad) + i] - cum_now;
+        int a = reinterpret_cast<const int*>(bnd)[hb_assign(npad) + i];
         if ((unsigned)a >= (unsigned)K) a = 0;
         keys[i] = 2 * a + ((lb >= 1.5 * (double)ub) ? 0 : 1); // (NaN: unsure)
     }
@@ -1155,10 +1148,10 @@ __global__ __launch_bounds__(256) void k_regroup_apply(const int* __restrict__ p
             const int o = perm[j];
             newmap[j] = oldmap != nullptr ? oldmap[o] : o;
             bnd_new[j] = bnd_old[o];
-            bnd_new[npad + j] = bnd_old[npad + o];
-            bnd_new[2 * npad + j] = bnd_old[2 * npad + o];
+            bnd_new[hb_lb(npad) + j] = bnd_old[hb_lb(npad) + o];
+            bnd_new[hb_assign(npad) + j] = bnd_old[hb_assign(npad) + o];
         } else {
-            bnd_new[j] = 0.f; bnd_new[npad + j] = 0.f; bnd_new[2 * npad + j] = 0.f;
+            bnd_new[j] = 0.f; bnd_new[hb_lb(npad) + j] = 0.f; bnd_new[hb_assign(npad) + j] = 0.f;
         }
     }
 }
@@ -1193,7 +1186,7 @@ __global__ void k_zero_u64_gated(unsigned long long* __restrict__ dst, int n, co
 }
 
 // Per point: best / second-best estimate over the G tiles, certification, candidate assignment.
-// Uncertified points are appended to list[] (count in *nlist); a tile that reports "no candidate"
+// Uncertified points are appended to list[] (count in nlist[NL_LISTED]); a tile that reports "no candidate"
 // (+inf, +inf, -1) can never certify.
 // PPT = 4 (calls over all points and step lists: the points of a thread's trip are contiguous): a thread takes 4 CONSECUTIVE
 // points -- a quarter of a listed step -- and fetches each result plane, xnr and the library's assignment with one 16-byte load
@@ -1224,14 +1217,14 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     // written to the caller's assignment buffer and into the events (the records are in the caller's order) goes through it;
     // trusted: the caller's buffer already holds the library's copy (lazy statistics, same buffer as last call), so only
     // CHANGES are stored -- through a map every store is a scattered 4-byte write.
-    // wgstat[4 b + 3] (calls over all points): 16-point steps whose points share one cluster -> nlist[21]; the host regroups a
+    // wgstat[WG_STRIDE b + WG_ONE_CLUSTER] (calls over all points): 16-point steps whose points share one cluster -> nlist[NL_ONE_CLUSTER]; the host regroups a
     // shard whose steps are mixed (data in arbitrary order).
     // ev_o != nullptr: PAIR events -- ONE event per mover, (point, new cluster in ev_k, old cluster or -1 in ev_o), and the
     // histogram nk_ev over the K new clusters only: the events are then sorted by (new, old) pair and every mover's record
     // is read once, into its new cluster's sums and out of its old one's (api_lloyd.hip, k_accumulate_events<.., PAIR>); else
     // two events per mover, (point, K + old) and (point, new), over 2 K keys, each applied on its own.
-    // wgstat[3 b .. 3 b + 2]: workgroup b's ambiguous points, "some assignment changed" flag and movers, as plain stores;
-    // k_assign_list (the next launch) adds them up into nlist[1], nlist[5], nlist[14].  One atomic per workgroup and counter
+    // wgstat[WG_STRIDE b + WG_AMBIG / WG_CHANGED / WG_MOVERS]: workgroup b's ambiguous points, "some assignment changed" flag and movers, as plain
+    // stores; k_assign_list (the next launch) adds them up into nlist[NL_AMBIG], nlist[NL_CHANGED], nlist[NL_MOVERS].  One atomic per workgroup and counter
     // on ONE cache line is served at ~10 ns apiece: 3500 workgroups of a settled call's point list (N = 1e8) spent 80 of
     // this kernel's 130 us queueing for them.
     // ev_cap: events appended at a position beyond it are counted but NOT stored -- the call's accumulation form is
@@ -1244,7 +1237,7 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     // every point that changes cluster is recorded as two EVENTS, (point, K + old cluster) and (point, new cluster), for
     // the incremental update of the per-cluster sums (k_accumulate_events).  Events are staged in LDS and appended with
     // one global atomic per ~1500 (half the points move in a run's first iterations: an atomic per wave on one address
-    // would take tens of milliseconds).  nlist[14] counts the movers in every mode, nlist[16] the events.
+    // would take tens of milliseconds).  nlist[NL_MOVERS] counts the movers in every mode, nlist[NL_EVENTS] the events.
     constexpr int EVCAP = 2048;
     // a wave stages at most 64 lanes x PPT points x 2 events per trip: all four waves' reservations fit the empty stage, so a
     // wave that retries after a flush cannot fail for ever
@@ -1256,21 +1249,21 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     // collecting events
     __shared__ unsigned s_evn, s_evbase, s_mov, s_over, s_valid, s_done;
     const double cum_now = cum ? *cum : 0.0; // lower bounds are stored relative to the accumulated drift (k_bounds_steps)
-    // The library's own copy of the assignment (bnd + 2 npad) is kept up to date here and in k_assign_list -- the only
+    // The library's own copy of the assignment (bnd + hb_assign(npad)) is kept up to date here and in k_assign_list -- the only
     // two places an assignment can change: a CERTIFIED point's new cluster is written at once; an uncertified one keeps
     // the previous call's value until k_assign_list has the exact answer.  lib_valid: the copy holds the previous call's
     // final assignment, so that a change is known on the spot --
-    //   nlist[5]: counts (per workgroup) that some assignment changed: the gate of the counting-sort reuse;
+    //   nlist[NL_CHANGED]: counts (per workgroup) that some assignment changed: the gate of the counting-sort reuse;
     //   touched[k] = 1 for every cluster a point left or entered (the unchanged-cluster shortcut, k_cluster_need);
     //   nk[k]: the cluster sizes, moved by the points that changed (collected per workgroup in K ints of dynamic LDS:
     //   half the points move in the first iterations of a run, and global atomics on K addresses would take 100 ms).
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     int* delta = reinterpret_cast<int*>(smem_c);
     unsigned* evc = reinterpret_cast<unsigned*>(smem_c) + (nk ? K : 0); // 2 K event counters (ev_pt != nullptr)
-    int* alib = bnd ? reinterpret_cast<int*>(bnd + 2 * npad) : nullptr;
+    int* alib = bnd ? reinterpret_cast<int*>(bnd + hb_assign(npad)) : nullptr;
     bool changed = false;
     // bnd != nullptr: write each point's new lower bound (k_center_drift's comment)
-    float* lbv = bnd ? bnd + npad : nullptr;
+    float* lbv = bnd ? bnd + npad : nullptr; // (= hb_lb(npad), spelt out: through the function this kernel's registers are allocated differently)
     const double cmax = __builtin_bit_cast(double, *cmax_bits);
     const double u = 0x1p-24;
     const double eu = (2.0 * u + u * u) * (1.0 + 1e-9);
@@ -1278,14 +1271,14 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     const double sqrt_s = sqrt((double)fixed_s) * (1.0 + 1e-15);
     const double nu = 0x1p-45;
     unsigned nambig = 0;
-    // skipping: k_bounds_steps has settled the skipped steps; only the listed ones (nlist[4] of them) are looked at
+    // skipping: k_bounds_steps has settled the skipped steps; only the listed ones (nlist[NL_TODO] of them) are looked at
     // PPT = 1 IS the point-list form (the template argument alone says how todo[] is read: no second flag to disagree with it)
     const bool by_slot = PPT == 1 && skipping;
-    const long long total = skipping ? (by_slot ? (long long)nlist[4] : (long long)nlist[4] * 16) : n;
+    const long long total = skipping ? (by_slot ? (long long)nlist[NL_TODO] : (long long)nlist[NL_TODO] * 16) : n;
     constexpr int WGP = 256 * PPT; // points of a workgroup's trip
     __shared__ unsigned s_amb, s_chg, s_hom;
     if ((long long)blockIdx.x * WGP >= total) { // (whole workgroup)
-        if (threadIdx.x == 0) { wgstat[4 * blockIdx.x] = 0u; wgstat[4 * blockIdx.x + 1] = 0u; wgstat[4 * blockIdx.x + 2] = 0u; wgstat[4 * blockIdx.x + 3] = 0u; }
+        if (threadIdx.x == 0) { wgstat[WG_STRIDE * blockIdx.x + WG_AMBIG] = 0u; wgstat[WG_STRIDE * blockIdx.x + WG_CHANGED] = 0u; wgstat[WG_STRIDE * blockIdx.x + WG_MOVERS] = 0u; wgstat[WG_STRIDE * blockIdx.x + WG_ONE_CLUSTER] = 0u; }
         return;
     }
     if (threadIdx.x == 0) { s_amb = 0u; s_chg = 0u; s_evn = 0u; s_mov = 0u; s_over = 0u; s_hom = 0u; s_valid = 0xffffffffu; s_done = 0u; }
@@ -1315,7 +1308,7 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
         __syncthreads(); // nobody stages from here to the last barrier; every filled slot is visible
         const unsigned nst = min(s_evn, s_valid);
         const unsigned done = s_done;
-        if (threadIdx.x == 0 && nst) { s_evbase = atomicAdd(nlist + 16, nst); if (s_evbase > ev_cap) s_over = 1u; }
+        if (threadIdx.x == 0 && nst) { s_evbase = atomicAdd(nlist + NL_EVENTS, nst); if (s_evbase > ev_cap) s_over = 1u; }
         __syncthreads();
         if (nst && s_evbase <= ev_cap)
             for (unsigned j = threadIdx.x; j < nst; j += blockDim.x) {
@@ -1413,7 +1406,7 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
           if (lazy && certified && bnd) { st_ub[c] = true; ubn[c] = __double2float_ru((r1 + e1) * (1.0 + nu) * (1.0 + 1e-12)); }
           if (lbv) { st_lb[c] = true; lbn[c] = __double2float_rd((certified ? fmax(0.0, (r2 - e2) * (1.0 - nu)) : 0.0) + cum_now); }
           unc[c] = !certified;
-          // nlist[1]: points whose runner-up is within 2.25x of the winner -- the ones a partial-sum lower bound (a
+          // nlist[NL_AMBIG]: points whose runner-up is within 2.25x of the winner -- the ones a partial-sum lower bound (a
           // quarter of the rounds: 5x in the squares leaves a margin)
           // could not separate; the host decides from this count whether the next call may use the two-phase screen
           if (!(r2 >= 2.25 * r1)) nambig++;
@@ -1435,7 +1428,7 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
           for (int c = 0; c < PPT; c++) { um[c] = __ballot(unc[c]); tot += (unsigned)__popcll(um[c]); }
           if (tot) {
               unsigned at = 0;
-              if (ln == 0) at = atomicAdd(nlist, tot);
+              if (ln == 0) at = atomicAdd(nlist + NL_LISTED, tot);
               at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
 #pragma unroll
               for (int c = 0; c < PPT; c++) {
@@ -1505,10 +1498,10 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     if ((threadIdx.x & 63) == 0 && nhomog) atomicAdd(&s_hom, nhomog);
     __syncthreads();
     if (threadIdx.x == 0) {
-        wgstat[4 * blockIdx.x] = s_amb;
-        wgstat[4 * blockIdx.x + 1] = s_chg;
-        wgstat[4 * blockIdx.x + 2] = s_mov;
-        wgstat[4 * blockIdx.x + 3] = s_hom;
+        wgstat[WG_STRIDE * blockIdx.x + WG_AMBIG] = s_amb;
+        wgstat[WG_STRIDE * blockIdx.x + WG_CHANGED] = s_chg;
+        wgstat[WG_STRIDE * blockIdx.x + WG_MOVERS] = s_mov;
+        wgstat[WG_STRIDE * blockIdx.x + WG_ONE_CLUSTER] = s_hom;
     }
     if (nk)
         for (int k = threadIdx.x; k < K; k += blockDim.x)
@@ -1539,29 +1532,29 @@ __global__ __launch_bounds__(256) void k_assign_list(const long long* __restrict
     // its place in the caller's assignment buffer, its id in the events
     // ev_o != nullptr: pair events, one per mover (k_combine_screen)
     // wgstat / nwg: k_combine_screen's per-workgroup statistics (ambiguous points, changed flag, movers); the LAST
-    // workgroup of this launch adds them into counters[1], *changed (counters[5]) and counters[14] -- nobody reads those
+    // workgroup of this launch adds them into counters[NL_AMBIG], *changed (counters[NL_CHANGED]) and counters[NL_MOVERS] -- nobody reads those
     // before this kernel has finished
     if (blockIdx.x == gridDim.x - 1) {
         unsigned a = 0u, c = 0u, m = 0u, h = 0u;
-        for (int b = threadIdx.x; b < nwg; b += blockDim.x) { a += wgstat[4 * b]; c += wgstat[4 * b + 1]; m += wgstat[4 * b + 2]; h += wgstat[4 * b + 3]; }
+        for (int b = threadIdx.x; b < nwg; b += blockDim.x) { a += wgstat[WG_STRIDE * b + WG_AMBIG]; c += wgstat[WG_STRIDE * b + WG_CHANGED]; m += wgstat[WG_STRIDE * b + WG_MOVERS]; h += wgstat[WG_STRIDE * b + WG_ONE_CLUSTER]; }
         for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); c += __shfl_down(c, off); m += __shfl_down(m, off); h += __shfl_down(h, off); }
         if ((threadIdx.x & 63) == 0) {
-            if (a) atomicAdd(counters + 1, a);
+            if (a) atomicAdd(counters + NL_AMBIG, a);
             if (c) atomicAdd(changed, c);
-            if (m) atomicAdd(counters + 14, m);
-            if (h) atomicAdd(counters + 21, h);
+            if (m) atomicAdd(counters + NL_MOVERS, m);
+            if (h) atomicAdd(counters + NL_ONE_CLUSTER, h);
         }
     }
     // alib / lib_valid / touched / nk: the library's copy of the assignment and what follows from a change, as in
     // k_combine_screen (these points kept their previous value there); few points: global atomics
     // ubv != nullptr (lazy calls): the point's upper bound = its exact distance, rounded up; ev_pt / ev_k: the two
-    // events of a point that changes cluster (k_combine_screen); counters[14] movers, counters[16] events
+    // events of a point that changes cluster (k_combine_screen); counters[NL_MOVERS] movers, counters[NL_EVENTS] events
     // rec != nullptr: the point's entries come from the record layout (x | ir side by side, R bytes per point) -- the
     // only copy of the exact entries once the shard's CSC arrays have been released (spkm_shard_release_csc)
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-    const long long cnt = *nlist;
+    const long long cnt = nlist[NL_LISTED];
     for (long long q = wave; q < cnt; q += nwaves) {
         const long long i = list[q];
         const long long ic = map != nullptr ? (long long)map[i] : i;
@@ -1627,16 +1620,16 @@ __global__ __launch_bounds__(256) void k_assign_list(const long long* __restrict
                     alib[i] = bk;
                     if (lib_valid) {
                         atomicAdd(changed, 1u);
-                        atomicAdd(counters + 14, 1u);
+                        atomicAdd(counters + NL_MOVERS, 1u);
                         const bool vo = (unsigned)old < (unsigned)K;
                         if (touched) { if (vo) touched[old] = 1; touched[bk] = 1; }
                         if (nk) { if (vo) atomicAdd(&nk[old], ~0ull); atomicAdd(&nk[bk], 1ull); }
                         if (ev_pt && ev_o != nullptr) {
-                            const unsigned at = atomicAdd(counters + 16, 1u);
+                            const unsigned at = atomicAdd(counters + NL_EVENTS, 1u);
                             if (at <= ev_cap) { ev_pt[at] = (int)ic; ev_k[at] = bk; ev_o[at] = vo ? old : -1; }
                             atomicAdd(&nk_ev[bk], 1ull);
                         } else if (ev_pt) {
-                            const unsigned at = atomicAdd(counters + 16, vo ? 2u : 1u);
+                            const unsigned at = atomicAdd(counters + NL_EVENTS, vo ? 2u : 1u);
                             if (at <= ev_cap) { // (k_combine_screen: past the cap the events are only counted)
                                 if (vo) { ev_pt[at] = (int)ic; ev_k[at] = K + old; }
                                 ev_pt[at + (vo ? 1u : 0u)] = (int)ic; ev_k[at + (vo ? 1u : 0u)] = bk;

@@ -89,7 +89,7 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // bounds this kernel goes through the LDS pipe (a ds_swizzle / ds_bpermute broadcast over 8 lanes would compete with it).
 // Nothing past a column's own s entries is read: a slot beyond the end takes x = 0 and row p without a load, and a point
 // past n reads point n - 1 and stores nothing.
-// LIST: the points are todo[0 .. counters[4]) (k_bounds_steps in point mode; the length is read on the device, no host
+// LIST: the points are todo[0 .. counters[NL_TODO]) (k_bounds_steps in point mode; the length is read on the device, no host
 // sync).  An empty list returns before the tile is loaded.  Slot q is point todo[q]; its results go to plane g at
 // scr_*[g * n + q] (k_combine_screen<1> reads them by slot); a slot past the length computes on the last listed point and
 // stores nothing.  The slots are dealt to a tile's workgroups in chunks sized from the length, so that every workgroup gets
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
     if (bm.tile < 0) return;
     int tp = 0; // LIST: the list's length
     if constexpr (LIST) {
-        tp = (int)counters[4];
+        tp = (int)counters[NL_TODO];
         if (tp <= 0) return; // an empty list: not even the tile is loaded
         if (tp > n) tp = n;
     }

@@ -867,7 +867,6 @@ __global__ void k_nk_to_f64(const unsigned long long* __restrict__ nk, int K, do
 
 // ... together with the other small hand-overs at the end of the fused call (each was a launch of its own): obj^2 into
 // the reduce buffer, the statistics and cluster sizes into the caller's buffers (either may be null)
-#define SPKM_REPORT_WORDS 24 // counters a fused call reports to the host ([19]: the device opened the full pass, k_pick_form)
 __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, double* __restrict__ nk_f,
                             const double* __restrict__ stats, double* __restrict__ obj2, double* __restrict__ d_stats,
                             unsigned long long* __restrict__ d_nk, const unsigned* __restrict__ bstat, int bstat_n,
@@ -878,31 +877,31 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
                             int work_flags = 0, unsigned long long screen_n = 0ull)
 {
     // screen_n: the shard's points -- what this call's screen evaluated: all of them, or (work_flags & 2) the points of its
-    // list, 16 per listed step -- into counters[40], and added to the running total at counters[38..39]
+    // list, 16 per listed step -- into counters[NL_SCREENED], and added to the running total at counters[NL_SCREENED_TOTAL]
     // (spkm_last_screen_points)
     if (screen_n > 0ull && blockIdx.x == 0 && threadIdx.x == 0) {
         unsigned long long v = screen_n;
-        if (work_flags & 2) v = (work_flags & 4) ? (unsigned long long)counters[4] : (unsigned long long)counters[4] * 16ull;
+        if (work_flags & 2) v = (work_flags & 4) ? (unsigned long long)counters[NL_TODO] : (unsigned long long)counters[NL_TODO] * 16ull;
         if (v > screen_n) v = screen_n;
-        counters[40] = (unsigned)v;
-        *reinterpret_cast<unsigned long long*>(counters + 38) += v;
+        counters[NL_SCREENED] = (unsigned)v;
+        *reinterpret_cast<unsigned long long*>(counters + NL_SCREENED_TOTAL) += v;
     }
     // work_*: what this call's 4-lanes-per-point screen launch did, in ROUNDS (4 stored entries of 16 points against the
-    // centroids of one tile) -- counters[34..35] += rounds executed for all centroids of a tile, counters[36..37] += rounds of
+    // centroids of one tile) -- counters[NL_ROUNDS_DONE] += rounds executed for all centroids of a tile, counters[NL_ROUNDS_FULL] += rounds of
     // a launch that does all the work (work_steps = ceil(n / 16) steps x work_tiles x work_nr); running totals, read by
     // spkm_screen_work_totals (bench.py weights the window's algorithmic bytes by their ratio).  work_flags: 1 = the
-    // unconditional two-phase form (every step stops after work_a rounds), 2 = the launch ran over a list (counters[4]
-    // entries), 4 = of points; the hinted form's early-finished (step, tile) pairs are counters[2].
+    // unconditional two-phase form (every step stops after work_a rounds), 2 = the launch ran over a list (counters[NL_TODO]
+    // entries), 4 = of points; the hinted form's early-finished (step, tile) pairs are counters[NL_EARLY].
     if (work_tiles > 0 && blockIdx.x == 0 && threadIdx.x == 0) {
         unsigned long long steps = work_steps;
-        if (work_flags & 2) steps = (work_flags & 4) ? ((unsigned long long)counters[4] + 15ull) / 16ull : (unsigned long long)counters[4];
+        if (work_flags & 2) steps = (work_flags & 4) ? ((unsigned long long)counters[NL_TODO] + 15ull) / 16ull : (unsigned long long)counters[NL_TODO];
         unsigned long long r = steps * (unsigned long long)work_tiles * (unsigned long long)((work_flags & 1) ? work_a : work_nr);
         if (!(work_flags & 1) && work_a < work_nr) {
-            const unsigned long long saved = (unsigned long long)counters[2] * (unsigned long long)(work_nr - work_a);
+            const unsigned long long saved = (unsigned long long)counters[NL_EARLY] * (unsigned long long)(work_nr - work_a);
             r -= saved < r ? saved : r;
         }
-        *reinterpret_cast<unsigned long long*>(counters + 34) += r;
-        *reinterpret_cast<unsigned long long*>(counters + 36) += work_steps * (unsigned long long)work_tiles * (unsigned long long)work_nr;
+        *reinterpret_cast<unsigned long long*>(counters + NL_ROUNDS_DONE) += r;
+        *reinterpret_cast<unsigned long long*>(counters + NL_ROUNDS_FULL) += work_steps * (unsigned long long)work_tiles * (unsigned long long)work_nr;
     }
     // host_out != nullptr: pinned host memory, device-mapped -- the call's first SPKM_REPORT_WORDS counters for the host policy go there, then
     // the report's number `seq` with a system-scope release (api_lloyd.hip reads them one call later, if the number is there)
@@ -920,12 +919,12 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
     }
     // lazy != 0: this call did not evaluate the objective, the largest distance and its index (spkm_shard_set_lazy_stats):
     // NaN in their places, so that a caller that reads them anyway cannot mistake them for values
-    // bstat: (points kept, steps skipped) per workgroup of k_bounds_steps -> counters[12], counters[3] and the running
-    // total at counters[8..9] (read by the host one call later)
+    // bstat: (points kept, steps skipped) per workgroup of k_bounds_steps -> counters[NL_KEPT], counters[NL_SKIPPED] and the running
+    // total at counters[NL_SKIPPED_TOTAL] (read by the host one call later)
     if (blockIdx.x == 0 && bstat_n > 0) {
         __shared__ unsigned s_k[256], s_s[256];
         unsigned a = 0, b = 0;
-        for (int t = threadIdx.x; t < bstat_n; t += blockDim.x) { a += bstat[2 * t]; b += bstat[2 * t + 1]; }
+        for (int t = threadIdx.x; t < bstat_n; t += blockDim.x) { a += bstat[BS_STRIDE * t + BS_KEPT]; b += bstat[BS_STRIDE * t + BS_SKIPPED]; }
         s_k[threadIdx.x] = a; s_s[threadIdx.x] = b;
         __syncthreads();
         for (int off = 128; off > 0; off >>= 1) {
@@ -933,9 +932,9 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            counters[12] += s_k[0];
-            counters[3] += s_s[0];
-            *reinterpret_cast<unsigned long long*>(counters + 8) += (unsigned long long)s_s[0];
+            counters[NL_KEPT] += s_k[0];
+            counters[NL_SKIPPED] += s_s[0];
+            *reinterpret_cast<unsigned long long*>(counters + NL_SKIPPED_TOTAL) += (unsigned long long)s_s[0];
         }
     }
     if (host_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { // (thread 0 made the last changes to the counters itself)

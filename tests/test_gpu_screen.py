@@ -55,6 +55,29 @@ def test_screen_path_equals_oracle(gpu_ctx, oracle, p, n, K, s):
     assert listed < 0.05 * n                                # random data: almost everything certifies
 
 
+def test_exact_call_after_a_screen_call_reports_no_screen(gpu_ctx, monkeypatch):
+    """A fused call that takes the exact path leaves every spkm_last_* accessor at its "no screen" answer, whatever the
+    screen call before it reported; the context's running total of screened points does not move."""
+    p, n, K, s = 64, 4096, 8, 8
+    X = random_csc(p, n, s, seed=5)
+    Cm = np.random.default_rng(5).standard_normal((p, K)) * 0.3
+    eng, path, _ = _run(gpu_ctx, X, Cm, s / p)
+    assert path == 1 and eng.last_screen_tile() == (32, 1) and eng.last_screen_rounds() == (2, 2)
+    assert eng.last_screen_mode()[0] == 0 and eng.last_assign_tile()[2] > 0
+    screened, total = eng.last_screen_points()
+    assert screened == n
+    set_switch(monkeypatch, gpu_ctx, "SPKM_NO_SCREEN")
+    eng.assign_accumulate_step(torch.tensor(np.ascontiguousarray(Cm.T), device=f"cuda:{gpu_ctx.device}"))
+    torch.cuda.synchronize()
+    assert tuple(eng.last_screen_mode()) == (-1, 0, 0, 0, 0, 0, 0, 0)
+    assert eng.last_events_form() == (0, 0)
+    assert eng.last_screen_tile() == (0, 0)
+    assert eng.last_screen_rounds() == (0, 0)
+    assert eng.last_assign_tile()[2] == 0
+    assert eng.last_path_info() == (0, 0)
+    assert eng.last_screen_points() == (0, total)
+
+
 @pytest.mark.parametrize("p,n,K,s", [(256, 4000, 44, 13),    # last tile 12 centroids: 2 pairs per lane
                                      (256, 4000, 48, 16),    # last tile 16: 2 pairs per lane, rounds of exactly 4
                                      (128, 3000, 64, 1),     # one entry per point, full tiles only
