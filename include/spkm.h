@@ -453,10 +453,39 @@ int spkm_dct_apply_dev(spkm_ctx *ctx, uint64_t p, uint64_t nvec, const double *d
 int spkm_shard_create_rec_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, uint64_t s, int ir_bits, const void *d_rec,
                               spkm_shard **out);
 
+/* Element types a streamed chunk may arrive in (a dataset of 1e9 points is not stored as doubles).  Every value of every
+ * kind is exactly representable as a double.  SPKM_SRC_F16 is IEEE binary16, SPKM_SRC_BF16 the top 16 bits of a binary32;
+ * subnormals and +-0 keep their value and sign, NaN stays NaN. */
+#define SPKM_SRC_F64 0
+#define SPKM_SRC_F32 1
+#define SPKM_SRC_U8 2
+#define SPKM_SRC_I16 3
+#define SPKM_SRC_I32 4
+#define SPKM_SRC_F16 5
+#define SPKM_SRC_BF16 6
+#define SPKM_SRC_I8 7
+#define SPKM_SRC_U16 8
+
 /* Widening copy in front of the sparsifier for streamed ingest (private/sampleAndMixFromLargeFile.m:100-113 reads a
- * chunk as doubles; a dataset of 1e9 points is stored narrower): d_dst[i] = (double) d_src[i], exact for every kind.
- * kind: 1 float32, 2 uint8, 3 int16, 4 int32.  Both buffers on the device, `count` elements. */
+ * chunk as doubles): d_dst[i] = (double) d_src[i], exact for every kind.
+ * kind: SPKM_SRC_F32 .. SPKM_SRC_U16 (1 .. 8; SPKM_ERR_BAD_VALUE otherwise).  Both buffers on the device, `count`
+ * elements. */
 int spkm_widen_f64_dev(spkm_ctx *ctx, int kind, uint64_t count, const void *d_src, double *d_dst);
+
+/* spkm_mix_sample_dev / spkm_mix_sample_rec_dev on a chunk in its own element type: d_src is the p x n chunk as src_kind
+ * elements (SPKM_SRC_*), every other argument as there.  For 16 <= p2 <= 16384 (the widths whose mixed column stays in
+ * LDS) the fused transform + sample kernel reads the source directly -- 16 bytes per load where p is a multiple of
+ * 16 / (element size) and d_src and d_sign are 16-byte aligned, one element per load otherwise -- so no float64 copy of
+ * the chunk is ever written: 2 bytes of HBM traffic per float16 element instead of 18.  Rows and values are, bit for bit,
+ * those of the float64 entries on the widened chunk.  SPKM_SRC_F64 forwards to those entries.
+ * SPKM_ERR_UNSUPPORTED for a narrow kind at any other width (widen with spkm_widen_f64_dev and call the float64 entry);
+ * SPKM_ERR_BAD_VALUE for an unknown src_kind, p == 0, and whatever the float64 entries refuse. */
+int spkm_mix_sample_src_dev(spkm_ctx *ctx, uint64_t p, uint64_t p2, uint64_t n, int src_kind, const void *d_src,
+                            const double *d_sign, double premul, double postdiv, uint64_t s, uint64_t seed,
+                            uint64_t col0, void *d_ir_out, int ir_bits, double *d_x_out);
+int spkm_mix_sample_rec_src_dev(spkm_ctx *ctx, uint64_t p, uint64_t p2, uint64_t n, int src_kind, const void *d_src,
+                                const double *d_sign, double premul, double postdiv, uint64_t s, uint64_t seed,
+                                uint64_t col0, int ir_bits, void *d_rec_out);
 
 /* Dense (unsampled) data behind the reference's two-pass outputs.
  * d_X: n x p, point i at d_X + i*p (= column-major p x n); d_centers: K x p, centre k at d_centers + k*p.

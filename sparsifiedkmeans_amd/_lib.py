@@ -126,6 +126,8 @@ def lib():
     L.spkm_record_bytes.argtypes = [_u64, C.c_int]
     L.spkm_record_bytes.restype = _u64
     L.spkm_mix_sample_rec_dev.argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _dbl, _dbl, _u64, _u64, _u64, C.c_int, _vp]
+    L.spkm_mix_sample_src_dev.argtypes = [_vp, _u64, _u64, _u64, C.c_int, _vp, _vp, _dbl, _dbl, _u64, _u64, _u64, _vp, C.c_int, _vp]
+    L.spkm_mix_sample_rec_src_dev.argtypes = [_vp, _u64, _u64, _u64, C.c_int, _vp, _vp, _dbl, _dbl, _u64, _u64, _u64, C.c_int, _vp]
     L.spkm_sketch_sample_dev.argtypes = [_vp, C.c_int, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, _vp, C.c_int, _vp]
     L.spkm_sketch_sample_rec_dev.argtypes = [_vp, C.c_int, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, C.c_int, _vp]
     L.spkm_dct_sample_dev.argtypes = [_vp, _u64, _u64, _vp, _vp, _dbl, _u64, _u64, _u64, _vp, C.c_int, _vp]

@@ -897,6 +897,94 @@ extern "C" int spkm_mix_sample_rec_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, u
     return fwht_launch(ctx, p, p2, n, d_x, d_sign, premul, postdiv, (double*)d_rec_out, ir0, ir_bits, (int)s, level, R);
 }
 
+// The typed-source forms of the two entries above for the LDS-resident widths: k_sample_rows as there, then
+// k_fwht_lds<false, SRC> reads the chunk in its own element type (no float64 copy of it exists).  The 16-byte load stage
+// needs whole 16-byte pieces that do not straddle the end of a column: p % (16 / sizeof(SRC)) == 0 and 16-byte aligned
+// d_src (every column then starts aligned) and d_sign; anything else (a source that starts inside an allocation, an odd
+// p) takes the element-wise stage.  Same doubles in LDS either way, so the same bits as the float64 entries on the widened
+// chunk.  stride > 0: records (ids at ir, values at out, column c at + c * stride); stride == 0: CSC.
+template <typename SRC>
+static int fwht_launch_src(spkm_ctx* ctx, uint64_t p, uint64_t m, uint64_t n, const void* d_src, const double* d_sign,
+                           double premul, double postdiv, double* d_y, const void* gather_ir, int gather_bits,
+                           int gather_s, double gather_level, long long gather_stride)
+{
+    int logm = 0;
+    while ((1ull << logm) < m) logm++;
+    const int T = (int)(m / 16);
+    const int threads = std::max(T, 256);
+    const int cpb = threads / T;
+    const size_t lds = (size_t)cpb * (m + m / 8) * 8;
+    const uint64_t epl = 16 / sizeof(SRC);
+    const int vec16 = p % epl == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_sign % 16 == 0;
+    HIP_TRY(hipFuncSetAttribute((const void*)k_fwht_lds<false, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const uint64_t want = (n + cpb - 1) / cpb;
+    hipLaunchKernelGGL((k_fwht_lds<false, SRC>), dim3((unsigned)std::min<uint64_t>(want, (uint64_t)std::max(1, ctx->num_cus) * 16)),
+                       dim3(threads), lds, ctx->stream, (const SRC*)d_src, d_y, (int)m, logm, (long long)n, (int)p, d_sign,
+                       premul, postdiv, cpb, gather_ir, gather_bits, gather_s, gather_level, gather_stride, 0, vec16);
+    HIP_TRY(hipGetLastError());
+    return SPKM_OK;
+}
+
+static int mix_sample_src(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint64_t n, int src_kind, const void* d_src,
+                          const double* d_sign, double premul, double postdiv, uint64_t s, uint64_t seed, uint64_t col0,
+                          void* ir, int ir_bits, double* out, long long stride)
+{
+    if (s == 0 || s > p2 || (ir_bits != 16 && ir_bits != 32) || (ir_bits == 16 && p2 > 65536)) return SPKM_ERR_BAD_VALUE;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return SPKM_OK;
+    int rc = check_pow2(p2);
+    if (rc) return rc;
+    if (p == 0 || p > p2) return SPKM_ERR_BAD_VALUE;
+    if (!mix_in_lds(ctx, p2)) return SPKM_ERR_UNSUPPORTED;   // the caller widens (spkm_widen_f64_dev) and takes the float64 entry
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, ctx->num_cus) * 16);
+    if (ir_bits == 16)
+        hipLaunchKernelGGL((k_sample_rows<unsigned short>), dim3(blocks), dim3(256), 0, ctx->stream,
+                           (unsigned long long)seed, (long long)col0, (long long)n, (int)p2, (int)s, (unsigned short*)ir, stride);
+    else
+        hipLaunchKernelGGL((k_sample_rows<unsigned int>), dim3(blocks), dim3(256), 0, ctx->stream,
+                           (unsigned long long)seed, (long long)col0, (long long)n, (int)p2, (int)s, (unsigned int*)ir, stride);
+    HIP_TRY(hipGetLastError());
+    const double level = (double)s / (double)p2;
+    switch (src_kind) {
+    case SPKM_SRC_F32: return fwht_launch_src<float>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    case SPKM_SRC_U8: return fwht_launch_src<unsigned char>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    case SPKM_SRC_I16: return fwht_launch_src<short>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    case SPKM_SRC_I32: return fwht_launch_src<int>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    case SPKM_SRC_F16: return fwht_launch_src<src_f16>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    case SPKM_SRC_BF16: return fwht_launch_src<src_bf16>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    case SPKM_SRC_I8: return fwht_launch_src<signed char>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    default: return fwht_launch_src<unsigned short>(ctx, p, p2, n, d_src, d_sign, premul, postdiv, out, ir, ir_bits, (int)s, level, stride);
+    }
+}
+
+extern "C" int spkm_mix_sample_src_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint64_t n, int src_kind, const void* d_src,
+                                       const double* d_sign, double premul, double postdiv, uint64_t s, uint64_t seed,
+                                       uint64_t col0, void* d_ir_out, int ir_bits, double* d_x_out)
+{
+    if (!ctx || (n && (!d_src || !d_ir_out || !d_x_out))) return SPKM_ERR_NULL_ARG;
+    if (src_kind < SPKM_SRC_F64 || src_kind > SPKM_SRC_U16) return SPKM_ERR_BAD_VALUE;
+    if (src_kind == SPKM_SRC_F64)
+        return spkm_mix_sample_dev(ctx, p, p2, n, (const double*)d_src, d_sign, premul, postdiv, s, seed, col0, d_ir_out,
+                                   ir_bits, d_x_out);
+    return mix_sample_src(ctx, p, p2, n, src_kind, d_src, d_sign, premul, postdiv, s, seed, col0, d_ir_out, ir_bits, d_x_out, 0);
+}
+
+extern "C" int spkm_mix_sample_rec_src_dev(spkm_ctx* ctx, uint64_t p, uint64_t p2, uint64_t n, int src_kind,
+                                           const void* d_src, const double* d_sign, double premul, double postdiv,
+                                           uint64_t s, uint64_t seed, uint64_t col0, int ir_bits, void* d_rec_out)
+{
+    if (!ctx || (n && (!d_src || !d_rec_out))) return SPKM_ERR_NULL_ARG;
+    if (src_kind < SPKM_SRC_F64 || src_kind > SPKM_SRC_U16) return SPKM_ERR_BAD_VALUE;
+    if (src_kind == SPKM_SRC_F64)
+        return spkm_mix_sample_rec_dev(ctx, p, p2, n, (const double*)d_src, d_sign, premul, postdiv, s, seed, col0, ir_bits,
+                                       d_rec_out);
+    if (s == 0 || (ir_bits != 16 && ir_bits != 32)) return SPKM_ERR_BAD_VALUE;
+    const long long R = (long long)spkm_record_bytes(s, ir_bits);
+    // (the gather reads column c's ids at d_rec_out + s * 8 + c R and writes its values at d_rec_out + c R)
+    return mix_sample_src(ctx, p, p2, n, src_kind, d_src, d_sign, premul, postdiv, s, seed, col0, (char*)d_rec_out + s * 8,
+                          ir_bits, (double*)d_rec_out, R);
+}
+
 // The sparsifier for the DCT and for no sketch (p2 = p): k_sample_rows draws the rows exactly as for the Hadamard path,
 // k_sketch_gather evaluates the sketch at them.  stride > 0: records (ids at d_out + s*8 + c*stride, values at d_out +
 // c*stride); stride == 0: CSC (ids in d_ir_out, values in d_out).
@@ -1030,7 +1118,7 @@ extern "C" int spkm_dct_apply_dev(spkm_ctx* ctx, uint64_t p, uint64_t nvec, cons
 extern "C" int spkm_widen_f64_dev(spkm_ctx* ctx, int kind, uint64_t count, const void* d_src, double* d_dst)
 {
     if (!ctx || (count && (!d_src || !d_dst))) return SPKM_ERR_NULL_ARG;
-    if (kind < 1 || kind > 4) return SPKM_ERR_BAD_VALUE;
+    if (kind < SPKM_SRC_F32 || kind > SPKM_SRC_U16) return SPKM_ERR_BAD_VALUE;
     HIP_TRY(hipSetDevice(ctx->device));
     if (count == 0) return SPKM_OK;
     const unsigned blocks = (unsigned)std::min<uint64_t>((count / 2 + 255) / 256 + 1, (uint64_t)std::max(1, ctx->num_cus) * 32);

@@ -17,6 +17,79 @@
 
 __device__ __forceinline__ int padidx(int e) { return e + ((e >> 4) << 1); }
 
+// ---- typed sources (SPKM_SRC_*): the element types a chunk may arrive in.  Every value of every one of them is a double,
+// so src_to_f64 is exact; float16 goes through float (v_cvt_f32_f16, v_cvt_f64_f32), bfloat16 is the top half of a float.
+// Neither conversion flushes on this target as the library is built (both denormal modes of the kernel descriptor are
+// "preserve"): subnormals and +-0 keep their value and sign (tests/test_gpu_half_sources.py takes all 65536 patterns).
+struct src_f16 { unsigned short bits; };
+struct src_bf16 { unsigned short bits; };
+__device__ __forceinline__ double src_to_f64(double v) { return v; }
+__device__ __forceinline__ double src_to_f64(float v) { return (double)v; }
+__device__ __forceinline__ double src_to_f64(unsigned char v) { return (double)v; }
+__device__ __forceinline__ double src_to_f64(signed char v) { return (double)v; }
+__device__ __forceinline__ double src_to_f64(short v) { return (double)v; }
+__device__ __forceinline__ double src_to_f64(unsigned short v) { return (double)v; }
+__device__ __forceinline__ double src_to_f64(int v) { return (double)v; }
+__device__ __forceinline__ double src_to_f64(src_f16 v)
+{
+    _Float16 h;
+    __builtin_memcpy(&h, &v.bits, 2);
+    return (double)(float)h;
+}
+__device__ __forceinline__ double src_to_f64(src_bf16 v) { return (double)__uint_as_float((unsigned)v.bits << 16); }
+
+// The load stage of k_fwht_lds for a source narrower than double, 16 bytes per load: EPL = 16 / sizeof(SRC) elements.  A
+// thread issues sizeof(SRC) such loads (its 16 elements of the column, as before): chunk j = tau + T*i covers elements
+// EPL*j .. EPL*j + EPL - 1.  The caller guarantees p_in % EPL == 0 and 16-byte aligned x and dsign, so that a chunk lies
+// wholly below or wholly at / above lim = p_in: the loads are unconditional on a clamped chunk index and the chunks past
+// lim are zeroed afterwards (the pattern of the element-wise stage).  Per element: widen, w = v * premul, w = sg * w.
+// LDS: a chunk's EPL doubles are consecutive in the padded column (EPL <= 16 never crosses a 16-element pad boundary)
+// and start at doubles EPL*j + 2*(EPL*j >> 4), a multiple of 2: EPL/2 ds_write_b128.  That instruction banks by
+// (a/4) mod 32 within groups of 8 consecutive lanes, and consecutive lanes hold consecutive j.  In dwords the k-th store
+// of chunk j starts at  2*EPL*j + 4*(EPL*j >> 4) + 4k:
+//   EPL = 16 (1-byte types): 36j + 4k == 4(j + k) mod 32
+//   EPL =  8 (2-byte types): 16j + 4(j >> 1) + 4k  -> j = 0..7: 0, 16, 4, 20, 8, 24, 12, 28 (+ 4k)
+//   EPL =  4 (4-byte types):  8j + 4(j >> 2) + 4k  -> j = 0..7: 0, 8, 16, 24, 4, 12, 20, 28 (+ 4k)
+// In each case the 8 lanes of a group start on 8 different multiples of 4 dwords and write 4 dwords each: all 32 banks
+// once, conflict-free (as the 16-B-aligned runs of fwht_round are).
+template <typename SRC>
+__device__ __forceinline__ void fwht_load16(const SRC* __restrict__ xc, const double* __restrict__ dsign, double premul,
+                                            int lim, int tau, int T, bool have, double* __restrict__ col)
+{
+    constexpr int EPL = 16 / (int)sizeof(SRC), NL = (int)sizeof(SRC);
+    struct alignas(16) chunk { SRC e[EPL]; };
+    chunk v[NL];
+    double2 sg[NL][EPL / 2];
+    const int last = lim / EPL - 1;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        const int j = tau + T * i;
+        v[i] = reinterpret_cast<const chunk*>(xc)[j * EPL < lim ? j : last];
+    }
+    if (dsign) {
+#pragma unroll
+        for (int i = 0; i < NL; i++)
+#pragma unroll
+            for (int k = 0; k < EPL / 2; k++)
+                sg[i][k] = reinterpret_cast<const double2*>(dsign)[(tau + T * i) * (EPL / 2) + k];
+    }
+    if (have) {
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            const int e0 = (tau + T * i) * EPL;
+            const bool in = e0 < lim;
+            double2* dst = reinterpret_cast<double2*>(col + padidx(e0));
+#pragma unroll
+            for (int k = 0; k < EPL / 2; k++) {
+                double w0 = in ? src_to_f64(v[i].e[2 * k]) : 0.0, w1 = in ? src_to_f64(v[i].e[2 * k + 1]) : 0.0;
+                if (premul != 1.0) { w0 = w0 * premul; w1 = w1 * premul; }
+                if (dsign) { w0 = sg[i][k].x * w0; w1 = sg[i][k].y * w1; }
+                dst[k] = make_double2(w0, w1);
+            }
+        }
+    }
+}
+
 // One round of NB (<= 4) butterfly stages, bits b .. b+NB-1, on the 16 elements this thread owns:
 //   NB == 4: e(q) = (H << (b+4)) | (q << b) | L      with tau = (H << b) | L
 //   NB <  4 (last round, b + NB == logm): the 4-NB spare bits of q come from the top of L
@@ -58,14 +131,18 @@ __device__ __forceinline__ void fwht_round(double* __restrict__ col, int tau, in
 // j = v mod 2^slice_log2 of input column c = v >> slice_log2, i.e. rows j*m .. j*m + m - 1 of the zero-padded p2-vector
 // (x column stride p_in; rows >= p_in read as 0; sign d[j*m + i]).  Its stages bit = 1 .. m/2 land at y + v*m = the
 // slice's place in the p2 x n result.  Callers pass postdiv = 0 and no gather: k_fwht_high applies the rest.
-template <bool SLICED>
-__global__ __launch_bounds__(1024) void k_fwht_lds(const double* __restrict__ x, double* __restrict__ y, int m,
+// SRC: the element type of x (double, or one of the typed sources above: the fused FWHT -> sample kernel then reads the
+// chunk in its own width and no float64 copy of it exists).  vec16 != 0 (SRC narrower than double only): fwht_load16,
+// see there for what the caller guarantees; otherwise the element-wise stage, whose every load is one element.  Both
+// stages put the same doubles into LDS, so everything after them gives the same bits.
+template <bool SLICED, typename SRC = double>
+__global__ __launch_bounds__(1024) void k_fwht_lds(const SRC* __restrict__ x, double* __restrict__ y, int m,
                                                    int logm, long long n, int p_in,
                                                    const double* __restrict__ dsign, double premul,
                                                    double postdiv, int cols_per_block,
                                                    const void* __restrict__ gather_ir, int gather_bits, int gather_s,
                                                    double gather_level, long long gather_stride = 0,
-                                                   int slice_log2 = 0)
+                                                   int slice_log2 = 0, int vec16 = 0)
 {
     // gather epilogue (sample.hip): when gather_ir != null the transformed column stays in LDS and only
     // its gather_s sampled rows are written, y[c*gather_s + t] = (Y[row_t] / postdiv) / gather_level.
@@ -102,7 +179,13 @@ __global__ __launch_bounds__(1024) void k_fwht_lds(const double* __restrict__ x,
         // thread (csub, tau) fetches elements tau + T*i, i = 0..15, of its own column: 16 independent loads
         // in flight per lane (a rolled loop would expose 16 HBM latencies one after the other)
         const long long ncols = (n - cbase < cols_per_block) ? (n - cbase) : cols_per_block;
-        {
+        if (sizeof(SRC) < 8 && !SLICED && vec16) {
+            if constexpr (sizeof(SRC) < 8 && !SLICED) {
+                const bool have = csub < ncols;
+                const long long vc = cbase + (have ? csub : 0);
+                fwht_load16<SRC>(x + (size_t)vc * p_in, dsign, premul, p_in, tau, T, have, col);
+            }
+        } else {
             double v[16];
             double sg[16];
             const bool have = csub < ncols;
@@ -113,11 +196,11 @@ __global__ __launch_bounds__(1024) void k_fwht_lds(const double* __restrict__ x,
             // whose clamped index lim - 1 still is the column's last element)
             const int off = SLICED ? (int)(vc & ((1 << slice_log2) - 1)) << logm : 0;
             const int lim = p_in - off;
-            const double* xc = SLICED ? x + (size_t)(vc >> slice_log2) * p_in + off : x + (size_t)vc * p_in;
+            const SRC* xc = SLICED ? x + (size_t)(vc >> slice_log2) * p_in + off : x + (size_t)vc * p_in;
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 const int r = tau + T * i;
-                v[i] = xc[r < lim ? r : lim - 1];
+                v[i] = src_to_f64(xc[r < lim ? r : lim - 1]);
             }
             if (dsign) {
 #pragma unroll

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_sample_rows(unsigned long long seed, lo
 // float32 features -- what a 1e9-point dataset is stored as) and is widened to the double
 // the reference's pipeline works in (sampleAndMixFromLargeFile.m:104-113 reads doubles).  Every uint8 / int16 /
 // float32 value is exactly representable: the copy is exact.  16 B stored per lane and iteration.
-//   kind: 1 float32, 2 uint8, 3 int16, 4 int32
+//   kind (SPKM_SRC_*): 1 float32, 2 uint8, 3 int16, 4 int32, 5 float16, 6 bfloat16, 7 int8, 8 uint16 (src_to_f64, fwht.hip)
 __global__ __launch_bounds__(256) void k_widen_f64(const void* __restrict__ src, int kind, long long count,
                                                    double* __restrict__ dst)
 {
@@ -79,6 +79,10 @@ __global__ __launch_bounds__(256) void k_widen_f64(const void* __restrict__ src,
         case 1: a = (double)static_cast<const float*>(src)[i]; if (two) b = (double)static_cast<const float*>(src)[i + 1]; break;
         case 2: a = (double)static_cast<const unsigned char*>(src)[i]; if (two) b = (double)static_cast<const unsigned char*>(src)[i + 1]; break;
         case 3: a = (double)static_cast<const short*>(src)[i]; if (two) b = (double)static_cast<const short*>(src)[i + 1]; break;
+        case 5: a = src_to_f64(static_cast<const src_f16*>(src)[i]); if (two) b = src_to_f64(static_cast<const src_f16*>(src)[i + 1]); break;
+        case 6: a = src_to_f64(static_cast<const src_bf16*>(src)[i]); if (two) b = src_to_f64(static_cast<const src_bf16*>(src)[i + 1]); break;
+        case 7: a = (double)static_cast<const signed char*>(src)[i]; if (two) b = (double)static_cast<const signed char*>(src)[i + 1]; break;
+        case 8: a = (double)static_cast<const unsigned short*>(src)[i]; if (two) b = (double)static_cast<const unsigned short*>(src)[i + 1]; break;
         default: a = (double)static_cast<const int*>(src)[i]; if (two) b = (double)static_cast<const int*>(src)[i + 1]; break;
         }
         dst[i] = a;

@@ -582,7 +582,43 @@ def dense_accumulate_device(ctx: Context, x: torch.Tensor, assign: torch.Tensor,
                                                     _p(counts)), "spkm_dense_accumulate_dev")
 
 
-_WIDEN_KIND = {torch.float32: 1, torch.uint8: 2, torch.int16: 3, torch.int32: 4}
+# SPKM_SRC_* of a chunk's dtype.  uint16 (SRC_U16 = 8) has no entry: it travels as an int16 view of the same bytes with the
+# kind given explicitly (StreamingSparsifier.append), never through torch.uint16 arithmetic.
+_WIDEN_KIND = {torch.float32: 1, torch.uint8: 2, torch.int16: 3, torch.int32: 4, torch.float16: 5, torch.bfloat16: 6,
+               torch.int8: 7}
+SRC_U16 = 8
+MIX_LDS_MIN_P2, MIX_LDS_MAX_P2 = 16, 16384   # spkm_mix_sample_src_dev / _rec_src_dev read a typed source at these widths
+
+
+def mix_sample_source_device(ctx: Context, src: torch.Tensor, src_kind: int, p2: int, sign: torch.Tensor | None,
+                             premul: float, postdiv: float, s: int, seed: int, col0: int, ir_out: torch.Tensor | None,
+                             x_out: torch.Tensor | None, rec_out: torch.Tensor | None = None, ir_bits: int = 16) -> bool:
+    """mix_sample_device / mix_sample_records_device (``rec_out`` given) on a device chunk [n, p] in its own element type
+    (spkm_mix_sample_src_dev / spkm_mix_sample_rec_src_dev): the fused kernel reads the source directly, no float64 copy
+    of the chunk exists.  ``src_kind`` is the SPKM_SRC_* of the elements (a uint16 chunk is an int16 tensor with kind 8).
+    Returns False, having done nothing, where the library offers no typed route (widths outside the LDS range): the
+    caller widens; every other failure raises."""
+    assert src.is_cuda and src.is_contiguous() and src.dim() == 2
+    n, p = src.shape
+    L = _lib.lib()
+    sg = _p(sign) if sign is not None else None
+    if rec_out is not None:
+        assert rec_out.dtype == torch.uint8 and rec_out.is_contiguous() and rec_out.numel() >= n * record_bytes(s, ir_bits)
+        rc = L.spkm_mix_sample_rec_src_dev(ctx.handle, p, p2, n, int(src_kind), _p(src), sg, float(premul), float(postdiv),
+                                           int(s), int(seed) & (2**64 - 1), int(col0), int(ir_bits), _p(rec_out))
+        where = "spkm_mix_sample_rec_src_dev"
+    else:
+        assert ir_out.numel() >= n * s and x_out.numel() >= n * s and x_out.dtype == torch.float64
+        rc = L.spkm_mix_sample_src_dev(ctx.handle, p, p2, n, int(src_kind), _p(src), sg, float(premul), float(postdiv),
+                                       int(s), int(seed) & (2**64 - 1), int(col0), _p(ir_out),
+                                       ir_out.element_size() * 8, _p(x_out))
+        where = "spkm_mix_sample_src_dev"
+    if rc == _lib.ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, where)
+    return True
+
+
 def _copy_threads() -> int:
     """threads of the host-side staging copy (SPKM_COPY_THREADS overrides).  Measured on the benchmark box (256 hardware
     threads, tools/ingest_probe2.py): torch's own parallel copy moves 93 GB/s into pinned memory with 16 threads, 21 GB/s
@@ -629,8 +665,12 @@ class StreamingSparsifier:
     p > DCT_TABLE_MAX_P = 16384, up to DCT_MAX_P = 131072, spkm_dct_sample_dev with the same rows).  The rows are
     drawn by the same generator for every kind.  Without ``kind``, ``sketch=True`` means "hadamard", False "none".
 
-    Chunks may arrive as float64 / float32 / uint8 / int16 / int32 (a 1e9-point dataset is not stored as doubles);
-    narrower types cross PCIe as they are and are widened on the device (spkm_widen_f64_dev, exact).  Host chunks go
+    Chunks may arrive as float64 / float32 / float16 / bfloat16 / uint8 / int8 / int16 / uint16 / int32 (a 1e9-point
+    dataset is not stored as doubles); narrower types cross PCIe as they are and become doubles on the device, exactly.
+    With ``fused_source`` (the default) and a Hadamard sketch of 16 <= p2 <= 16384 the fused transform + sample kernel
+    reads them in their own type (spkm_mix_sample_src_dev) and no float64 copy of the chunk exists; otherwise
+    (``fused_source=False``, the DCT, no sketch, the other Hadamard widths) the chunk is widened into a float64 buffer
+    first (spkm_widen_f64_dev).  The samples are the same bits on either route.  Host chunks go
     through PINNED memory and a copy stream with two device staging buffers: the transfer of chunk c+1 overlaps the
     transform + sampling of chunk c.  A chunk that already is a pinned torch tensor is sent from where it lies; numpy
     arrays and pageable tensors are first copied into one of two pinned staging buffers (that copy is the "read").
@@ -639,7 +679,9 @@ class StreamingSparsifier:
     (seed, global index) only, so any chunking / sharding yields the same dataset)."""
 
     def __init__(self, ctx: Context, p: int, n_local: int, s: int, seed: int, sign: torch.Tensor | None,
-                 first: int = 0, sketch: bool = True, layout: str = "csc", kind: str | None = None):
+                 first: int = 0, sketch: bool = True, layout: str = "csc", kind: str | None = None,
+                 fused_source: bool = True):
+        self.fused_source = bool(fused_source)
         self.ctx, self.p, self.n, self.s, self.seed, self.first = ctx, int(p), int(n_local), int(s), int(seed), int(first)
         self.kind = kind if kind is not None else ("hadamard" if sketch else "none")
         if self.kind not in ("hadamard", "dct", "none"):
@@ -680,21 +722,30 @@ class StreamingSparsifier:
             self._src_inflight = None
 
     def append(self, chunk) -> None:
-        """chunk: [m, p] points as rows (numpy array or torch tensor, host or device; float64 / float32 / uint8 /
-        int16 / int32).  A PINNED host tensor is read asynchronously after this returns: call wait_source() before
-        overwriting it."""
+        """chunk: [m, p] points as rows (numpy array or torch tensor, host or device; float64 / float32 / float16 /
+        bfloat16 / uint8 / int8 / int16 / uint16 / int32).  A PINNED host tensor is read asynchronously after this
+        returns: call wait_source() before overwriting it.  A device tensor is read where it lies, storage offset and
+        all."""
         dev = self._dev
-        t = torch.from_numpy(np.ascontiguousarray(chunk)) if isinstance(chunk, np.ndarray) else chunk
+        src_kind = None
+        if isinstance(chunk, np.ndarray):
+            a = np.ascontiguousarray(chunk)
+            if a.dtype == np.uint16:
+                a, src_kind = a.view(np.int16), SRC_U16
+            t = torch.from_numpy(a)
+        else:
+            t = chunk
+            if t.dtype == getattr(torch, "uint16", None):
+                t, src_kind = t.view(torch.int16), SRC_U16
         if t.dtype not in _WIDEN_KIND and t.dtype != torch.float64:
             t = t.to(torch.float64)
+        if src_kind is None and t.dtype != torch.float64:
+            src_kind = _WIDEN_KIND[t.dtype]
         t = t.contiguous()
         m = t.shape[0]
         assert t.dim() == 2 and t.shape[1] == self.p and self.filled + m <= self.n
         # the stream the library launches on (the context's), not whatever torch's current stream happens to be now
         main = torch.cuda.ExternalStream(self.ctx.stream, device=dev) if self.ctx.stream else torch.cuda.default_stream(dev)
-        if self._buf is None or self._buf.shape[0] < m:
-            self._buf = torch.empty((m, self.p), dtype=torch.float64, device=dev)
-        buf = self._buf[:m]
         if t.is_cuda:
             src = t
         else:
@@ -731,15 +782,28 @@ class StreamingSparsifier:
             main.wait_event(self._ev_copied[b])
             src = self._stage[b][:m]
             self.bytes_in += m * self.p * t.element_size()
+        o = self.filled * self.s
+        premul = 1.0 + 2.0 * float(np.finfo(np.float64).eps)
+        postdiv = float(np.sqrt(np.float64(self.p2)))
+        typed = False
         if src.dtype == torch.float64:
             fin = src if src.is_contiguous() else src.contiguous()
         else:
-            _lib.check(_lib.lib().spkm_widen_f64_dev(self.ctx.handle, _WIDEN_KIND[src.dtype], m * self.p, _p(src), _p(buf)),
-                       "spkm_widen_f64_dev")
-            fin = buf
-        o = self.filled * self.s
-        premul = 1.0 + 2.0 * float(np.finfo(np.float64).eps)
-        if self.kind == "dct" and self.p > DCT_TABLE_MAX_P:
+            if self.fused_source and self.kind == "hadamard" and MIX_LDS_MIN_P2 <= self.p2 <= MIX_LDS_MAX_P2:
+                # the fused kernel reads the chunk in its own type: no float64 copy of it (False: no typed route here)
+                typed = mix_sample_source_device(self.ctx, src, src_kind, self.p2, self.sign, premul, postdiv, self.s,
+                                                 self.seed, self.first + self.filled,
+                                                 None if self.records else self.ir[o:], None if self.records else self.x[o:],
+                                                 self.rec[self.filled * self.R:] if self.records else None, self.ir_bits)
+            if not typed:
+                if self._buf is None or self._buf.shape[0] < m:
+                    self._buf = torch.empty((m, self.p), dtype=torch.float64, device=dev)
+                fin = self._buf[:m]
+                _lib.check(_lib.lib().spkm_widen_f64_dev(self.ctx.handle, src_kind, m * self.p, _p(src), _p(fin)),
+                           "spkm_widen_f64_dev")
+        if typed:
+            pass
+        elif self.kind == "dct" and self.p > DCT_TABLE_MAX_P:
             if self.records:
                 dct_sample_records_device(self.ctx, fin, self.sign, premul, self.s, self.seed, self.first + self.filled,
                                           self.rec[self.filled * self.R:], self.ir_bits)
@@ -754,13 +818,11 @@ class StreamingSparsifier:
                 sketch_sample_device(self.ctx, self.kind, fin, self.sign, premul, self.s, self.seed,
                                      self.first + self.filled, self.ir[o:], self.x[o:])
         elif self.records:
-            mix_sample_records_device(self.ctx, fin, self.p2, self.sign, premul,
-                                      float(np.sqrt(np.float64(self.p2))), self.s, self.seed, self.first + self.filled,
-                                      self.rec[self.filled * self.R:], self.ir_bits)
+            mix_sample_records_device(self.ctx, fin, self.p2, self.sign, premul, postdiv, self.s, self.seed,
+                                      self.first + self.filled, self.rec[self.filled * self.R:], self.ir_bits)
         else:
-            mix_sample_device(self.ctx, fin, self.p2, self.sign, premul,
-                              float(np.sqrt(np.float64(self.p2))), self.s, self.seed, self.first + self.filled,
-                              self.ir[o:], self.x[o:])
+            mix_sample_device(self.ctx, fin, self.p2, self.sign, premul, postdiv, self.s, self.seed,
+                              self.first + self.filled, self.ir[o:], self.x[o:])
         if not t.is_cuda:
             self._ev_free[b] = torch.cuda.Event()
             self._ev_free[b].record(main)

@@ -186,10 +186,42 @@ def _weighted_draw(rng, w):
     return int(min(np.searchsorted(c, rng.random() * c[-1], side="right"), len(w) - 1))
 
 
+# Element types that stay as they are on their way to the sparsifier: they cross PCIe in their own width and become doubles
+# on the device, exactly (StreamingSparsifier).  int32 and everything else becomes float64 on the host, as in MATLAB.
+_KEEP_NARROW_NP = (np.float32, np.float16, np.uint8, np.int8, np.int16, np.uint16)
+_KEEP_NARROW_TORCH = tuple(t for t in (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int8, torch.int16,
+                                       getattr(torch, "uint16", None)) if t is not None)
+
+
+def _source_chunk(blk):
+    """a [m, p] slice of the source, contiguous, in the source's own dtype and place (numpy array or tensor; a tensor
+    never goes through numpy: bfloat16 cannot)"""
+    return blk.contiguous() if isinstance(blk, torch.Tensor) else np.ascontiguousarray(blk)
+
+
+def _chunk_f64(blk, dev) -> torch.Tensor:
+    """a [m, p] slice of the source as a float64 tensor on ``dev`` (converted where the source lies)"""
+    if isinstance(blk, torch.Tensor):
+        return blk.to(torch.float64).contiguous().to(dev)
+    return torch.tensor(np.ascontiguousarray(blk, dtype=np.float64), device=dev)
+
+
+def _tensor_source(X: torch.Tensor, ctx) -> torch.Tensor:
+    """checks on a torch.Tensor X (host, pinned, or on the context's device)"""
+    if X.is_complex():
+        raise ValueError("Code and distance computations require real data")       # :312-314
+    if X.dim() != 2:
+        raise ValueError("X must be a matrix")
+    if X.is_cuda and X.device.index != ctx.device:
+        raise ValueError(f"X lies on {X.device}, the run is on cuda:{ctx.device}")
+    return X.detach()
+
+
 def kmeans_sparsified(X, K, **options):
     """[IDX, C, SUMD, D, OUTPUT] = kmeans_sparsified(X, K, 'Name', value, ...)   (kmeans_sparsified.m:1)
 
-    X: n x p array (points are rows; 'ColumnSamples',True for p x n).  Returns the tuple
+    X: n x p numpy array or torch.Tensor (pageable, pinned, or on the run's device; points are rows, 'ColumnSamples',True
+    for p x n).  float32 / float16 / bfloat16 / uint8 / int8 / int16 / uint16 data is streamed in its own width.  Returns the tuple
     (IDX, C, SUMD, D, OUTPUT); IDX is 1-based.  With nargout=6..9 the two-pass outputs follow:
     (..., C_twoPass, IDX_twoPass, D_twoPass, SUMD_twoPass)[:nargout].  See module docstring for scope."""
     t0 = time.time()
@@ -223,13 +255,20 @@ def kmeans_sparsified(X, K, **options):
         p, n = (Xmm.shape if o["ColumnSamples"] else Xmm.shape[::-1])
         OUTPUT["TimeToReadSizeOfFile"] = time.time() - t1
         X = None
+    elif isinstance(X, torch.Tensor):
+        X = _tensor_source(X, ctx)
+        if X.dtype not in _KEEP_NARROW_TORCH and X.dtype != torch.float64:
+            X = X.to(torch.float64)
+        if not o["ColumnSamples"]:
+            X = X.T
+        p, n = X.shape
     else:
         if np.iscomplexobj(X):
             raise ValueError("Code and distance computations require real data")   # :312-314
         X = np.asarray(X)
-        # float32 / uint8 / int16 data stays as it is on the host (it crosses PCIe narrow and is widened on the device,
-        # exactly); everything else becomes float64 as in MATLAB
-        keep_narrow = X.dtype in (np.float32, np.uint8, np.int16)
+        # narrow data stays as it is on the host (it crosses PCIe narrow and becomes doubles on the device, exactly);
+        # everything else becomes float64 as in MATLAB
+        keep_narrow = X.dtype in _KEEP_NARROW_NP
         if not keep_narrow:
             X = np.asarray(X, np.float64)
         if not o["ColumnSamples"]:
@@ -287,8 +326,9 @@ def kmeans_sparsified(X, K, **options):
                 blk = Xmm[:, c0:c0 + nn].T if o["ColumnSamples"] else Xmm[c0:c0 + nn, :]
             else:
                 blk = X[:, c0:c0 + nn].T
-            sp_.append(np.ascontiguousarray(blk))
+            sp_.append(_source_chunk(blk))
         shard = sp_.finish()
+        OUTPUT["ingestBytes"] = sp_.bytes_in       # (not a reference field: bytes that crossed PCIe into the sparsifier)
         vals_ = sp_.x[: n * small_p]
         # with a sketch, one Inf / NaN entry makes its whole mixed column non-finite (every output of the transform is a
         # signed sum of all inputs), so the sampled values tell (without one, the sampled entries themselves).  The
@@ -331,8 +371,7 @@ def kmeans_sparsified(X, K, **options):
             else:
                 blk = X[:, c0:c0 + nn].T
             t1 = time.time()
-            Xmixed = sketch.mix(torch.tensor(np.ascontiguousarray(blk, dtype=np.float64), device=dev),
-                                premul=1.0 + 2.0 * EPS)                          # :292,295 (X*(1+2eps) then mix)
+            Xmixed = sketch.mix(_chunk_f64(blk, dev), premul=1.0 + 2.0 * EPS)     # :292,295 (X*(1+2eps) then mix)
             torch.cuda.synchronize()
             t_mix += time.time() - t1
             t1 = time.time()
@@ -623,9 +662,10 @@ def kmeans_sparsified(X, K, **options):
                 blk = Xmm[:, c0:c0 + nn].T if o["ColumnSamples"] else Xmm[c0:c0 + nn, :]
             else:
                 blk = X[:, c0:c0 + nn].T
-            blk = np.ascontiguousarray(blk, dtype=np.float64)
+            if not isinstance(blk, torch.Tensor):
+                blk = np.ascontiguousarray(blk, dtype=np.float64)
             t_read += time.time() - tr
-            xb = torch.tensor(blk, device=dev)
+            xb = _chunk_f64(blk, dev)
             if idx0 is not None:
                 dense_accumulate_device(ctx, xb, idx0[c0:c0 + nn].contiguous(), sums, counts)
             if want_assign:
@@ -679,9 +719,12 @@ def _kmeans_dense(X, K, o, nargout, t0):
     rng = o["rng"] if isinstance(o["rng"], np.random.Generator) else np.random.default_rng(o["rng"])
     ctx = torch_context(o["device"])
     dev = f"cuda:{ctx.device}"
-    X = np.asarray(X, np.float64)
-    if np.iscomplexobj(X):
-        raise ValueError("Code and distance computations require real data")
+    if isinstance(X, torch.Tensor):
+        X = _tensor_source(X, ctx)
+    else:
+        X = np.asarray(X, np.float64)
+        if np.iscomplexobj(X):
+            raise ValueError("Code and distance computations require real data")
     if o["ColumnSamples"]:
         X = X.T                                                                   # here: points as rows [n, p]
     n, p = X.shape
@@ -690,7 +733,7 @@ def _kmeans_dense(X, K, o, nargout, t0):
     free, _ = torch.cuda.mem_get_info()
     if n * p * 8 > 0.8 * free:
         raise NotImplementedError("'Sparsify',false keeps the dense data on the GPU; it does not fit")
-    Xd = torch.tensor(np.ascontiguousarray(X), device=dev)
+    Xd = _chunk_f64(X, dev)
     Display = o["Display"] if isinstance(o["Display"], str) else "off"
     Replicates = int(o["Replicates"])
     OUTPUT = dict(LoadFromDisk=False, Options=dict(o), Sparsify=False, iterations=np.zeros(Replicates, int),
