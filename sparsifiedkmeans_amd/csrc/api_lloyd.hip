@@ -659,15 +659,7 @@ static void launch_scatter(spkm_ctx* ctx, int sb, size_t sc_lds, const int* d_as
                            (unsigned long long*)ctx->cursor.p, (int*)ctx->perm.p, gate, need, n_dev, ids);
 }
 
-static constexpr int SEG_POINTS = 2048;
-// confirmation pass: longer segments amortise the per-segment slab reset / flush (13.4 -> 12.4 ms at N = 1e8 from
-// 2048 to 8192 points) as long as every workgroup still gets >= 16 of them
-static int seg_points(long long n, int blocks)
-{
-    const long long want = n / ((long long)std::max(1, blocks) * 16);
-    return (int)std::max<long long>(SEG_POINTS, std::min<long long>(8192, want));
-}
-
+// (the segment lengths of the counting sort -- SEG_POINTS, seg_points, SEG_EVENTS, SEG_DENSE -- are policy.h's)
 extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, const int32_t* d_assign,
                                    double* d_reduce)
 {
@@ -1150,7 +1142,7 @@ extern "C" int spkm_dense_accumulate_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n
     const int p = (int)p64, K = (int)K64;
     const long long n = (long long)n64;
     int rc;
-    const int seg = 256;
+    const int seg = SEG_DENSE;
     const int max_items = (int)(n / seg) + K + 1;
     if ((rc = ensure(ctx, ctx->dn_nk, (size_t)K * 8))) return rc;
     if ((rc = ensure(ctx, ctx->perm, (size_t)n * 4))) return rc;

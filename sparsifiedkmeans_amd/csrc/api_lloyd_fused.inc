@@ -640,8 +640,8 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     c.plan_input(prune_a, want_hint);
     spkm_plan_call(c.pl, c, c.sm->pol);
     if ((rc = c.resources()) || (rc = c.bounds()) || (rc = c.screen<IR>())) return rc;
-    // the sort buffers: at the events' sizes (2 per point, 2 K keys, 256-event segments) from the start where there may be events
-    const int ev = c.pl.ev_possible ? 2 : 1, max_items_ev_all = ev == 2 ? (int)((2 * c.n) / 256) + 2 * K + 1 : 0;
+    // the sort buffers: at the events' sizes (2 per point, 2 K keys, SEG_EVENTS-event segments) from the start where there may be events
+    const int ev = c.pl.ev_possible ? 2 : 1, max_items_ev_all = ev == 2 ? (int)((2 * c.n) / SEG_EVENTS) + 2 * K + 1 : 0;
     if ((rc = ensure(ctx, ctx->perm, (size_t)ev * c.n * 4)) || (rc = ensure(ctx, ctx->offs, (size_t)(ev * K + 1) * 8)) ||
         (rc = ensure(ctx, ctx->cursor, (size_t)ev * K * 8)) ||
         (rc = ensure(ctx, ctx->items, (size_t)std::max(c.max_items, max_items_ev_all) * 16)) || (rc = ensure(ctx, ctx->nitems, NI_WORDS * 4)))

@@ -237,8 +237,21 @@ struct spkm_policy {
 // device's limits, the switches and the shard's state.  Pure but for take_hinted_split (a hinted call's bookkeeping).
 // Device outcomes are fed back: the event buffers (lose_events), the pair plan's LDS and the pair buffer (lose_pair)
 // before the screen, the record layout (spkm_plan_sums) after it.  Constants of the kernels sized here: checked against
-// SCREEN_KT, BOUNDS_SPAN[_PT] and SEG_POINTS in api_lloyd_fused.inc.
-constexpr int spkm_plan_kt = 32, spkm_plan_span = 16384, spkm_plan_span_pt = 4096, spkm_plan_seg = 2048;
+// SCREEN_KT and BOUNDS_SPAN[_PT] in api_lloyd_fused.inc.
+// Segment lengths of the counting sort's work items (k_plan_segments cuts every cluster -- every event key -- into items of
+// at most `seg` points; the kernels take seg as an argument): SEG_POINTS for the accumulation and exact passes over a shard
+// (seg_points: longer on very large shards), SEG_EVENTS for the events of a call whose predecessor counted few movers,
+// SEG_DENSE for spkm_dense_accumulate_dev.  tests/designed_sizes.py builds its cluster sizes around these numbers and
+// tests/test_policy.py pins them.
+constexpr int SEG_POINTS = 2048, SEG_POINTS_MAX = 8192, SEG_EVENTS = 256, SEG_DENSE = 256;
+// confirmation pass: longer segments amortise the per-segment slab reset / flush (13.4 -> 12.4 ms at N = 1e8 from
+// 2048 to 8192 points) as long as every workgroup still gets >= 16 of them
+inline int seg_points(long long n, int blocks)
+{
+    const long long want = n / ((long long)std::max(1, blocks) * 16);
+    return (int)std::max<long long>(SEG_POINTS, std::min<long long>(SEG_POINTS_MAX, want));
+}
+constexpr int spkm_plan_kt = 32, spkm_plan_span = 16384, spkm_plan_span_pt = 4096, spkm_plan_seg = SEG_POINTS;
 // Narrow tiles of the screen (screen_wide.hip, k_screen_wide) for rows whose 32-centroid f32 tile no longer fits the LDS:
 // the widest of 16 and 8 centroids whose tile -- p + 1 rows of kt floats and the work ticket -- fits; 0: neither.  (160 KB:
 // 16 up to p = 2558, 8 up to 5118; the exact pass behind the screen stops before a 4-centroid tile would be needed.)
@@ -435,5 +448,5 @@ inline void spkm_plan_sums(spkm_call_plan& pl, const spkm_call_in& in, const spk
     // few movers known (a settled run): the events are applied where they were appended, no counting sort
     // (k_events_direct; SPKM_NO_DIRECT_EVENTS=1: A/B switch); few events: short segments, spread over more workgroups
     pl.direct = pl.ev_path && !pl.dual && pol.events_direct() && !in.no_direct_events;
-    pl.seg_ev = (pol.movers_known && pol.last_movers < 100000) ? 256 : spkm_plan_seg;
+    pl.seg_ev = (pol.movers_known && pol.last_movers < 100000) ? SEG_EVENTS : spkm_plan_seg;
 }

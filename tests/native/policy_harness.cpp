@@ -102,6 +102,17 @@ void pol_observe_regroup(void* p, double ambig, double one_cluster_steps, int ma
     c.ambig = ambig; c.one_cluster_steps = one_cluster_steps; c.may_regroup = may_regroup != 0;
     ((spkm_policy*)p)->observe(c, n, 4, 13);
 }
+// the segment lengths of the counting sort's work items, by name (-1: no such constant), and seg_points
+int seg_const(const char* name)
+{
+    if (!strcmp(name, "SEG_POINTS")) return SEG_POINTS;
+    if (!strcmp(name, "SEG_POINTS_MAX")) return SEG_POINTS_MAX;
+    if (!strcmp(name, "SEG_EVENTS")) return SEG_EVENTS;
+    if (!strcmp(name, "SEG_DENSE")) return SEG_DENSE;
+    if (!strcmp(name, "spkm_plan_seg")) return spkm_plan_seg;
+    return -1;
+}
+int pol_seg_points(long long n, int blocks) { return seg_points(n, blocks); }
 int pol_quad_split(int nr) { return quad_split(nr); }
 int pol_quad_split_late(int nr) { return quad_split_late(nr); }
 int pol_quad_split_pts(int nr) { return quad_split(nr, true); }

@@ -45,6 +45,8 @@ def pol(tmp_path_factory):
     L.pol_set.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int]
     L.pol_regroup_wanted.argtypes = [C.c_void_p]
     L.pol_observe_regroup.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double]
+    L.seg_const.argtypes = [C.c_char_p]
+    L.pol_seg_points.argtypes = [C.c_longlong, C.c_int]
     sizes = (C.c_int * 2)()
     L.plan_sizes(sizes)
     assert (sizes[0], sizes[1]) == (C.sizeof(CallIn), C.sizeof(Plan)), "the ctypes mirror of policy.h's plan structs is stale"
@@ -647,3 +649,23 @@ def test_regroup_is_wanted_after_a_full_call_over_mixed_steps(pol):
     assert pol.pol_regroup_wanted(p) == 1
     pol.pol_reset(p)
     assert pol.pol_regroup_wanted(p) == 0
+
+
+def test_segment_lengths_are_the_ones_the_designed_size_fixture_is_built_around(pol):
+    """SEG_POINTS / SEG_EVENTS / SEG_DENSE (policy.h): the lengths k_plan_segments cuts clusters, event keys and the dense
+    path's clusters into.  tests/designed_sizes.py restates them under the same names and builds its cluster sizes on
+    either side of them: a change here must be made there as well."""
+    import designed_sizes as D
+
+    assert [pol.seg_const(s.encode()) for s in ("SEG_POINTS", "SEG_POINTS_MAX", "SEG_EVENTS", "SEG_DENSE", "spkm_plan_seg")] == \
+        [2048, 8192, 256, 256, 2048]
+    assert pol.seg_const(b"no_such_name") == -1
+    for name in ("SEG_POINTS", "SEG_POINTS_MAX", "SEG_EVENTS", "SEG_DENSE"):
+        assert pol.seg_const(name.encode()) == getattr(D, name), name
+    # seg_points: SEG_POINTS while a workgroup would get fewer than 16 longer segments, then n / (16 blocks), at most 8192
+    assert [pol.pol_seg_points(n, 256) for n in (0, 1, 12_000, 2048 * 4096, 2049 * 4096, 5000 * 4096, 8192 * 4096, 10 ** 9)] == \
+        [2048, 2048, 2048, 2048, 2049, 5000, 8192, 8192]
+    assert pol.pol_seg_points(10 ** 8, 0) == 8192 and pol.pol_seg_points(40_000, 1) == 2500
+    # the events' segment: the short one once the previous call's movers are known to be few, SEG_POINTS otherwise
+    for known, movers, want in ((False, 0, 2048), (True, 99_999, 256), (True, 100_000, 2048)):
+        assert Call(pol, movers=movers, known=known).plan().seg_ev == want, (known, movers)
