@@ -504,6 +504,22 @@ int spkm_dense_assign_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, const double *d
 int spkm_dense_accumulate_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, const double *d_X, uint64_t K,
                               const int32_t *d_assign, double *d_sums, double *d_counts);
 
+/* spkm_dense_assign_dev / spkm_dense_accumulate_dev on a chunk in its own element type: d_X is the n x p chunk as src_kind
+ * elements (SPKM_SRC_*), aligned to its element size; layout, accumulate semantics and every other argument as there.  The
+ * kernels read the source directly and widen each element in registers (exactly: every value of every kind is a double), so
+ * no float64 copy of the chunk is written: a uint8 chunk costs 1 byte of HBM traffic per element and pass instead of 8, and an
+ * eighth of the PCIe transfer in front of it.  Loads are 16 bytes per lane where p * (element size) is a multiple of 16 and
+ * d_X is 16-byte aligned, one element per load otherwise.  The order of every floating-point sum is that of the float64
+ * kernels: assignments, distances, counts and (up to the order in which the segments of one cluster arrive, as there) sums
+ * are, bit for bit, those of the float64 entries on the widened chunk.  SPKM_SRC_F64 forwards to those entries.
+ * Checked in this order: SPKM_ERR_NULL_ARG for a null argument (whatever src_kind is), SPKM_ERR_BAD_VALUE for an unknown
+ * src_kind, SPKM_ERR_UNSUPPORTED for the shapes the float64 entries refuse (K == 0, K > 65536, p == 0, p > 2^24, n >= 2^31);
+ * n == 0 returns SPKM_OK and touches nothing. */
+int spkm_dense_assign_src_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, int src_kind, const void *d_X, uint64_t K,
+                              const double *d_centers, int32_t *d_assign, double *d_dist);
+int spkm_dense_accumulate_src_dev(spkm_ctx *ctx, uint64_t p, uint64_t n, int src_kind, const void *d_X, uint64_t K,
+                                  const int32_t *d_assign, double *d_sums, double *d_counts);
+
 /* ------------------------------------------------------------------------------------------
  * Part 3 -- one whole Lloyd iteration, and the data-parallel exchange
  *

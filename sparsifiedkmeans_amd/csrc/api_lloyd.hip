@@ -1107,6 +1107,32 @@ extern "C" int spkm_kpp_draw_dev(spkm_ctx* ctx, uint64_t n64, const double* d_cu
 // ------------------------------------------------------------------------------------------
 // dense (unsampled) data: two-pass outputs
 // ------------------------------------------------------------------------------------------
+// A narrow source is read 16 bytes per lane where every row is a whole number of 16-byte pieces and starts on one
+template <typename SRC> static int dense_vec16(const SRC* d_X, int p)
+{
+    return sizeof(SRC) < 8 && ((size_t)p * sizeof(SRC)) % 16 == 0 && ((uintptr_t)d_X & 15) == 0;
+}
+
+template <typename SRC>
+static int dense_assign_launch(spkm_ctx* ctx, int p, long long n, const SRC* d_X, int K, const double* d_centers,
+                               int32_t* d_assign, double* d_dist)
+{
+    int rc;
+    if ((rc = ensure(ctx, ctx->dn_x, (size_t)n * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->dn_c, (size_t)K * 8))) return rc;
+    const int wb = (int)std::min<long long>(4096, (n + 3) / 4);
+    hipLaunchKernelGGL((k_rows_normsq<SRC>), dim3(wb), dim3(256), 0, ctx->stream, d_X, n, p, (double*)ctx->dn_x.p);
+    hipLaunchKernelGGL((k_rows_normsq<double>), dim3((K + 3) / 4), dim3(256), 0, ctx->stream, d_centers, (long long)K, p,
+                       (double*)ctx->dn_c.p);
+    const size_t lds = (size_t)(DA_PTS + DA_KP) * DA_LD * 8;
+    HIP_TRY(hipFuncSetAttribute((const void*)k_dense_assign<SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_dense_assign<SRC>), dim3((unsigned)((n + DA_PTS - 1) / DA_PTS)), dim3(256), lds, ctx->stream, d_X, n,
+                       p, d_centers, K, (const double*)ctx->dn_x.p, (const double*)ctx->dn_c.p, (int*)d_assign, d_dist,
+                       dense_vec16(d_X, p));
+    HIP_TRY(hipGetLastError());
+    return SPKM_OK;
+}
+
 extern "C" int spkm_dense_assign_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n64, const double* d_X, uint64_t K64,
                                      const double* d_centers, int32_t* d_assign, double* d_dist)
 {
@@ -1114,33 +1140,13 @@ extern "C" int spkm_dense_assign_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n64, 
     if (K64 == 0 || K64 > 65536 || p64 == 0 || p64 > (1u << 24) || n64 > 0x7fffffffull) return SPKM_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n64 == 0) return SPKM_OK;
-    const int p = (int)p64, K = (int)K64;
-    const long long n = (long long)n64;
-    int rc;
-    if ((rc = ensure(ctx, ctx->dn_x, (size_t)n * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->dn_c, (size_t)K * 8))) return rc;
-    const int wb = (int)std::min<long long>(4096, (n + 3) / 4);
-    hipLaunchKernelGGL(k_rows_normsq, dim3(wb), dim3(256), 0, ctx->stream, d_X, n, p, (double*)ctx->dn_x.p);
-    hipLaunchKernelGGL(k_rows_normsq, dim3((K + 3) / 4), dim3(256), 0, ctx->stream, d_centers, (long long)K, p,
-                       (double*)ctx->dn_c.p);
-    const size_t lds = (size_t)(DA_PTS + DA_KP) * DA_LD * 8;
-    HIP_TRY(hipFuncSetAttribute((const void*)k_dense_assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_dense_assign, dim3((unsigned)((n + DA_PTS - 1) / DA_PTS)), dim3(256), lds, ctx->stream, d_X, n, p,
-                       d_centers, K, (const double*)ctx->dn_x.p, (const double*)ctx->dn_c.p, (int*)d_assign, d_dist);
-    HIP_TRY(hipGetLastError());
-    return SPKM_OK;
+    return dense_assign_launch<double>(ctx, (int)p64, (long long)n64, d_X, (int)K64, d_centers, d_assign, d_dist);
 }
 
-extern "C" int spkm_dense_accumulate_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n64, const double* d_X, uint64_t K64,
-                                         const int32_t* d_assign, double* d_sums, double* d_counts)
+template <typename SRC>
+static int dense_accumulate_launch(spkm_ctx* ctx, int p, long long n, const SRC* d_X, int K, const int32_t* d_assign,
+                                   double* d_sums, double* d_counts)
 {
-    if (!ctx || !d_X || !d_assign || !d_sums || !d_counts) return SPKM_ERR_NULL_ARG;
-    if (K64 == 0 || K64 > 65536 || p64 == 0 || p64 > (1u << 24) || n64 > 0x7fffffffull) return SPKM_ERR_UNSUPPORTED;
-    ctx->sort_owner = nullptr; // this call overwrites (some of) the buffers a kept counting sort lives in
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n64 == 0) return SPKM_OK;
-    const int p = (int)p64, K = (int)K64;
-    const long long n = (long long)n64;
     int rc;
     const int seg = SEG_DENSE;
     const int max_items = (int)(n / seg) + K + 1;
@@ -1160,10 +1166,71 @@ extern "C" int spkm_dense_accumulate_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n
     const size_t sc_lds = (size_t)((K + 1) & ~1) * 4 + (size_t)K * 12;
     launch_scatter(ctx, sb, sc_lds, (const int*)d_assign, n, K, (const unsigned*)nullptr, (const int*)nullptr);
     const int ab = std::min(max_items, std::max(1, ctx->num_cus) * 8);
-    hipLaunchKernelGGL(k_dense_accumulate, dim3(ab), dim3(256), 0, ctx->stream, d_X, p, (const int*)ctx->perm.p,
-                       (const long long*)ctx->offs.p, (const int4*)ctx->items.p, (const int*)ctx->nitems.p, d_sums);
+    hipLaunchKernelGGL((k_dense_accumulate<SRC>), dim3(ab), dim3(256), 0, ctx->stream, d_X, p, (const int*)ctx->perm.p,
+                       (const long long*)ctx->offs.p, (const int4*)ctx->items.p, (const int*)ctx->nitems.p, d_sums,
+                       dense_vec16(d_X, p));
     hipLaunchKernelGGL(k_nk_add_f64, dim3((K + 255) / 256), dim3(256), 0, ctx->stream,
                        (const unsigned long long*)ctx->dn_nk.p, K, d_counts);
     HIP_TRY(hipGetLastError());
     return SPKM_OK;
+}
+
+extern "C" int spkm_dense_accumulate_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n64, const double* d_X, uint64_t K64,
+                                         const int32_t* d_assign, double* d_sums, double* d_counts)
+{
+    if (!ctx || !d_X || !d_assign || !d_sums || !d_counts) return SPKM_ERR_NULL_ARG;
+    if (K64 == 0 || K64 > 65536 || p64 == 0 || p64 > (1u << 24) || n64 > 0x7fffffffull) return SPKM_ERR_UNSUPPORTED;
+    ctx->sort_owner = nullptr; // this call overwrites (some of) the buffers a kept counting sort lives in
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n64 == 0) return SPKM_OK;
+    return dense_accumulate_launch<double>(ctx, (int)p64, (long long)n64, d_X, (int)K64, d_assign, d_sums, d_counts);
+}
+
+// The same two on a chunk in its own element type (SPKM_SRC_*): the kernels read it as it is and widen in registers.
+
+extern "C" int spkm_dense_assign_src_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n64, int src_kind, const void* d_X,
+                                         uint64_t K64, const double* d_centers, int32_t* d_assign, double* d_dist)
+{
+    if (!ctx || !d_X || !d_centers || !d_assign || !d_dist) return SPKM_ERR_NULL_ARG;
+    if (src_kind < SPKM_SRC_F64 || src_kind > SPKM_SRC_U16) return SPKM_ERR_BAD_VALUE;
+    if (src_kind == SPKM_SRC_F64) return spkm_dense_assign_dev(ctx, p64, n64, (const double*)d_X, K64, d_centers, d_assign, d_dist);
+    if (K64 == 0 || K64 > 65536 || p64 == 0 || p64 > (1u << 24) || n64 > 0x7fffffffull) return SPKM_ERR_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n64 == 0) return SPKM_OK;
+    const int p = (int)p64, K = (int)K64;
+    const long long n = (long long)n64;
+    switch (src_kind) {
+    case SPKM_SRC_F32: return dense_assign_launch(ctx, p, n, (const float*)d_X, K, d_centers, d_assign, d_dist);
+    case SPKM_SRC_U8: return dense_assign_launch(ctx, p, n, (const unsigned char*)d_X, K, d_centers, d_assign, d_dist);
+    case SPKM_SRC_I16: return dense_assign_launch(ctx, p, n, (const short*)d_X, K, d_centers, d_assign, d_dist);
+    case SPKM_SRC_I32: return dense_assign_launch(ctx, p, n, (const int*)d_X, K, d_centers, d_assign, d_dist);
+    case SPKM_SRC_F16: return dense_assign_launch(ctx, p, n, (const src_f16*)d_X, K, d_centers, d_assign, d_dist);
+    case SPKM_SRC_BF16: return dense_assign_launch(ctx, p, n, (const src_bf16*)d_X, K, d_centers, d_assign, d_dist);
+    case SPKM_SRC_I8: return dense_assign_launch(ctx, p, n, (const signed char*)d_X, K, d_centers, d_assign, d_dist);
+    default: return dense_assign_launch(ctx, p, n, (const unsigned short*)d_X, K, d_centers, d_assign, d_dist);
+    }
+}
+
+extern "C" int spkm_dense_accumulate_src_dev(spkm_ctx* ctx, uint64_t p64, uint64_t n64, int src_kind, const void* d_X,
+                                             uint64_t K64, const int32_t* d_assign, double* d_sums, double* d_counts)
+{
+    if (!ctx || !d_X || !d_assign || !d_sums || !d_counts) return SPKM_ERR_NULL_ARG;
+    if (src_kind < SPKM_SRC_F64 || src_kind > SPKM_SRC_U16) return SPKM_ERR_BAD_VALUE;
+    if (src_kind == SPKM_SRC_F64) return spkm_dense_accumulate_dev(ctx, p64, n64, (const double*)d_X, K64, d_assign, d_sums, d_counts);
+    if (K64 == 0 || K64 > 65536 || p64 == 0 || p64 > (1u << 24) || n64 > 0x7fffffffull) return SPKM_ERR_UNSUPPORTED;
+    ctx->sort_owner = nullptr; // as spkm_dense_accumulate_dev
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n64 == 0) return SPKM_OK;
+    const int p = (int)p64, K = (int)K64;
+    const long long n = (long long)n64;
+    switch (src_kind) {
+    case SPKM_SRC_F32: return dense_accumulate_launch(ctx, p, n, (const float*)d_X, K, d_assign, d_sums, d_counts);
+    case SPKM_SRC_U8: return dense_accumulate_launch(ctx, p, n, (const unsigned char*)d_X, K, d_assign, d_sums, d_counts);
+    case SPKM_SRC_I16: return dense_accumulate_launch(ctx, p, n, (const short*)d_X, K, d_assign, d_sums, d_counts);
+    case SPKM_SRC_I32: return dense_accumulate_launch(ctx, p, n, (const int*)d_X, K, d_assign, d_sums, d_counts);
+    case SPKM_SRC_F16: return dense_accumulate_launch(ctx, p, n, (const src_f16*)d_X, K, d_assign, d_sums, d_counts);
+    case SPKM_SRC_BF16: return dense_accumulate_launch(ctx, p, n, (const src_bf16*)d_X, K, d_assign, d_sums, d_counts);
+    case SPKM_SRC_I8: return dense_accumulate_launch(ctx, p, n, (const signed char*)d_X, K, d_assign, d_sums, d_counts);
+    default: return dense_accumulate_launch(ctx, p, n, (const unsigned short*)d_X, K, d_assign, d_sums, d_counts);
+    }
 }

@@ -14,7 +14,16 @@
 // not defined by the reference: parity here is to a tolerance (tests), not bitwise.
 // sqrt of a slightly negative rounded value (a point equal to a centre) is clamped to 0; MATLAB would return
 // a complex number there.
+//
+// Typed sources.  The three kernels that read the data matrix are templates over its element type SRC (double, or one of
+// the SPKM_SRC_* kinds: src_types.h) and widen each element exactly with src_to_f64 on its way to a register or to LDS; the
+// centres, the norms and everything downstream of LDS are float64.  The order of every floating-point sum is that of the
+// double instantiation, so for every kind the outputs are the bits the double kernels give on the widened chunk.  Where a
+// row is a whole number of 16-byte pieces (p * sizeof(SRC) a multiple of 16) and X is 16-byte aligned (`vec16`, decided by
+// the host), a narrow source is fetched 16 bytes per lane and load: a piece lies wholly inside or wholly outside a row.
+// Otherwise, and for double, one element per lane and load.
 #include "common.h"
+#include "src_types.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #define DA_PTS 64    // points per workgroup (16 per wave)
@@ -24,27 +33,33 @@
 
 typedef double d4v __attribute__((ext_vector_type(4)));
 
-// out[i] = sum_r A[i*ld + r]^2   (one wave per row of A)
-__global__ __launch_bounds__(256) void k_rows_normsq(const double* __restrict__ A, long long nrows, int p,
+// out[i] = sum_r A[i*ld + r]^2   (one wave per row of A).  Element r stays with lane r % 64 and a lane adds its elements
+// in increasing r for every SRC: one element per lane and load (the chunk is read from HBM once).
+template <typename SRC>
+__global__ __launch_bounds__(256) void k_rows_normsq(const SRC* __restrict__ A, long long nrows, int p,
                                                      double* __restrict__ out)
 {
     const int lane = threadIdx.x & 63;
     const long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
     for (long long i = w; i < nrows; i += nw) {
-        const double* a = A + (size_t)i * p;
+        const SRC* a = A + (size_t)i * p;
         double s = 0.0;
-        for (int r = lane; r < p; r += 64) s += a[r] * a[r];
+        for (int r = lane; r < p; r += 64) {
+            const double v = src_to_f64(a[r]);
+            s += v * v;
+        }
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
         if (lane == 0) out[i] = s;
     }
 }
 
 // X: n x p (point i at X + i*p), C: K x p (centre k at C + k*p)
-__global__ __launch_bounds__(256) void k_dense_assign(const double* __restrict__ X, long long n, int p,
+template <typename SRC>
+__global__ __launch_bounds__(256) void k_dense_assign(const SRC* __restrict__ X, long long n, int p,
                                                       const double* __restrict__ C, int K,
                                                       const double* __restrict__ xn2, const double* __restrict__ cn2,
-                                                      int* __restrict__ assign, double* __restrict__ dist)
+                                                      int* __restrict__ assign, double* __restrict__ dist, int vec16)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* Xs = reinterpret_cast<double*>(smem);          // [DA_PTS][DA_LD]
@@ -64,10 +79,28 @@ __global__ __launch_bounds__(256) void k_dense_assign(const double* __restrict__
         const int ntile = (min(K - kb, DA_KP) + 15) >> 4;
         for (int r0 = 0; r0 < p; r0 += DA_ROWS) {
             __syncthreads();
-            for (int idx = tid; idx < DA_PTS * DA_ROWS; idx += 256) {
-                const int pt = idx >> 6, r = idx & 63;
-                const long long i = i0 + pt;
-                Xs[pt * DA_LD + r] = (i < n && r0 + r < p) ? X[(size_t)i * p + r0 + r] : 0.0;
+            if (sizeof(SRC) < 8 && vec16) {
+                // 16 bytes of one point's row per lane: EPL elements from row r0 + r on, r a multiple of EPL as p is, so the
+                // piece lies wholly below p or wholly at / above it.  Its doubles go to Xs[pt][r ..], 16-byte aligned
+                // (DA_LD * 8 = 528 and r * 8 are multiples of 16).
+                constexpr int EPL = 16 / (int)sizeof(SRC), CPP = DA_ROWS / EPL;   // elements per load, loads per point
+                for (int idx = tid; idx < DA_PTS * CPP; idx += 256) {
+                    const int pt = idx / CPP, r = (idx % CPP) * EPL;
+                    const long long i = i0 + pt;
+                    const bool in = i < n && r0 + r < p;
+                    src_chunk16<SRC> v = {};
+                    if (in) v = *reinterpret_cast<const src_chunk16<SRC>*>(X + (size_t)i * p + r0 + r);
+                    double2* dst = reinterpret_cast<double2*>(Xs + pt * DA_LD + r);
+#pragma unroll
+                    for (int k = 0; k < EPL / 2; k++)
+                        dst[k] = in ? make_double2(src_to_f64(v.e[2 * k]), src_to_f64(v.e[2 * k + 1])) : make_double2(0.0, 0.0);
+                }
+            } else {
+                for (int idx = tid; idx < DA_PTS * DA_ROWS; idx += 256) {
+                    const int pt = idx >> 6, r = idx & 63;
+                    const long long i = i0 + pt;
+                    Xs[pt * DA_LD + r] = (i < n && r0 + r < p) ? src_to_f64(X[(size_t)i * p + r0 + r]) : 0.0;
+                }
             }
             for (int idx = tid; idx < ntile * 16 * DA_ROWS; idx += 256) {
                 const int kk = idx >> 6, r = idx & 63;
@@ -116,20 +149,40 @@ __global__ __launch_bounds__(256) void k_dense_assign(const double* __restrict__
 
 // One workgroup per counting-sort item (cluster k, segment of its points): sums[k*p + r] += sum over the
 // segment's points of X[i*p + r] (point order), one hardware f64 atomic per row and segment.
-__global__ __launch_bounds__(256) void k_dense_accumulate(const double* __restrict__ X, int p,
+// vec16 (narrow SRC only): a thread owns the 16 / sizeof(SRC) consecutive rows of one 16-byte piece and still adds each
+// row's points in j order, so every row's sum is the one the element-wise loop forms.
+template <typename SRC>
+__global__ __launch_bounds__(256) void k_dense_accumulate(const SRC* __restrict__ X, int p,
                                                           const int* __restrict__ perm,
                                                           const long long* __restrict__ offs,
                                                           const int4* __restrict__ items,
-                                                          const int* __restrict__ nitems, double* __restrict__ sums)
+                                                          const int* __restrict__ nitems, double* __restrict__ sums,
+                                                          int vec16)
 {
     const int ni = *nitems;
     for (int it = blockIdx.x; it < ni; it += gridDim.x) {
         const int4 item = items[it];
         const int* pp = perm + offs[item.x] + item.y;
-        for (int r = threadIdx.x; r < p; r += blockDim.x) {
-            double s = 0.0;
-            for (int j = 0; j < item.z; j++) s += X[(size_t)pp[j] * p + r];
-            unsafeAtomicAdd(&sums[(size_t)item.x * p + r], s);
+        if (sizeof(SRC) < 8 && vec16) {
+            constexpr int EPL = 16 / (int)sizeof(SRC);
+            for (int r = threadIdx.x * EPL; r < p; r += blockDim.x * EPL) {   // p is a multiple of EPL: r + EPL <= p
+                double s[EPL];
+#pragma unroll
+                for (int k = 0; k < EPL; k++) s[k] = 0.0;
+                for (int j = 0; j < item.z; j++) {
+                    const src_chunk16<SRC> v = *reinterpret_cast<const src_chunk16<SRC>*>(X + (size_t)pp[j] * p + r);
+#pragma unroll
+                    for (int k = 0; k < EPL; k++) s[k] += src_to_f64(v.e[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < EPL; k++) unsafeAtomicAdd(&sums[(size_t)item.x * p + r + k], s[k]);
+            }
+        } else {
+            for (int r = threadIdx.x; r < p; r += blockDim.x) {
+                double s = 0.0;
+                for (int j = 0; j < item.z; j++) s += src_to_f64(X[(size_t)pp[j] * p + r]);
+                unsafeAtomicAdd(&sums[(size_t)item.x * p + r], s);
+            }
         }
     }
 }

@@ -14,29 +14,9 @@
 // (16 elements per thread), with an LDS exchange between rounds.  LDS index padding
 // P(e) = e + 2*(e>>4) keeps the 16-B-aligned per-thread runs conflict-free.
 #include "common.h"
+#include "src_types.h" // typed sources (SPKM_SRC_*): src_f16, src_bf16, src_to_f64
 
 __device__ __forceinline__ int padidx(int e) { return e + ((e >> 4) << 1); }
-
-// ---- typed sources (SPKM_SRC_*): the element types a chunk may arrive in.  Every value of every one of them is a double,
-// so src_to_f64 is exact; float16 goes through float (v_cvt_f32_f16, v_cvt_f64_f32), bfloat16 is the top half of a float.
-// Neither conversion flushes on this target as the library is built (both denormal modes of the kernel descriptor are
-// "preserve"): subnormals and +-0 keep their value and sign (tests/test_gpu_half_sources.py takes all 65536 patterns).
-struct src_f16 { unsigned short bits; };
-struct src_bf16 { unsigned short bits; };
-__device__ __forceinline__ double src_to_f64(double v) { return v; }
-__device__ __forceinline__ double src_to_f64(float v) { return (double)v; }
-__device__ __forceinline__ double src_to_f64(unsigned char v) { return (double)v; }
-__device__ __forceinline__ double src_to_f64(signed char v) { return (double)v; }
-__device__ __forceinline__ double src_to_f64(short v) { return (double)v; }
-__device__ __forceinline__ double src_to_f64(unsigned short v) { return (double)v; }
-__device__ __forceinline__ double src_to_f64(int v) { return (double)v; }
-__device__ __forceinline__ double src_to_f64(src_f16 v)
-{
-    _Float16 h;
-    __builtin_memcpy(&h, &v.bits, 2);
-    return (double)(float)h;
-}
-__device__ __forceinline__ double src_to_f64(src_bf16 v) { return (double)__uint_as_float((unsigned)v.bits << 16); }
 
 // The load stage of k_fwht_lds for a source narrower than double, 16 bytes per load: EPL = 16 / sizeof(SRC) elements.  A
 // thread issues sizeof(SRC) such loads (its 16 elements of the column, as before): chunk j = tau + T*i covers elements

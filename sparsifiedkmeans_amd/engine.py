@@ -12,6 +12,8 @@ One iteration (kmeans_sparsified.m:417-486 with dense centres):
 from __future__ import annotations
 
 import ctypes as C
+import time
+import warnings
 
 import numpy as np
 import torch
@@ -555,31 +557,64 @@ def dct_apply_device(ctx: Context, x: torch.Tensor, sign: torch.Tensor, inverse:
     return y
 
 
-def dense_assign_device(ctx: Context, x: torch.Tensor, centers: torch.Tensor):
+def _dense_source(x: torch.Tensor, src_kind: int | None):
+    """(tensor, SPKM_SRC_* kind) of a dense chunk for the typed dense entries: float64 is kind 0 (the float64 entries), a
+    dtype in _WIDEN_KIND its own kind, a torch.uint16 tensor an int16 view of the same bytes with kind SRC_U16; an explicit
+    ``src_kind`` names the elements of a tensor of the same width (uint16 travelling as int16)."""
+    if src_kind is None:
+        if x.dtype == torch.float64:
+            return x, 0
+        if x.dtype == getattr(torch, "uint16", None):
+            return x.view(torch.int16), SRC_U16
+        if x.dtype not in _WIDEN_KIND:
+            raise TypeError(f"dense chunk of dtype {x.dtype}: expected float64 or one of {sorted(map(str, _WIDEN_KIND))}")
+        return x, _WIDEN_KIND[x.dtype]
+    src_kind = int(src_kind)
+    if src_kind not in _KIND_BYTES or _KIND_BYTES[src_kind] != x.element_size():
+        raise ValueError(f"src_kind {src_kind} does not describe {x.element_size()}-byte elements")
+    if src_kind == 0 and x.dtype != torch.float64:
+        raise ValueError(f"src_kind 0 is float64, the chunk is {x.dtype}")
+    return x, src_kind
+
+
+def dense_assign_device(ctx: Context, x: torch.Tensor, centers: torch.Tensor, src_kind: int | None = None):
     """[assignments, distances] = findClusterAssignments(full(X), centers), dense branch / expanded quadratic
     (private/findClusterAssignments.m:157-171) for a dense device chunk ``x`` [n, p] and ``centers`` [K, p].
-    Returns (assign int32 0-based [n], dist float64 [n])."""
-    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2
+    ``x`` is float64, or float32 / float16 / bfloat16 / uint8 / int8 / int16 / int32 (uint16: an int16 view with
+    ``src_kind=SRC_U16``), which the kernels read as it is (spkm_dense_assign_src_dev): the bits of the float64 call on
+    the widened chunk.  Returns (assign int32 0-based [n], dist float64 [n])."""
+    x, kind = _dense_source(x, src_kind)
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 2
     assert centers.dtype == torch.float64 and centers.is_contiguous() and centers.shape[1] == x.shape[1]
     n, p = x.shape
     a = torch.empty(n, dtype=torch.int32, device=x.device)
     d = torch.empty(n, dtype=torch.float64, device=x.device)
-    _lib.check(_lib.lib().spkm_dense_assign_dev(ctx.handle, p, n, _p(x), centers.shape[0], _p(centers), _p(a), _p(d)),
-               "spkm_dense_assign_dev")
+    if kind == 0:
+        _lib.check(_lib.lib().spkm_dense_assign_dev(ctx.handle, p, n, _p(x), centers.shape[0], _p(centers), _p(a), _p(d)),
+                   "spkm_dense_assign_dev")
+    else:
+        _lib.check(_lib.lib().spkm_dense_assign_src_dev(ctx.handle, p, n, kind, _p(x), centers.shape[0], _p(centers), _p(a),
+                                                        _p(d)), "spkm_dense_assign_src_dev")
     return a, d
 
 
 def dense_accumulate_device(ctx: Context, x: torch.Tensor, assign: torch.Tensor, sums: torch.Tensor,
-                            counts: torch.Tensor):
+                            counts: torch.Tensor, src_kind: int | None = None):
     """sums[k] += sum of the rows of ``x`` [n, p] with assign == k, counts[k] += their number: the numerators
-    and denominators of mean(full(XFull(:,ind)),2) (kmeans_sparsified.m:545-550), chunk by chunk."""
-    assert x.dtype == torch.float64 and x.is_contiguous() and x.dim() == 2
+    and denominators of mean(full(XFull(:,ind)),2) (kmeans_sparsified.m:545-550), chunk by chunk.  ``x`` and ``src_kind``
+    as in dense_assign_device (spkm_dense_accumulate_src_dev for a narrow chunk)."""
+    x, kind = _dense_source(x, src_kind)
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 2
     assert assign.dtype == torch.int32 and assign.is_contiguous() and assign.numel() == x.shape[0]
     assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.shape[1] == x.shape[1]
     assert counts.dtype == torch.float64 and counts.numel() == sums.shape[0]
     n, p = x.shape
-    _lib.check(_lib.lib().spkm_dense_accumulate_dev(ctx.handle, p, n, _p(x), sums.shape[0], _p(assign), _p(sums),
-                                                    _p(counts)), "spkm_dense_accumulate_dev")
+    if kind == 0:
+        _lib.check(_lib.lib().spkm_dense_accumulate_dev(ctx.handle, p, n, _p(x), sums.shape[0], _p(assign), _p(sums),
+                                                        _p(counts)), "spkm_dense_accumulate_dev")
+    else:
+        _lib.check(_lib.lib().spkm_dense_accumulate_src_dev(ctx.handle, p, n, kind, _p(x), sums.shape[0], _p(assign),
+                                                            _p(sums), _p(counts)), "spkm_dense_accumulate_src_dev")
 
 
 # SPKM_SRC_* of a chunk's dtype.  uint16 (SRC_U16 = 8) has no entry: it travels as an int16 view of the same bytes with the
@@ -587,6 +622,7 @@ def dense_accumulate_device(ctx: Context, x: torch.Tensor, assign: torch.Tensor,
 _WIDEN_KIND = {torch.float32: 1, torch.uint8: 2, torch.int16: 3, torch.int32: 4, torch.float16: 5, torch.bfloat16: 6,
                torch.int8: 7}
 SRC_U16 = 8
+_KIND_BYTES = {0: 8, 1: 4, 2: 1, 3: 2, 4: 4, 5: 2, 6: 2, 7: 1, 8: 2}   # element size of each SPKM_SRC_* kind
 MIX_LDS_MIN_P2, MIX_LDS_MAX_P2 = 16, 16384   # spkm_mix_sample_src_dev / _rec_src_dev read a typed source at these widths
 
 
@@ -650,6 +686,143 @@ def _parallel_host_copy(dst: torch.Tensor, src: torch.Tensor, threads: int | Non
     finally:
         if before != want:
             torch.set_num_threads(before)
+
+
+class SourceChunkStager:
+    """Brings the chunks of a dense source to the device in the source's own dtype, one after the other, for the kernels
+    that read typed chunks (the second pass of the two-pass outputs: dense_accumulate_device / dense_assign_device).  The
+    discipline is StreamingSparsifier.append's: a numpy array or pageable tensor is copied into one of two PINNED host
+    buffers (that copy is the "read", timed in ``host_seconds``) and sent from there on a copy stream into one of two device
+    staging buffers, so the transfer of chunk c + 1 overlaps the kernels of chunk c; a pinned tensor is sent from where it
+    lies (wait_source() before refilling it); a device tensor is used in place.  ``bytes_in`` counts what crossed PCIe.
+
+    put(chunk) returns (device tensor [m, p], SPKM_SRC_* kind); the context's stream already waits for its transfer.  The
+    tensor is valid until the NEXT put() but one: everything enqueued on the context's stream before the following put()
+    (or finish()) counts as its reader.  float64 / float32 / float16 / bfloat16 / uint8 / int8 / int16 / int32 travel as
+    they are, uint16 as an int16 view with kind SRC_U16, anything else as float64 (converted on the host)."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._dev = torch.device("cuda", ctx.device)
+        self._stage = [None, None]             # device staging buffers in the source's dtype
+        self._pin = [None, None]               # pinned host staging buffers (for pageable sources)
+        self._ev_copied = [torch.cuda.Event(), torch.cuda.Event()]
+        self._ev_free = [None, None]           # recorded on the main stream when a staging buffer has been consumed
+        self._ev_pin_free = [None, None]       # recorded on the copy stream when a pinned buffer has been sent
+        self._turn = 0
+        self._out = None                       # staging buffer handed out by the last put() and not yet released
+        self._copy_stream = torch.cuda.Stream(device=self._dev)
+        self.bytes_in = 0
+        self.host_seconds = 0.0
+        self._src_inflight = None              # event of the last PINNED source chunk sent in place
+
+    def _main(self):
+        # the stream the library launches on (the context's), not whatever torch's current stream happens to be now
+        return (torch.cuda.ExternalStream(self.ctx.stream, device=self._dev) if self.ctx.stream
+                else torch.cuda.default_stream(self._dev))
+
+    def _release(self) -> None:
+        if self._out is not None:
+            self._ev_free[self._out] = torch.cuda.Event()
+            self._ev_free[self._out].record(self._main())
+            self._out = None
+
+    def wait_source(self) -> None:
+        """Block until the last pinned chunk handed to put() has left host memory."""
+        if self._src_inflight is not None:
+            self._src_inflight.synchronize()
+            self._src_inflight = None
+
+    def finish(self) -> None:
+        """The readers of the last chunk are enqueued: wait for outstanding transfers and drop the buffers."""
+        self._release()
+        self.wait_source()
+        for ev in self._ev_free:
+            if ev is not None:
+                ev.synchronize()
+        self._stage = [None, None]
+        self._pin = [None, None]
+        self._ev_free = [None, None]
+        self._ev_pin_free = [None, None]
+
+    def put(self, chunk):
+        self._release()
+        src_kind = None
+        if isinstance(chunk, np.ndarray):
+            a = chunk
+            if a.dtype == np.uint16:
+                a, src_kind = a.view(np.int16), SRC_U16
+            elif a.dtype.type not in (np.float64, np.float32, np.float16, np.uint8, np.int8, np.int16, np.int32):
+                t0 = time.time()
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                self.host_seconds += time.time() - t0
+            if not a.flags.c_contiguous:
+                t0 = time.time()
+                a = np.ascontiguousarray(a)
+                self.host_seconds += time.time() - t0
+            if not a.flags.writeable:
+                # (a read-only memory map: torch only warns about a tensor over memory it may not write; it is only read)
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    t = torch.from_numpy(a)
+            else:
+                t = torch.from_numpy(a)
+        else:
+            t = chunk
+            if t.dtype == getattr(torch, "uint16", None):
+                t, src_kind = t.view(torch.int16), SRC_U16
+            elif t.dtype not in _WIDEN_KIND and t.dtype != torch.float64:
+                t = t.to(torch.float64)
+        if src_kind is None:
+            src_kind = 0 if t.dtype == torch.float64 else _WIDEN_KIND[t.dtype]
+        assert t.dim() == 2
+        if not t.is_contiguous():
+            t0 = time.time()
+            t = t.contiguous()
+            if not t.is_cuda:
+                self.host_seconds += time.time() - t0
+        if t.is_cuda:
+            return t, src_kind
+        m, p = t.shape
+        main = self._main()
+        b = self._turn
+        self._turn ^= 1
+        st = self._stage[b]
+        if st is None or st.shape[0] < m or st.shape[1] != p or st.dtype != t.dtype:
+            if self._ev_free[b] is not None:
+                self._ev_free[b].synchronize()               # kernels on the context's stream may still read the old block
+            self._stage[b] = torch.empty((m, p), dtype=t.dtype, device=self._dev)
+            self._ev_free[b] = None
+        host = t
+        pinned = t.is_pinned()
+        if not pinned:
+            pn = self._pin[b]
+            if pn is None or pn.shape[0] < m or pn.shape[1] != p or pn.dtype != t.dtype:
+                if self._ev_pin_free[b] is not None:
+                    self._ev_pin_free[b].synchronize()
+                self._pin[b] = torch.empty((m, p), dtype=t.dtype, pin_memory=True)
+                self._ev_pin_free[b] = None
+            if self._ev_pin_free[b] is not None:
+                self._ev_pin_free[b].synchronize()           # the previous transfer out of this pinned buffer is done
+            t0 = time.time()
+            _parallel_host_copy(self._pin[b][:m], t)          # the host-side "read" of the chunk
+            self.host_seconds += time.time() - t0
+            host = self._pin[b][:m]
+        with torch.cuda.stream(self._copy_stream):
+            if self._ev_free[b] is not None:
+                self._copy_stream.wait_event(self._ev_free[b])   # the kernels that read this staging buffer are done
+            self._stage[b][:m].copy_(host, non_blocking=True)
+            self._ev_copied[b].record(self._copy_stream)
+            ev = torch.cuda.Event()
+            ev.record(self._copy_stream)
+            if pinned:
+                self._src_inflight = ev                      # sent from where it lies: wait_source() before refilling it
+            else:
+                self._ev_pin_free[b] = ev
+        main.wait_event(self._ev_copied[b])
+        self._out = b
+        self.bytes_in += m * p * t.element_size()
+        return self._stage[b][:m], src_kind
 
 
 class StreamingSparsifier:

@@ -10,7 +10,11 @@ the DCT sketch ('auto' picks it when p is not a power of two; p <= 131072) and n
 dtype, rows are drawn by one counter-based generator keyed by (seed, global index), and the sketch is applied in HIP
 (the DCT evaluated at the sampled rows only).  Mixing the start and unmixing the K centres of the DCT is a p x p GEMM
 up to p = 16384 and a matrix-free HIP transform above; a Hadamard sketch with p2 > 2^24 samples on the host.  'Sparsify',false -- the reference's default -- runs plain Lloyd on the dense data with the
-dense kernels of the two-pass outputs (one GPU, data resident in HBM).  'MLcorrection',false (plain means of the sparse columns,
+dense kernels of the two-pass outputs (one GPU, data resident in HBM).  Narrow data stays narrow on the dense kernels too:
+the second pass of the two-pass outputs streams chunks in the source's dtype (pinned staging, a copy stream;
+OUTPUT["secondPassBytes"]), 'Sparsify',false keeps float32 / float16 / bfloat16 / uint8 / int8 / int16 data resident as it
+is (OUTPUT["residentBytes"]), findClusterAssignments sends narrow dense X narrow, and the kernels read each type directly,
+with the results of float64 data.  'MLcorrection',false (plain means of the sparse columns,
 kmeans_sparsified.m:449-451) runs on the same accumulation with a different final division.
 
 MATLAB's RNG cannot be reproduced here; every random product (sign vector, sampled rows, initial
@@ -39,8 +43,9 @@ import torch
 from . import _lib
 from . import distributed as D_
 from . import synth
-from .engine import (DCT_MAX_P, DCT_TABLE_MAX_P, MIX_MAX_P2, LloydEngine, Shard, StreamingSparsifier, dct_apply_device,
-                     dense_accumulate_device, dense_assign_device, mix_device, torch_context)
+from .engine import (DCT_MAX_P, DCT_TABLE_MAX_P, MIX_MAX_P2, SRC_U16, LloydEngine, Shard, SourceChunkStager,
+                     StreamingSparsifier, dct_apply_device, dense_accumulate_device, dense_assign_device, mix_device,
+                     torch_context)
 
 EPS = np.finfo(np.float64).eps
 
@@ -150,17 +155,23 @@ def findClusterAssignments(X, centers, tryBuiltinMex=None, gamma=None, ctx=None)
     """[assignments, distances] = findClusterAssignments(X, centers, tryBuiltinMex, gamma)
     (private/findClusterAssignments.m).  Sparse X (p x n scipy matrix): dense centres use the tiled HIP
     kernel, sparse centres (scipy matrix) the sparse-centres kernel.  Dense X (p x n array): the expanded
-    quadratic of :157-165 on the f64 matrix cores (gamma is ignored there, as in the reference).
+    quadratic of :157-165 on the f64 matrix cores (gamma is ignored there, as in the reference); float32 / float16 /
+    uint8 / int8 / int16 / uint16 X is sent and read in its own width, with the outputs of the float64 call.
     assignments are 1-based."""
     if not sp.issparse(X):
         ctx = ctx or torch_context()
-        Xd = np.asarray(X, np.float64)
+        Xd, kind = np.asarray(X), None
+        if Xd.dtype == np.uint16:
+            Xd, kind = Xd.view(np.int16), SRC_U16                                # the same bytes; the kernel reads uint16
+        elif Xd.dtype.type not in _KEEP_NARROW_NP:
+            Xd = np.asarray(Xd, np.float64)
         Cd = np.asarray(centers.toarray() if sp.issparse(centers) else centers, np.float64)
         if Cd.shape[0] != Xd.shape[0]:
             raise ValueError("Array of centers not of correct size")  # :55
         dev = f"cuda:{ctx.device}"
-        a, d = dense_assign_device(ctx, torch.tensor(np.ascontiguousarray(Xd.T), device=dev),
-                                   torch.tensor(np.ascontiguousarray(Cd.T), device=dev))
+        # narrow X crosses PCIe and is read by the kernel in its own type: the bits of the float64 call
+        a, d = dense_assign_device(ctx, torch.from_numpy(np.ascontiguousarray(Xd.T)).to(dev),
+                                   torch.tensor(np.ascontiguousarray(Cd.T), device=dev), src_kind=kind)
         return a.cpu().numpy().astype(np.int64) + 1, d.cpu().numpy()
     ctx = ctx or torch_context()
     p, n = X.shape
@@ -191,6 +202,10 @@ def _weighted_draw(rng, w):
 _KEEP_NARROW_NP = (np.float32, np.float16, np.uint8, np.int8, np.int16, np.uint16)
 _KEEP_NARROW_TORCH = tuple(t for t in (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int8, torch.int16,
                                        getattr(torch, "uint16", None)) if t is not None)
+# Element types 'Sparsify',false keeps resident as they are (_kmeans_dense gathers rows and takes min / max on the resident
+# tensor, which torch does not offer for uint16)
+_DENSE_RESIDENT_NP = (np.float32, np.float16, np.uint8, np.int8, np.int16)
+_DENSE_RESIDENT_TORCH = (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int8, torch.int16)
 
 
 def _source_chunk(blk):
@@ -655,22 +670,39 @@ def kmeans_sparsified(X, K, **options):
         d2 = torch.empty(n, dtype=torch.float64, device=dev) if want_assign else None
         idx0 = None if not IDX.size else torch.tensor((IDX - 1).astype(np.int32), device=dev)
         nn = max(1, min(n, int(o["MB_limit"] * 2**20 // (8 * p))))               # recalculateAssignmentLargeFile.m:66
-        t_read = 0.0
+        # Narrow sources (the types the ingest keeps narrow) travel in their own dtype through pinned staging buffers and
+        # a copy stream, the transfer of chunk c + 1 under the kernels of chunk c, and the dense kernels read them as they
+        # are: the sums, assignments and distances are those of float64 chunks.  float64 sources, and files of any other
+        # type (float64 on the host, as in MATLAB), keep the blocking copy: at 8 bytes per element the staging copy into
+        # pinned memory costs more than it hides (1e7 x 784 from pageable memory: 1.9 - 2.7 s staged, 1.45 s like this).
+        src0 = Xmm if LoadFromDisk else X
+        narrow = (src0.dtype in _KEEP_NARROW_TORCH) if isinstance(src0, torch.Tensor) else (src0.dtype.type in _KEEP_NARROW_NP)
+        stager = SourceChunkStager(ctx) if narrow else None
+        t_read, bytes2 = 0.0, 0
         for c0 in range(0, n, nn):
             tr = time.time()
             if LoadFromDisk:
                 blk = Xmm[:, c0:c0 + nn].T if o["ColumnSamples"] else Xmm[c0:c0 + nn, :]
             else:
                 blk = X[:, c0:c0 + nn].T
-            if not isinstance(blk, torch.Tensor):
-                blk = np.ascontiguousarray(blk, dtype=np.float64)
-            t_read += time.time() - tr
-            xb = _chunk_f64(blk, dev)
+            if narrow:
+                xb, kind = stager.put(blk)
+            else:
+                if not isinstance(blk, torch.Tensor):
+                    blk = np.ascontiguousarray(blk, dtype=np.float64)
+                t_read += time.time() - tr
+                xb, kind = _chunk_f64(blk, dev), None
+                if not (isinstance(blk, torch.Tensor) and blk.is_cuda):
+                    bytes2 += xb.numel() * 8
             if idx0 is not None:
-                dense_accumulate_device(ctx, xb, idx0[c0:c0 + nn].contiguous(), sums, counts)
+                dense_accumulate_device(ctx, xb, idx0[c0:c0 + nn].contiguous(), sums, counts, src_kind=kind)
             if want_assign:
-                a_, d_ = dense_assign_device(ctx, xb, Cdev)
+                a_, d_ = dense_assign_device(ctx, xb, Cdev, src_kind=kind)
                 a2[c0:c0 + nn], d2[c0:c0 + nn] = a_, d_
+        if narrow:
+            stager.finish()
+            t_read, bytes2 = stager.host_seconds, stager.bytes_in               # the host-side read / staging copies
+        OUTPUT["secondPassBytes"] = bytes2                 # (not a reference field: bytes that crossed PCIe in this pass)
         if dist_on:
             torch.distributed.all_reduce(sums, op=torch.distributed.ReduceOp.SUM)
             torch.distributed.all_reduce(counts, op=torch.distributed.ReduceOp.SUM)
@@ -710,8 +742,11 @@ def _kmeans_dense(X, K, o, nargout, t0):
     """'Sparsify',false -- the reference's DEFAULT: plain Lloyd on the dense data, no sketch, no sampling
     (kmeans_sparsified.m:362-364,378-486 with findClusterAssignments.m:124-171 and the plain mean of :449-451).
     Assignment = spkm_dense_assign_dev (expanded quadratic on the f64 matrix cores), centres = per-cluster means
-    from spkm_dense_accumulate_dev.  The data must fit in HBM as one n x p float64 tensor; 'DataFile' is not
-    offered on this branch (neither does the reference's code path load it)."""
+    from spkm_dense_accumulate_dev.  The data must fit in HBM as one n x p tensor: float32 / float16 / bfloat16 / uint8 /
+    int8 / int16 data stays resident in its own dtype (OUTPUT["residentBytes"]) and the kernels read it as it is
+    (spkm_dense_assign_src_dev / spkm_dense_accumulate_src_dev), with the results of a float64 run; uint16 (which torch
+    cannot index or reduce) and everything else is resident as float64.  'DataFile' is not offered on this branch
+    (neither does the reference's code path load it)."""
     if o["DataFile"] is not None:
         raise NotImplementedError("'DataFile' needs 'Sparsify',true (kmeans_sparsified.m:298-307 only loads it there)")
     if D_.is_distributed():
@@ -721,8 +756,12 @@ def _kmeans_dense(X, K, o, nargout, t0):
     dev = f"cuda:{ctx.device}"
     if isinstance(X, torch.Tensor):
         X = _tensor_source(X, ctx)
+        narrow = X.dtype in _DENSE_RESIDENT_TORCH
     else:
-        X = np.asarray(X, np.float64)
+        X = np.asarray(X)
+        narrow = X.dtype.type in _DENSE_RESIDENT_NP
+        if not narrow:
+            X = np.asarray(X, np.float64)
         if np.iscomplexobj(X):
             raise ValueError("Code and distance computations require real data")
     if o["ColumnSamples"]:
@@ -731,12 +770,23 @@ def _kmeans_dense(X, K, o, nargout, t0):
     if n < K:
         raise ValueError("X must have more samples than the number of clusters.")  # :219-221
     free, _ = torch.cuda.mem_get_info()
-    if n * p * 8 > 0.8 * free:
+    itemsize = (X.element_size() if isinstance(X, torch.Tensor) else X.dtype.itemsize) if narrow else 8
+    if n * p * itemsize > 0.8 * free:
         raise NotImplementedError("'Sparsify',false keeps the dense data on the GPU; it does not fit")
-    Xd = _chunk_f64(X, dev)
+    if not narrow:
+        Xd = _chunk_f64(X, dev)
+    elif isinstance(X, torch.Tensor):
+        Xd = X.contiguous().to(dev)
+    else:
+        Xd = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
+
+    def rows(idx):
+        """the points ``idx`` as float64 rows: only what is gathered is widened"""
+        return Xd[idx].to(torch.float64)
     Display = o["Display"] if isinstance(o["Display"], str) else "off"
     Replicates = int(o["Replicates"])
-    OUTPUT = dict(LoadFromDisk=False, Options=dict(o), Sparsify=False, iterations=np.zeros(Replicates, int),
+    OUTPUT = dict(LoadFromDisk=False, Options=dict(o), Sparsify=False, residentBytes=Xd.numel() * Xd.element_size(),
+                  iterations=np.zeros(Replicates, int),
                   stoppingDiff=np.zeros(Replicates), objectives=np.zeros(Replicates), replicateTimes=np.zeros(Replicates),
                   replicateTimesJustInitialization=np.zeros(Replicates))
     start = o["Start"]
@@ -747,15 +797,15 @@ def _kmeans_dense(X, K, o, nargout, t0):
         if isinstance(start, str):
             sl = start.lower()
             if sl == "sample":
-                centers = Xd[torch.tensor(rng.choice(n, K, replace=False), device=dev)].clone()       # :387
+                centers = rows(torch.tensor(rng.choice(n, K, replace=False), device=dev)).clone()      # :387
             elif sl == "uniform":
-                mn, mx = float(Xd.min().item()), float(Xd.max().item())
+                mn, mx = float(Xd.min().item()), float(Xd.max().item())                   # (on the data as it is)
                 centers = torch.tensor((mx - mn) * rng.random((K, p)) - mn, device=dev)   # :390 (subtracts mn)
             elif sl in ("arthur", "++", "kmeans++", "k-means++", "k-means-++"):
                 chosen = [int(rng.integers(n))]                                   # Arthur_initialization.m:35
                 dist = None
                 for k in range(1, K):
-                    _, dnew = dense_assign_device(ctx, Xd, Xd[chosen[-1]][None, :].contiguous())
+                    _, dnew = dense_assign_device(ctx, Xd, rows(chosen[-1])[None, :].contiguous())
                     dist = dnew if dist is None else torch.minimum(dist, dnew)    # same dist vector as :39
                     cum = torch.cumsum(dist * dist, 0)
                     tot = float(cum[-1].item())
@@ -771,7 +821,7 @@ def _kmeans_dense(X, K, o, nargout, t0):
                     if i in chosen:
                         raise RuntimeError("Cannot sample with replacement with this distribution")
                     chosen.append(i)
-                centers = Xd[torch.tensor(chosen, device=dev)].clone()
+                centers = rows(torch.tensor(chosen, device=dev)).clone()
             else:
                 raise ValueError('cannot handle other types of "Start" values')  # :398
         else:
@@ -802,7 +852,7 @@ def _kmeans_dense(X, K, o, nargout, t0):
                 if act == "error":
                     raise RuntimeError("One cluster lost all its members")      # :439
                 if act == "singleton":
-                    centers[torch.tensor(empty, device=dev)] = Xd[int(torch.argmax(dmin).item())]   # :436-437
+                    centers[torch.tensor(empty, device=dev)] = rows(int(torch.argmax(dmin).item()))   # :436-437
                 else:                                                            # 'drop' (:441,454-459)
                     keep = torch.nonzero(nz).flatten()
                     centers, old, Kc, dropped = centers[keep].contiguous(), old[keep].contiguous(), int(keep.numel()), True
