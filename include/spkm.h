@@ -150,6 +150,20 @@ int spkm_shard_set_lazy_stats(spkm_shard *s, int on);
  * 32-wide limit the setting changes nothing.  Turning it on or off forgets the shard's policy state, like spkm_shard_reset_policy.
  * SPKM_WIDE_SCREEN=1 opts every shard of a context in (read with the other switches: spkm_ctx_reload_switches). */
 int spkm_shard_set_wide_screen(spkm_shard *s, int on);
+/* Shapes that no LDS tile serves (on != 0; default off).  The narrowest tile of the certified screen, 8 centroids, stops at
+ * p = 5118 with 160 KB of LDS, and the exact pass behind every tile needs p * 20 bytes plus its staged points itself (p = 410
+ * with 150 entries per column is past it); beyond either limit a fused call runs the all-exact kernels, at these widths the
+ * generic one.  A shard that opts in takes the FAR screen there (csrc/screen_far.hip): the same f32 estimates with the
+ * centroid table left in global memory -- one wave per point, its lanes across a plane of 64, 128 or 256 centroids, rows
+ * gathered from the L2 -- in front of the same certificate and exact list; sums, counts and, when the call wants them, the
+ * distances and statistics come from the kernels of spkm_accumulate_dev and spkm_distances_stats_dev.  Every output is what
+ * the all-exact kernels give, bit for bit where they are reproducible.  Fixed-stride shards, K >= 2, a table of at most
+ * 256 MB; no bounds, hints or incremental sums: every call screens every point and accumulates over every point, and a
+ * lazy call without distances returns NaN statistics.  spkm_last_screen_tile reports (centroids per plane, planes).  Where
+ * a tile serves the shard the setting changes nothing.  Turning it on or off forgets the shard's policy state, like
+ * spkm_shard_reset_policy.  SPKM_FAR_SCREEN=1 opts every shard of a context in (read with the other switches:
+ * spkm_ctx_reload_switches). */
+int spkm_shard_set_far_screen(spkm_shard *s, int on);
 /* Carried bounds beyond the 4-lanes-per-point screen (on != 0; default off).  Despite the name it covers BOTH shapes that
  * leave that screen: wide rows (the narrow tiles of spkm_shard_set_wide_screen) and long columns (more than 64 entries per
  * column, the 16-lanes-per-point kernel).  A shard that opts in keeps the per-point bounds of spkm_assign_accumulate_dev
@@ -318,8 +332,9 @@ int spkm_last_events_form(spkm_ctx *ctx, int64_t info[2]);
  * 0 = none; info[5] = kernel of the last spkm_distances[_stats]_dev: 1 = streaming record kernel, 2 = generic, 0 = none. */
 int spkm_last_assign_tile(spkm_ctx *ctx, int64_t info[6]);
 /* The screen of the last fused call (stored values; does not block): info[0] = centroids per tile -- 32 (the 4- and
- * 16-lanes-per-point kernels), 16 or 8 (the narrow tiles of a shard that opted in, spkm_shard_set_wide_screen), 0 = that
- * call took no screen; info[1] = its number of tiles (result slots per point). */
+ * 16-lanes-per-point kernels), 16 or 8 (the narrow tiles of a shard that opted in, spkm_shard_set_wide_screen), 64, 128 or
+ * 256 (the planes of the far screen, spkm_shard_set_far_screen), 0 = that call took no screen; info[1] = its number of tiles
+ * (result slots per point). */
 int spkm_last_screen_tile(spkm_ctx *ctx, int64_t info[2]);
 /* How many points the screen of the last fused call evaluated (any screen kernel): info[0] = n for a call over all points,
  * the length of the list for a call that skipped on its carried bounds (points; 16 per listed step for a step list), 0

@@ -37,6 +37,7 @@ static spkm_switches read_switches()
     w.force_point_list = on("SPKM_FORCE_POINT_LIST");
     w.wide_screen = on("SPKM_WIDE_SCREEN");
     w.wide_bounds = on("SPKM_WIDE_BOUNDS");
+    w.far_screen = on("SPKM_FAR_SCREEN");
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
     if (const char* v = getenv("SPKM_X_HINT_CHUNK")) w.x_hint_chunk = atoi(v);   // points per chunk in the two-phase screen launches (default 256)
     if (const char* v = getenv("SPKM_X_PLAIN_CHUNK")) w.x_plain_chunk = atoi(v); // ... in the plain launch (default: n / (8 x teams), at most 4096)
@@ -347,6 +348,13 @@ extern "C" int spkm_shard_set_wide_screen(spkm_shard* s, int on)
     if (!s) return SPKM_ERR_NULL_ARG;
     s->wide = on != 0;
     return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other screen, or to none)
+}
+
+extern "C" int spkm_shard_set_far_screen(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->far = on != 0;
+    return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
 }
 
 extern "C" int spkm_shard_set_wide_bounds(spkm_shard* s, int on)

@@ -56,6 +56,7 @@ struct spkm_switches {
     int force_form = 0;           // SPKM_FORCE_FORM=1|2|3: plain / unconditional two-phase / hinted screen, where legal (test aid, spkm.h)
     bool wide_screen = false;     // SPKM_WIDE_SCREEN: every shard of the context takes the narrow-tile screen (k_screen_wide) past the 32-wide tile, as if opted in
     bool wide_bounds = false;     // SPKM_WIDE_BOUNDS: every shard of the context that takes the narrow-tile or the 16-lanes-per-point screen carries bounds, as if opted in (spkm_shard_set_wide_bounds)
+    bool far_screen = false;      // SPKM_FAR_SCREEN: every shard of the context that no LDS tile serves takes the far screen (k_screen_far: centroid rows gathered from L2), as if opted in (spkm_shard_set_far_screen)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
 };
 // What one fused call did on the screen path: written by the stages of that call (screen_call, api_lloyd_fused.inc), read
@@ -64,7 +65,7 @@ struct spkm_switches {
 // "no screen" answer).  After a FAILED call the context's report is unspecified (the previous call's, or the exact path's).
 struct spkm_screen_report {
     int path = 0;                 // 0 = exact tiled/generic, 1 = f32 screen + exact confirmation
-    int kt = 0, tiles = 0;        // centroids per tile and tiles of the screen
+    int kt = 0, tiles = 0;        // centroids per tile and tiles of the screen (the far screen: per plane, and planes)
     int pl_last = 0;              // the plan: centroid pairs per lane of its last tile (5: carried)
     int rounds_all = 0, rounds = 0; // rounds for all centroids / total rounds of a 4-lanes-per-point screen
     int mode = 0;                 // 0 plain screen, 1 two-phase, 2 hinted two-phase
@@ -139,6 +140,7 @@ struct spkm_shard {
     uint64_t slack = 0; // entries readable past nnz in ir / x
     bool wide = false; // spkm_shard_set_wide_screen: past the 32-wide tile this shard's fused calls take the narrow-tile screen
     bool wide_bounds = false; // spkm_shard_set_wide_bounds: where this shard takes the narrow-tile or the 16-lanes-per-point screen it carries bounds between calls
+    bool far = false; // spkm_shard_set_far_screen: where no LDS tile serves this shard its fused calls take the far screen (policy.h, spkm_far_screen)
     float* xfs = nullptr;  // screen copy for the 4-lanes-per-point kernel: f32 values, columns partitioned by row parity
     void* irs = nullptr;   // ... and their row ids
     bool norms_done = false, xf_done = false;

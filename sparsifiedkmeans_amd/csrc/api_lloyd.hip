@@ -5,6 +5,7 @@
 #include "update.hip"
 #include "screen.hip"
 #include "screen_wide.hip"
+#include "screen_far.hip"
 #include "dense.hip"
 
 #include "api_internal.h"

@@ -24,6 +24,13 @@ static int screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
     return spkm_screen_width((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
                              s->wide || ctx->sw.wide_screen);
 }
+// ... and where that is 0 for want of LDS, the plane width of the far screen (policy.h, spkm_far_screen): 64, 128, 256
+// centroids for a shard or a context that opted in (spkm_shard_set_far_screen, SPKM_FAR_SCREEN=1); 0: the all-exact kernels.
+static int far_screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
+{
+    return spkm_far_screen((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
+                           s->wide || ctx->sw.wide_screen, s->far || ctx->sw.far_screen);
+}
 
 
 static_assert(spkm_plan_kt == SCREEN_KT && spkm_plan_span == BOUNDS_SPAN && spkm_plan_span_pt == BOUNDS_SPAN_PT &&
@@ -341,6 +348,67 @@ struct screen_call : spkm_call_in {
         rep.pt_mode = pl.pt_mode;
         return SPKM_OK;
     }
+    // The far screen (screen_far.hip): the table in planes of kt = 64 / 128 / 256 centroids by k_prep_tiles_wide -- with cmax and
+    // the row-major f64 centres of the exact list, in one launch -- then one wave per (point, plane) over every point.
+    template <typename IR> int screen_far()
+    {
+        zero_flush();
+        const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
+        hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256), 0,
+                           ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p, (unsigned long long*)ctx->cmax.p,
+                           (double*)ctx->ct.p, (double*)nullptr);
+        rep.pl_last = pl.pl_last;
+        rep.kt = kt;
+        rep.tiles = pl.Gs;
+        rep.rounds_all = rep.rounds = 0;
+        rep.mode = 0;
+        const int npl = kt / 64;
+        const void* kern = npl == 1 ? (const void*)k_screen_far<IR, 1> : (npl == 2 ? (const void*)k_screen_far<IR, 2> : (const void*)k_screen_far<IR, 4>);
+        HIP_TRY(timing_begin(ctx));
+        const IR* a_ir = (const IR*)sm->ir;
+        const float* a_xf = (const float*)sm->xf;
+        const float* a_t = (const float*)ctx->t32.p;
+        int a_p = p, a_n = (int)n, a_s = sm->fixed_s, a_K = K;
+        float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
+        int* a_k = (int*)ctx->scr_k.p;
+        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_m1, &a_m2, &a_k};
+        // (4 waves per workgroup, a wave per point; 32 workgroups per CU and plane at most: the waves stride over the points)
+        const unsigned gx = (unsigned)std::min<long long>((n + 3) / 4, (long long)std::max(1, num_cus) * 32);
+        HIP_TRY(hipLaunchKernel(kern, dim3(gx, (unsigned)pl.G), dim3(256), args, 0, ctx->stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(timing_end(ctx));
+        return SPKM_OK;
+    }
+    // The sums behind the far screen, by the kernels that work at any p: the cluster sizes (k_hist), the distances and the
+    // three statistics when the call wants them (the route of spkm_distances_stats_dev), sums and counts (the route of
+    // spkm_accumulate_dev: k_accumulate_sorted, or k_accumulate_atomic past its slab).  Returns in *no_stats whether the
+    // call is a lazy one that skipped the distances.
+    int far_sums(bool* no_stats)
+    {
+        int rc;
+        hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long*)ctx->nk.p, K,
+                           (const unsigned*)nullptr);
+        if ((size_t)K * 4 > 48 * 1024) HIP_TRY(allow_lds(ctx, (const void*)k_hist, (size_t)K * 4));
+        hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
+                           ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, (const unsigned*)nullptr);
+        HIP_TRY(hipGetLastError());
+        *no_stats = sm->lazy && mind == nullptr;
+        if (!*no_stats) {
+            // (no buffer of the caller's for the distances: the context's scratch; the statistics stay in ctx->stats for the
+            //  tail, the copy the entry makes goes to scratch as well)
+            double* dm = mind;
+            if (!dm) {
+                if ((rc = ensure(ctx, ctx->mscr, (size_t)n * 8))) return rc;
+                dm = (double*)ctx->mscr.p;
+            }
+            if ((rc = ensure(ctx, ctx->tmp_assign, 64))) return rc;
+            if ((rc = spkm_distances_stats_dev(ctx, sm, (uint64_t)K, C, gamma, assign, dm, (double*)ctx->tmp_assign.p))) return rc;
+        }
+        sm->cl_valid = false;
+        sm->cl_stats_valid = false;
+        sm->sp_clean = false;
+        return spkm_accumulate_dev(ctx, sm, (uint64_t)K, assign, sums);
+    }
     // Certification (k_combine_screen) and exact evaluation of the uncertified points (k_assign_list).  Only they change an
     // assignment: they keep the library's copy (hb + hb_assign(npad)) up to date in place and, against the previous value, mark the
     // clusters a point left or entered, move the cluster sizes and record the events.
@@ -588,7 +656,8 @@ struct screen_call : spkm_call_in {
         return SPKM_OK;
     }
     // The tail (k_call_tail): sizes, statistics and counters handed over; after events the sums and counts ARE the cache.
-    int tail(double* d_stats, uint64_t* d_nk_u64)
+    // no_stats: the call evaluated no distance (a lazy far call): NaN statistics, as after events or a sums-only pass.
+    int tail(double* d_stats, uint64_t* d_nk_u64, bool no_stats = false)
     {
         const bool ev = pl.ev_path;
         double* nk_f = sums + 2 * pk;
@@ -600,7 +669,7 @@ struct screen_call : spkm_call_in {
         const unsigned grid = ev ? (unsigned)std::max<size_t>((K + 255) / 256, std::min<size_t>((pk + 255) / 256, 1024)) : (unsigned)(K + 255) / 256;
         hipLaunchKernelGGL(k_call_tail, dim3(grid), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk.p, K, nk_f,
                            (const double*)ctx->stats.p, nk_f + K, d_stats, (unsigned long long*)d_nk_u64, (const unsigned*)ctx->bstat.p,
-                           bstat_n, (unsigned*)ctx->nlist.p, (ev || pl.sums_only) ? 1 : 0, ev ? sm->cl_cache : (double*)nullptr,
+                           bstat_n, (unsigned*)ctx->nlist.p, (ev || pl.sums_only || no_stats) ? 1 : 0, ev ? sm->cl_cache : (double*)nullptr,
                            ev ? (const double*)(sm->cl_cache + cc_counts(pk)) : (const double*)nullptr, ev ? pk : (size_t)0,
                            ev ? sums : (double*)nullptr, ev ? counts : (double*)nullptr,
                            sm->nlist_pending ? (unsigned*)nullptr : sm->h_nlist_dev, sm->nlist_seq + 1u,
@@ -661,6 +730,31 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     return SPKM_OK;
 }
 
+// One FAR screen call: run_screen's stages where they fit -- buffers, the (empty) bounds stage, certification, the tail --
+// around the far screen and the any-p kernels for the sums.  No bounds, hints, events or cluster cache at these shapes: every
+// call screens every point and accumulates over every point, and leaves nothing behind for the next one.
+template <typename IR>
+static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_centers, double gamma, int32_t* d_assign,
+                   double* d_mind, double* d_reduce, double* d_stats, uint64_t* d_nk_u64, int kp, spkm_screen_report* report)
+{
+    screen_call c;
+    c.kt = kp;
+    c.ctx = ctx; c.sm = const_cast<spkm_shard*>(s); c.C = d_centers; c.gamma = gamma; c.assign = d_assign; c.mind = d_mind;
+    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = false; c.carry_bounds = false; c.carry = false;
+    c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
+    c.zj.n = 0;
+    spkm_plan_tiles(c.pl, c, kp);
+    int rc;
+    if ((rc = c.buffers<IR>())) return rc;
+    c.plan_input(0, false);
+    spkm_plan_call(c.pl, c, c.sm->pol);
+    if ((rc = c.bounds()) || (rc = c.screen_far<IR>()) || (rc = c.certify<IR>())) return rc;
+    bool no_stats = false;
+    if ((rc = c.far_sums(&no_stats)) || (rc = c.tail(d_stats, d_nk_u64, no_stats))) return rc;
+    *report = c.rep;
+    return SPKM_OK;
+}
+
 extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, const double* d_centers,
                                           double gamma, int32_t* d_assign, double* d_mind, double* d_stats,
                                           uint64_t* d_nk_u64, double* d_reduce)
@@ -702,7 +796,8 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
     }
     const bool cooling = ch.exact;
     const int kt = screen_width(ctx, s, (int)K64);
-    if (s->n > 0 && !cooling && kt > 0) {
+    const int kp = kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64); // (the far screen: only where no tile serves, policy.h)
+    if (s->n > 0 && !cooling && (kt > 0 || kp > 0)) {
         ctx->ev_valid = false;
         // Hinted two-phase screen: when the unconditional two-phase form is not chosen and hints are not paused, the
         // screen compares the competition's partial sums with per-point upper bounds taken from the carried bounds
@@ -710,15 +805,19 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         const int prune_a = ch.prune_a;
         const bool want_hint = ch.want_hint;
         spkm_screen_report rep;
-        rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep)
-                                : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep);
+        if (kp > 0)
+            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep)
+                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep);
+        else
+            rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep)
+                                    : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep);
         if (rc) return rc;
         ctx->last = rep;
         if (!sm->nlist_pending) { // (run_screen's k_call_tail was told to report under the number nlist_seq + 1)
             sm->nlist_seq++;
             sm->nlist_pending = true;
             sm->pol.launched(rep.rounds_all, rep.rounds, rep.hinted, rep.hint_late, rep.skipping, rep.lib_valid, rep.incremental, rep.dual);
-            sm->pend_full = !rep.skipping && screen_use_quad(ctx, s);
+            sm->pend_full = kp == 0 && !rep.skipping && screen_use_quad(ctx, s); // (a far call's step statistics regroup nothing)
         }
         return SPKM_OK; // (statistics and cluster sizes were handed over by run_screen's last kernel)
     }

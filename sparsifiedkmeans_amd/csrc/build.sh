@@ -4,7 +4,7 @@
 # process (PyTorch's bundled copy when torch is imported, /opt/rocm otherwise), so that device
 # pointers handed over from torch tensors belong to the same runtime.
 # Six translation units, compiled in parallel: api.hip (contexts, shards, operators, FWHT, RCCL), api_lloyd.hip (the Lloyd
-# engine and the kernels it launches, screen_wide.hip among them) and the four instantiation sets of the 4-lanes-per-point screen kernel (screen_quad.hip).
+# engine and the kernels it launches, screen_wide.hip and screen_far.hip among them) and the four instantiation sets of the 4-lanes-per-point screen kernel (screen_quad.hip).
 set -euo pipefail
 cd "$(dirname "$0")"
 python3 gen_assign_steps.py

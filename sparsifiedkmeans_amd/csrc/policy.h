@@ -291,6 +291,48 @@ inline int spkm_screen_width(long long p, int K, int fixed_s, unsigned long long
     if ((size_t)p * 20 + 1024 + 16 * 8 * per_pt > lds_max) return 0;
     return kt;
 }
+// The FAR screen (screen_far.hip, k_screen_far): the same f32 estimates with the centroid table left in global memory --
+// one wave per point, lane l owning centroids l, l + 64, ... of a PLANE of KP = 64, 128 or 256 centroids, rows gathered from
+// L2 -- for the shards that spkm_screen_width turns away for want of LDS: no tile fits (p > 5118 with 160 KB), or a tile
+// fits and the exact pass behind it does not (the phase-2 formula: p = 410 with s = 150).  Returns KP, or 0: not opted in
+// (the shard, spkm_shard_set_far_screen, or the context, SPKM_FAR_SCREEN=1); SPKM_NO_SCREEN; a ragged or empty shard; K < 2;
+// a screen that exists (spkm_screen_width != 0) or is refused for any other reason than the LDS (no narrow-tile opt-in where
+// a narrow tile fits, K <= 16 on the 16-lanes-per-point kernel, more tiles than workgroups); more planes than workgroups, the
+// cap of the other screens; a table beyond spkm_far_table_max.  The policy's cool-down is the caller's to add.
+// KP: the narrowest plane that holds all K centroids in one (a lane's accumulators: 1, 2, 4), 256 beyond.
+// The table cap: G planes of (p + 1) rows of KP floats.  The kernel gathers whole rows, and pays while they come from the L2
+// and the 256-MB Infinity Cache; a table larger than that is gathered from HBM in 256-byte pieces (and at p = 2^24 would
+// not fit beside the shard at all).
+constexpr unsigned long long spkm_far_table_max = 256ull << 20;
+inline int spkm_far_plane(int K) { return K <= 64 ? 64 : (K <= 128 ? 128 : 256); }
+inline int spkm_far_planes(int K, int kp) { return kp > 0 ? (K + kp - 1) / kp : 0; }
+inline int spkm_far_screen(long long p, int K, int fixed_s, unsigned long long slack, unsigned long long nnz, size_t lds_max,
+                           int num_cus, bool no_screen, bool wide, bool far)
+{
+    if (!far || no_screen) return 0;
+    if (fixed_s <= 0 || slack < 48 || nnz == 0 || K < 2) return 0;
+    if (spkm_screen_width(p, K, fixed_s, slack, nnz, lds_max, num_cus, no_screen, wide) != 0) return 0;
+    // why there is no screen: the tile ...
+    const bool fits32 = (unsigned long long)(p + 1) * (unsigned)spkm_plan_kt * 4ull + 16ull <= (unsigned long long)lds_max;
+    const int kt = fits32 ? spkm_plan_kt : spkm_wide_kt(p, lds_max);
+    const int nb = num_cus > 0 ? num_cus : 256;
+    if (kt != 0) {
+        // ... or, with a tile that fits, the exact pass -- and nothing else (spkm_screen_width's tests, in its order)
+        if (!fits32 && !wide) return 0;
+        const bool quad = spkm_screen_quad(kt, fixed_s);
+        if (kt == spkm_plan_kt && K <= 16 && !quad) return 0;
+        const int tiles = (K + kt - 1) / kt;
+        if (tiles > nb) return 0;
+        if (quad && tiles > ((nb % 8 == 0) ? nb / 8 : nb)) return 0;
+        // (what is left is the phase-2 formula)
+    }
+    const int kp = spkm_far_plane(K);
+    const int G = spkm_far_planes(K, kp);
+    if (G > nb) return 0;
+    if ((unsigned long long)G * (unsigned long long)(p + 1) * (unsigned)kp * 4ull > spkm_far_table_max) return 0;
+    if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (the cluster sizes behind it: k_hist counts in LDS)
+    return kp;
+}
 struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;

@@ -89,6 +89,14 @@ class Shard:
         state is forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_wide_screen(self.handle, 1 if on else 0), "spkm_shard_set_wide_screen")
 
+    def set_far_screen(self, on: bool = True):
+        """Let fused calls on this shard take the certified screen where no LDS tile serves it -- rows past the narrowest
+        tile, p > 5118 with 160 KB of LDS, or an exact pass that does not fit behind the tile -- with the centroid rows
+        gathered from L2, in planes of 64, 128 or 256 centroids, instead of the all-exact kernels
+        (spkm_shard_set_far_screen; off by default at the C interface).  Outputs never depend on it; the shard's policy
+        state is forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_far_screen(self.handle, 1 if on else 0), "spkm_shard_set_far_screen")
+
     def set_wide_bounds(self, on: bool = True):
         """Let this shard carry its per-point distance bounds between fused calls also where it leaves the
         4-lanes-per-point screen -- the narrow tiles of set_wide_screen() AND columns of more than 64 entries -- so that a
@@ -372,8 +380,9 @@ class LloydEngine:
         return tuple(int(v) for v in a)
 
     def last_screen_tile(self) -> tuple[int, int]:
-        """(centroids per tile of the last fused call's screen: 32, or 16 / 8 on a shard with set_wide_screen(); 0 = it
-        took no screen, its number of tiles) -- spkm_last_screen_tile."""
+        """(centroids per tile of the last fused call's screen: 32, or 16 / 8 on a shard with set_wide_screen(), or 64 /
+        128 / 256 per plane on one with set_far_screen(); 0 = it took no screen, its number of tiles) --
+        spkm_last_screen_tile."""
         a = (C.c_int64 * 2)()
         _lib.check(_lib.lib().spkm_last_screen_tile(self.ctx.handle, a))
         return int(a[0]), int(a[1])

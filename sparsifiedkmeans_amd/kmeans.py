@@ -59,7 +59,9 @@ _DEFAULTS = dict(
 # 160 KB of LDS) are screened on narrow tiles instead of running the all-exact kernels (Shard.set_wide_screen); False: off.
 # wideBounds: on those tiles, and with more than 64 entries per column, the shard carries its distance bounds between
 # iterations and a call screens only the points they do not settle (Shard.set_wide_bounds); False: every call screens all
-_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True)
+# farScreen: shapes that no LDS tile serves (p2 > 5118 with 160 KB: the Hadamard widths from 8192 on) are screened with the
+# centroid rows gathered from L2 instead of running the all-exact kernels (Shard.set_far_screen); False: off.
+_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True)
 
 
 def _parse(opts: dict) -> dict:
@@ -406,6 +408,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_lazy_stats(lazy_stats)
     shard.set_wide_screen(bool(o["wideScreen"]))
     shard.set_wide_bounds(bool(o["wideBounds"]))
+    shard.set_far_screen(bool(o["farScreen"]))
     if Display in ("iter", "final"):
         print(f"Randomly mixing of type {sk}")
         print(f"Randomly taking {100 * gamma:.1f}% of the data; actual dataset is {100 * nnz / (p2 * n):.1f}% sparse")
@@ -605,7 +608,7 @@ def kmeans_sparsified(X, K, **options):
             if not np.isfinite(dff2) and bool(torch.isnan(centers).any().item()):
                 raise RuntimeError("Found NaN in centers")                       # :480-484 (a NaN centre makes dff NaN)
         last_path = eng.last_path_info()[0] if fused_iters else 0
-        OUTPUT["screenTile"] = eng.last_screen_tile()[0] if fused_iters else 0   # (not a reference field: 32 / 16 / 8 centroids, 0 = no screen)
+        OUTPUT["screenTile"] = eng.last_screen_tile()[0] if fused_iters else 0   # (not a reference field: 32 / 16 / 8 centroids per tile, 64 / 128 / 256 per plane of the far screen, 0 = no screen)
         if its > 0 and mind_pending:
             eng_used.distances(centers_used)                                     # `distances` of the last iteration (:420)
             dist_t = eng_used.mind
