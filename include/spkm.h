@@ -164,6 +164,19 @@ int spkm_shard_set_wide_screen(spkm_shard *s, int on);
  * spkm_shard_reset_policy.  SPKM_FAR_SCREEN=1 opts every shard of a context in (read with the other switches:
  * spkm_ctx_reload_switches). */
 int spkm_shard_set_far_screen(spkm_shard *s, int on);
+/* Sums and counts of rows past the 64-KB slab (on != 0; default off).  spkm_accumulate_dev keeps a cluster's sums and counts
+ * in an LDS slab of 12 bytes per row while the whole row fits 64 KB (p <= 5461); past that every stored entry is two
+ * scattered f64 atomics on the p x K tables.  A shard that opts in keeps the slab there too, a SLICE of the rows at a time
+ * (csrc/update.hip, k_accumulate_sliced): as many rows as the LDS of one workgroup holds -- 13653 with 160 KB -- per pass
+ * over the entries, and one coalesced f64 atomic per touched row when a slab is added to the tables.  Every slice is one
+ * more pass over the shard's entries, so shapes that would need more than a fixed number of them (csrc/policy.h,
+ * spkm_acc_max_slices) stay on the atomics.  The arithmetic is that of the 64-KB slab: sums to the last bits (the order
+ * of the f64 additions is not fixed in any of the three kernels), counts exactly.  It is also what a fused call on the far
+ * screen (spkm_shard_set_far_screen) and LloydEngine.accumulate_step run.  Where the 64-KB slab fits the setting changes
+ * nothing; no policy state depends on it.  spkm_last_assign_tile info[4] says which kernel ran.  SPKM_SLICED_SUMS=1 opts
+ * every shard of a context in (read with the other switches: spkm_ctx_reload_switches).  SPKM_X_SLAB_ROWS=r: experiments and
+ * tests -- at most r rows per slab, at any p and any number of slices, for a shard or context that opted in. */
+int spkm_shard_set_sliced_sums(spkm_shard *s, int on);
 /* Carried bounds beyond the 4-lanes-per-point screen (on != 0; default off).  Despite the name it covers BOTH shapes that
  * leave that screen: wide rows (the narrow tiles of spkm_shard_set_wide_screen) and long columns (more than 64 entries per
  * column, the 16-lanes-per-point kernel).  A shard that opts in keeps the per-point bounds of spkm_assign_accumulate_dev
@@ -329,6 +342,7 @@ int spkm_last_events_form(spkm_ctx *ctx, int64_t info[2]);
  * the last exact pass: 8 .. 64 (fused call: k_exact_accumulate; 16 .. 64 for the K = 1 stream of spkm_assign_dev), 16 for
  * the pipelined record kernel, 0 when the last call ran none (tiles, generic kernel, incremental sums); info[4] = kernel
  * of the last spkm_accumulate_dev: 1 = LDS slab over a counting sort, 2 = global atomics (rows beyond a 64-KB slab),
+ * 3 = LDS slabs over row slices (rows beyond a 64-KB slab on a shard that opted in, spkm_shard_set_sliced_sums),
  * 0 = none; info[5] = kernel of the last spkm_distances[_stats]_dev: 1 = streaming record kernel, 2 = generic, 0 = none. */
 int spkm_last_assign_tile(spkm_ctx *ctx, int64_t info[6]);
 /* The screen of the last fused call (stored values; does not block): info[0] = centroids per tile -- 32 (the 4- and

@@ -38,6 +38,8 @@ static spkm_switches read_switches()
     w.wide_screen = on("SPKM_WIDE_SCREEN");
     w.wide_bounds = on("SPKM_WIDE_BOUNDS");
     w.far_screen = on("SPKM_FAR_SCREEN");
+    w.sliced_sums = on("SPKM_SLICED_SUMS");
+    if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
     if (const char* v = getenv("SPKM_X_HINT_CHUNK")) w.x_hint_chunk = atoi(v);   // points per chunk in the two-phase screen launches (default 256)
     if (const char* v = getenv("SPKM_X_PLAIN_CHUNK")) w.x_plain_chunk = atoi(v); // ... in the plain launch (default: n / (8 x teams), at most 4096)
@@ -355,6 +357,13 @@ extern "C" int spkm_shard_set_far_screen(spkm_shard* s, int on)
     if (!s) return SPKM_ERR_NULL_ARG;
     s->far = on != 0;
     return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
+}
+
+extern "C" int spkm_shard_set_sliced_sums(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->sliced = on != 0; // (which kernel adds the sums: no policy state depends on it)
+    return SPKM_OK;
 }
 
 extern "C" int spkm_shard_set_wide_bounds(spkm_shard* s, int on)

@@ -57,6 +57,8 @@ struct spkm_switches {
     bool wide_screen = false;     // SPKM_WIDE_SCREEN: every shard of the context takes the narrow-tile screen (k_screen_wide) past the 32-wide tile, as if opted in
     bool wide_bounds = false;     // SPKM_WIDE_BOUNDS: every shard of the context that takes the narrow-tile or the 16-lanes-per-point screen carries bounds, as if opted in (spkm_shard_set_wide_bounds)
     bool far_screen = false;      // SPKM_FAR_SCREEN: every shard of the context that no LDS tile serves takes the far screen (k_screen_far: centroid rows gathered from L2), as if opted in (spkm_shard_set_far_screen)
+    bool sliced_sums = false;     // SPKM_SLICED_SUMS: spkm_accumulate_dev on every shard of the context keeps its sums in LDS past the 64-KB slab too, a row slice at a time (k_accumulate_sliced; policy.h, spkm_accumulate_form), as if opted in (spkm_shard_set_sliced_sums)
+    int x_slab_rows = 0;          // SPKM_X_SLAB_ROWS: at most this many rows per slab of k_accumulate_sliced, at any p and any number of slices (0: the default, what the LDS holds; experiments and tests)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
 };
 // What one fused call did on the screen path: written by the stages of that call (screen_call, api_lloyd_fused.inc), read
@@ -117,7 +119,7 @@ struct spkm_ctx {
     int assign_KT = 0, assign_G = 0; // of the last assign call
     spkm_screen_report last;         // of the last spkm_assign_accumulate_dev
     int last_exact_pts = 0;          // points staged per wave by the last exact pass / K = 1 stream (16: the pipelined kernel)
-    int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics
+    int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics, 3 LDS slabs over row slices
     int last_dist_form = 0;          // the last distances call: 1 streaming record kernel, 2 generic kernel
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
     bool sort_perm_valid = false;    // ... and perm / offs / items really hold that call's counting sort (not after an incremental call)
@@ -141,6 +143,7 @@ struct spkm_shard {
     bool wide = false; // spkm_shard_set_wide_screen: past the 32-wide tile this shard's fused calls take the narrow-tile screen
     bool wide_bounds = false; // spkm_shard_set_wide_bounds: where this shard takes the narrow-tile or the 16-lanes-per-point screen it carries bounds between calls
     bool far = false; // spkm_shard_set_far_screen: where no LDS tile serves this shard its fused calls take the far screen (policy.h, spkm_far_screen)
+    bool sliced = false; // spkm_shard_set_sliced_sums: past the 64-KB slab spkm_accumulate_dev on this shard takes k_accumulate_sliced (policy.h, spkm_accumulate_form)
     float* xfs = nullptr;  // screen copy for the 4-lanes-per-point kernel: f32 values, columns partitioned by row parity
     void* irs = nullptr;   // ... and their row ids
     bool norms_done = false, xf_done = false;

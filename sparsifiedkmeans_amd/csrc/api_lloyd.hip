@@ -661,8 +661,8 @@ static void launch_scatter(spkm_ctx* ctx, int sb, size_t sc_lds, const int* d_as
 }
 
 // (the segment lengths of the counting sort -- SEG_POINTS, seg_points, SEG_EVENTS, SEG_DENSE -- are policy.h's)
-extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, const int32_t* d_assign,
-                                   double* d_reduce)
+// timed: a fused call's far path brackets the accumulation kernel with the second event pair of spkm_timing_log(ctx, 2)
+static int accumulate_impl(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, const int32_t* d_assign, double* d_reduce, bool timed)
 {
     if (!ctx || !s || !d_assign || !d_reduce) return SPKM_ERR_NULL_ARG;
     if (K64 == 0 || K64 > 65536) return SPKM_ERR_UNSUPPORTED;
@@ -679,11 +679,13 @@ extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t 
     HIP_TRY(hipMemsetAsync(d_reduce, 0, (2 * pk + K + 1) * 8, ctx->stream));
     if (!ctx->nk.p || !ctx->stats.p) return SPKM_ERR_BAD_VALUE; // spkm_assign_dev must come first
     int rc;
-    const size_t slab = (size_t)p * 12;
+    // the kernel: LDS slab over a counting sort (1), the same over row slices for a shard that opted in (3), atomics (2)
+    const spkm_acc_plan ap = spkm_accumulate_form((long long)s->p, ctx->lds_max, s->sliced || ctx->sw.sliced_sums, ctx->sw.x_slab_rows);
+    const size_t slab = (size_t)ap.R * spkm_acc_row_bytes;
     ctx->last_acc_form = 0;
     if (n > 0 && s->nnz > 0) {
-        if (slab <= ctx->lds_max && slab <= 64 * 1024) {
-            ctx->last_acc_form = 1;
+        ctx->last_acc_form = ap.form;
+        if (ap.form == 1 || ap.form == 3) {
             const int max_items = (int)(n / SEG_POINTS) + K + 1;
             if ((rc = ensure(ctx, ctx->perm, (size_t)n * 4))) return rc;
             if ((rc = ensure(ctx, ctx->offs, (size_t)(K + 1) * 8))) return rc;
@@ -696,20 +698,41 @@ extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t 
             const int sb = (int)std::min<long long>(1024, (n + 1023) / 1024);
             const size_t sc_lds = (size_t)((K + 1) & ~1) * 4 + (size_t)K * 12;
             launch_scatter(ctx, sb, sc_lds, (const int*)d_assign, n, K, (const unsigned*)nullptr, (const int*)nullptr);
-            const int ab = std::min(max_items, std::max(1, ctx->num_cus) * 8);
-            if (s->ir_bits == 16)
-                hipLaunchKernelGGL((k_accumulate_sorted<unsigned short>), dim3(ab), dim3(256), slab, ctx->stream,
-                                   (const long long*)s->jc, (const unsigned short*)s->ir, (const double*)s->x,
-                                   (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
-                                   (const int*)ctx->nitems.p, p, s->fixed_s, sums, counts);
-            else
-                hipLaunchKernelGGL((k_accumulate_sorted<unsigned int>), dim3(ab), dim3(256), slab, ctx->stream,
-                                   (const long long*)s->jc, (const unsigned int*)s->ir, (const double*)s->x,
-                                   (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
-                                   (const int*)ctx->nitems.p, p, s->fixed_s, sums, counts);
+            if (ap.form == 3) {
+                // workgroups: as many of 1024 threads as a CU holds beside each other's slabs (one above half the LDS, two at most)
+                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_max / std::max<size_t>(slab, 1)));
+                const long long units = (long long)max_items * ap.slices;
+                const int ab = (int)std::min<long long>(units, (long long)std::max(1, ctx->num_cus) * per_cu);
+                if (s->ir_bits == 16) HIP_TRY(allow_lds(ctx, (const void*)k_accumulate_sliced<unsigned short>, slab));
+                else HIP_TRY(allow_lds(ctx, (const void*)k_accumulate_sliced<unsigned int>, slab));
+                if (timed) HIP_TRY(timing_begin(ctx));
+                if (s->ir_bits == 16)
+                    hipLaunchKernelGGL((k_accumulate_sliced<unsigned short>), dim3(ab), dim3(ap.wg), slab, ctx->stream,
+                                       (const long long*)s->jc, (const unsigned short*)s->ir, (const double*)s->x,
+                                       (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
+                                       (const int*)ctx->nitems.p, p, s->fixed_s, ap.R, ap.slices, sums, counts);
+                else
+                    hipLaunchKernelGGL((k_accumulate_sliced<unsigned int>), dim3(ab), dim3(ap.wg), slab, ctx->stream,
+                                       (const long long*)s->jc, (const unsigned int*)s->ir, (const double*)s->x,
+                                       (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
+                                       (const int*)ctx->nitems.p, p, s->fixed_s, ap.R, ap.slices, sums, counts);
+            } else {
+                const int ab = std::min(max_items, std::max(1, ctx->num_cus) * 8);
+                if (timed) HIP_TRY(timing_begin(ctx));
+                if (s->ir_bits == 16)
+                    hipLaunchKernelGGL((k_accumulate_sorted<unsigned short>), dim3(ab), dim3(256), slab, ctx->stream,
+                                       (const long long*)s->jc, (const unsigned short*)s->ir, (const double*)s->x,
+                                       (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
+                                       (const int*)ctx->nitems.p, p, s->fixed_s, sums, counts);
+                else
+                    hipLaunchKernelGGL((k_accumulate_sorted<unsigned int>), dim3(ab), dim3(256), slab, ctx->stream,
+                                       (const long long*)s->jc, (const unsigned int*)s->ir, (const double*)s->x,
+                                       (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
+                                       (const int*)ctx->nitems.p, p, s->fixed_s, sums, counts);
+            }
         } else {
-            ctx->last_acc_form = 2;
             const int blocks = std::max(1, ctx->num_cus) * 8;
+            if (timed) HIP_TRY(timing_begin(ctx));
             if (s->ir_bits == 16)
                 hipLaunchKernelGGL((k_accumulate_atomic<unsigned short>), dim3(blocks), dim3(256), 0, ctx->stream,
                                    (const long long*)s->jc, (const unsigned short*)s->ir, (const double*)s->x,
@@ -719,12 +742,20 @@ extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t 
                                    (const long long*)s->jc, (const unsigned int*)s->ir, (const double*)s->x,
                                    (const int*)d_assign, p, n, sums, counts);
         }
+        HIP_TRY(hipGetLastError());
+        if (timed) HIP_TRY(timing_end(ctx));
     }
     hipLaunchKernelGGL(k_nk_to_f64, dim3((K + 255) / 256), dim3(256), 0, ctx->stream,
                        (const unsigned long long*)ctx->nk.p, K, nk_f);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(obj2, ctx->stats.p, 8, hipMemcpyDeviceToDevice, ctx->stream));
     return SPKM_OK;
+}
+
+extern "C" int spkm_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, const int32_t* d_assign,
+                                   double* d_reduce)
+{
+    return accumulate_impl(ctx, s, K64, d_assign, d_reduce, false);
 }
 
 #include "api_lloyd_fused.inc" // the fused call: screen_use_quad, screen_eligible, run_screen, spkm_assign_accumulate_dev

@@ -381,7 +381,7 @@ struct screen_call : spkm_call_in {
     }
     // The sums behind the far screen, by the kernels that work at any p: the cluster sizes (k_hist), the distances and the
     // three statistics when the call wants them (the route of spkm_distances_stats_dev), sums and counts (the route of
-    // spkm_accumulate_dev: k_accumulate_sorted, or k_accumulate_atomic past its slab).  Returns in *no_stats whether the
+    // spkm_accumulate_dev: k_accumulate_sorted, past its slab k_accumulate_sliced or k_accumulate_atomic).  Returns in *no_stats whether the
     // call is a lazy one that skipped the distances.
     int far_sums(bool* no_stats)
     {
@@ -407,7 +407,9 @@ struct screen_call : spkm_call_in {
         sm->cl_valid = false;
         sm->cl_stats_valid = false;
         sm->sp_clean = false;
-        return spkm_accumulate_dev(ctx, sm, (uint64_t)K, assign, sums);
+        // (spkm_accumulate_dev's kernels, the sliced slab among them for a shard that opted in; with spkm_timing_log(ctx, 2) the
+        //  accumulation kernel is the call's second pair, as the exact pass is on the other screen paths)
+        return accumulate_impl(ctx, sm, (uint64_t)K, assign, sums, ctx->tlog_on && ctx->tlog_both);
     }
     // Certification (k_combine_screen) and exact evaluation of the uncertified points (k_assign_list).  Only they change an
     // assignment: they keep the library's copy (hb + hb_assign(npad)) up to date in place and, against the previous value, mark the

@@ -333,6 +333,52 @@ inline int spkm_far_screen(long long p, int K, int fixed_s, unsigned long long s
     if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (the cluster sizes behind it: k_hist counts in LDS)
     return kp;
 }
+// Which kernel spkm_accumulate_dev runs (update.hip), from the rows, the device's LDS and the opt-in alone -- the form that
+// spkm_last_assign_tile reports in info[4]:
+//  1  k_accumulate_sorted: a cluster's sums and counts, 12 B per row, in one LDS slab of at most 64 KB (p <= 5461) --
+//     wherever it fits, opted in or not;
+//  3  k_accumulate_sliced: the same slab over a SLICE of R rows, slice j owning rows [j R, min(p, (j + 1) R)), one pass over
+//     the item's entries per slice -- only for a shard (spkm_shard_set_sliced_sums) or a context (SPKM_SLICED_SUMS=1) that
+//     opted in, where form 1 does not fit, with at most spkm_acc_max_slices slices;
+//  2  k_accumulate_atomic: one global f64 atomic per entry for the sum and one for the count -- everything else.
+// R: the largest slab the LDS of one workgroup holds (the kernel has no static LDS: 13653 rows with 160 KB), so that as few
+// passes as possible re-read the entries -- p = 8192 is one slice, 16384 two, the second of 2731 rows.  wg: threads per
+// workgroup; a slab above half the LDS leaves one workgroup per CU, and 1024 threads are then 16 waves of loads in flight
+// where the 256 threads of form 1 would be 4 (the kernel's header).
+// The slice cap: every slice re-reads the shard's entries (nnz x 10 B), so the form pays only while that many passes stay
+// cheaper than two scattered atomics per entry; p2 = 2^24 (1229 slices) stays on the atomics.  The value is the measurement
+// of profiles/sliced_sums_ab.txt: on 6.55e8 entries the atomics take 54 ms at any p, 2 / 3 / 5 / 8 slices 3.6 / 5.1 / 7.8 /
+// 11.3 ms, every A/B pair a win; 8 is the largest count measured with a slab above half the LDS, as this policy plans them
+// (16 and 32 slices of smaller slabs won too; with the 32-bit row ids that p > 65536 brings, 32 is extrapolated to break even).
+// SPKM_X_SLAB_ROWS=r (x_slab_rows > 0: experiments and tests, not a tuning knob) caps R at r and lets an opted-in shard take
+// form 3 at ANY p and any slice count -- many slices and a short last one on small shapes, and the sweep behind the cap.
+constexpr int spkm_acc_max_slices = 8;
+constexpr int spkm_acc_row_bytes = 12, spkm_acc_sorted_lds = 64 * 1024, spkm_acc_wg = 1024;
+struct spkm_acc_plan {
+    int form = 2;    // 1 slab, 2 atomics, 3 sliced slab
+    int R = 0;       // rows per slab (form 1: p; form 2: 0)
+    int slices = 0;  // passes over an item's entries (form 1: 1; form 2: 0)
+    int wg = 256;    // threads per workgroup
+};
+inline spkm_acc_plan spkm_accumulate_form(long long p, size_t lds_max, bool sliced, int x_slab_rows)
+{
+    spkm_acc_plan a;
+    if (p <= 0 || p > 0x7fffffffLL) return a;
+    const bool x = sliced && x_slab_rows > 0;
+    const unsigned long long slab = (unsigned long long)p * spkm_acc_row_bytes;
+    if (!x && slab <= (unsigned long long)lds_max && slab <= (unsigned long long)spkm_acc_sorted_lds) {
+        a.form = 1; a.R = (int)p; a.slices = 1;
+        return a;
+    }
+    if (!sliced) return a;
+    long long R = std::min<long long>(p, (long long)(lds_max / spkm_acc_row_bytes));
+    if (x) R = std::min<long long>(R, x_slab_rows);
+    if (R <= 0) return a;
+    const long long slices = (p + R - 1) / R;
+    if (!x && slices > spkm_acc_max_slices) return a;
+    a.form = 3; a.R = (int)R; a.slices = (int)slices; a.wg = spkm_acc_wg;
+    return a;
+}
 struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;

@@ -588,6 +588,109 @@ __global__ __launch_bounds__(256) void k_accumulate_sorted(const long long* __re
     }
 }
 
+// The same accumulation for rows whose 12-B-per-row slab no longer fits one workgroup's LDS whole (policy.h,
+// spkm_accumulate_form: form 3, a shard or context that opted in).  The work list is k_accumulate_sorted's -- k_plan_segments
+// with SEG_POINTS, k_scatter_by_cluster -- and a unit of work is (item, slice): slice j owns rows [j R, min(p, (j + 1) R)),
+// its slab is R x (f64 sum + u32 count), cleared per unit.  A wave fetches 64 point ids and their column bounds with one
+// coalesced load each and walks them four at a time, 64 entries of each column per step, so that eight entry loads are
+// outstanding per lane (columns longer than a wave take more steps of the same shape, empty ones none); an entry is added
+// only if (unsigned)(row - j R) < rows of the slice, by LDS atomics.  Then the slab's touched rows go to sums[k p + r] and
+// counts[k p + r], consecutive lanes on consecutive rows: the only global atomics left, one per touched row and unit, in
+// whole 512-B pieces of a row of the table.  The arithmetic is k_accumulate_sorted's: f64 adds in arbitrary order within a
+// slab, counts exact integers.
+// Sizing.  R is the largest slab the LDS holds (13653 rows of 163840 B): every slice is one more pass over the entries, so
+// p = 8192 costs one pass and 16384 two, and a smaller R that let two workgroups share a CU would double the passes at 8192
+// to gain nothing a larger workgroup does not give.  One workgroup per CU it is, then, and 1024 threads: 16 waves, each with
+// 4 columns x (8 B + 2 B) x 64 lanes = 2.5 KB of loads in flight, 40 KB per CU and 10 MB over 256 CUs, which at 2 us of
+// latency is the HBM rate; the 256 threads of k_accumulate_sorted would be a quarter of that.  Clearing and flushing R rows
+// by 1024 threads is 14 trips per unit against 164 entries per thread of a full item at s = 82.  Measured
+// (profiles/sliced_sums_ab.txt): 3.3 ms for the 8.2e8 entries of N = 1e7, s = 82 at p = 8192 -- 2.5 TB/s, 0.42 of the read
+// stream, where the atomics took 68.8 ms; a further slice costs 1.2-1.4 ms per 6.55e8 entries.
+// 48 VGPRs, 77 SGPRs, no scratch (hipcc -Rpass-analysis=kernel-resource-usage, both index widths): the register file would
+// hold 8 waves per SIMD, the slab allows 4.
+// Order of units: unit = item x slices + j and workgroup b takes units b, b + grid, ..., so the slices of one item run at the
+// same time on neighbouring workgroups and all but the first read of its columns (1.7 MB at s = 82) comes from the Infinity
+// Cache (the workgroups of one step sit on different XCDs: not from one L2).
+template <typename IR>
+__global__ __launch_bounds__(1024) void k_accumulate_sliced(const long long* __restrict__ jc,
+                                                            const IR* __restrict__ ir,
+                                                            const double* __restrict__ x,
+                                                            const int* __restrict__ perm,
+                                                            const long long* __restrict__ offs,
+                                                            const int4* __restrict__ items,
+                                                            const int* __restrict__ nitems, int p, int fixed_s, int R,
+                                                            int nslices, double* __restrict__ sums,
+                                                            double* __restrict__ counts)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* ssum = reinterpret_cast<double*>(smem);
+    unsigned int* scnt = reinterpret_cast<unsigned int*>(ssum + R);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const long long units = (long long)*nitems * nslices;
+    for (long long unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const int item = (int)(unit / nslices), sl = (int)(unit - (long long)item * nslices);
+        const int4 it = items[item];
+        const int k = it.x;
+        const long long start = offs[k] + it.y;
+        const int len = it.z;
+        const int base = sl * R;                              // (< p: the policy plans ceil(p / R) slices)
+        const int rows = (p - base < R) ? p - base : R;       // the last slice may be short
+        for (int r = tid; r < rows; r += blockDim.x) { ssum[r] = 0.0; scnt[r] = 0u; }
+        __syncthreads();
+        for (int qb = wave * 64; qb < len; qb += nwaves * 64) {
+            const int have = (len - qb < 64) ? len - qb : 64;
+            long long my_j0 = 0;
+            int my_cnt = 0;
+            if (lane < have) {
+                const long long i = perm[start + qb + lane];
+                if (fixed_s > 0) { my_j0 = i * fixed_s; my_cnt = fixed_s; }
+                else { my_j0 = jc[i]; my_cnt = (int)(jc[i + 1] - my_j0); }
+            }
+            for (int u = 0; u < have; u += 4) {
+                long long j0[4];
+                int cn[4];
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const int src = (u + v < have) ? u + v : u; // clamp: duplicates are masked by cn = 0
+                    const int lo = __builtin_amdgcn_readlane((int)my_j0, src);
+                    const int hi = __builtin_amdgcn_readlane((int)(my_j0 >> 32), src);
+                    j0[v] = ((long long)hi << 32) | (unsigned)lo;
+                    cn[v] = (u + v < have) ? __builtin_amdgcn_readlane(my_cnt, src) : 0;
+                }
+                const int most = max(max(cn[0], cn[1]), max(cn[2], cn[3]));
+                for (int off = lane; off - lane < most; off += 64) {
+                    double xv[4];
+                    unsigned rv[4];
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        const bool ok = off < cn[v];
+                        xv[v] = ok ? x[j0[v] + off] : 0.0;
+                        rv[v] = ok ? (unsigned)((int)ir[j0[v] + off] - base) : 0xffffffffu; // (rows <= 2^31 - 1: never a slab row)
+                    }
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        if (rv[v] < (unsigned)rows) {
+                            unsafeAtomicAdd(&ssum[rv[v]], xv[v]);
+                            atomicAdd(&scnt[rv[v]], 1u);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int r = tid; r < rows; r += blockDim.x) {
+            const unsigned int c = scnt[r];
+            if (c) {
+                const size_t at = (size_t)k * p + (size_t)(base + r);
+                unsafeAtomicAdd(&sums[at], ssum[r]);
+                unsafeAtomicAdd(&counts[at], (double)c);
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // Incremental update of the per-cluster sums and counts (kmeans_sparsified.m:447-448's S and Cnt) by the points that
 // CHANGED cluster: an event (point, key) with key = k adds the point to cluster k, key = K + k takes it out.  The events
 // were sorted by key (k_hist / k_plan_segments / k_scatter_by_cluster over 2K keys), so a work item is a run of points
@@ -960,3 +1063,7 @@ template __global__ void k_accumulate_sorted<unsigned short>(const long long*, c
     const int*, const long long*, const int4*, const int*, int, int, double*, double*);
 template __global__ void k_accumulate_sorted<unsigned int>(const long long*, const unsigned int*, const double*,
     const int*, const long long*, const int4*, const int*, int, int, double*, double*);
+template __global__ void k_accumulate_sliced<unsigned short>(const long long*, const unsigned short*, const double*,
+    const int*, const long long*, const int4*, const int*, int, int, int, int, double*, double*);
+template __global__ void k_accumulate_sliced<unsigned int>(const long long*, const unsigned int*, const double*,
+    const int*, const long long*, const int4*, const int*, int, int, int, int, double*, double*);

@@ -97,6 +97,13 @@ class Shard:
         state is forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_far_screen(self.handle, 1 if on else 0), "spkm_shard_set_far_screen")
 
+    def set_sliced_sums(self, on: bool = True):
+        """Let accumulate_step -- and the fused calls that get their sums from it, the far screen's -- keep this shard's
+        per-cluster sums and counts in LDS past the 64-KB slab too (p > 5461), a slice of the rows at a time, instead of
+        adding every entry by two global atomics (spkm_shard_set_sliced_sums; off by default at the C interface).  Counts
+        are exact and sums agree to the last bits either way; last_assign_tile()[4] reads back which kernel ran."""
+        _lib.check(_lib.lib().spkm_shard_set_sliced_sums(self.handle, 1 if on else 0), "spkm_shard_set_sliced_sums")
+
     def set_wide_bounds(self, on: bool = True):
         """Let this shard carry its per-point distance bounds between fused calls also where it leaves the
         4-lanes-per-point screen -- the narrow tiles of set_wide_screen() AND columns of more than 64 entries -- so that a
@@ -373,7 +380,7 @@ class LloydEngine:
     def last_assign_tile(self) -> tuple[int, ...]:
         """(tile width of the last assign call: 64 / 32 / 16, 0 = generic kernel or K = 1 stream; its tiles; last-tile body
         of the last screen plan, 5 = carried, 0 = no screen; points staged per wave by the last exact pass, 0 = none;
-        kernel of the last accumulate_step: 1 slab / 2 atomics; kernel of the last distances(): 1 streaming / 2 generic)
+        kernel of the last accumulate_step: 1 slab / 2 atomics / 3 slabs over row slices; kernel of the last distances(): 1 streaming / 2 generic)
         -- spkm_last_assign_tile."""
         a = (C.c_int64 * 6)()
         _lib.check(_lib.lib().spkm_last_assign_tile(self.ctx.handle, a))

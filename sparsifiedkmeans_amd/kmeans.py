@@ -61,7 +61,10 @@ _DEFAULTS = dict(
 # iterations and a call screens only the points they do not settle (Shard.set_wide_bounds); False: every call screens all
 # farScreen: shapes that no LDS tile serves (p2 > 5118 with 160 KB: the Hadamard widths from 8192 on) are screened with the
 # centroid rows gathered from L2 instead of running the all-exact kernels (Shard.set_far_screen); False: off.
-_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True)
+# slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
+# in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
+_EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
+              slicedSums=True)
 
 
 def _parse(opts: dict) -> dict:
@@ -409,6 +412,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_wide_screen(bool(o["wideScreen"]))
     shard.set_wide_bounds(bool(o["wideBounds"]))
     shard.set_far_screen(bool(o["farScreen"]))
+    shard.set_sliced_sums(bool(o["slicedSums"]))
     if Display in ("iter", "final"):
         print(f"Randomly mixing of type {sk}")
         print(f"Randomly taking {100 * gamma:.1f}% of the data; actual dataset is {100 * nnz / (p2 * n):.1f}% sparse")
@@ -609,8 +613,9 @@ def kmeans_sparsified(X, K, **options):
                 raise RuntimeError("Found NaN in centers")                       # :480-484 (a NaN centre makes dff NaN)
         last_path = eng.last_path_info()[0] if fused_iters else 0
         OUTPUT["screenTile"] = eng.last_screen_tile()[0] if fused_iters else 0   # (not a reference field: 32 / 16 / 8 centroids per tile, 64 / 128 / 256 per plane of the far screen, 0 = no screen)
+        OUTPUT["accumulateForm"] = eng.last_assign_tile()[4]   # (not a reference field: the kernel of the context's last spkm_accumulate_dev -- 1 LDS slab, 2 global atomics, 3 LDS slabs over row slices, 0 = none; the far screen's calls get their sums from it)
         if its > 0 and mind_pending:
-            eng_used.distances(centers_used)                                     # `distances` of the last iteration (:420)
+            eng_used.distances(centers_used)                                    # `distances` of the last iteration (:420)
             dist_t = eng_used.mind
             if np.isnan(obj):                                                    # ... and its objective (:471), left out by a lazy call
                 o2 = eng_used.stats[0:1].clone()
