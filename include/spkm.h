@@ -158,8 +158,8 @@ int spkm_shard_set_wide_screen(spkm_shard *s, int on);
  * gathered from the L2 -- in front of the same certificate and exact list; sums, counts and, when the call wants them, the
  * distances and statistics come from the kernels of spkm_accumulate_dev and spkm_distances_stats_dev.  Every output is what
  * the all-exact kernels give, bit for bit where they are reproducible.  Fixed-stride shards, K >= 2, a table of at most
- * 256 MB; no bounds, hints or incremental sums: every call screens every point and accumulates over every point, and a
- * lazy call without distances returns NaN statistics.  spkm_last_screen_tile reports (centroids per plane, planes).  Where
+ * 256 MB; no hints or incremental sums: every call accumulates over every point and, unless the shard carries bounds
+ * (spkm_shard_set_far_bounds), screens every point, and a lazy call without distances returns NaN statistics.  spkm_last_screen_tile reports (centroids per plane, planes).  Where
  * a tile serves the shard the setting changes nothing.  Turning it on or off forgets the shard's policy state, like
  * spkm_shard_reset_policy.  SPKM_FAR_SCREEN=1 opts every shard of a context in (read with the other switches:
  * spkm_ctx_reload_switches). */
@@ -188,6 +188,21 @@ int spkm_shard_set_sliced_sums(spkm_shard *s, int on);
  * state and its bounds, like spkm_shard_reset_policy.  SPKM_WIDE_BOUNDS=1 opts every shard of a context in (read with the
  * other switches); SPKM_NO_BOUNDS=1 keeps the bounds but skips nothing on them. */
 int spkm_shard_set_wide_bounds(spkm_shard *s, int on);
+/* Carried bounds on the far screen (on != 0; default off).  A shard that takes the far screen (spkm_shard_set_far_screen)
+ * and opts in keeps the per-point bounds of spkm_assign_accumulate_dev between its far calls: the next call tests them point
+ * by point and screens only the points they do not settle, by a point-list form of the far kernel; the caller's d_assign
+ * still holds every point's assignment after the call.  No exact pass writes upper bounds at these shapes, so a point that
+ * passes the test takes its centroid's drift onto its upper bound (Hamerly's update) and a screened point gets a fresh one
+ * from the certificate or the exact list; a bound that has loosened too far fails the test, and the screen renews it.  The
+ * accumulation, the cluster sizes and the optional distance pass still run over every point, so every output is
+ * unchanged.  No hints, step lists, block summaries, regrouping or incremental sums.  A switch of its own, not
+ * spkm_shard_set_wide_bounds: callers that set that one for every shard keep what they run at these widths.  Such a call
+ * reports info[7] = 2 in spkm_last_screen_mode, spkm_last_screen_points says how many points it screened,
+ * spkm_last_screen_tile still reports (centroids per plane, planes).  On a shard that takes another screen the setting
+ * changes nothing.  Turning it on or off forgets the shard's policy state and its bounds, like spkm_shard_reset_policy.
+ * SPKM_FAR_BOUNDS=1 opts every shard of a context in (read with the other switches); SPKM_NO_BOUNDS=1 keeps the bounds but
+ * skips nothing on them. */
+int spkm_shard_set_far_bounds(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by

@@ -38,6 +38,7 @@ static spkm_switches read_switches()
     w.wide_screen = on("SPKM_WIDE_SCREEN");
     w.wide_bounds = on("SPKM_WIDE_BOUNDS");
     w.far_screen = on("SPKM_FAR_SCREEN");
+    w.far_bounds = on("SPKM_FAR_BOUNDS");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
@@ -370,6 +371,13 @@ extern "C" int spkm_shard_set_wide_bounds(spkm_shard* s, int on)
 {
     if (!s) return SPKM_ERR_NULL_ARG;
     s->wide_bounds = on != 0;
+    return spkm_shard_reset_policy(s); // (the bounds of the other setting are forgotten with the rest)
+}
+
+extern "C" int spkm_shard_set_far_bounds(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->far_bounds = on != 0;
     return spkm_shard_reset_policy(s); // (the bounds of the other setting are forgotten with the rest)
 }
 

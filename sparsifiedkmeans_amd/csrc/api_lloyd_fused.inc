@@ -81,7 +81,7 @@ struct screen_call : spkm_call_in {
     spkm_screen_report rep; // what this call did, as its stages decide it (stored in the context when the call has gone through)
     spkm_zero_jobs zj;
     int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
-    bool carry = false; // this shard carries bounds between screen calls: quad, or carry_bounds (spkm_shard_set_wide_bounds)
+    bool carry = false; // this shard carries bounds between screen calls: quad, or carry_bounds (spkm_shard_set_wide_bounds; on the far screen spkm_shard_set_far_bounds)
     int bstat_n = 0, seg = 0, max_items = 0; // bstat_n: workgroups of k_bounds_steps whose statistics wait in ctx->bstat
     // everything this call needs zeroed, in one launch (flushed in front of the first kernel)
     void zero_later(void* q, size_t bytes) { zj.p[zj.n] = (unsigned*)q; zj.words[zj.n] = bytes / 4; zj.n++; }
@@ -349,21 +349,26 @@ struct screen_call : spkm_call_in {
         return SPKM_OK;
     }
     // The far screen (screen_far.hip): the table in planes of kt = 64 / 128 / 256 centroids by k_prep_tiles_wide -- with cmax and
-    // the row-major f64 centres of the exact list, in one launch -- then one wave per (point, plane) over every point.
+    // the row-major f64 centres of the exact list and, for a shard that carries bounds, the library's copy of the centres that
+    // the next call's drift is measured from, in one launch -- then one wave per (point, plane): over every point, or (a shard
+    // that skips on its bounds) the LIST form over the points of todo[].
     template <typename IR> int screen_far()
     {
         zero_flush();
         const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
         hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256), 0,
                            ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p, (unsigned long long*)ctx->cmax.p,
-                           (double*)ctx->ct.p, (double*)nullptr);
+                           (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
         rep.pl_last = pl.pl_last;
         rep.kt = kt;
         rep.tiles = pl.Gs;
         rep.rounds_all = rep.rounds = 0;
         rep.mode = 0;
         const int npl = kt / 64;
-        const void* kern = npl == 1 ? (const void*)k_screen_far<IR, 1> : (npl == 2 ? (const void*)k_screen_far<IR, 2> : (const void*)k_screen_far<IR, 4>);
+        const bool flist = pl.skip_enabled;
+        const void* kern = flist ? (npl == 1 ? (const void*)k_screen_far<IR, 1, true>
+                                             : (npl == 2 ? (const void*)k_screen_far<IR, 2, true> : (const void*)k_screen_far<IR, 4, true>))
+                                 : (npl == 1 ? (const void*)k_screen_far<IR, 1> : (npl == 2 ? (const void*)k_screen_far<IR, 2> : (const void*)k_screen_far<IR, 4>));
         HIP_TRY(timing_begin(ctx));
         const IR* a_ir = (const IR*)sm->ir;
         const float* a_xf = (const float*)sm->xf;
@@ -371,12 +376,18 @@ struct screen_call : spkm_call_in {
         int a_p = p, a_n = (int)n, a_s = sm->fixed_s, a_K = K;
         float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
         int* a_k = (int*)ctx->scr_k.p;
-        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_m1, &a_m2, &a_k};
-        // (4 waves per workgroup, a wave per point; 32 workgroups per CU and plane at most: the waves stride over the points)
+        const int* a_todo = flist ? (const int*)ctx->todo.p : (const int*)nullptr;
+        const unsigned* a_cnt = (const unsigned*)ctx->nlist.p;
+        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt};
+        // (4 waves per workgroup, a wave per point; 32 workgroups per CU and plane at most: the waves stride over the points --
+        //  the LIST form over the slots of a list whose length only the device knows: the same grid, and the waves past its
+        //  end return at once)
         const unsigned gx = (unsigned)std::min<long long>((n + 3) / 4, (long long)std::max(1, num_cus) * 32);
         HIP_TRY(hipLaunchKernel(kern, dim3(gx, (unsigned)pl.G), dim3(256), args, 0, ctx->stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(timing_end(ctx));
+        rep.skipping = pl.skip_enabled;
+        rep.pt_mode = pl.pt_mode;
         return SPKM_OK;
     }
     // The sums behind the far screen, by the kernels that work at any p: the cluster sizes (k_hist), the distances and the
@@ -733,8 +744,11 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
 }
 
 // One FAR screen call: run_screen's stages where they fit -- buffers, the (empty) bounds stage, certification, the tail --
-// around the far screen and the any-p kernels for the sums.  No bounds, hints, events or cluster cache at these shapes: every
-// call screens every point and accumulates over every point, and leaves nothing behind for the next one.
+// around the far screen and the any-p kernels for the sums.  No hints, events or cluster cache at these shapes: every call
+// accumulates over every point.  A shard that opted in (spkm_shard_set_far_bounds, SPKM_FAR_BOUNDS=1) carries its bounds from
+// call to call, point by point: the bounds stage settles the points it can, the LIST form of k_screen_far screens the others,
+// and the certify stage leaves every screened point's bounds behind (policy.h: the far case of the carry_bounds branch);
+// without the opt-in every call screens every point and leaves nothing behind for the next one.
 template <typename IR>
 static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_centers, double gamma, int32_t* d_assign,
                    double* d_mind, double* d_reduce, double* d_stats, uint64_t* d_nk_u64, int kp, spkm_screen_report* report)
@@ -742,7 +756,8 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     screen_call c;
     c.kt = kp;
     c.ctx = ctx; c.sm = const_cast<spkm_shard*>(s); c.C = d_centers; c.gamma = gamma; c.assign = d_assign; c.mind = d_mind;
-    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = false; c.carry_bounds = false; c.carry = false;
+    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = false; c.far = true;
+    c.carry_bounds = c.carry = s->far_bounds || ctx->sw.far_bounds;
     c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
     c.zj.n = 0;
     spkm_plan_tiles(c.pl, c, kp);

@@ -383,7 +383,8 @@ struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;
     bool quad = false;          // the 4-lanes-per-point screen (s <= 64)
-    bool carry_bounds = false;  // this non-quad shard carries bounds (spkm_shard_set_wide_bounds): point lists only
+    bool carry_bounds = false;  // this non-quad shard carries bounds (spkm_shard_set_wide_bounds; far: spkm_shard_set_far_bounds): point lists only
+    bool far = false;           // the far screen (k_screen_far): no exact pass behind it
     size_t lds_max = 0;
     int num_cus = 0, teams = 1; // teams: chunk divisor of the screen launch (quad ? bmapq_blocks / 4 : bmap_streams)
     bool no_bounds = false, no_point_list = false, force_point_list = false, no_late_split = false, no_incremental = false,
@@ -496,6 +497,19 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
             pl.span = spkm_plan_span_pt;
             pl.bgrid = 4 * std::max(1, in.num_cus);
             while (pl.span > 1024 && (pl.npad + pl.span - 1) / pl.span < 4LL * pl.bgrid) pl.span /= 2;
+        }
+        if (in.far) {
+            // The FAR screen with carried bounds (spkm_shard_set_far_bounds) takes the same branch -- the LIST form of
+            // k_screen_far screens the listed points -- with two differences.  (i) NO exact pass writes upper bounds behind
+            // it: the sums come from the any-p accumulation and the distances, when the caller wants them at all, from a
+            // pass that stores no bounds.  So every test ERODES (a point that passes takes its centroid's drift, Hamerly's
+            // update in k_bounds_steps), and the certify stage writes every screened point's upper bound in EVERY call,
+            // bounds valid or not, test on or off (SPKM_NO_BOUNDS: they are still maintained): the certificate (r1 + eps1)
+            // rounded up, k_assign_list the exact value.  run_far never reaches spkm_plan_sums, so lazy_ub is set here.
+            // (ii) No refresh schedule: an eroded bound only loosens, until the point fails the test; the next screen then
+            // gives it a fresh one -- the looseness of a bound costs a screened point, never a wrong answer, and mends itself.
+            pl.erode = pl.drift;
+            pl.lazy_ub = true;
         }
     }
     pl.prune_a = prune_a;

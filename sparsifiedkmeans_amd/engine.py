@@ -111,6 +111,14 @@ class Shard:
         interface).  Outputs never depend on it; the shard's policy state and bounds are forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_wide_bounds(self.handle, 1 if on else 0), "spkm_shard_set_wide_bounds")
 
+    def set_far_bounds(self, on: bool = True):
+        """Let this shard carry its per-point distance bounds between fused calls where it takes the far screen of
+        set_far_screen(), so that a call screens only the points the bounds do not settle, by the point-list form of the
+        far kernel (spkm_shard_set_far_bounds; off by default at the C interface, and a switch of its own: set_wide_bounds()
+        does not reach these shapes).  Outputs never depend on it; the shard's policy state and bounds are forgotten as by
+        reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_far_bounds(self.handle, 1 if on else 0), "spkm_shard_set_far_bounds")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""

@@ -61,10 +61,12 @@ _DEFAULTS = dict(
 # iterations and a call screens only the points they do not settle (Shard.set_wide_bounds); False: every call screens all
 # farScreen: shapes that no LDS tile serves (p2 > 5118 with 160 KB: the Hadamard widths from 8192 on) are screened with the
 # centroid rows gathered from L2 instead of running the all-exact kernels (Shard.set_far_screen); False: off.
+# farBounds: on the far screen the shard carries its distance bounds between iterations and a call screens only the points
+# they do not settle (Shard.set_far_bounds: every shape of profiles/far_bounds_ab.txt gains); False: every call screens all.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
-              slicedSums=True)
+              slicedSums=True, farBounds=True)
 
 
 def _parse(opts: dict) -> dict:
@@ -412,6 +414,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_wide_screen(bool(o["wideScreen"]))
     shard.set_wide_bounds(bool(o["wideBounds"]))
     shard.set_far_screen(bool(o["farScreen"]))
+    shard.set_far_bounds(bool(o["farBounds"]))
     shard.set_sliced_sums(bool(o["slicedSums"]))
     if Display in ("iter", "final"):
         print(f"Randomly mixing of type {sk}")
