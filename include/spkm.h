@@ -402,6 +402,35 @@ int spkm_kpp_update_dev(spkm_ctx *ctx, uint64_t n, const double *d_dist_new, dou
                         double *d_cum, double *total);
 int spkm_kpp_draw_dev(spkm_ctx *ctx, uint64_t n, const double *d_cum, double target, int64_t *index);
 
+/* k-means++ seeding of R replicates in one call (private/Arthur_initialization.m:34-69 with gamma given: the dense form of
+ * findClusterAssignments, what the rounds above run through spkm_assign_dev).  Nothing in a round depends on another
+ * replicate and the newest centre is one sparse column, so the replicates are processed in batches of RB <= 8 that share
+ * ONE read of the shard per round; the running minimum, the prefix chains of dist.^2 and the draw stay on the device, and
+ * the call blocks on the stream once, at the end.  The random stream stays the host's:
+ *   first   host [R]: the first centre of each replicate (randi(n,1), :35), a local column index < n;
+ *   u       host [R][K-1]: one uniform number in [0,1) per later draw -- the draw's target is u * total (an f64 multiply);
+ *   chosen  host [R][K]: the picks, local column indices;
+ *   status  host [R]: 0 ok, else code + (round << 8) of the FIRST event of the replicate, round = 1 .. K-1 the draw it
+ *           happened in: code 1 = the total of dist.^2 was 0 or not finite (the reference redraws uniformly, :49),
+ *           code 2 = the draw repeated an earlier pick (the reference's 400-retry rule, :54-61).  Both consume more random
+ *           numbers than were handed in, so nothing is retried here: the picks of such a replicate from that round on
+ *           are not the reference's and the caller seeds it round by round instead;
+ *   d_run   device [R][n] or NULL: the running minima dist(:) of every replicate after its last round.
+ * For every replicate whose status is 0, chosen[r][:] is the sequence the round-by-round calls above pick from the same
+ * first and the same uniform numbers, and d_run[r] the running minimum they hold after their last round, bit for bit, in
+ * every form and at every RB: per (entry, replicate) one subtract, one multiply and one add, rounded separately, entries in
+ * storage order; the prefix sums by the addition chains of spkm_kpp_update_dev.
+ * The form -- the table of the RB newest centres in LDS over a fixed-stride shard, or in global memory over any CSC and
+ * any p -- RB and the number of batches are planned in csrc/policy.h and read back by spkm_last_kpp_plan.  RB * n doubles of
+ * scratch are held for the length of the call unless d_run is given.  CSC arrays that were released are brought back.
+ * K = 1: chosen[r][0] = first[r], no launch.  SPKM_ERR_BAD_VALUE: K = 0, R = 0, gamma not > 0 (the sparse-centres form of
+ * a seeding without gamma stays on the round-by-round calls), first[r] not in [0, n); SPKM_ERR_UNSUPPORTED: n > 0x7ff00000. */
+int spkm_kpp_seed_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, double gamma, uint32_t R, const int64_t *first,
+                      const double *u, int64_t *chosen, int32_t *status, double *d_run);
+/* What the context's last spkm_kpp_seed_dev ran: info = { form (1 = table in LDS, 2 = table in global memory; 0 = none yet,
+ * K = 1 or a failed call), RB, batches, points staged per wave (form 1) }.  Stored values; does not block. */
+int spkm_last_kpp_plan(spkm_ctx *ctx, int info[4]);
+
 /* centers(:,k) = gamma*S(:,k) ./ (Cnt(:,k) + 1e-16) for clusters with nk > 0
  * (kmeans_sparsified.m:448); empty clusters keep their column.  d_centers is updated in place;
  * d_out double[2] (device) = { ||old-new||_F^2, obj2 } (kmeans_sparsified.m:470-471 before sqrt). */

@@ -122,6 +122,7 @@ struct spkm_ctx {
     int last_exact_pts = 0;          // points staged per wave by the last exact pass / K = 1 stream (16: the pipelined kernel)
     int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics, 3 LDS slabs over row slices
     int last_dist_form = 0;          // the last distances call: 1 streaming record kernel, 2 generic kernel
+    int last_kpp[4] = {0, 0, 0, 0};  // the last spkm_kpp_seed_dev: form (policy.h, spkm_kpp_plan; 0: none yet or K = 1), RB, batches, points staged per wave
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
     bool sort_perm_valid = false;    // ... and perm / offs / items really hold that call's counting sort (not after an incremental call)
     char errmsg[256] = {0};

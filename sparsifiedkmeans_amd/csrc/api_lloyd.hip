@@ -3,6 +3,7 @@
 // finalisation, k-means++ helpers, the dense two-pass outputs.  Unity build of the kernels it launches.
 #include "assign.hip"
 #include "update.hip"
+#include "kpp.hip"
 #include "screen.hip"
 #include "screen_wide.hip"
 #include "screen_far.hip"
@@ -1133,6 +1134,140 @@ extern "C" int spkm_kpp_draw_dev(spkm_ctx* ctx, uint64_t n64, const double* d_cu
     HIP_TRY(hipMemcpyAsync(&v, ctx->tmp_assign.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *index = (int64_t)v;
+    return SPKM_OK;
+}
+
+// R replicates seeded together (kpp.hip): per batch of RB replicates and round, three asynchronous launches; the host is
+// needed once, at the end.  Scratch of the call's own, freed before it returns: T | block totals | u | first | chosen |
+// status | the running minima (unless the caller brings d_run).
+template <typename IR, int RB>
+static void kpp_launch_round(spkm_ctx* ctx, const spkm_shard* s, const spkm_kpp_plan_t& pl, int nblocks, size_t lds,
+                             const double* T, int live, int first_round, double* run)
+{
+    const long long n = (long long)s->n;
+    if (pl.form == 1)
+        hipLaunchKernelGGL((k_kpp_round<IR, RB>), dim3(nblocks), dim3(64 * pl.nw), lds, ctx->stream, (const IR*)s->ir,
+                           (const double*)s->x, T, (int)s->p, n, s->fixed_s, pl.pts, live, first_round, run);
+    else
+        hipLaunchKernelGGL((k_kpp_round_generic<IR, RB>), dim3(nblocks), dim3(256), 0, ctx->stream, (const long long*)s->jc,
+                           (const IR*)s->ir, (const double*)s->x, T, n, live, first_round, run);
+}
+
+template <typename IR, int RB>
+static int kpp_seed_run(spkm_ctx* ctx, const spkm_shard* s, int K, double gamma, int R, const spkm_kpp_plan_t& pl,
+                        const int64_t* first, const double* u, int64_t* chosen, int32_t* status, double* d_run)
+{
+    const long long n = (long long)s->n;
+    const int p = (int)s->p;
+    const int nb = (int)((n + KPP_BLOCK - 1) / KPP_BLOCK);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_T = up((size_t)p * RB * 8), b_tot = up((size_t)RB * (nb + 1) * 8), b_u = up((size_t)R * (K - 1) * 8),
+                 b_first = up((size_t)R * 8), b_ch = up((size_t)R * K * 8), b_st = up((size_t)R * 4),
+                 b_run = d_run ? 0 : (size_t)RB * n * 8;
+    struct Owned {
+        char* p = nullptr;
+        ~Owned() { if (p) (void)hipFree(p); }
+    } own;
+    if (hipError_t e = hipMalloc((void**)&own.p, b_T + b_tot + b_u + b_first + b_ch + b_st + b_run)) {
+        (void)hipGetLastError(); // (nothing is queued yet: the caller may go on, round by round, without a stale error)
+        own.p = nullptr;
+        snprintf(ctx->errmsg, sizeof(ctx->errmsg), "spkm_kpp_seed_dev: hipMalloc of %zu bytes of scratch: %s",
+                 b_T + b_tot + b_u + b_first + b_ch + b_st + b_run, hipGetErrorString(e));
+        return (int)e;
+    }
+    double* T = (double*)own.p;
+    double* tot = (double*)(own.p + b_T);
+    double* du = (double*)(own.p + b_T + b_tot);
+    long long* dfirst = (long long*)(own.p + b_T + b_tot + b_u);
+    long long* dch = (long long*)(own.p + b_T + b_tot + b_u + b_first);
+    int* dst = (int*)(own.p + b_T + b_tot + b_u + b_first + b_ch);
+    double* scratch_run = (double*)(own.p + b_T + b_tot + b_u + b_first + b_ch + b_st);
+    HIP_TRY(hipMemcpyAsync(du, u, (size_t)R * (K - 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dfirst, first, (size_t)R * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dst, 0, (size_t)R * 4, ctx->stream));
+    size_t lds = 0;
+    int nblocks;
+    if (pl.form == 1) {
+        const int nw = pl.nw;
+        lds = (size_t)p * RB * 8 + (size_t)nw * pl.pts * (s->fixed_s | 1) * 12;
+        HIP_TRY(allow_lds(ctx, (const void*)k_kpp_round<IR, RB>, lds));
+        const long long per = (long long)nw * pl.pts;
+        // (workgroups of fewer than 16 waves go several to a CU where their LDS allows)
+        const long long per_cu = std::max<long long>(1, std::min<long long>(spkm_kpp_nw_max / nw, (long long)(ctx->lds_max / (lds + 1024))));
+        nblocks = (int)std::min<long long>(std::max(1, ctx->num_cus) * per_cu, (n + per - 1) / per);
+    } else
+        nblocks = (int)std::min<long long>((long long)std::max(1, ctx->num_cus) * 8, (n + 255) / 256);
+    for (int r0 = 0; r0 < R; r0 += RB) {
+        const int live = std::min(RB, R - r0);
+        double* run = d_run ? d_run + (size_t)r0 * n : scratch_run;
+        HIP_TRY(hipMemsetAsync(T, 0, (size_t)p * RB * 8, ctx->stream));
+        for (int k = 0; k < K; k++) {
+            if (k > 0) {
+                kpp_launch_round<IR, RB>(ctx, s, pl, nblocks, lds, T, live, k == 1, run);
+                hipLaunchKernelGGL(k_kpp_totals, dim3(nb, live), dim3(256), 0, ctx->stream, (const double*)run, n, nb, tot);
+            }
+            hipLaunchKernelGGL((k_kpp_pick<IR>), dim3(live), dim3(256), 0, ctx->stream, (const long long*)s->jc, (const IR*)s->ir,
+                               (const double*)s->x, gamma, n, nb, RB, r0, K, k, (const long long*)dfirst, (const double*)du,
+                               (const double*)run, tot, dch, dst, T);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(chosen, dch, (size_t)R * K * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(status, dst, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SPKM_OK;
+}
+
+// (the one place where the plan's RB becomes a template argument)
+template <typename IR>
+static int kpp_seed_dispatch(spkm_ctx* ctx, const spkm_shard* s, int K, double gamma, int R, const spkm_kpp_plan_t& pl,
+                             const int64_t* first, const double* u, int64_t* chosen, int32_t* status, double* d_run)
+{
+    switch (pl.RB) {
+    case 8: return kpp_seed_run<IR, 8>(ctx, s, K, gamma, R, pl, first, u, chosen, status, d_run);
+    case 4: return kpp_seed_run<IR, 4>(ctx, s, K, gamma, R, pl, first, u, chosen, status, d_run);
+    case 2: return kpp_seed_run<IR, 2>(ctx, s, K, gamma, R, pl, first, u, chosen, status, d_run);
+    default: return kpp_seed_run<IR, 1>(ctx, s, K, gamma, R, pl, first, u, chosen, status, d_run);
+    }
+}
+
+extern "C" int spkm_kpp_seed_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64, double gamma, uint32_t R,
+                                 const int64_t* first, const double* u, int64_t* chosen, int32_t* status, double* d_run)
+{
+    if (!ctx || !s || !first || !chosen || !status || (K64 > 1 && !u)) return SPKM_ERR_NULL_ARG;
+    if (K64 == 0 || R == 0 || !(gamma > 0.0)) return SPKM_ERR_BAD_VALUE;
+    if (s->n > 0x7ff00000ull || K64 > 0x7fffffffull || (uint64_t)R * K64 > 0x7fffffffull) return SPKM_ERR_UNSUPPORTED;
+    for (uint32_t r = 0; r < R; r++)
+        if (first[r] < 0 || (uint64_t)first[r] >= s->n) return SPKM_ERR_BAD_VALUE;
+    ctx->last_kpp[0] = ctx->last_kpp[1] = ctx->last_kpp[2] = ctx->last_kpp[3] = 0;
+    for (uint32_t r = 0; r < R; r++) status[r] = 0;
+    if (K64 == 1) {
+        for (uint32_t r = 0; r < R; r++) chosen[r] = first[r];
+        return SPKM_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rcc = ensure_csc(ctx, s)) return rcc;
+    size_t free_b = ~(size_t)0, total_b = 0;
+    if (!d_run && hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        free_b = ctx->mem_bytes;
+    }
+    const spkm_kpp_plan_t pl = spkm_kpp_plan((long long)s->p, s->nnz > 0 ? s->fixed_s : 0, s->slack, R, (long long)s->n, ctx->lds_max,
+                                             (unsigned long long)free_b);
+    const int rc = s->ir_bits == 16
+        ? kpp_seed_dispatch<unsigned short>(ctx, s, (int)K64, gamma, (int)R, pl, first, u, chosen, status, d_run)
+        : kpp_seed_dispatch<unsigned int>(ctx, s, (int)K64, gamma, (int)R, pl, first, u, chosen, status, d_run);
+    if (rc) return rc;
+    ctx->last_kpp[0] = pl.form; ctx->last_kpp[1] = pl.RB; ctx->last_kpp[2] = pl.batches; ctx->last_kpp[3] = pl.pts;
+    return SPKM_OK;
+}
+
+// What the context's last spkm_kpp_seed_dev ran: info = { form (1 staged, 2 generic; 0: none yet, K = 1 or a failed call),
+// replicates per batch, batches, points staged per wave }.  Stored values; does not block.
+extern "C" int spkm_last_kpp_plan(spkm_ctx* ctx, int info[4])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    for (int j = 0; j < 4; j++) info[j] = ctx->last_kpp[j];
     return SPKM_OK;
 }
 

@@ -379,6 +379,70 @@ inline spkm_acc_plan spkm_accumulate_form(long long p, size_t lds_max, bool slic
     a.form = 3; a.R = (int)R; a.slices = (int)slices; a.wg = spkm_acc_wg;
     return a;
 }
+// ---- batched k-means++ seeding (spkm_kpp_seed_dev; kpp.hip) ----
+// R replicates are seeded RB at a time (RB = 8, 4, 2 or 1, at most the next power of two >= R), each batch sharing one read
+// of the shard per round.  form reported by spkm_last_kpp_plan:
+//  1  k_kpp_round: fixed-stride shard, the table T f64[p][RB] in LDS beside the staged entries of pts points per wave (12 B
+//     per entry: value and row) -- p * RB * 8 + 1024 + nw * pts * S1 * 12 bytes with S1 = fixed_s | 1 and pts >= 16, the
+//     1024 being room for a kernel's static LDS as in the K = 1 stream.  RB is the largest that fits with ANY of nw = 16, 8
+//     or 4 waves per workgroup -- sharing the read between more replicates saves more than waves in flight hide -- nw then
+//     the largest that fits beside that table, pts the largest multiple of 16 up to 64.  With 160 KB: s = 13 takes RB = 8
+//     up to p = 2388 (16 waves up to p = 1920) and RB = 1 up to p = 19104; s = 51, p = 1024 takes RB = 8 with 8 waves.
+//     The kernel's loads are clamped to the stored entries as k_exact_dist1's are: it needs no slack behind them
+//     (spkm_kpp_slack = 0);
+//  2  k_kpp_round_generic: a ragged shard, or a p whose single column of T does not fit -- T stays in global memory and
+//     RB = min(8, next power of two >= R).
+// The running minima take RB * n * 8 bytes of scratch for the length of the call.  RB is halved while that exceeds a
+// QUARTER of the free device memory (free_bytes; a caller that brings its own d_run passes ~0): the scratch is held only for
+// the length of the call, but a quarter leaves the allocator room for whatever the caller allocates concurrently and keeps
+// a nearly full device (a shard that fills most of HBM) on small batches instead of failing.  At n = 1e8 a batch of 8 is
+// 6.4 GB.  batches = ceil(R / RB).
+constexpr int spkm_kpp_nw_max = 16, spkm_kpp_nw_min = 4, spkm_kpp_rb_max = 8, spkm_kpp_mem_share = 4;
+// (slack: the entries readable behind the stored ones, as the other plans take it.  This kernel needs none, so today every
+//  value passes; the argument stays so that a staged form that reads ahead -- 16-byte loads of the entries -- has its
+//  condition in this plan and in its tests, not in the launch code.)
+constexpr unsigned long long spkm_kpp_slack = 0;
+struct spkm_kpp_plan_t {
+    int form = 2;    // 1 staged (T in LDS), 2 generic
+    int RB = 1;      // replicates per batch
+    int pts = 0;     // points staged per wave (form 1)
+    int batches = 1;
+    int nw = 0;      // waves per workgroup (form 1)
+};
+// points staged per wave beside a table of RB replicates at nw waves per workgroup (0: does not fit)
+inline int spkm_kpp_pts(long long p, int fixed_s, int RB, int nw, size_t lds_max)
+{
+    const unsigned long long per_pt = (unsigned long long)(fixed_s | 1) * 12, fixed_lds = (unsigned long long)p * RB * 8 + 1024;
+    if (fixed_lds + (unsigned long long)nw * 16 * per_pt > (unsigned long long)lds_max) return 0;
+    const unsigned long long pts = ((unsigned long long)lds_max - fixed_lds) / nw / per_pt;
+    return (int)std::min<unsigned long long>(64, pts & ~15ull);
+}
+// the most waves per workgroup (16, 8, 4) that fit beside a table of RB replicates (0: none)
+inline int spkm_kpp_waves(long long p, int fixed_s, int RB, size_t lds_max)
+{
+    for (int nw = spkm_kpp_nw_max; nw >= spkm_kpp_nw_min; nw /= 2)
+        if (spkm_kpp_pts(p, fixed_s, RB, nw, lds_max) > 0) return nw;
+    return 0;
+}
+inline spkm_kpp_plan_t spkm_kpp_plan(long long p, int fixed_s, unsigned long long slack, unsigned R, long long n, size_t lds_max,
+                                     unsigned long long free_bytes)
+{
+    spkm_kpp_plan_t a;
+    if (R == 0) R = 1;
+    int cap = 1;
+    while (cap < spkm_kpp_rb_max && (unsigned)cap < R) cap *= 2;
+    a.RB = cap;
+    if (fixed_s > 0 && slack >= spkm_kpp_slack && p > 0)
+        for (int rb = cap; rb >= 1; rb /= 2)
+            if (spkm_kpp_waves(p, fixed_s, rb, lds_max) > 0) { a.form = 1; a.RB = rb; break; }
+    while (a.RB > 1 && (unsigned long long)a.RB * (unsigned long long)std::max<long long>(n, 0) * 8 > free_bytes / spkm_kpp_mem_share) a.RB /= 2;
+    if (a.form == 1) {
+        a.nw = spkm_kpp_waves(p, fixed_s, a.RB, lds_max);
+        a.pts = spkm_kpp_pts(p, fixed_s, a.RB, a.nw, lds_max);
+    }
+    a.batches = (int)((R + a.RB - 1) / a.RB);
+    return a;
+}
 struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;

@@ -187,6 +187,38 @@ def torch_context(device: int | None = None) -> Context:
     return Context(device, torch.cuda.current_stream(device).cuda_stream)
 
 
+KPP_FORMS = {0: "none", 1: "staged", 2: "generic"}   # spkm_last_kpp_plan's info[0]
+
+
+def last_kpp_plan(ctx: Context) -> tuple[str, int, int, int]:
+    """(form, RB, batches, points staged per wave) of the context's last ``kpp_seed`` (spkm_last_kpp_plan): form
+    'staged' = the newest centres' table in LDS, 'generic' = in global memory, 'none' = no seeding yet or K = 1."""
+    a = (C.c_int * 4)()
+    _lib.check(_lib.lib().spkm_last_kpp_plan(ctx.handle, a), "spkm_last_kpp_plan")
+    return KPP_FORMS[int(a[0])], int(a[1]), int(a[2]), int(a[3])
+
+
+def kpp_seed(shard: Shard, K: int, gamma: float, first, u, want_run: bool = False):
+    """K-means++ seeding of R replicates in one call (spkm_kpp_seed_dev): ``first`` [R] local indices of the first
+    centres, ``u`` [R, K-1] uniform numbers in [0, 1), one per later draw.  Returns (chosen int64 [R, K], status int32
+    [R][, run float64 [R, n] on the device: the running minima after the last round]).  status[r] = 0, or code +
+    (round << 8): 1 the total of dist.^2 was 0 or not finite, 2 a draw repeated an earlier pick -- such a replicate is
+    to be seeded round by round.  Replicates with status 0 hold exactly the picks of the round-by-round path."""
+    first = np.ascontiguousarray(np.asarray(first, np.int64).ravel())
+    R, K = int(first.size), int(K)
+    u = np.ascontiguousarray(np.asarray(u, np.float64).reshape(R, max(K - 1, 0)))
+    chosen = np.zeros((R, K), np.int64)
+    status = np.zeros(R, np.int32)
+    run = None
+    if want_run:
+        run = torch.zeros((R, shard.n), dtype=torch.float64, device=torch.device("cuda", shard.ctx.device))
+    _lib.check(_lib.lib().spkm_kpp_seed_dev(shard.ctx.handle, shard.handle, K, float(gamma), R, C.c_void_p(first.ctypes.data),
+                                            C.c_void_p(u.ctypes.data) if u.size else None, C.c_void_p(chosen.ctypes.data),
+                                            C.c_void_p(status.ctypes.data), _p(run) if want_run else None),
+               "spkm_kpp_seed_dev")
+    return (chosen, status, run) if want_run else (chosen, status)
+
+
 def comm_size(ctx: Context) -> int:
     """ranks of the RCCL communicator attached to ``ctx`` inside libspkm.so (0 = none)."""
     n, r = C.c_int(), C.c_int()

@@ -44,8 +44,8 @@ from . import _lib
 from . import distributed as D_
 from . import synth
 from .engine import (DCT_MAX_P, DCT_TABLE_MAX_P, MIX_MAX_P2, SRC_U16, LloydEngine, Shard, SourceChunkStager,
-                     StreamingSparsifier, dct_apply_device, dense_accumulate_device, dense_assign_device, mix_device,
-                     torch_context)
+                     StreamingSparsifier, dct_apply_device, dense_accumulate_device, dense_assign_device, kpp_seed,
+                     last_kpp_plan, mix_device, torch_context)
 
 EPS = np.finfo(np.float64).eps
 
@@ -65,8 +65,13 @@ _DEFAULTS = dict(
 # they do not settle (Shard.set_far_bounds: every shape of profiles/far_bounds_ab.txt gains); False: every call screens all.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
+# seedTogether: the k-means++ starts of ALL replicates are drawn in one library call that shares each round's read of the
+# shard between them (engine.kpp_seed) -- with 'Sparsify',true, unbiasedInitialization, one process and an EmptyAction other
+# than 'drop' (a drop shrinks K for the later replicates); False: replicate by replicate (_arthur).  Outputs never depend on
+# it: OUTPUT["seedPoints"] records the picks of either path.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
-              slicedSums=True, farBounds=True)
+              slicedSums=True, farBounds=True, seedTogether=True)
+_KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
 def _parse(opts: dict) -> dict:
@@ -457,6 +462,34 @@ def kmeans_sparsified(X, K, **options):
             torch.distributed.all_reduce(mm, op=torch.distributed.ReduceOp.MAX)
             mn, mx = -float(mm[0].item()), float(mm[1].item())
 
+    # k-means++ starts: all replicates in one call where nothing between them can change K or needs another rank
+    is_kpp = isinstance(start, str) and start.lower() in _KPP_STARTS
+    seed_batch, t_seed_batch = None, 0.0
+    if is_kpp:
+        OUTPUT["seedPoints"] = np.full((Replicates, K), -1, np.int64)   # (not a reference field: global indices of every replicate's picks)
+    if (is_kpp and o["seedTogether"] and o["unbiasedInitialization"] and not dist_on and K >= 1 and n >= 1
+            and Replicates >= 1 and str(o["EmptyAction"]).lower() != "drop"):
+        t1 = time.time()
+        rng_state = rng.bit_generator.state
+        firsts, us = _predraw_kpp(rng, n, K, Replicates)
+        try:
+            picked, status = kpp_seed(shard, K, gamma, firsts, us)
+            OUTPUT["seedPlan"] = last_kpp_plan(ctx)[:3]      # (not a reference field: form, replicates per batch, batches)
+            OUTPUT["seedFallback"] = bool(np.any(status != 0))
+        except _lib.SpkmError as e:
+            # the batched call could not run (no room for its running minima, a shape it does not support): the option must
+            # not change what a run can do -- the round-by-round path needs the existing per-point arrays only.  Said aloud.
+            warnings.warn(f"seedTogether: {e}; seeding replicate by replicate")
+            OUTPUT["seedPlan"] = ("none", 0, 0)
+            OUTPUT["seedFallback"] = True
+        if OUTPUT["seedFallback"]:
+            # a draw repeated a pick (the 400-retry rule, :54-61) or a total was zero (the uniform redraw, :49): both
+            # consume more random numbers -- host logic.  Every replicate again, round by round, from the same stream.
+            rng.bit_generator.state = rng_state
+        else:
+            seed_batch = picked
+        t_seed_batch = time.time() - t1
+
     best = dict(obj=np.inf)
     distances = None
     K_start = K                               # K of a 'Start' matrix
@@ -472,9 +505,16 @@ def kmeans_sparsified(X, K, **options):
                 sparse_mask = (centers_np != 0).astype(np.uint8)
             elif s == "uniform":
                 centers_np = (mx - mn) * rng.random((p2, K)) - mn                # :390 (the reference subtracts mn)
-            elif s in ("arthur", "++", "kmeans++", "k-means++", "k-means-++"):
-                g_init = gamma if o["unbiasedInitialization"] else None          # :392-396
-                centers_np, sparse_mask = _arthur(ctx, shard, column, n, K, g_init, rng, first, n_glob, dist_on)
+            elif s in _KPP_STARTS:
+                picks = []
+                if seed_batch is not None:
+                    picks = [int(i) for i in seed_batch[trial]]
+                    centers_np = np.stack([column(i) for i in picks], axis=1)    # columns of the sparse X (:36,68)
+                    sparse_mask = (centers_np != 0).astype(np.uint8)
+                else:
+                    g_init = gamma if o["unbiasedInitialization"] else None      # :392-396
+                    centers_np, sparse_mask = _arthur(ctx, shard, column, n, K, g_init, rng, first, n_glob, dist_on, picks=picks)
+                OUTPUT["seedPoints"][trial, :len(picks)] = picks
             else:
                 raise ValueError('cannot handle other types of "Start" values')  # :398
         else:
@@ -489,7 +529,7 @@ def kmeans_sparsified(X, K, **options):
                 warnings.warn("initialization is specified, so running more than 1 replicate is not helpful")
         if o["denseCenters"]:
             sparse_mask = None                                                   # centers = full(centers) (:412-414)
-        OUTPUT["replicateTimesJustInitialization"][trial] = time.time() - t1
+        OUTPUT["replicateTimesJustInitialization"][trial] = time.time() - t1 + t_seed_batch / Replicates
 
         shard.reset_policy()                                                     # new start: nothing learned carries over
         eng = LloydEngine(shard, Kc, gamma, unbiased=unbiased)
@@ -625,7 +665,7 @@ def kmeans_sparsified(X, K, **options):
                 if dist_on:
                     torch.distributed.all_reduce(o2, op=torch.distributed.ReduceOp.SUM)
                 obj = float(np.sqrt(o2.item()))
-        OUTPUT["replicateTimes"][trial] = time.time() - t1
+        OUTPUT["replicateTimes"][trial] = time.time() - t1 + t_seed_batch / Replicates   # (with its share of a batched seeding, as above)
         OUTPUT["stoppingDiff"][trial], OUTPUT["objectives"][trial], OUTPUT["iterations"][trial] = dff, obj, its
         # (not reference fields) how many iterations went through the fused call, and which path the library took for
         # the last of them: 1 = certified screen + exact confirmation, 0 = all-exact kernels
@@ -900,7 +940,18 @@ def _kmeans_dense(X, K, o, nargout, t0):
     return ((IDX, Cout, SUMD, best["dist"], OUTPUT) + extra)[:max(nargout, 5)]
 
 
-def _arthur(ctx, shard, column, n, K, gamma, rng, first=0, n_glob=None, dist_on=False):
+def _predraw_kpp(rng, n, K, R):
+    """The random numbers R replicates of _arthur consume when no draw is retried, in its order: per replicate
+    rng.integers(n) for the first centre, then K - 1 uniform numbers, one per later draw.  Returns (first int64 [R],
+    u float64 [R, K-1]); the generator is left where R such replicates leave it."""
+    firsts, us = np.zeros(R, np.int64), np.zeros((R, max(K - 1, 0)))
+    for t in range(R):
+        firsts[t] = int(rng.integers(n))
+        us[t] = rng.random(K - 1)
+    return firsts, us
+
+
+def _arthur(ctx, shard, column, n, K, gamma, rng, first=0, n_glob=None, dist_on=False, picks=None):
     """K-means++ seeding, private/Arthur_initialization.m:24-69: first centre uniform; then K-1 rounds of
     [~,dist] = findClusterAssignments(X, full(centres), [], gamma) and a draw ∝ dist.^2 with the 400-retry
     duplicate rule.  The reference recomputes the distances to ALL chosen centres every round (K^2/2
@@ -908,7 +959,8 @@ def _arthur(ctx, shard, column, n, K, gamma, rng, first=0, n_glob=None, dist_on=
     centres, keeping a running minimum and evaluating only the NEW centre gives the same ``dist`` vector bit for
     bit at 1/K of the work.  Everything stays on the device; the draw is a cumulative sum + binary search
     (distributed: the rank is picked from the all-gathered block totals first, with the same random number).
-    Returns (p2 x K dense values, p2 x K support mask): the centres are columns of the sparse X (:36,68)."""
+    Returns (p2 x K dense values, p2 x K support mask): the centres are columns of the sparse X (:36,68); ``picks``
+    (a list) receives their global indices."""
     if K < 1:
         raise ValueError("K must be >= 1")
     n_glob = n if n_glob is None else n_glob
@@ -973,5 +1025,7 @@ def _arthur(ctx, shard, column, n, K, gamma, rng, first=0, n_glob=None, dist_on=
             raise RuntimeError("Cannot sample with replacement with this distribution")  # :62-65
         chosen.append(i)
         cols.append(column(i))
+    if picks is not None:
+        picks.extend(chosen)
     Cd = np.stack(cols, axis=1)
     return Cd, (Cd != 0).astype(np.uint8)
