@@ -158,8 +158,9 @@ int spkm_shard_set_wide_screen(spkm_shard *s, int on);
  * gathered from the L2 -- in front of the same certificate and exact list; sums, counts and, when the call wants them, the
  * distances and statistics come from the kernels of spkm_accumulate_dev and spkm_distances_stats_dev.  Every output is what
  * the all-exact kernels give, bit for bit where they are reproducible.  Fixed-stride shards, K >= 2, a table of at most
- * 256 MB; no hints or incremental sums: every call accumulates over every point and, unless the shard carries bounds
- * (spkm_shard_set_far_bounds), screens every point, and a lazy call without distances returns NaN statistics.  spkm_last_screen_tile reports (centroids per plane, planes).  Where
+ * 256 MB; no hints; unless the shard opts in to incremental sums (spkm_shard_set_far_events) every call accumulates over
+ * every point and, unless the shard carries bounds (spkm_shard_set_far_bounds), screens every point, and a lazy call
+ * without distances returns NaN statistics.  spkm_last_screen_tile reports (centroids per plane, planes).  Where
  * a tile serves the shard the setting changes nothing.  Turning it on or off forgets the shard's policy state, like
  * spkm_shard_reset_policy.  SPKM_FAR_SCREEN=1 opts every shard of a context in (read with the other switches:
  * spkm_ctx_reload_switches). */
@@ -194,8 +195,9 @@ int spkm_shard_set_wide_bounds(spkm_shard *s, int on);
  * still holds every point's assignment after the call.  No exact pass writes upper bounds at these shapes, so a point that
  * passes the test takes its centroid's drift onto its upper bound (Hamerly's update) and a screened point gets a fresh one
  * from the certificate or the exact list; a bound that has loosened too far fails the test, and the screen renews it.  The
- * accumulation, the cluster sizes and the optional distance pass still run over every point, so every output is
- * unchanged.  No hints, step lists, block summaries, regrouping or incremental sums.  A switch of its own, not
+ * accumulation -- unless the shard opts in to incremental sums as well (spkm_shard_set_far_events) -- the cluster sizes and
+ * the optional distance pass still run over every point, so every output is unchanged.  No hints, step lists, block
+ * summaries or regrouping.  A switch of its own, not
  * spkm_shard_set_wide_bounds: callers that set that one for every shard keep what they run at these widths.  Such a call
  * reports info[7] = 2 in spkm_last_screen_mode, spkm_last_screen_points says how many points it screened,
  * spkm_last_screen_tile still reports (centroids per plane, planes).  On a shard that takes another screen the setting
@@ -203,6 +205,23 @@ int spkm_shard_set_wide_bounds(spkm_shard *s, int on);
  * SPKM_FAR_BOUNDS=1 opts every shard of a context in (read with the other switches); SPKM_NO_BOUNDS=1 keeps the bounds but
  * skips nothing on them. */
 int spkm_shard_set_far_bounds(spkm_shard *s, int on);
+/* Incremental sums on the far screen (on != 0; default off).  A shard that takes the far screen, carries bounds there
+ * (spkm_shard_set_far_bounds) and has lazy statistics (spkm_shard_set_lazy_stats) keeps, when it opts in, its own sums and
+ * counts of the last call; a call without distances (d_mind == NULL) whose predecessor counted few movers -- at most a third
+ * of the points -- then runs NO accumulation pass: every point that changes cluster is recorded as two events, and the
+ * kept sums move by them -- fewer than 2048 movers one by one, more of them sorted by cluster and added up in the row-sliced
+ * LDS slabs of spkm_shard_set_sliced_sums (csrc/update.hip, k_accumulate_events_sliced; a shard whose accumulation stays on
+ * the global atomics takes the full pass instead).  The cluster sizes are counted over every point and stay exact, the
+ * counts are exact, a row that no member stores any more has the sum exactly 0, and the sums carry one rounding per update
+ * on top of a fresh summation's: after 256 such calls, or once the movers add up to 8 n, a full pass starts them afresh.
+ * The statistics are NaN, as in every lazy far call.  A run's first two lazy calls, eager calls, calls with distances and
+ * calls in a cool-down run what they run without the setting.  spkm_last_screen_mode reports info[6] = 2 (events sorted and
+ * applied through slabs) or 4 (applied one by one), spkm_last_events_form info[0] = 1 / 2 and info[1] = 0; info[4] of
+ * spkm_last_assign_tile keeps the kernel of the last full accumulation.  Everywhere else the setting changes nothing.
+ * Turning it on or off forgets the shard's policy state, its bounds and its kept sums, like spkm_shard_reset_policy.
+ * SPKM_FAR_EVENTS=1 opts every shard of a context in (read with the other switches); SPKM_NO_INCREMENTAL=1 and
+ * SPKM_NO_DIRECT_EVENTS=1 act as on the 4-lanes-per-point screen. */
+int spkm_shard_set_far_events(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by

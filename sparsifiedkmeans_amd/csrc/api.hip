@@ -39,6 +39,7 @@ static spkm_switches read_switches()
     w.wide_bounds = on("SPKM_WIDE_BOUNDS");
     w.far_screen = on("SPKM_FAR_SCREEN");
     w.far_bounds = on("SPKM_FAR_BOUNDS");
+    w.far_events = on("SPKM_FAR_EVENTS");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
@@ -379,6 +380,13 @@ extern "C" int spkm_shard_set_far_bounds(spkm_shard* s, int on)
     if (!s) return SPKM_ERR_NULL_ARG;
     s->far_bounds = on != 0;
     return spkm_shard_reset_policy(s); // (the bounds of the other setting are forgotten with the rest)
+}
+
+extern "C" int spkm_shard_set_far_events(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->far_events = on != 0;
+    return spkm_shard_reset_policy(s); // (the policy state, the bounds and the kept sums are forgotten with the rest)
 }
 
 extern "C" int spkm_shard_order_info(const spkm_shard* s, int64_t info[2])

@@ -58,6 +58,7 @@ struct spkm_switches {
     bool wide_bounds = false;     // SPKM_WIDE_BOUNDS: every shard of the context that takes the narrow-tile or the 16-lanes-per-point screen carries bounds, as if opted in (spkm_shard_set_wide_bounds)
     bool far_screen = false;      // SPKM_FAR_SCREEN: every shard of the context that no LDS tile serves takes the far screen (k_screen_far: centroid rows gathered from L2), as if opted in (spkm_shard_set_far_screen)
     bool far_bounds = false;      // SPKM_FAR_BOUNDS: every shard of the context that takes the far screen carries bounds, as if opted in (spkm_shard_set_far_bounds)
+    bool far_events = false;      // SPKM_FAR_EVENTS: every shard of the context that takes the far screen, carries bounds there and has lazy statistics moves its sums by events once few points change cluster, as if opted in (spkm_shard_set_far_events)
     bool sliced_sums = false;     // SPKM_SLICED_SUMS: spkm_accumulate_dev on every shard of the context keeps its sums in LDS past the 64-KB slab too, a row slice at a time (k_accumulate_sliced; policy.h, spkm_accumulate_form), as if opted in (spkm_shard_set_sliced_sums)
     int x_slab_rows = 0;          // SPKM_X_SLAB_ROWS: at most this many rows per slab of k_accumulate_sliced, at any p and any number of slices (0: the default, what the LDS holds; experiments and tests)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
@@ -146,6 +147,7 @@ struct spkm_shard {
     bool wide_bounds = false; // spkm_shard_set_wide_bounds: where this shard takes the narrow-tile or the 16-lanes-per-point screen it carries bounds between calls
     bool far = false; // spkm_shard_set_far_screen: where no LDS tile serves this shard its fused calls take the far screen (policy.h, spkm_far_screen)
     bool far_bounds = false; // spkm_shard_set_far_bounds: where this shard takes the far screen it carries bounds between calls
+    bool far_events = false; // spkm_shard_set_far_events: where this shard takes the far screen with carried bounds and lazy statistics, a call with few movers moves the kept sums (cl_cache's first two planes) by events instead of accumulating over every point
     bool sliced = false; // spkm_shard_set_sliced_sums: past the 64-KB slab spkm_accumulate_dev on this shard takes k_accumulate_sliced (policy.h, spkm_accumulate_form)
     float* xfs = nullptr;  // screen copy for the 4-lanes-per-point kernel: f32 values, columns partitioned by row parity
     void* irs = nullptr;   // ... and their row ids

@@ -161,7 +161,21 @@ struct screen_call : spkm_call_in {
             HIP_TRY(hipMemsetAsync(sm->hb_cum, 0, 16, ctx->stream));
             sm->cum_par = 0;
         }
-        if (!quad) return SPKM_OK; // (no cluster cache or flags: the exact pass streams every cluster in every call)
+        if (far && far_events && sm->lazy) {
+            // the KEPT sums of a far shard with incremental sums: the first two planes of the cluster cache (layout.h) --
+            // this shard's own sums and counts of its previous call, which a call with few movers moves by events.  No flags.
+            // (no room for them: this call plans without the opt-in)
+            if (!sm->cl_cache || sm->cl_pk != pk || sm->cl_K != K) {
+                if (regrow(sm->cl_cache, cc_doubles(pk, K) * 8, &sm->cl_valid) != hipSuccess) {
+                    (void)hipGetLastError();
+                    sm->cl_pk = 0; sm->cl_K = 0;
+                    far_events = false;
+                } else {
+                    sm->cl_pk = pk; sm->cl_K = K;
+                }
+            }
+        }
+        if (!quad) return SPKM_OK; // (no cluster flags: the exact pass streams every cluster in every call)
         // per-cluster cache / flags of the unchanged-cluster shortcut
         if (!sm->cl_cache || sm->cl_pk != pk || sm->cl_K != K) {
             HIP_TRY(regrow(sm->cl_cache, cc_doubles(pk, K) * 8, &sm->cl_valid));
@@ -420,7 +434,75 @@ struct screen_call : spkm_call_in {
         sm->sp_clean = false;
         // (spkm_accumulate_dev's kernels, the sliced slab among them for a shard that opted in; with spkm_timing_log(ctx, 2) the
         //  accumulation kernel is the call's second pair, as the exact pass is on the other screen paths)
-        return accumulate_impl(ctx, sm, (uint64_t)K, assign, sums, ctx->tlog_on && ctx->tlog_both);
+        if ((rc = accumulate_impl(ctx, sm, (uint64_t)K, assign, sums, ctx->tlog_on && ctx->tlog_both))) return rc;
+        // a shard with incremental sums (spkm_shard_set_far_events) KEEPS this call's sums and counts -- its own, before any
+        // all-reduce of the caller's -- for the next calls' events to move: eager calls of a lazy shard included, so that the
+        // lazy call behind one may be incremental again
+        if (far_events && sm->lazy && carry && sm->cl_cache != nullptr) {
+            HIP_TRY(hipMemcpyAsync(sm->cl_cache, sums, 2 * pk * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            sm->cl_valid = true;
+        }
+        return SPKM_OK;
+    }
+    // ... or, on a shard with incremental sums in a call that plans them (policy.h: the far case of the carry_bounds branch),
+    // NO accumulation pass: the kept sums move by the events that certify() recorded, two per mover -- few of them one by one
+    // (k_events_direct: no LDS, any p), otherwise sorted by key and added up in row-sliced slabs (k_accumulate_events_sliced;
+    // ap: the geometry of the full pass's slabs, spkm_accumulate_form).  The cluster sizes stay exact: k_hist over all points.
+    // The tail hands the kept sums over.  spkm_last_assign_tile keeps the form of the last full accumulation.
+    template <typename IR> int far_events_apply(const spkm_acc_plan& ap)
+    {
+        int rc;
+        hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long*)ctx->nk.p, K,
+                           (const unsigned*)nullptr);
+        if ((size_t)K * 4 > 48 * 1024) HIP_TRY(allow_lds(ctx, (const void*)k_hist, (size_t)K * 4));
+        hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
+                           ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, (const unsigned*)nullptr);
+        HIP_TRY(hipGetLastError());
+        sm->cl_stats_valid = false;
+        sm->sp_clean = false;
+        const int K2 = 2 * K;
+        const unsigned* ev_n = (const unsigned*)ctx->nlist.p + NL_EVENTS;
+        double *cache_s = sm->cl_cache, *cache_c = cache_s + cc_counts(pk);
+        rep.direct_events = pl.direct;
+        const bool timed = ctx->tlog_on && ctx->tlog_both;
+        if (pl.direct) {
+            if (timed) HIP_TRY(timing_begin(ctx));
+            hipLaunchKernelGGL((k_events_direct<IR>), dim3(1024), dim3(256), 0, ctx->stream, (const char*)nullptr, 0,
+                               (const IR*)sm->ir, (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k, ev_n, p,
+                               sm->fixed_s, K, cache_s, cache_c, (const int*)nullptr);
+        } else {
+            const int seg_ev = pl.seg_ev;
+            const int max_items_ev = (int)((2 * n) / seg_ev) + K2 + 1;
+            if ((rc = ensure(ctx, ctx->perm, (size_t)2 * n * 4)) || (rc = ensure(ctx, ctx->offs, (size_t)(K2 + 1) * 8)) ||
+                (rc = ensure(ctx, ctx->cursor, (size_t)K2 * 8)) || (rc = ensure(ctx, ctx->items, (size_t)max_items_ev * 16)) ||
+                (rc = ensure(ctx, ctx->nitems, NI_WORDS * 4)))
+                return rc;
+            ctx->sort_owner = nullptr; // (the sort buffers hold this call's events now)
+            // (sized by what usually moves, not by the worst case: every kernel strides over the device-side count)
+            const long long ev_est = std::max<long long>(4096, (long long)std::min<unsigned long long>(4 * sm->pol.last_movers + 4096, (unsigned long long)2 * n));
+            const int hb_ = (int)std::min<long long>(1024, (ev_est + 1023) / 1024);
+            // (the histogram over the 2 K keys was collected by k_combine_screen / k_assign_list as they appended the events)
+            hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk_ev.p, K2,
+                               seg_ev, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
+                               (int*)ctx->nitems.p + NI_FULL, (const unsigned*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
+            const size_t sc_lds_ev = (size_t)((K2 + 1) & ~1) * 4 + (size_t)K2 * 12;
+            launch_scatter(ctx, hb_, sc_lds_ev, (const int*)sm->ev_k, 0, K2, (const unsigned*)nullptr, (const int*)nullptr, ev_n,
+                           (const int*)sm->ev_pt);
+            const size_t slab = (size_t)ap.R * spkm_acc_row_bytes;
+            const void* kern = (const void*)k_accumulate_events_sliced<IR>;
+            HIP_TRY(allow_lds(ctx, kern, slab));
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_max / std::max<size_t>(slab, 1)));
+            const long long units = (long long)max_items_ev * ap.slices;
+            const int ab = (int)std::max<long long>(1, std::min<long long>(units, (long long)std::max(1, ctx->num_cus) * per_cu));
+            if (timed) HIP_TRY(timing_begin(ctx));
+            hipLaunchKernelGGL((k_accumulate_events_sliced<IR>), dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream, (const IR*)sm->ir,
+                               (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
+                               (const int4*)ctx->items.p, (const int*)ctx->nitems.p + NI_FULL, p, sm->fixed_s, K, ap.R, ap.slices,
+                               cache_s, cache_c);
+        }
+        HIP_TRY(hipGetLastError());
+        if (timed) HIP_TRY(timing_end(ctx));
+        return SPKM_OK;
     }
     // Certification (k_combine_screen) and exact evaluation of the uncertified points (k_assign_list).  Only they change an
     // assignment: they keep the library's copy (hb + hb_assign(npad)) up to date in place and, against the previous value, mark the
@@ -744,7 +826,8 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
 }
 
 // One FAR screen call: run_screen's stages where they fit -- buffers, the (empty) bounds stage, certification, the tail --
-// around the far screen and the any-p kernels for the sums.  No hints, events or cluster cache at these shapes: every call
+// around the far screen and the any-p kernels for the sums.  No hints or cluster shortcut at these shapes, and unless the
+// shard opted in to incremental sums (spkm_shard_set_far_events, SPKM_FAR_EVENTS=1: far_events_apply) every call
 // accumulates over every point.  A shard that opted in (spkm_shard_set_far_bounds, SPKM_FAR_BOUNDS=1) carries its bounds from
 // call to call, point by point: the bounds stage settles the points it can, the LIST form of k_screen_far screens the others,
 // and the certify stage leaves every screened point's bounds behind (policy.h: the far case of the carry_bounds branch);
@@ -758,6 +841,7 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     c.ctx = ctx; c.sm = const_cast<spkm_shard*>(s); c.C = d_centers; c.gamma = gamma; c.assign = d_assign; c.mind = d_mind;
     c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = false; c.far = true;
     c.carry_bounds = c.carry = s->far_bounds || ctx->sw.far_bounds;
+    c.far_events = c.carry && (s->far_events || ctx->sw.far_events); // (incremental sums: only on a shard that carries bounds)
     c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
     c.zj.n = 0;
     spkm_plan_tiles(c.pl, c, kp);
@@ -765,9 +849,13 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     if ((rc = c.buffers<IR>())) return rc;
     c.plan_input(0, false);
     spkm_plan_call(c.pl, c, c.sm->pol);
-    if ((rc = c.bounds()) || (rc = c.screen_far<IR>()) || (rc = c.certify<IR>())) return rc;
-    bool no_stats = false;
-    if ((rc = c.far_sums(&no_stats)) || (rc = c.tail(d_stats, d_nk_u64, no_stats))) return rc;
+    // the slabs of this shard's accumulation (spkm_accumulate_form): the sorted events take the same ones; where the full pass
+    // stays on the global atomics there is no slab, and a call with too many movers for the direct form takes the full pass
+    const spkm_acc_plan ap = spkm_accumulate_form((long long)s->p, ctx->lds_max, s->sliced || ctx->sw.sliced_sums, ctx->sw.x_slab_rows);
+    if (c.pl.ev_path && !c.pl.direct && ap.form == 2) c.pl.lose_events();
+    if ((rc = c.resources()) || (rc = c.bounds()) || (rc = c.screen_far<IR>()) || (rc = c.certify<IR>())) return rc;
+    bool no_stats = c.pl.ev_path; // (an event call is a lazy call without distances: NaN statistics)
+    if ((rc = c.pl.ev_path ? c.far_events_apply<IR>(ap) : c.far_sums(&no_stats)) || (rc = c.tail(d_stats, d_nk_u64, no_stats))) return rc;
     *report = c.rep;
     return SPKM_OK;
 }

@@ -443,12 +443,16 @@ inline spkm_kpp_plan_t spkm_kpp_plan(long long p, int fixed_s, unsigned long lon
     a.batches = (int)((R + a.RB - 1) / a.RB);
     return a;
 }
+// far shards with incremental sums: k_combine_screen keeps 2 K event counters (8 K bytes) in dynamic LDS beside 16 KB of
+// static stage -- 32 KB of counters (K <= 4096) stay inside the 64 KB every launch may use without asking
+constexpr size_t spkm_far_events_kmax_bytes = 32 * 1024;
 struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;
     bool quad = false;          // the 4-lanes-per-point screen (s <= 64)
     bool carry_bounds = false;  // this non-quad shard carries bounds (spkm_shard_set_wide_bounds; far: spkm_shard_set_far_bounds): point lists only
     bool far = false;           // the far screen (k_screen_far): no exact pass behind it
+    bool far_events = false;    // ... on a shard that opted in to incremental sums there (spkm_shard_set_far_events; SPKM_FAR_EVENTS=1)
     size_t lds_max = 0;
     int num_cus = 0, teams = 1; // teams: chunk divisor of the screen launch (quad ? bmapq_blocks / 4 : bmap_streams)
     bool no_bounds = false, no_point_list = false, force_point_list = false, no_late_split = false, no_incremental = false,
@@ -574,6 +578,28 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
             // gives it a fresh one -- the looseness of a bound costs a screened point, never a wrong answer, and mends itself.
             pl.erode = pl.drift;
             pl.lazy_ub = true;
+            // INCREMENTAL SUMS at these widths (spkm_shard_set_far_events; a plan made without the flag is the plan above in
+            // every field).  The call's sums are the shard's kept sums of its previous call (cl_valid: the first two planes
+            // of cl_cache) moved by two events per mover, keys `new` and `K + old`, instead of an accumulation over every
+            // point.  Needs lazy statistics without distances, the library's copy of the previous assignment -- valid with
+            // the bounds, tested or not -- the kept sums, and a KNOWN count of few movers: with no count yet (a run's second
+            // lazy call, where from a random start nearly every point moves) the call takes the full pass -- there is no
+            // device-chosen form at these shapes, and no pair events, cluster shortcut, kept sort or record layout.
+            // K: the 2 K event counters of k_combine_screen sit in LDS beside its 16-KB stage.
+            // The mover bar is few_movers' third of the points, the constant measured on records at s = 51, and stays it for
+            // far shards: teacher-forced at d = 8192, s = 82, N = 1e7 (profiles/far_events_ab.txt, tools/far_events_bar.py) the
+            // sorted events take 0.15 / 0.70 / 1.37 / 2.21 ms at 1 / 10 / 20 / 32 % movers against 3.37 ms for the full pass,
+            // same-build spread 0.01 ms -- they win up to the bar; nothing past it was measured, so it is not raised.
+            // direct: as spkm_plan_sums decides it; it needs no LDS, so it serves any p.  The sorted form needs the slab
+            // geometry of spkm_accumulate_form, which run_far knows (the opt-in to sliced sums is not the plan's input): where
+            // the full pass stays on the global atomics it gives the event path up for the call (lose_events).
+            if (in.far_events) {
+                pl.ev_possible = in.lazy && !in.no_incremental && (size_t)K * 8 <= spkm_far_events_kmax_bytes;
+                pl.ev_path = pl.ev_possible && !in.want_dist && pl.bounds_ok && in.cl_valid && pol.movers_known &&
+                             pol.few_movers((double)n) && !pol.refresh_due((double)n);
+                pl.direct = pl.ev_path && pol.events_direct() && !in.no_direct_events;
+                if (pl.ev_path) pl.seg_ev = pol.last_movers < 100000 ? SEG_EVENTS : spkm_plan_seg;
+            }
         }
     }
     pl.prune_a = prune_a;

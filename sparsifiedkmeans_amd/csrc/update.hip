@@ -788,6 +788,98 @@ __global__ __launch_bounds__(256) void k_accumulate_events(const char* __restric
     }
 }
 
+// k_accumulate_events past its slab (the far screen's shards with incremental sums, spkm_shard_set_far_events: p = 8192,
+// 16384, ...), built the way k_accumulate_sliced is.  The work list is the events' -- k_plan_segments over the 2 K keys with
+// pl.seg_ev, k_scatter_by_cluster -- and a unit of work is (item, slice), unit = item x slices + j, so that an item's slices
+// run side by side: slice j owns rows [j R, min(p, (j + 1) R)) in a dynamic slab of R x (f64 sum + u32 count), cleared per
+// unit.  A wave takes 64 events of the item: their point ids come from perm with one coalesced load, and it walks them four
+// columns at a time, 64 entries of each per step (columns longer than 64 entries take more steps of the same shape: p = 410,
+// s = 150); an entry is added by LDS atomics only if (unsigned)(row - j R) < rows of the slice.  The slab's touched rows
+// then go to the table -- the shard's KEPT sums and counts -- with one f64 atomic per row and unit for the sum and one for
+// the count, both times the item's sign: +1 for key < K (the points enter cluster key), -1 for key >= K (they leave cluster
+// key - K).  Counts are integers held in doubles, exact under + and -; the sums pick up one rounding per update (the
+// refresh rule of policy.h bounds how many).  Fixed-stride CSC arrays, both row-id widths; far shards have no record layout.
+// Sizing: k_accumulate_sliced's -- the slab is the largest the LDS holds (one pass over the events' entries at p = 8192, two
+// at 16384), so one workgroup of 1024 threads per CU: 16 waves, each with 4 columns x (8 B + 2 B) x 64 lanes of loads in
+// flight.  An item of SEG_EVENTS = 256 events keeps 4 of the 16 waves busy and one of 2048 all of them twice: the short
+// items belong to calls with fewer than 1e5 movers, a thousand units whose clear and flush (8 trips each at R = 8192) are the
+// cost, some tens of microseconds.  The LDS atomics of a slice land on R rows from 64 lanes x 4 columns: same-row collisions
+// within a wave are as rare as in k_accumulate_sliced (s entries over p rows).
+// 41 VGPRs, 82 SGPRs, no scratch, no static LDS (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, both index widths):
+// the register file would hold 8 waves per SIMD, the slab allows 4.
+template <typename IR>
+__global__ __launch_bounds__(1024) void k_accumulate_events_sliced(const IR* __restrict__ ir,
+                                                                   const double* __restrict__ x,
+                                                                   const int* __restrict__ perm,
+                                                                   const long long* __restrict__ offs,
+                                                                   const int4* __restrict__ items,
+                                                                   const int* __restrict__ nitems, int p, int s, int K,
+                                                                   int R, int nslices, double* __restrict__ sums,
+                                                                   double* __restrict__ counts)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* ssum = reinterpret_cast<double*>(smem);
+    unsigned int* scnt = reinterpret_cast<unsigned int*>(ssum + R);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const long long units = (long long)*nitems * nslices;
+    for (long long unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const int item = (int)(unit / nslices), sl = (int)(unit - (long long)item * nslices);
+        const int4 it = items[item];
+        const int key = it.x;
+        const int k = key >= K ? key - K : key;
+        const double sign = key >= K ? -1.0 : 1.0;
+        const long long start = offs[key] + it.y;
+        const int len = it.z;
+        const int base = sl * R;                        // (< p: the policy plans ceil(p / R) slices)
+        const int rows = (p - base < R) ? p - base : R; // the last slice may be short
+        for (int r = tid; r < rows; r += blockDim.x) { ssum[r] = 0.0; scnt[r] = 0u; }
+        __syncthreads();
+        for (int qb = wave * 64; qb < len; qb += nwaves * 64) {
+            const int have = (len - qb < 64) ? len - qb : 64;
+            int my_i = 0;
+            if (lane < have) my_i = perm[start + qb + lane];
+            for (int u = 0; u < have; u += 4) {
+                long long j0[4];
+                int cn[4];
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const int src = (u + v < have) ? u + v : u; // clamp: duplicates are masked by cn = 0
+                    j0[v] = (long long)(unsigned)__builtin_amdgcn_readlane(my_i, src) * s;
+                    cn[v] = (u + v < have) ? s : 0;
+                }
+                for (int off = lane; off - lane < s; off += 64) {
+                    double xv[4];
+                    unsigned rv[4];
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        const bool ok = off < cn[v];
+                        xv[v] = ok ? x[j0[v] + off] : 0.0;
+                        rv[v] = ok ? (unsigned)((int)ir[j0[v] + off] - base) : 0xffffffffu; // (rows <= 2^31 - 1: never a slab row)
+                    }
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        if (rv[v] < (unsigned)rows) {
+                            unsafeAtomicAdd(&ssum[rv[v]], xv[v]);
+                            atomicAdd(&scnt[rv[v]], 1u);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int r = tid; r < rows; r += blockDim.x) {
+            const unsigned int c = scnt[r];
+            if (c) {
+                const size_t at = (size_t)k * p + (size_t)(base + r);
+                unsafeAtomicAdd(&sums[at], sign * ssum[r]);
+                unsafeAtomicAdd(&counts[at], sign * (double)c);
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // Pair events, second level of the sort.  After the placement by NEW cluster (k_scatter_by_cluster over K keys; the old
 // clusters travel as the second payload) the events of bucket b lie together; the work items of that first plan are
 // chunks of one bucket.  k_pair_hist counts, per chunk, the old clusters in an LDS table of K + 1 bins and adds them to

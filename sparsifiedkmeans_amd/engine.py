@@ -119,6 +119,15 @@ class Shard:
         reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_far_bounds(self.handle, 1 if on else 0), "spkm_shard_set_far_bounds")
 
+    def set_far_events(self, on: bool = True):
+        """Let this shard, where it takes the far screen of set_far_screen() with the carried bounds of set_far_bounds() and
+        lazy statistics, keep its sums and counts between fused calls and move them by the points that change cluster --
+        events, applied one by one or sorted and added up in row-sliced LDS slabs -- instead of accumulating over every
+        point, once a call has counted few movers (spkm_shard_set_far_events; off by default at the C interface).
+        Assignments, counts and cluster sizes never depend on it, sums to rounding; last_events_form() reads back what a
+        call did.  The shard's policy state, bounds and kept sums are forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_far_events(self.handle, 1 if on else 0), "spkm_shard_set_far_events")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""

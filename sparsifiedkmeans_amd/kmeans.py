@@ -63,6 +63,9 @@ _DEFAULTS = dict(
 # centroid rows gathered from L2 instead of running the all-exact kernels (Shard.set_far_screen); False: off.
 # farBounds: on the far screen the shard carries its distance bounds between iterations and a call screens only the points
 # they do not settle (Shard.set_far_bounds: every shape of profiles/far_bounds_ab.txt gains); False: every call screens all.
+# farEvents: on the far screen with carried bounds, a lazy iteration whose predecessor counted few movers moves the kept
+# per-cluster sums by the movers' events instead of accumulating over every point (Shard.set_far_events: every shape of
+# profiles/far_events_ab.txt gains; OUTPUT["eventIterations"] counts such iterations); False: every call accumulates over all.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
 # seedTogether: the k-means++ starts of ALL replicates are drawn in one library call that shares each round's read of the
@@ -70,7 +73,7 @@ _DEFAULTS = dict(
 # than 'drop' (a drop shrinks K for the later replicates); False: replicate by replicate (_arthur).  Outputs never depend on
 # it: OUTPUT["seedPoints"] records the picks of either path.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
-              slicedSums=True, farBounds=True, seedTogether=True)
+              slicedSums=True, farBounds=True, farEvents=True, seedTogether=True)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -420,6 +423,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_wide_bounds(bool(o["wideBounds"]))
     shard.set_far_screen(bool(o["farScreen"]))
     shard.set_far_bounds(bool(o["farBounds"]))
+    shard.set_far_events(bool(o["farEvents"]))
     shard.set_sliced_sums(bool(o["slicedSums"]))
     if Display in ("iter", "final"):
         print(f"Randomly mixing of type {sk}")
@@ -543,7 +547,7 @@ def kmeans_sparsified(X, K, **options):
         csc_released = False
         dist_t = eng.mind                     # min-distances of the latest iteration (survives a 'drop' re-build of eng)
         mind_pending, eng_used, centers_used = False, eng, centers
-        fused_iters = 0
+        fused_iters = event_iters = 0
         screened0 = eng.last_screen_points()[1]   # (the context's running total: this replicate's share is the difference)
         for its in range(1, int(o["MaxIter"]) + 1):
             # [assignments,distances] = findClusters(X,centers) (:420) and the per-cluster sums of :430-453
@@ -567,6 +571,7 @@ def kmeans_sparsified(X, K, **options):
                 else:
                     eng.assign_accumulate_step(centers, want_mind=False)
                 fused_iters += 1
+                event_iters += 1 if eng.last_events_form()[0] else 0   # (a stored value of the call just queued: no synchronisation)
                 if Y is None and not csc_released and fused_iters == 1:
                     # the first fused call has built the library's record layout and screen copy: the CSC value / row
                     # arrays of the device-built shard can go (spkm_shard_release_csc; an entry point that needs them
@@ -670,6 +675,8 @@ def kmeans_sparsified(X, K, **options):
         # (not reference fields) how many iterations went through the fused call, and which path the library took for
         # the last of them: 1 = certified screen + exact confirmation, 0 = all-exact kernels
         OUTPUT.setdefault("fusedIterations", np.zeros(Replicates, int))[trial] = fused_iters
+        # ... and how many of them moved their sums by events instead of a full accumulation pass
+        OUTPUT.setdefault("eventIterations", np.zeros(Replicates, int))[trial] = event_iters
         # ... and how many points their screens evaluated in all: fusedIterations x n unless carried bounds settled some
         OUTPUT.setdefault("screenedPoints", np.zeros(Replicates, np.int64))[trial] = eng.last_screen_points()[1] - screened0
         OUTPUT.setdefault("lastPath", np.zeros(Replicates, int))[trial] = last_path
