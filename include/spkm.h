@@ -222,6 +222,23 @@ int spkm_shard_set_far_bounds(spkm_shard *s, int on);
  * SPKM_FAR_EVENTS=1 opts every shard of a context in (read with the other switches); SPKM_NO_INCREMENTAL=1 and
  * SPKM_NO_DIRECT_EVENTS=1 act as on the 4-lanes-per-point screen. */
 int spkm_shard_set_far_events(spkm_shard *s, int on);
+/* Ragged shards on the far screen (on != 0; default off).  A RAGGED shard -- columns of different lengths, empty ones among
+ * them: a sample whose exact zeros were dropped, as MATLAB's sparse() drops them -- is turned away by every other screen and
+ * runs the all-exact kernels; past the last p with an exact LDS tile ((p + 1) * 128 + 16 bytes: p = 1278 with 160 KB) that
+ * is the generic one.  A ragged shard that opted in to the far screen (spkm_shard_set_far_screen) AND opts in here takes
+ * the far screen there, in a form of the kernel that reads each point's column bounds from jc: the same estimates, the same
+ * certificate -- with the shard's longest column where it takes a column length, which bounds every shorter one -- and the
+ * same exact list behind it.  An empty column is at distance 0 from every centre and goes to centroid 0, as MATLAB's min
+ * returns index 1: the screen certifies it without a load and never lists it.  Carried bounds (spkm_shard_set_far_bounds)
+ * and incremental sums (spkm_shard_set_far_events) work on such a shard as on a fixed-stride one, and spkm_last_screen_tile,
+ * spkm_last_path_info, spkm_last_screen_mode and spkm_last_screen_points report its calls in the same way.  K >= 2, 48
+ * entries of slack behind ir / x, the caps of the far screen.  Every output is what the all-exact kernels give.  Opting in
+ * measures the shard's longest column once (a shard of device arrays: one small reduction over jc and one read-back, here;
+ * a shard that comes in by the context's switch alone pays it in its first far call).  On a fixed-stride shard, and on a
+ * ragged one that an exact tile serves, the setting changes nothing.  Turning it on or off forgets the shard's policy
+ * state, like spkm_shard_reset_policy.  SPKM_FAR_RAGGED=1 opts every shard of a context in (read with the other switches:
+ * spkm_ctx_reload_switches); the far screen's own opt-in is still needed. */
+int spkm_shard_set_far_ragged(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by

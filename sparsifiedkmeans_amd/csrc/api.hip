@@ -40,6 +40,7 @@ static spkm_switches read_switches()
     w.far_screen = on("SPKM_FAR_SCREEN");
     w.far_bounds = on("SPKM_FAR_BOUNDS");
     w.far_events = on("SPKM_FAR_EVENTS");
+    w.far_ragged = on("SPKM_FAR_RAGGED");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
@@ -220,6 +221,12 @@ extern "C" int spkm_shard_create_host(spkm_ctx* ctx, uint64_t p, uint64_t n, con
         for (uint64_t i = 0; fixed && i <= n; i++) fixed = (jc[i] == i * st);
         if (fixed) s->fixed_s = (int)st;
     }
+    { // the longest column (host arrays: known here; fixed stride: fixed_s)
+        uint64_t mx = 0;
+        for (uint64_t i = 0; i < n; i++) mx = std::max(mx, jc[i + 1] - jc[i]);
+        s->max_s = (int)std::min<uint64_t>(mx, 0x7fffffffull);
+        s->max_s_known = true;
+    }
     const size_t irb = (size_t)s->ir_bits / 8;
     // +48 entries of slack so that the batch loads of the fixed-stride kernels never leave the allocation
     hipError_t e = hipMalloc((void**)&s->jc, (n + 1) * sizeof(long long));
@@ -288,6 +295,7 @@ extern "C" int spkm_shard_create_dev(spkm_ctx* ctx, uint64_t p, uint64_t n, uint
         if (e != hipSuccess) { delete s; return (int)e; }
         if (flag) s->fixed_s = (int)(nnz / n);
     }
+    if (s->fixed_s > 0) { s->max_s = s->fixed_s; s->max_s_known = true; } // (ragged: ensure_max_s, when it is first needed)
     *out = s;
     return SPKM_OK;
 }
@@ -387,6 +395,54 @@ extern "C" int spkm_shard_set_far_events(spkm_shard* s, int on)
     if (!s) return SPKM_ERR_NULL_ARG;
     s->far_events = on != 0;
     return spkm_shard_reset_policy(s); // (the policy state, the bounds and the kept sums are forgotten with the rest)
+}
+
+// max over the columns of jc[i + 1] - jc[i] (atomicMax on one word: a launch per shard, once)
+__global__ void k_max_column(const long long* __restrict__ jc, long long n, int* __restrict__ out)
+{
+    long long mx = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        mx = max(mx, jc[i + 1] - jc[i]);
+    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
+    if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(out, (int)min(mx, 0x7fffffffLL));
+}
+
+// The shard's longest column, spkm_shard.max_s: known from the start for a fixed-stride shard and for host arrays; for a
+// ragged shard of device arrays one reduction over jc and ONE read-back, the first time it is asked for -- when the shard
+// opts in to the ragged far screen or in its first ragged far call -- and never again.
+int ensure_max_s(spkm_ctx* ctx, spkm_shard* s)
+{
+    if (s->max_s_known) return SPKM_OK;
+    if (s->fixed_s > 0 || s->n == 0) {
+        s->max_s = s->fixed_s;
+        s->max_s_known = true;
+        return SPKM_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = ensure(ctx, ctx->tmp_assign, 64);
+    if (rc) return rc;
+    int mx = 0;
+    HIP_TRY(hipMemsetAsync(ctx->tmp_assign.p, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(k_max_column, dim3((unsigned)std::min<uint64_t>((s->n + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                       (const long long*)s->jc, (long long)s->n, (int*)ctx->tmp_assign.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&mx, ctx->tmp_assign.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    s->max_s = mx;
+    s->max_s_known = true;
+    return SPKM_OK;
+}
+
+extern "C" int spkm_shard_set_far_ragged(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->far_ragged = on != 0;
+    if (s->far_ragged && s->ctx) {
+        spkm_ctx* ctx = s->ctx;
+        const int rc = ensure_max_s(ctx, s); // (here, so that no fused call waits for it)
+        if (rc) return rc;
+    }
+    return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
 }
 
 extern "C" int spkm_shard_order_info(const spkm_shard* s, int64_t info[2])

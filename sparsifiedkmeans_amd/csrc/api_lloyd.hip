@@ -53,6 +53,7 @@ extern "C" int spkm_shard_create_rec_dev(spkm_ctx* ctx, uint64_t p, uint64_t n, 
     spkm_shard* s = new spkm_shard();
     s->ctx = ctx; s->p = p; s->n = n; s->nnz = n * s_entries; s->ir_bits = ir_bits;
     s->fixed_s = (int)s_entries;
+    s->max_s = s->fixed_s; s->max_s_known = true;
     s->rec = (char*)d_rec; s->rec_R = (int)spkm_record_bytes(s_entries, ir_bits); s->rec_owned = false; s->rec_tried = true;
     s->slack = 48;            // (what ensure_csc gives the arrays it re-materialises)
     s->csc_released = true;

@@ -26,8 +26,12 @@ static int screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
 }
 // ... and where that is 0 for want of LDS, the plane width of the far screen (policy.h, spkm_far_screen): 64, 128, 256
 // centroids for a shard or a context that opted in (spkm_shard_set_far_screen, SPKM_FAR_SCREEN=1); 0: the all-exact kernels.
+// A RAGGED shard asks the ragged policy (spkm_far_screen_ragged: both opt-ins, and no exact LDS tile either).
 static int far_screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
 {
+    if (s->fixed_s <= 0)
+        return spkm_far_screen_ragged((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
+                                      s->far || ctx->sw.far_screen, s->far_ragged || ctx->sw.far_ragged);
     return spkm_far_screen((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
                            s->wide || ctx->sw.wide_screen, s->far || ctx->sw.far_screen);
 }
@@ -95,6 +99,9 @@ struct screen_call : spkm_call_in {
         zj.n = 0;
     }
     int* cl(int row) const { return pl.cl_on ? sm->cl_flags + (size_t)row * K : nullptr; } // row: CL_* (layout.h)
+    // the column length the certificate and the support-aware drift take: the stride, or a ragged far shard's longest column
+    int col_s() const { return sm->fixed_s > 0 ? sm->fixed_s : sm->max_s; }
+    bool ragged() const { return sm->fixed_s <= 0; } // (only the far screen takes such a shard)
     // Buffers: the screen's inputs and scratch, the shard's carried bounds and cluster cache; a regrouping asked for.
     template <typename IR> int buffers()
     {
@@ -255,7 +262,7 @@ struct screen_call : spkm_call_in {
             zero_later(sm->hb + hb_dmax(npad, K), 4);
             zero_flush();
             hipLaunchKernelGGL(k_center_drift, dim3(K), dim3(256), 0, ctx->stream, (const double*)sm->hb_centers, C, K, p,
-                               gamma, sm->hb + hb_delta(npad), same, ctx->sw.no_support_drift ? 0 : sm->fixed_s,
+                               gamma, sm->hb + hb_delta(npad), same, ctx->sw.no_support_drift ? 0 : col_s(),
                                2.0f * (float)sm->fixed_s / (float)p, quad ? sm->hb + hb_hterm(npad) : (float*)nullptr);
             int rc;
             if ((rc = ensure(ctx, ctx->todo, pl.pt_mode ? (size_t)(npad + 64) * 4 : (size_t)(npad / 16 + 1) * 4))) return rc;
@@ -383,6 +390,11 @@ struct screen_call : spkm_call_in {
         const void* kern = flist ? (npl == 1 ? (const void*)k_screen_far<IR, 1, true>
                                              : (npl == 2 ? (const void*)k_screen_far<IR, 2, true> : (const void*)k_screen_far<IR, 4, true>))
                                  : (npl == 1 ? (const void*)k_screen_far<IR, 1> : (npl == 2 ? (const void*)k_screen_far<IR, 2> : (const void*)k_screen_far<IR, 4>));
+        if (ragged()) // (columns [jc[pt], jc[pt + 1]): the RAGGED forms, which read jc and not the stride)
+            kern = flist ? (npl == 1 ? (const void*)k_screen_far<IR, 1, true, true>
+                                     : (npl == 2 ? (const void*)k_screen_far<IR, 2, true, true> : (const void*)k_screen_far<IR, 4, true, true>))
+                         : (npl == 1 ? (const void*)k_screen_far<IR, 1, false, true>
+                                     : (npl == 2 ? (const void*)k_screen_far<IR, 2, false, true> : (const void*)k_screen_far<IR, 4, false, true>));
         HIP_TRY(timing_begin(ctx));
         const IR* a_ir = (const IR*)sm->ir;
         const float* a_xf = (const float*)sm->xf;
@@ -392,7 +404,8 @@ struct screen_call : spkm_call_in {
         int* a_k = (int*)ctx->scr_k.p;
         const int* a_todo = flist ? (const int*)ctx->todo.p : (const int*)nullptr;
         const unsigned* a_cnt = (const unsigned*)ctx->nlist.p;
-        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt};
+        const long long* a_jc = (const long long*)sm->jc;
+        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
         // (4 waves per workgroup, a wave per point; 32 workgroups per CU and plane at most: the waves stride over the points --
         //  the LIST form over the slots of a list whose length only the device knows: the same grid, and the waves past its
         //  end return at once)
@@ -467,9 +480,14 @@ struct screen_call : spkm_call_in {
         const bool timed = ctx->tlog_on && ctx->tlog_both;
         if (pl.direct) {
             if (timed) HIP_TRY(timing_begin(ctx));
-            hipLaunchKernelGGL((k_events_direct<IR>), dim3(1024), dim3(256), 0, ctx->stream, (const char*)nullptr, 0,
-                               (const IR*)sm->ir, (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k, ev_n, p,
-                               sm->fixed_s, K, cache_s, cache_c, (const int*)nullptr);
+            if (ragged())
+                hipLaunchKernelGGL((k_events_direct<IR, true>), dim3(1024), dim3(256), 0, ctx->stream, (const char*)nullptr, 0,
+                                   (const IR*)sm->ir, (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k, ev_n, p,
+                                   0, K, cache_s, cache_c, (const int*)nullptr, (const long long*)sm->jc);
+            else
+                hipLaunchKernelGGL((k_events_direct<IR>), dim3(1024), dim3(256), 0, ctx->stream, (const char*)nullptr, 0,
+                                   (const IR*)sm->ir, (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k, ev_n, p,
+                                   sm->fixed_s, K, cache_s, cache_c, (const int*)nullptr);
         } else {
             const int seg_ev = pl.seg_ev;
             const int max_items_ev = (int)((2 * n) / seg_ev) + K2 + 1;
@@ -489,16 +507,22 @@ struct screen_call : spkm_call_in {
             launch_scatter(ctx, hb_, sc_lds_ev, (const int*)sm->ev_k, 0, K2, (const unsigned*)nullptr, (const int*)nullptr, ev_n,
                            (const int*)sm->ev_pt);
             const size_t slab = (size_t)ap.R * spkm_acc_row_bytes;
-            const void* kern = (const void*)k_accumulate_events_sliced<IR>;
+            const void* kern = ragged() ? (const void*)k_accumulate_events_sliced<IR, true> : (const void*)k_accumulate_events_sliced<IR>;
             HIP_TRY(allow_lds(ctx, kern, slab));
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_max / std::max<size_t>(slab, 1)));
             const long long units = (long long)max_items_ev * ap.slices;
             const int ab = (int)std::max<long long>(1, std::min<long long>(units, (long long)std::max(1, ctx->num_cus) * per_cu));
             if (timed) HIP_TRY(timing_begin(ctx));
-            hipLaunchKernelGGL((k_accumulate_events_sliced<IR>), dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream, (const IR*)sm->ir,
-                               (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
-                               (const int4*)ctx->items.p, (const int*)ctx->nitems.p + NI_FULL, p, sm->fixed_s, K, ap.R, ap.slices,
-                               cache_s, cache_c);
+            if (ragged())
+                hipLaunchKernelGGL((k_accumulate_events_sliced<IR, true>), dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream,
+                                   (const IR*)sm->ir, (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
+                                   (const int4*)ctx->items.p, (const int*)ctx->nitems.p + NI_FULL, p, 0, K, ap.R, ap.slices,
+                                   cache_s, cache_c, (const long long*)sm->jc);
+            else
+                hipLaunchKernelGGL((k_accumulate_events_sliced<IR>), dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream, (const IR*)sm->ir,
+                                   (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
+                                   (const int4*)ctx->items.p, (const int*)ctx->nitems.p + NI_FULL, p, sm->fixed_s, K, ap.R, ap.slices,
+                                   cache_s, cache_c);
         }
         HIP_TRY(hipGetLastError());
         if (timed) HIP_TRY(timing_end(ctx));
@@ -523,7 +547,7 @@ struct screen_call : spkm_call_in {
         hipLaunchKernelGGL(pl.pt_mode ? k_combine_screen<1> : k_combine_screen<4>, dim3(cb), dim3(256),
                            ((pl.nk_incr ? (size_t)K : 0) + (pl.ev_path ? (size_t)2 * K : 0)) * 4,
                            ctx->stream, (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, pl.Gs,
-                           (const float*)sm->xnr, sm->fixed_s, (const unsigned long long*)ctx->cmax.p, (int*)assign,
+                           (const float*)sm->xnr, col_s(), (const unsigned long long*)ctx->cmax.p, (int*)assign,
                            (int*)ctx->list.p, (unsigned int*)ctx->nlist.p, carry ? sm->hb : (float*)nullptr, pl.npad,
                            pl.skip_enabled ? 1 : 0, (const int*)ctx->todo.p,
                            carry ? (const double*)(sm->hb_cum + sm->cum_par) : (const double*)nullptr, pl.bounds_ok ? 1 : 0,
@@ -793,7 +817,7 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     screen_call c;
     c.kt = kt;
     c.ctx = ctx; c.sm = const_cast<spkm_shard*>(s); c.C = d_centers; c.gamma = gamma; c.assign = d_assign; c.mind = d_mind;
-    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = s->fixed_s; c.quad = spkm_screen_quad(kt, s->fixed_s);
+    c.n = (long long)s->n; c.p = (int)s->p; c.K = K; c.fixed_s = c.max_s = s->fixed_s; c.quad = spkm_screen_quad(kt, s->fixed_s);
     c.carry_bounds = !c.quad && (s->wide_bounds || ctx->sw.wide_bounds); c.carry = c.quad || c.carry_bounds;
     c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
     c.zj.n = 0;
@@ -844,8 +868,12 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     c.far_events = c.carry && (s->far_events || ctx->sw.far_events); // (incremental sums: only on a shard that carries bounds)
     c.lds_max = ctx->lds_max; c.num_cus = ctx->num_cus; c.pk = (size_t)c.p * K; c.sums = d_reduce; c.counts = d_reduce + c.pk;
     c.zj.n = 0;
-    spkm_plan_tiles(c.pl, c, kp);
     int rc;
+    // (a ragged shard's longest column: known since the opt-in; a shard that came in by the context's switch alone pays one
+    //  read-back here, in its first far call)
+    if ((rc = ensure_max_s(ctx, c.sm))) return rc;
+    c.max_s = c.sm->max_s;
+    spkm_plan_tiles(c.pl, c, kp);
     if ((rc = c.buffers<IR>())) return rc;
     c.plan_input(0, false);
     spkm_plan_call(c.pl, c, c.sm->pol);

@@ -333,6 +333,33 @@ inline int spkm_far_screen(long long p, int K, int fixed_s, unsigned long long s
     if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (the cluster sizes behind it: k_hist counts in LDS)
     return kp;
 }
+// ... and for a RAGGED shard (fixed_s <= 0: columns of different lengths -- a sample with exact zeros dropped, as sparse()
+// drops them), which spkm_screen_width and spkm_far_screen both turn away: the RAGGED form of k_screen_far, point pt owning
+// entries [jc[pt], jc[pt + 1]).  Returns KP, or 0: a fixed-stride shard (spkm_far_screen answers for it); not opted in to the
+// far screen (far) or to its ragged form (far_ragged: the shard, spkm_shard_set_far_ragged, or the context,
+// SPKM_FAR_RAGGED=1); SPKM_NO_SCREEN; K < 2, an empty shard, less than 48 entries of slack (the contract of every screen);
+// a p that an exact LDS tile serves -- pick_kt's narrowest, 16 centroids of f64: (p + 1) 16 8 + 16 <= lds_max, p <= 1278 with
+// 160 KB -- where a ragged shard stays on k_assign_tile: only past it do the all-exact kernels mean k_assign_generic, the
+// kernel this form replaces; the plane, table and cluster-size caps of spkm_far_screen.
+constexpr int spkm_exact_kt_min = 16;
+inline bool spkm_exact_tile_fits(long long p, size_t lds_max)
+{
+    return (unsigned long long)(p + 1) * (unsigned)spkm_exact_kt_min * 8ull + 16ull <= (unsigned long long)lds_max;
+}
+inline int spkm_far_screen_ragged(long long p, int K, int fixed_s, unsigned long long slack, unsigned long long nnz, size_t lds_max,
+                                  int num_cus, bool no_screen, bool far, bool far_ragged)
+{
+    if (!far || !far_ragged || no_screen) return 0;
+    if (fixed_s > 0 || slack < 48 || nnz == 0 || K < 2) return 0;
+    if (spkm_exact_tile_fits(p, lds_max)) return 0;
+    const int nb = num_cus > 0 ? num_cus : 256;
+    const int kp = spkm_far_plane(K);
+    const int G = spkm_far_planes(K, kp);
+    if (G > nb) return 0;
+    if ((unsigned long long)G * (unsigned long long)(p + 1) * (unsigned)kp * 4ull > spkm_far_table_max) return 0;
+    if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (k_hist, as above)
+    return kp;
+}
 // Which kernel spkm_accumulate_dev runs (update.hip), from the rows, the device's LDS and the opt-in alone -- the form that
 // spkm_last_assign_tile reports in info[4]:
 //  1  k_accumulate_sorted: a cluster's sums and counts, 12 B per row, in one LDS slab of at most 64 KB (p <= 5461) --
@@ -468,6 +495,10 @@ struct spkm_call_in {
     long long sp_blocks = 0;
     bool same_assign = false, assign_synced = false, sort_kept = false, sort_reusable = false;
     int prune_a = 0; bool want_hint = false; // the caller's choice (spkm_policy::next)
+    // the shard's LONGEST column: fixed_s on a fixed-stride shard; on a ragged one (fixed_s = 0: the RAGGED far screen,
+    // spkm_far_screen_ragged) the length a plan takes wherever it needs one.  (In the padding behind want_hint: the input
+    // keeps its size and the offsets tests/test_policy.py mirrors.)
+    int max_s = 0;
 };
 struct spkm_call_plan {
     // tiles of G x 32 centroids (G x 16 / G x 8: the narrow tiles of k_screen_wide, pl_last 4); pl_last = centroid pairs per lane of the last one (1, 2, 4; 5: its <= 4 centroids ride on
@@ -496,7 +527,7 @@ inline void spkm_plan_tiles(spkm_call_plan& pl, const spkm_call_in& in, int kt =
     pl.pl_last = !in.quad ? 4 : (k_last <= 8 ? 1 : (k_last <= 16 ? 2 : 4));
     if (in.quad && pl.G >= 2 && k_last <= 4 && (size_t)(in.p + 1) * (spkm_plan_kt * 4 + 16) + 16 <= in.lds_max) pl.pl_last = 5;
     pl.Gs = pl.pl_last == 5 ? pl.G - 1 : pl.G;
-    pl.nr = (in.fixed_s + 3) / 4;
+    pl.nr = ((in.fixed_s > 0 ? in.fixed_s : in.max_s) + 3) / 4; // (a ragged shard: by its longest column)
     pl.npad = (in.n + 63) / 64 * 64;
 }
 // Everything decided before the screen launches, every device resource assumed granted (after spkm_plan_tiles).
@@ -576,6 +607,8 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
             // rounded up, k_assign_list the exact value.  run_far never reaches spkm_plan_sums, so lazy_ub is set here.
             // (ii) No refresh schedule: an eroded bound only loosens, until the point fails the test; the next screen then
             // gives it a fresh one -- the looseness of a bound costs a screened point, never a wrong answer, and mends itself.
+            // A RAGGED far shard (fixed_s = 0, spkm_far_screen_ragged) takes this branch and the events below as they are:
+            // nothing here depends on the stride (the point-mode test reads bounds, the events name points).
             pl.erode = pl.drift;
             pl.lazy_ub = true;
             // INCREMENTAL SUMS at these widths (spkm_shard_set_far_events; a plan made without the flag is the plan above in

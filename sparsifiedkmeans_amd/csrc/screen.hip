@@ -547,8 +547,9 @@ __global__ __launch_bounds__(1024) void k_screen_tile(
 // the full 2-norm for a difference spread over p = 1024 rows at s = 51, and far below it once a centroid only moves in
 // a few coordinates.  Exact selection: the s-th largest square is found by a radix search over the high 32 bits of the
 // (non-negative) doubles, entries above it are added up, the rest of the s slots are charged the upper end of its
-// bucket -- an upper bound that is tight to 2^-20.  top_s <= 0 or >= p (ragged shards, SPKM_NO_SUPPORT_DRIFT): the
-// full 2-norm, as before.
+// bucket -- an upper bound that is tight to 2^-20.  top_s <= 0 or >= p (SPKM_NO_SUPPORT_DRIFT; a ragged shard off the far
+// screen): the full 2-norm, as before.  A ragged shard on the far screen passes its LONGEST column (spkm_shard.max_s): a
+// support of fewer rows is a subset of some set of max_s rows, and the sum of the max_s largest squares bounds it as well.
 // The reference divides each entry by gamma in f64 first: 2^-50 (|c| + |c'|)/gamma covers those roundings.
 // hterm[k] = hint_w x (full 2-norm drift)^2: the screen's hints estimate sqrt(ub^2 + hterm) (k_bounds_steps) -- an
 // estimate of the typical support, not a bound, hence the full norm scaled by s / p.
@@ -1267,6 +1268,9 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     const double cmax = __builtin_bit_cast(double, *cmax_bits);
     const double u = 0x1p-24;
     const double eu = (2.0 * u + u * u) * (1.0 + 1e-9);
+    // (fixed_s: the column length s of the header's proof.  A RAGGED far shard passes its LONGEST column: s enters the
+    //  certificate in these two terms only -- the accumulation error (s + 1) u of s FMAs and sqrt(s) max|c|, the bound of the
+    //  centroid's norm on the support -- and both grow with s, so the bound of the longest column holds for every shorter one)
     const double gacc = (double)(fixed_s + 1) * u * (1.0 + 1e-4);
     const double sqrt_s = sqrt((double)fixed_s) * (1.0 + 1e-15);
     const double nu = 0x1p-45;

@@ -807,7 +807,10 @@ __global__ __launch_bounds__(256) void k_accumulate_events(const char* __restric
 // within a wave are as rare as in k_accumulate_sliced (s entries over p rows).
 // 41 VGPRs, 82 SGPRs, no scratch, no static LDS (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, both index widths):
 // the register file would hold 8 waves per SIMD, the slab allows 4.
-template <typename IR>
+// RAGGED (a ragged far shard, spkm_shard_set_far_ragged; an instantiation of its own, the fixed-stride one is the code it
+// was): point i's column is [jc[i], jc[i + 1]) -- the four columns of a step have their own lengths, the step runs to the
+// longest of them, and s is not read.
+template <typename IR, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void k_accumulate_events_sliced(const IR* __restrict__ ir,
                                                                    const double* __restrict__ x,
                                                                    const int* __restrict__ perm,
@@ -815,7 +818,8 @@ __global__ __launch_bounds__(1024) void k_accumulate_events_sliced(const IR* __r
                                                                    const int4* __restrict__ items,
                                                                    const int* __restrict__ nitems, int p, int s, int K,
                                                                    int R, int nslices, double* __restrict__ sums,
-                                                                   double* __restrict__ counts)
+                                                                   double* __restrict__ counts,
+                                                                   const long long* __restrict__ jc = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* ssum = reinterpret_cast<double*>(smem);
@@ -845,10 +849,17 @@ __global__ __launch_bounds__(1024) void k_accumulate_events_sliced(const IR* __r
 #pragma unroll
                 for (int v = 0; v < 4; v++) {
                     const int src = (u + v < have) ? u + v : u; // clamp: duplicates are masked by cn = 0
-                    j0[v] = (long long)(unsigned)__builtin_amdgcn_readlane(my_i, src) * s;
-                    cn[v] = (u + v < have) ? s : 0;
+                    if constexpr (RAGGED) {
+                        const long long pt = (long long)(unsigned)__builtin_amdgcn_readlane(my_i, src);
+                        j0[v] = jc[pt];
+                        cn[v] = (u + v < have) ? (int)(jc[pt + 1] - j0[v]) : 0;
+                    } else {
+                        j0[v] = (long long)(unsigned)__builtin_amdgcn_readlane(my_i, src) * s;
+                        cn[v] = (u + v < have) ? s : 0;
+                    }
                 }
-                for (int off = lane; off - lane < s; off += 64) {
+                const int smax = RAGGED ? max(max(cn[0], cn[1]), max(cn[2], cn[3])) : s;
+                for (int off = lane; off - lane < smax; off += 64) {
                     double xv[4];
                     unsigned rv[4];
 #pragma unroll
@@ -954,12 +965,15 @@ __global__ __launch_bounds__(256) void k_pair_scatter(const int* __restrict__ pt
 // entries to (key < K) or takes them out of (key >= K) its cluster's rows of the table, one f64 atomic per entry and
 // table.  Three launches (plan, placement, k_accumulate_events: 27 us of latency for 200 events) become one of 6 us.
 // The events are read where k_combine_screen / k_assign_list appended them; their number is read on the device.
-template <typename IR>
+// RAGGED (a ragged far shard, spkm_shard_set_far_ragged; an instantiation of its own): the event's point i owns entries
+// [jc[i], jc[i + 1]) of ir / x; no records, s is not read.
+template <typename IR, bool RAGGED = false>
 __global__ __launch_bounds__(256) void k_events_direct(const char* __restrict__ rec, int R, const IR* __restrict__ ir,
                                                        const double* __restrict__ x, const int* __restrict__ ev_pt,
                                                        const int* __restrict__ ev_k, const unsigned* __restrict__ n_ev,
                                                        int p, int s, int K, double* __restrict__ sums,
-                                                       double* __restrict__ counts, const int* __restrict__ ev_o = nullptr)
+                                                       double* __restrict__ counts, const int* __restrict__ ev_o = nullptr,
+                                                       const long long* __restrict__ jc = nullptr)
 {
     // ev_o != nullptr: pair events (one per mover: into cluster ev_k, out of cluster ev_o unless that is -1)
     const int lane = threadIdx.x & 63;
@@ -972,6 +986,16 @@ __global__ __launch_bounds__(256) void k_events_direct(const char* __restrict__ 
         const int k = (ev_o == nullptr && key >= K) ? key - K : key;
         const double sign = (ev_o == nullptr && key >= K) ? -1.0 : 1.0;
         const int kold = ev_o != nullptr ? ev_o[e] : -1;
+        if constexpr (RAGGED) {
+            const long long j0 = jc[i], j1 = jc[i + 1];
+            for (long long j = j0 + lane; j < j1; j += 64) {
+                const double xe = x[j];
+                const int re = (int)ir[j];
+                unsafeAtomicAdd(&sums[(size_t)k * p + re], sign * xe);
+                unsafeAtomicAdd(&counts[(size_t)k * p + re], sign);
+            }
+            continue; // (two events per mover: no pair form on a far shard)
+        }
         for (int j = lane; j < s; j += 64) {
             double xe;
             int re;

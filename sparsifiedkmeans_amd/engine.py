@@ -128,6 +128,15 @@ class Shard:
         call did.  The shard's policy state, bounds and kept sums are forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_far_events(self.handle, 1 if on else 0), "spkm_shard_set_far_events")
 
+    def set_far_ragged(self, on: bool = True):
+        """Let this shard, when it is RAGGED (columns of different lengths: a sample whose exact zeros were dropped) and
+        opted in with set_far_screen(), take the far screen past the last p with an exact LDS tile (p > 1278 with 160 KB)
+        instead of the generic all-exact kernel, by the form of the far kernel that reads each point's column bounds
+        (spkm_shard_set_far_ragged; off by default at the C interface).  set_far_bounds() and set_far_events() apply to it
+        as to a fixed-stride shard; an empty column goes to centroid 0 at distance 0 and is never listed.  Outputs never
+        depend on it; the shard's policy state is forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_far_ragged(self.handle, 1 if on else 0), "spkm_shard_set_far_ragged")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""

@@ -66,6 +66,11 @@ _DEFAULTS = dict(
 # farEvents: on the far screen with carried bounds, a lazy iteration whose predecessor counted few movers moves the kept
 # per-cluster sums by the movers' events instead of accumulating over every point (Shard.set_far_events: every shape of
 # profiles/far_events_ab.txt gains; OUTPUT["eventIterations"] counts such iterations); False: every call accumulates over all.
+# farRagged: a RAGGED shard -- the sample held exact zeros, which are dropped as sparse() drops them: integer data under a
+# Hadamard or DCT mix, 'SketchType','none' on images, all-zero points -- takes the far screen too, past the last p2 with an
+# exact LDS tile (p2 > 1278 with 160 KB), instead of the generic all-exact kernel (Shard.set_far_ragged).  Off by default: the
+# decision shapes of profiles/far_ragged_ab.txt have not been measured yet (record runs at small N gain 3-6x), and the
+# default goes on only once every pair of every shape wins.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
 # seedTogether: the k-means++ starts of ALL replicates are drawn in one library call that shares each round's read of the
@@ -73,7 +78,7 @@ _DEFAULTS = dict(
 # than 'drop' (a drop shrinks K for the later replicates); False: replicate by replicate (_arthur).  Outputs never depend on
 # it: OUTPUT["seedPoints"] records the picks of either path.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
-              slicedSums=True, farBounds=True, farEvents=True, seedTogether=True)
+              slicedSums=True, farBounds=True, farEvents=True, farRagged=False, seedTogether=True)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -422,6 +427,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_wide_screen(bool(o["wideScreen"]))
     shard.set_wide_bounds(bool(o["wideBounds"]))
     shard.set_far_screen(bool(o["farScreen"]))
+    shard.set_far_ragged(bool(o["farRagged"]))
     shard.set_far_bounds(bool(o["farBounds"]))
     shard.set_far_events(bool(o["farEvents"]))
     shard.set_sliced_sums(bool(o["slicedSums"]))
