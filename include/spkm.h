@@ -405,6 +405,15 @@ int spkm_last_screen_tile(spkm_ctx *ctx, int64_t info[2]);
  * the length of the list for a call that skipped on its carried bounds (points; 16 per listed step for a step list), 0
  * when the call took no screen; info[1] = the running total over the context.  Blocks on the stream. */
 int spkm_last_screen_points(spkm_ctx *ctx, int64_t info[2]);
+/* The mover tile.  On the 4-lanes-per-point screen with 64 <= K <= 1024, a lazy call without distances whose carried-bounds
+ * test lists 16-point steps (no block summaries, the shard not regrouped) picks the 32 centroids that moved furthest since
+ * the previous call and tests every step a second time against the largest drift of the OTHERS: a step that fails the usual
+ * test only because of those 32 is screened against one tile that holds them and certified there, or sent on to the main
+ * launch of the same call.  No output changes.  out[0] = steps that passed the second test but not the first (counted on
+ * every such call, whether or not the form runs), out[1] = steps certified on the tile, out[2] = steps sent on; all 0 for a
+ * call that took no screen or is not of this kind.  SPKM_MOVER_TILE=1 turns the form on for a context, SPKM_NO_MOVER_TILE=1
+ * off (read with the other switches; DESIGN.md section 6.1 states the default).  Blocks on the stream. */
+int spkm_last_mover_steps(spkm_ctx *ctx, uint64_t out[3]);
 
 /* Unchanged-cluster shortcut of the fused call's exact pass.  A cluster (i) whose centroid is BITWISE the one the
  * previous fused call on this shard was given and (ii) that no point left or entered is not streamed again: every

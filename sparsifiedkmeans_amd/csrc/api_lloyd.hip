@@ -311,11 +311,12 @@ static int build_blockmap(spkm_ctx* ctx, int G)
 // c % NX) in the same order, so a chunk is fetched from HBM once and re-read from that XCD's L2.
 //   entry: tile, stream = index among the tile's workgroups on this XCD, nstreams = their number,
 //          pad = NX | xcd << 8 | pairs-per-lane << 16
-static int build_blockmap_quad(spkm_ctx* ctx, int G, int pl_last, int rounds)
+// mover: the second cached map, of the mover tile's launch (1 tile, pl 4: every workgroup its own team; policy.h, spkm_plan_movers)
+static int build_blockmap_quad(spkm_ctx* ctx, int G, int pl_last, int rounds, bool mover = false)
 {
-    devbuf& buf = ctx->bmapq;
-    int& slot_key = ctx->bmapq_key;
-    int& slot_blocks = ctx->bmapq_blocks;
+    devbuf& buf = mover ? ctx->bmapm : ctx->bmapq;
+    int& slot_key = mover ? ctx->bmapm_key : ctx->bmapq_key;
+    int& slot_blocks = mover ? ctx->bmapm_blocks : ctx->bmapq_blocks;
     const int NB = ctx->num_cus > 0 ? ctx->num_cus : 256;
     const int key = G * 64 + pl_last * 8 + 1000003 * rounds + (ctx->sw.no_teams ? 7 : 0);
     if (slot_key == key && slot_blocks == NB) return SPKM_OK;
@@ -934,6 +935,22 @@ extern "C" int spkm_last_screen_points(spkm_ctx* ctx, int64_t info[2])
         HIP_TRY(hipMemcpy(v, (const unsigned*)ctx->nlist.p + NL_SCREENED_TOTAL, sizeof(v), hipMemcpyDeviceToHost));
         info[1] = (int64_t)(((unsigned long long)v[1] << 32) | v[0]);
         info[0] = ctx->last.path == 1 ? (int64_t)v[2] : 0; // (the slot keeps the last SCREEN call's count)
+    }
+    return SPKM_OK;
+}
+
+// The mover tile in the last fused call: steps that passed test B but not test A (counted on every eligible call, form on or
+// off), steps certified on the tile, steps it sent on to the main list.  Blocks on the stream.
+extern "C" int spkm_last_mover_steps(spkm_ctx* ctx, uint64_t out[3])
+{
+    if (!ctx || !out) return SPKM_ERR_NULL_ARG;
+    out[0] = out[1] = out[2] = 0;
+    if (ctx->last.path == 1 && ctx->nlist.p) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        unsigned v[SPKM_REPORT_WORDS] = {0};
+        HIP_TRY(hipMemcpy(v, ctx->nlist.p, sizeof(v), hipMemcpyDeviceToHost));
+        out[0] = v[NL_MSTEPS]; out[1] = v[NL_MCERT]; out[2] = v[NL_MSENT];
     }
     return SPKM_OK;
 }

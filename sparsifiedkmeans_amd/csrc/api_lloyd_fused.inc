@@ -37,6 +37,8 @@ static int far_screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
 }
 
 
+static_assert(spkm_movers == SPKM_MOVERS && spkm_movers == SCREEN_KT && spkm_mover_kmin == SPKM_MOVER_KMIN && spkm_mover_kmax == SPKM_MOVER_KMAX &&
+              SPKM_MOVER_KMAX <= BOUNDS_KTAB, "the mover tile is one full screen tile; policy.h and layout.h agree on its limits");
 static_assert(spkm_plan_kt == SCREEN_KT && spkm_plan_span == BOUNDS_SPAN && spkm_plan_span_pt == BOUNDS_SPAN_PT &&
               spkm_plan_seg == SEG_POINTS, "policy.h sizes the kernels with these constants");
 
@@ -82,6 +84,7 @@ struct screen_call : spkm_call_in {
     double *mind, *sums, *counts; // sums | counts | nk | obj2: the caller's reduce buffer
     size_t pk;
     spkm_call_plan pl;
+    spkm_mover_plan mv;     // the mover tile (policy.h, spkm_plan_movers): decided after the plan, in run_screen
     spkm_screen_report rep; // what this call did, as its stages decide it (stored in the context when the call has gone through)
     spkm_zero_jobs zj;
     int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
@@ -126,7 +129,8 @@ struct screen_call : spkm_call_in {
         if (quad) rc = build_blockmap_quad(ctx, Gs, pl.pl_last, pl.nr);
         else rc = build_blockmap(ctx, pl.G);
         if (rc) return rc;
-        if ((rc = ensure(ctx, ctx->t32, (size_t)pl.G * (p + 1) * kt * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
+        // (one tile more than the plan's where the mover tile may follow: k_prep_tiles_f32 gathers it behind the others)
+        if ((rc = ensure(ctx, ctx->t32, (size_t)(pl.G + (quad ? 1 : 0)) * (p + 1) * kt * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
             (rc = ensure(ctx, ctx->scr_m1, (size_t)Gs * n * 4)) || (rc = ensure(ctx, ctx->scr_m2, (size_t)Gs * n * 4)) ||
             (rc = ensure(ctx, ctx->scr_k, (size_t)Gs * n * 4)) || (rc = ensure(ctx, ctx->list, (size_t)n * 4)))
             return rc;
@@ -148,6 +152,8 @@ struct screen_call : spkm_call_in {
         if (!sm->hb || sm->hb_npad != pl.npad) {
             HIP_TRY(regrow(sm->hb, hb_floats(pl.npad) * 4, &sm->hb_valid));
             sm->hb_npad = pl.npad;
+            // (the movers' ticket starts at 0 and k_center_drift's last workgroup leaves it there)
+            HIP_TRY(hipMemsetAsync(sm->hb + hb_mticket(pl.npad), 0, (size_t)(HB_TAIL - HB_MOVERS) * 4, ctx->stream));
         }
         if (sm->hb_centers_len < pk) {
             HIP_TRY(regrow(sm->hb_centers, pk * 8, &sm->hb_valid));
@@ -248,6 +254,14 @@ struct screen_call : spkm_call_in {
         }
         return SPKM_OK;
     }
+    // The mover tile's own resources, once the plan is made: its cached blockmap and the second list.
+    int mover_resources()
+    {
+        if (!mv.on) return SPKM_OK;
+        int rc;
+        if ((rc = build_blockmap_quad(ctx, mv.tiles, mv.pl, mv.nr, true))) return rc;
+        return ensure(ctx, ctx->todo_m, (size_t)mv.cap * 4);
+    }
     // The bounds test: the centroids' drift, then the steps (points) the bounds certify settled, the others listed, hints written.
     int bounds()
     {
@@ -263,7 +277,10 @@ struct screen_call : spkm_call_in {
             zero_flush();
             hipLaunchKernelGGL(k_center_drift, dim3(K), dim3(256), 0, ctx->stream, (const double*)sm->hb_centers, C, K, p,
                                gamma, sm->hb + hb_delta(npad), same, ctx->sw.no_support_drift ? 0 : col_s(),
-                               2.0f * (float)sm->fixed_s / (float)p, quad ? sm->hb + hb_hterm(npad) : (float*)nullptr);
+                               2.0f * (float)sm->fixed_s / (float)p, quad ? sm->hb + hb_hterm(npad) : (float*)nullptr,
+                               mv.eligible ? reinterpret_cast<unsigned*>(sm->hb + hb_mticket(npad)) : (unsigned*)nullptr,
+                               sm->hb + hb_mdr(npad), reinterpret_cast<int*>(sm->hb + hb_mlist(npad)),
+                               reinterpret_cast<int*>(sm->hb + hb_mslot(npad)));
             int rc;
             if ((rc = ensure(ctx, ctx->todo, pl.pt_mode ? (size_t)(npad + 64) * 4 : (size_t)(npad / 16 + 1) * 4))) return rc;
             // (its statistics leave per workgroup, bstat, and are added up by the call's last kernel: same-address atomics of
@@ -292,12 +309,14 @@ struct screen_call : spkm_call_in {
                 }
             }
             const long long blocks = std::min<long long>((npad + pl.span - 1) / pl.span, pl.bgrid);
-            hipLaunchKernelGGL(sm->map != nullptr ? k_bounds_steps<true> : k_bounds_steps<false>, dim3((unsigned)blocks), dim3(256), 0,
+            // (an eligible call tests every step against the non-movers' drift as well and counts; with the form on it lists)
+            hipLaunchKernelGGL(sm->map != nullptr ? k_bounds_steps<true> : (mv.eligible ? k_bounds_steps<false, true> : k_bounds_steps<false>),
+                               dim3((unsigned)blocks), dim3(256), 0,
                                ctx->stream, sm->hb, npad, n, K, pl.trusted ? (int*)nullptr : (int*)assign, (int*)ctx->todo.p,
                                (unsigned*)ctx->nlist.p, pl.hinted ? sm->hintu : (float*)nullptr, pl.skip_enabled ? 1 : 0,
                                pl.pt_mode ? 1 : 0, (const double*)(sm->hb_cum + sm->cum_par), sm->hb_cum + (sm->cum_par ^ 1),
                                (int)pl.span, (unsigned*)ctx->bstat.p, pl.erode ? 1 : 0, sp_slack, sp_mask, sp_valid, pl.sp_reset ? 1 : 0,
-                               (const int*)same, (const int*)sm->map);
+                               (const int*)same, (const int*)sm->map, mv.on ? (int*)ctx->todo_m.p : (int*)nullptr);
             bstat_n = (int)blocks;
             if (pl.skip_enabled) sm->cum_par ^= 1; // the drift has been added
         }
@@ -317,7 +336,8 @@ struct screen_call : spkm_call_in {
             hipLaunchKernelGGL(k_prep_tiles_f32, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
                                0, ctx->stream, C, p, K, pl.G, gamma, (float*)ctx->t32.p,
                                (unsigned long long*)ctx->cmax.p, pl.pl_last, quad ? 1 : 0, (double*)ctx->ct.p,
-                               carry ? sm->hb_centers : (double*)nullptr);
+                               carry ? sm->hb_centers : (double*)nullptr,
+                               mv.on ? reinterpret_cast<const int*>(sm->hb + hb_mlist(pl.npad)) : (const int*)nullptr);
         else
             hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
                                0, ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p,
@@ -356,8 +376,29 @@ struct screen_call : spkm_call_in {
         const char* a_rec = (pl.pt_mode && sm->rec) ? sm->rec : (const char*)nullptr;
         int a_recR = sm->rec_R, a_tp = pl.pt_mode ? 1 : 0;
         const int* a_recmap = sm->map;
+        int a_slot = NL_TODO; // (k_screen_quad only: the counter that holds its list's length)
         void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_extra,
-                        &a_hint, &a_hc, &a_cnt, &a_todo, &a_tp, &a_rec, &a_recR, &a_recmap};
+                        &a_hint, &a_hc, &a_cnt, &a_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &a_slot};
+        if (mv.on) {
+            // The mover tile: the call's own instantiation over todo_m[] against the ONE tile behind the plan's (slot kk =
+            // centroid mlist[kk]: K = SPKM_MOVERS for the kernel), results into plane 0 -- the main launch runs afterwards and
+            // rewrites the entries of its own steps only.  Then k_certify_movers settles those steps or sends them on to todo[].
+            // An empty list: both return at once, the screen before its tile load.
+            const float* m_t = a_t + (size_t)pl.G * (p + 1) * SCREEN_KT;
+            const spkm_blockmap* m_bm = (const spkm_blockmap*)ctx->bmapm.p;
+            const int* m_todo = (const int*)ctx->todo_m.p;
+            int m_K = SPKM_MOVERS, m_extra = 0, m_slot = NL_TODO_M;
+            void* margs[] = {&a_ir, &a_xf, &m_t, &a_p, &a_n, &a_s, &m_K, &m_bm, &a_chunk, &a_m1, &a_m2, &a_k, &m_extra,
+                             &a_hint, &a_hc, &a_cnt, &m_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &m_slot};
+            HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmapm_blocks), dim3(1024), margs, lds, ctx->stream));
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_certify_movers, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
+                               (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, (const float*)sm->xnr,
+                               col_s(), (const unsigned long long*)ctx->cmax.p, sm->hb, pl.npad, K, m_todo, (int*)ctx->todo.p,
+                               (unsigned*)ctx->nlist.p, (const double*)(sm->hb_cum + (sm->cum_par ^ 1)), (const double*)(sm->hb_cum + sm->cum_par));
+            HIP_TRY(hipGetLastError());
+        }
+        rep.movers = mv.on;
         // (k_screen_wide: the first twelve, then the list and the counters)
         void* args_w[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt};
         const bool wide_args = !quad && (wlist || kt != SCREEN_KT);
@@ -792,7 +833,7 @@ struct screen_call : spkm_call_in {
                            ev ? (const double*)(sm->cl_cache + cc_counts(pk)) : (const double*)nullptr, ev ? pk : (size_t)0,
                            ev ? sums : (double*)nullptr, ev ? counts : (double*)nullptr,
                            sm->nlist_pending ? (unsigned*)nullptr : sm->h_nlist_dev, sm->nlist_seq + 1u,
-                           work_steps, work_tiles, pl.nr, rep.rounds_all, work_flags, (unsigned long long)n);
+                           work_steps, work_tiles, pl.nr, rep.rounds_all, work_flags, (unsigned long long)n, mv.on ? 1 : 0);
         HIP_TRY(hipGetLastError());
         if (carry) { // the bounds now describe this call: its centroids are what the next call's drift is measured from
             sm->hb_K = K; sm->hb_gamma = gamma; sm->hb_valid = true;
@@ -827,7 +868,8 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     if ((rc = c.buffers<IR>())) return rc;
     c.plan_input(prune_a, want_hint);
     spkm_plan_call(c.pl, c, c.sm->pol);
-    if ((rc = c.resources()) || (rc = c.bounds()) || (rc = c.screen<IR>())) return rc;
+    c.mv = spkm_plan_movers(c, c.pl, K, ctx->sw.mover_tile);
+    if ((rc = c.resources()) || (rc = c.mover_resources()) || (rc = c.bounds()) || (rc = c.screen<IR>())) return rc;
     // the sort buffers: at the events' sizes (2 per point, 2 K keys, SEG_EVENTS-event segments) from the start where there may be events
     const int ev = c.pl.ev_possible ? 2 : 1, max_items_ev_all = ev == 2 ? (int)((2 * c.n) / SEG_EVENTS) + 2 * K + 1 : 0;
     if ((rc = ensure(ctx, ctx->perm, (size_t)ev * c.n * 4)) || (rc = ensure(ctx, ctx->offs, (size_t)(ev * K + 1) * 8)) ||
@@ -915,6 +957,7 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         spkm_policy_counters c;
         c.listed = h[NL_LISTED]; c.ambig = h[NL_AMBIG]; c.early = h[NL_EARLY]; c.skipped = h[NL_SKIPPED];
         c.kept = h[NL_KEPT]; c.movers = h[NL_MOVERS];
+        c.msteps = h[NL_MCERT]; // (the steps settled on the mover tile never reached the main launch; 0 with the form off)
         c.full_opened = h[NL_GATE_FULL] != 0u;
         c.one_cluster_steps = h[NL_ONE_CLUSTER];
         c.may_regroup = sm->pend_full && sm->lazy && !sm->regroup_done;

@@ -15,7 +15,11 @@ enum spkm_counter_slot : int {
     NL_SKIPPED = 3,        // 16-point steps settled by the carried bounds
     NL_TODO = 4,           // length of todo[]: the steps / points the bounds test listed (k_bounds_steps)
     NL_CHANGED = 5,        // "some assignment changed": the gate of the counting-sort reuse
+    NL_MSTEPS = 6,         // 16-point steps that only the movers unsettle: test B passed, test A did not (k_bounds_steps)
+    NL_TODO_M = 7,         // length of todo_m[]: those steps, listed for the mover tile (0 with the form off)
     NL_SKIPPED_TOTAL = 8,  // u64, running: steps skipped
+    NL_MCERT = 10,         // steps certified on the mover tile (k_certify_movers) ...
+    NL_MSENT = 11,         // ... and steps it sent on to todo[] instead
     NL_KEPT = 12,          // points that passed the carried-bounds test
     NL_EXACT_PTS = 13,     // points the exact pass processes (k_cluster_need)
     NL_MOVERS = 14,        // points that changed cluster
@@ -24,6 +28,7 @@ enum spkm_counter_slot : int {
     NL_GATE_FULL = 19,     // ... or the full pass
     NL_CHECK_DIFF = 20,    // places where d_assign differs from the library's copy (count_assign_diff)
     NL_ONE_CLUSTER = 21,   // 16-point steps whose points share one cluster
+    NL_MEARLY = 22,        // steps the hinted mover launch finished early (NL_EARLY stays the main launch's)
     NL_PER_CALL_END = 32,
     NL_EXACT_TOTAL = 32,    // u64, running: points the exact passes processed
     NL_ROUNDS_DONE = 34,    // u64, running: screen rounds executed for all centroids of a tile
@@ -46,6 +51,9 @@ static_assert(nl_reported(NL_LISTED) && nl_reported(NL_AMBIG) && nl_reported(NL_
               "every counter the host policy reads is in the report");
 static_assert(SPKM_REPORT_WORDS + 1 <= SPKM_REPORT_BUF_WORDS && SPKM_REPORT_WORDS <= NL_WORDS, "the report and its number fit");
 static_assert(NL_SCREENED < NL_WORDS && NL_ONE_CLUSTER < NL_PER_CALL_END, "every slot fits the buffer");
+static_assert(nl_reported(NL_MSTEPS) && nl_reported(NL_MCERT) && nl_reported(NL_MSENT) && nl_zeroed(NL_MSTEPS) && nl_zeroed(NL_TODO_M) &&
+              nl_zeroed(NL_MCERT) && nl_zeroed(NL_MSENT) && nl_zeroed(NL_MEARLY) && NL_MEARLY < SPKM_REPORT_WORDS,
+              "the mover tile's counters are per-call words of the report");
 static_assert(nl_total_ok(NL_SKIPPED_TOTAL) && nl_total_ok(NL_EXACT_TOTAL) && nl_total_ok(NL_ROUNDS_DONE) &&
               nl_total_ok(NL_ROUNDS_FULL) && nl_total_ok(NL_SCREENED_TOTAL),
               "a running total is an aligned 64-bit pair that the per-call zeroing leaves alone");
@@ -61,17 +69,29 @@ enum { NI_FULL = 0, NI_EVENTS = 1, NI_PAIR_CHUNKS = 2, NI_REGROUP = 4, NI_WORDS 
 // NI_EVENTS: a dual call's events (its full pass keeps NI_FULL); NI_PAIR_CHUNKS: the first level of the pair events' sort
 
 // ---- bounds carried between screen calls, spkm_shard::hb (floats; `bnd` in the kernels) ------------------------------------
-//   ub[npad] | lb[npad] | assignment[npad] (int32) | delta[K] | dmax | ... | hterm[K] at HB_HTERM | ...
+//   ub[npad] | lb[npad] | assignment[npad] (int32) | delta[K] | dmax | ... | hterm[K] at HB_HTERM | ... | movers at HB_MOVERS
 //   delta[k], dmax   drift of every centroid on a point's support (k_center_drift) and its maximum
 //   hterm[k]         hint_w x (full 2-norm drift)^2 per centroid: the hints' estimate, not a bound
+//   movers           the SPKM_MOVERS centroids of largest drift, picked by k_center_drift's last workgroup (K <= SPKM_MOVER_KMAX):
+//                    ticket (unsigned) | d_R = the largest drift among the OTHER centroids (float) | ... | list[SPKM_MOVERS]
+//                    (int, by rank) | slot[K] (int: a centroid's place in the list, -1: not a mover)
 constexpr int HB_KMAX = 65536;           // the largest K a fused call takes
 constexpr int HB_HTERM = HB_KMAX + 16;   // within the tail
-constexpr int HB_TAIL = 2 * HB_KMAX + 32; // floats behind the three per-point arrays
+constexpr int SPKM_MOVERS = 32;          // centroids on the mover tile: one full tile of the 4-lanes-per-point screen
+constexpr int SPKM_MOVER_KMIN = 64, SPKM_MOVER_KMAX = 1024; // (policy.h, spkm_plan_movers)
+constexpr int HB_MOVERS = 2 * HB_KMAX + 32;                 // behind hterm
+constexpr int HB_MTICKET = HB_MOVERS, HB_MDR = HB_MOVERS + 1, HB_MLIST = HB_MOVERS + 16, HB_MSLOT = HB_MLIST + SPKM_MOVERS;
+constexpr int HB_TAIL = HB_MSLOT + SPKM_MOVER_KMAX + 16; // floats behind the three per-point arrays
+static_assert(HB_HTERM + HB_KMAX <= HB_MOVERS && HB_MLIST % 4 == 0, "the movers lie behind hterm[], the list 16-byte aligned");
 constexpr long long hb_lb(long long npad) { return npad; }
 constexpr long long hb_assign(long long npad) { return 2 * npad; }
 constexpr long long hb_delta(long long npad) { return 3 * npad; }
 constexpr long long hb_dmax(long long npad, int K) { return 3 * npad + K; }
 constexpr long long hb_hterm(long long npad) { return 3 * npad + HB_HTERM; }
+constexpr long long hb_mticket(long long npad) { return 3 * npad + HB_MTICKET; }
+constexpr long long hb_mdr(long long npad) { return 3 * npad + HB_MDR; }
+constexpr long long hb_mlist(long long npad) { return 3 * npad + HB_MLIST; }
+constexpr long long hb_mslot(long long npad) { return 3 * npad + HB_MSLOT; }
 constexpr size_t hb_floats(long long npad) { return (size_t)3 * npad + HB_TAIL; }
 
 // ---- block summaries of the carried bounds, spkm_shard::sp (bytes): per 1024 points the clusters present (K <= 128 bits),

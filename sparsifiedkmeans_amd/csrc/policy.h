@@ -48,6 +48,7 @@ SPKM_HD constexpr int quad_split(int nr, bool pts = false)
 
 struct spkm_policy_counters {
     double listed = 0, ambig = 0, early = 0, skipped = 0, kept = 0, movers = 0;
+    double msteps = 0;        // steps that went to the mover tile's list and not to the main launch (0: no such list)
     bool full_opened = false; // a call that queued both accumulation forms: the device opened the full pass (k_pick_form)
     double one_cluster_steps = 0; // 16-point steps whose points all sit in one cluster (counted by a call over every point)
     bool may_regroup = false;     // that call screened every point of a lazy shard not yet regrouped (pend_full, lazy, !regroup_done)
@@ -141,7 +142,8 @@ struct spkm_policy {
         if (hint_pending) {
             // hinted call: worth it only if a fair share of the (step, tile) pairs was finished early, and only while the
             // hints do not mislead (many listed points).  Steps skipped on the carried bounds never got as far as their hints.
-            const double steps = std::max(0.0, n / 16.0 - c.skipped) * t;
+            // ... and the steps certified on the mover tile never reached the main launch, whose pairs `early` counts.
+            const double steps = std::max(0.0, n / 16.0 - c.skipped - c.msteps) * t;
             // early or late split: a run's first three hinted calls use the late one, then the early one; an early call
             // that finishes fewer than 15 % of its pairs early sends the next two back to the late split.  (The late
             // split's own early-finish share says little about when to leave it -- it moves from 0.37 to 0.44 over the
@@ -674,4 +676,71 @@ inline void spkm_plan_sums(spkm_call_plan& pl, const spkm_call_in& in, const spk
     // (k_events_direct; SPKM_NO_DIRECT_EVENTS=1: A/B switch); few events: short segments, spread over more workgroups
     pl.direct = pl.ev_path && !pl.dual && pol.events_direct() && !in.no_direct_events;
     pl.seg_ev = (pol.movers_known && pol.last_movers < 100000) ? SEG_EVENTS : spkm_plan_seg;
+}
+// ---- the mover tile ----
+// The carried lower bound of a point erodes by the LARGEST centroid drift of every call.  While a handful of centroids still
+// migrate and the others have stopped, that one number unsettles every step of the shard.  So k_center_drift's last workgroup
+// picks M, the spkm_movers centroids of largest drift (ties to the lower index; centroids that did not move fill it up), and
+// d_R, the largest drift among the others; k_bounds_steps tests every step a second time with d_R in place of the largest
+// drift (test B), and a step that passes B but not the usual test is screened against the ONE tile that holds M
+// (k_prep_tiles_f32 gathers it, k_screen_quad's own instantiation of the call runs over the second list) and certified
+// against it by k_certify_movers -- or sent on to the main list.
+// The pick, as the kernel and tests/test_mover_plan.py both call it: a centroid's key orders by drift, then by index;
+// its rank is the number of larger keys.  rank < spkm_movers: a mover, at list[rank]; rank == spkm_movers: its drift is d_R.
+constexpr int spkm_movers = 32, spkm_mover_kmin = 64, spkm_mover_kmax = 1024;
+SPKM_HD constexpr unsigned long long spkm_mover_key(float d, int k)
+{
+    const float v = d >= 0.f ? d : __builtin_inff(); // (a drift that is not a number sorts first: such a centroid is a mover)
+    return ((unsigned long long)__builtin_bit_cast(unsigned, v) << 32) | (unsigned long long)(unsigned)(0x7fffffff - k);
+}
+SPKM_HD constexpr int spkm_mover_rank(const float* delta, int K, int k)
+{
+    const unsigned long long mine = spkm_mover_key(delta[k], k);
+    int r = 0;
+    for (int j = 0; j < K; j++) r += spkm_mover_key(delta[j], j) > mine ? 1 : 0;
+    return r;
+}
+// d_R from the drift of the centroid of rank spkm_movers and the largest drift of all: with ANY drift that is not finite
+// (a NaN or infinite centre) d_R is infinite too and nothing passes test B -- such a call screens as it does today.
+SPKM_HD constexpr float spkm_mover_dr(float d_next, float dmax)
+{
+    return (dmax >= 0.f && dmax < __builtin_inff() && d_next >= 0.f) ? d_next : __builtin_inff();
+}
+// The whole pick on the host (the tests' reference for the kernel's): list[spkm_movers], slot[K], returns d_R.
+inline float spkm_pick_movers(const float* delta, int K, int* list, int* slot)
+{
+    float dmax = 0.f, dn = __builtin_inff();
+    bool bad = false;
+    for (int k = 0; k < K; k++) {
+        const int r = spkm_mover_rank(delta, K, k);
+        slot[k] = r < spkm_movers ? r : -1;
+        if (r < spkm_movers) list[r] = k;
+        if (r == spkm_movers) dn = delta[k];
+        if (!(delta[k] >= 0.f)) bad = true; else dmax = std::max(dmax, delta[k]);
+    }
+    return spkm_mover_dr(dn, bad ? __builtin_inff() : dmax);
+}
+// Which calls take the form.  eligible: the 4-lanes-per-point screen with spkm_mover_kmin <= K (below that one tile is no
+// less than half of the whole screen) <= spkm_mover_kmax (the pick ranks K keys against K in one workgroup's LDS; the quad
+// screen's one-workgroup-per-tile-and-XCD rule stops at 32 tiles on a 256-CU part anyway), on a call whose bounds test runs over
+// STEP lists without block summaries and erodes (a lazy call without distances: nobody else writes the upper bound of a
+// point that keeps its centroid, so k_certify_movers may).  A regrouped shard is excluded: the mapped
+// instantiation of k_bounds_steps keeps one list.  Eligible calls pick M and count the steps
+// that pass B only (NL_MSTEPS), form on or off; `on` also lists them and runs the two extra launches.
+// sw: -1 SPKM_NO_MOVER_TILE=1, +1 SPKM_MOVER_TILE=1, 0 the default (spkm_mover_default_on: DESIGN section 7, decision rule of 6).
+constexpr bool spkm_mover_default_on = true;
+struct spkm_mover_plan {
+    bool eligible = false, on = false;
+    long long cap = 0;            // entries of the second list
+    int tiles = 1, pl = 4, nr = 0; // the mover launch's blockmap: one full tile, the call's rounds
+};
+inline spkm_mover_plan spkm_plan_movers(const spkm_call_in& in, const spkm_call_plan& pl, int K, int sw)
+{
+    spkm_mover_plan m;
+    m.nr = pl.nr;
+    m.eligible = in.quad && K >= spkm_mover_kmin && K <= spkm_mover_kmax && pl.drift && pl.skip_enabled && !pl.pt_mode &&
+                 !pl.sp_on && pl.erode && !in.has_map;
+    m.on = m.eligible && (sw > 0 || (sw == 0 && spkm_mover_default_on));
+    m.cap = m.on ? pl.npad / 16 + 1 : 0;
+    return m;
 }

@@ -48,8 +48,11 @@
 //    q ^ ((r >> 1) & 3) (the kernel's stored row ids carry the same two bits, k_screen_reorder).
 __global__ void k_prep_tiles_f32(const double* __restrict__ C, int p, int K, int G, double gamma,
                                  float* __restrict__ T32, unsigned long long* __restrict__ cmax_bits, int pl_last,
-                                 int swz, double* __restrict__ Cs, double* __restrict__ keep)
+                                 int swz, double* __restrict__ Cs, double* __restrict__ keep,
+                                 const int* __restrict__ mlist = nullptr)
 {
+    // mlist != nullptr (the mover tile; policy.h, spkm_plan_movers): one more full tile, tile G, whose slot kk holds centroid
+    // mlist[kk] -- the SPKM_MOVERS centroids of largest drift, as k_center_drift's last workgroup picked them in this call
     // Two more views of the same centres ride along (they were launches of their own: a small shard's settled iteration is
     // a chain of ~5-us kernels): Cs[r*K + k] = C[k*p + r] / gamma, row-major for the exact list kernel (k_assign_list),
     // and keep = C itself, the library's copy that the NEXT call's drift is measured from (k_center_drift has already
@@ -67,7 +70,7 @@ __global__ void k_prep_tiles_f32(const double* __restrict__ C, int p, int K, int
             }
         }
     }
-    const size_t total = (size_t)G * (p + 1) * SCREEN_KT;
+    const size_t total = (size_t)(G + (mlist != nullptr ? 1 : 0)) * (p + 1) * SCREEN_KT;
     double mx = 0.0;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         int kk = (int)(t % SCREEN_KT);
@@ -76,7 +79,8 @@ __global__ void k_prep_tiles_f32(const double* __restrict__ C, int p, int K, int
         const int g = (int)(rest / (p + 1));
         if (swz) kk ^= ((r >> 1) & 3) << 2; // physical -> logical position
         int k = g * SCREEN_KT + kk;
-        if (g == G - 1 && pl_last == 5) {
+        if (g == G) k = mlist[kk];
+        else if (g == G - 1 && pl_last == 5) {
             const size_t local = t - (size_t)g * (p + 1) * SCREEN_KT; // compact (p+1) x 4 table first, rest unused
             r = (int)(local >> 2);
             k = local < (size_t)(p + 1) * 4 ? g * SCREEN_KT + (int)(local & 3) : K;
@@ -558,8 +562,14 @@ __global__ __launch_bounds__(1024) void k_screen_tile(
 __global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__ prev, const double* __restrict__ cur,
                                                       int K, int p, double gamma, float* __restrict__ delta,
                                                       int* __restrict__ same, int top_s, float hint_w,
-                                                      float* __restrict__ hterm)
+                                                      float* __restrict__ hterm, unsigned* __restrict__ mticket = nullptr,
+                                                      float* __restrict__ mdr = nullptr, int* __restrict__ mlist = nullptr,
+                                                      int* __restrict__ mslot = nullptr)
 {
+    // mticket != nullptr (SPKM_MOVER_KMIN <= K <= SPKM_MOVER_KMAX; policy.h, spkm_plan_movers): the workgroup that finishes
+    // last picks the movers -- mlist[r] = the centroid of rank r < SPKM_MOVERS by (drift descending, index ascending),
+    // mslot[k] = centroid k's rank or -1, *mdr = the drift of rank SPKM_MOVERS, i.e. the largest among the others (infinite
+    // when any drift is) -- and leaves the ticket at 0 for the next call.  No launch of its own: the settled iteration is launch-bound.
     __shared__ double sh[4][4];
     __shared__ int s_diff;
     __shared__ unsigned s_hist[256];
@@ -649,6 +659,28 @@ __global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__
         }
         if (same) same[k] = s_diff ? 0 : 1;
     }
+    if (mticket != nullptr) { // (uniform)
+        __shared__ unsigned s_last;
+        __shared__ float s_dl[SPKM_MOVER_KMAX];
+        if (threadIdx.x == 0) {
+            __threadfence(); // delta[k] and the maximum, before the ticket
+            s_last = atomicAdd(mticket, 1u) == (unsigned)(K - 1) ? 1u : 0u;
+        }
+        __syncthreads();
+        if (s_last) { // (whole workgroup)
+            __threadfence();
+            for (int j = threadIdx.x; j < K; j += blockDim.x) s_dl[j] = __hip_atomic_load(delta + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const float dmx = __hip_atomic_load(delta + K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            for (int j = threadIdx.x; j < K; j += blockDim.x) {
+                const int r = spkm_mover_rank(s_dl, K, j);
+                mslot[j] = r < SPKM_MOVERS ? r : -1;
+                if (r < SPKM_MOVERS) mlist[r] = j;
+                if (r == SPKM_MOVERS) *mdr = spkm_mover_dr(s_dl[j], dmx);
+            }
+            if (threadIdx.x == 0) *mticket = 0u;
+        }
+    }
 }
 
 // PPT consecutive points of one array, per thread: ONE 16-byte access where the caller knows that all four exist and that
@@ -701,7 +733,17 @@ __device__ __forceinline__ void st_points(T* __restrict__ p, size_t at, bool wid
 // passed, counters[NL_KEPT], and the steps whose 16 points all passed, counters[NL_SKIPPED]): >= 90 % of the points passed and the
 // steps left over hold several times as many points as failed (entered at 4x, left below 2.5x).  The screen then fetches 16 B per quad instead of
 // 256 B per wave, which only pays while few points are listed.
-template <bool MAPPED> // MAPPED: a regrouped shard (map != nullptr) -- a compile-time flag: with the choice made at run time the
+// MOV (a call eligible for the mover tile: step lists, no block summaries, an eroding call; policy.h, spkm_plan_movers): every
+// point is tested a second time, test B, with d_R -- the largest drift among the centroids that are NOT movers
+// (k_center_drift) -- in place of the largest drift of all: (ub + delta_a)(1 + 1e-6) < (lb_stored - cum_R)(1 - 1e-6),
+// cum_R = cum_in + d_R rounded up as cum_now is.  lb_stored - cum_in bounded the distance to every other centroid at the end
+// of the previous call, whatever the age of the bound, and in this call a centroid outside M moves by at most d_R on the
+// point's support: a point that passes B can only have lost its centroid to a mover.  A step whose 16 points all pass B
+// but not all pass A is counted in counters[NL_MSTEPS]; with todo_m != nullptr it is appended to todo_m[] (length
+// counters[NL_TODO_M]) INSTEAD of todo[], its points' upper bounds are left as they are (k_certify_movers moves them, or
+// the step goes on to todo[] and k_combine_screen / k_assign_list write them) and the caller's buffer is repaired as for a
+// settled step.  cum_out, NL_SKIPPED, NL_KEPT and the hints are test A's, as without MOV.
+template <bool MAPPED, bool MOV = false> // MAPPED: a regrouped shard (map != nullptr) -- a compile-time flag: with the choice made at run time the
 // compiler puts the caller-buffer load behind a branch, apart from the other loads of its group (44 -> 113 us per settled call)
 __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, long long npad, long long n, int K,
                                                       int* __restrict__ assign,
@@ -713,7 +755,8 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
                                                       float* __restrict__ sp_slack = nullptr, unsigned* __restrict__ sp_mask = nullptr,
                                                       int* __restrict__ sp_valid = nullptr, int sp_reset = 0,
                                                       const int* __restrict__ same = nullptr,
-                                                      const int* __restrict__ map = nullptr)
+                                                      const int* __restrict__ map = nullptr,
+                                                      int* __restrict__ todo_m = nullptr)
 {
     // assign == nullptr: the caller's buffer is known to hold the library's copy already (lazy statistics, the same buffer as
     // in the previous call: spkm.h) -- it is neither read nor restored.  map != nullptr (a regrouped shard, api_lloyd.hip): point i of
@@ -760,9 +803,21 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     const double cum_rn = *cum_in + (double)dmx * (1.0 + 1e-12);
     const double cum_now = cum_rn + fabs(cum_rn) * 0x1p-52;
     if (skip_enabled && blockIdx.x == 0 && threadIdx.x == 0) *cum_out = cum_now;
+    // MOV: the same sum with d_R (infinite or NaN: nothing passes B); the second list shares s_todo[] -- a span of step
+    // lists is at most BOUNDS_SPAN / 16 = 1024 steps, and the two lists are disjoint
+    double cum_r = __builtin_inf();
+    if constexpr (MOV) {
+        const double cr = *cum_in + (double)bnd[hb_mdr(npad)] * (1.0 + 1e-12);
+        cum_r = cr + fabs(cr) * 0x1p-52;
+    }
+    static_assert(BOUNDS_SPAN / 16 <= BOUNDS_SPAN_PT / 2, "both step lists of a span fit s_todo[]");
+    int* const s_todo_m = s_todo + BOUNDS_SPAN_PT / 2;
+    __shared__ unsigned s_cnt_m, s_pos_m, s_mst;
+    const bool list_m = MOV && todo_m != nullptr;
+    unsigned nmst = 0;
     const int lane = threadIdx.x & 63;
     unsigned nskip = 0, nkept = 0;
-    if (threadIdx.x == 0) { s_cnt = 0; s_skip = 0; s_kept = 0; }
+    if (threadIdx.x == 0) { s_cnt = 0; s_skip = 0; s_kept = 0; s_cnt_m = 0; s_mst = 0; }
     __syncthreads();
     constexpr int UN = 4; // consecutive points per thread
     // delta[k] and hterm[k], gathered by every point's assignment: from LDS (K <= BOUNDS_KTAB), else from global memory
@@ -900,11 +955,13 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
             st_points<UN>(hintu, (size_t)i0, wide, in, hv);
         if (!skip_enabled) continue;
         bool keep[UN], st_er[UN];
+        bool keep_b = true; // MOV: this thread's points all pass test B (or test A: cum_r <= cum_now, spelt out for the roundings)
         float ubn[UN];
         unsigned long long b[UN];
 #pragma unroll
         for (int c = 0; c < UN; c++) {
             keep[c] = !in[c] || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_now) * 0.999999; // false for NaN
+            if constexpr (MOV) keep_b = keep_b && (keep[c] || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_r) * 0.999999);
             b[c] = __ballot(keep[c]);
             nkept += (unsigned)__popcll(__ballot(keep[c] && in[c]));
             ubn[c] = (erode && dav[c] > 0.f) ? __double2float_ru((double)ubv[c] + (double)dav[c]) : ubv[c]; // Hamerly's update
@@ -917,13 +974,25 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
                 bm0 |= w == 0 ? bit : 0u; bm1 |= w == 1 ? bit : 0u; bm2 |= w == 2 ? bit : 0u; bm3 |= w == 3 ? bit : 0u;
             }
         }
-        if (erode) st_points<UN>(bnd, (size_t)i0, wide, st_er, ubn);
+        if (!MOV && erode) st_points<UN>(bnd, (size_t)i0, wide, st_er, ubn);
         // a step is 16 / UN neighbouring lanes
         constexpr int LPS = 16 / UN;
         const unsigned long long bq = __ballot(keep[0] && keep[1] && keep[2] && keep[3]);
         const bool whole = ((unsigned)(bq >> (lane & ~(LPS - 1))) & ((1u << LPS) - 1u)) == (1u << LPS) - 1u; // all 16 points of the step pass
         const bool live_step = (i0 - UN * (lane & (LPS - 1))) < n; // the step has at least one point
         const bool lead_lane = (lane & (LPS - 1)) == 0 && live_step;
+        bool mstep = false; // MOV: all 16 points pass B, not all pass A
+        if constexpr (MOV) {
+            const unsigned long long bqb = __ballot(keep_b);
+            mstep = !whole && ((unsigned)(bqb >> (lane & ~(LPS - 1))) & ((1u << LPS) - 1u)) == (1u << LPS) - 1u;
+            nmst += (unsigned)__popcll(__ballot(lead_lane && mstep));
+            mstep = mstep && list_m; // (from here on: the step goes to the second list)
+            if (erode) { // (the eroded bounds of a step on the second list are k_certify_movers' to store)
+#pragma unroll
+                for (int c = 0; c < UN; c++) st_er[c] = st_er[c] && !mstep;
+                st_points<UN>(bnd, (size_t)i0, wide, st_er, ubn);
+            }
+        }
         if (pt_mode) {
             unsigned long long lm[UN];
             unsigned tot = 0;
@@ -953,11 +1022,20 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
             for (int c = 0; c < UN; c++) {
                 // a caller that passes the same buffer call after call already holds this value: a 4-B read instead of a
                 // 4-B store (a gigabyte of stores costs as much as several of loads here)
-                if (skip && in[c] && have_cur && curv[c] != apv[c]) assign[MAPPED ? (long long)map[i0 + c] : i0 + c] = apv[c];
+                if ((skip || mstep) && in[c] && have_cur && curv[c] != apv[c]) assign[MAPPED ? (long long)map[i0 + c] : i0 + c] = apv[c];
                 st_h[c] = !skip && in[c] && hintu != nullptr;
             }
             if (hintu != nullptr) st_points<UN>(hintu, (size_t)i0, wide, st_h, hv);
-            const bool lead = lead_lane && !skip;
+            if constexpr (MOV) {
+                const unsigned long long lmm = __ballot(lead_lane && mstep);
+                if (lmm) {
+                    unsigned bp = 0;
+                    if (lane == 0) bp = atomicAdd(&s_cnt_m, (unsigned)__popcll(lmm));
+                    bp = __builtin_amdgcn_readfirstlane(bp);
+                    if (lead_lane && mstep) s_todo_m[bp + __popcll(lmm & ((1ull << lane) - 1ull))] = (int)(i0 >> 4);
+                }
+            }
+            const bool lead = lead_lane && !skip && !mstep;
             const unsigned long long lm = __ballot(lead);
             if (lm) {
                 unsigned basepos = 0;
@@ -995,14 +1073,23 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
     if (threadIdx.x == 0) s_pos = s_cnt ? atomicAdd(counters + NL_TODO, s_cnt) : 0u;
     __syncthreads();
     for (unsigned j = threadIdx.x; j < s_cnt; j += 256) todo[s_pos + j] = s_todo[j];
+    if constexpr (MOV) {
+        if (list_m) { // (uniform) the second list of the span, the same way
+            if (threadIdx.x == 0) s_pos_m = s_cnt_m ? atomicAdd(counters + NL_TODO_M, s_cnt_m) : 0u;
+            __syncthreads();
+            for (unsigned j = threadIdx.x; j < s_cnt_m; j += 256) todo_m[s_pos_m + j] = s_todo_m[j];
+        }
+    }
     __syncthreads();
-    if (threadIdx.x == 0) s_cnt = 0;
+    if (threadIdx.x == 0) { s_cnt = 0; s_cnt_m = 0; }
     __syncthreads();
     }
     }
     if (lane == 0 && nskip) atomicAdd(&s_skip, nskip);
     if (lane == 0 && nkept) atomicAdd(&s_kept, nkept);
+    if (MOV && lane == 0 && nmst) atomicAdd(&s_mst, nmst);
     __syncthreads();
+    if (MOV && threadIdx.x == 0 && s_mst) atomicAdd(counters + NL_MSTEPS, s_mst); // (one per workgroup that saw such a step)
     if (threadIdx.x == 0) { // points that passed the test (either mode), steps whose 16 points all passed: k_call_tail adds them up
         blkstat[BS_STRIDE * blockIdx.x + BS_KEPT] = s_kept;
         blkstat[BS_STRIDE * blockIdx.x + BS_SKIPPED] = s_skip;
@@ -1513,6 +1600,144 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
     if (ev_pt)
         for (int k = threadIdx.x; k < (pair ? K : 2 * K); k += blockDim.x)
             if (evc[k]) atomicAdd(&nk_ev[k], (unsigned long long)evc[k]);
+}
+
+// The steps of todo_m[] (k_bounds_steps, MOV: all 16 points pass test B) after the mover tile's launch: plane 0 of the
+// result arrays holds, per point, m1 = the estimate of the tile's leader, m2 = a lower bound of the tile's other centroids
+// and the leader's SLOT (centroid mlist[slot]).  With eps as in k_combine_screen and
+//     L_R = lb_stored - cum_R   (rounded down)   <= the distance to every centroid that is not a mover, after this call's move
+// (cum_R = cum_in + d_R rounded up, as k_bounds_steps takes it), point i with previous centroid a keeps a iff
+//   a not in M:  U (1 + 2^-45) < min(L_R, L_M) (1 - 2^-45),  U = ub + delta_a rounded up, L_M = min(sqrt m1 - eps1, sqrt m2 - eps2)
+//                floored at 0: every mover is at least L_M away, every other centroid at least L_R.
+//                ub <- U (stored only where delta_a > 0, as the bounds test does), lb_stored <- min(L_R, L_M) + cum_now, rounded down.
+//   a in M:      the tile's leader is a and (sqrt m1 + eps1)(1 + 2^-45) < min(sqrt m2 - eps2, L_R)(1 - 2^-45).
+//                ub <- sqrt m1 + eps1 rounded up, lb_stored <- min(sqrt m2 - eps2, L_R) + cum_now, rounded down.
+// NaN, infinite or missing estimates, equal estimates of a leader and its runner-up (duplicate centres are movers together),
+// a leader other than a, bounds that do not separate: the point fails.  A STEP with a failing point writes nothing for any
+// of its 16 points and is appended to todo[] (one global atomic per workgroup and trip; the lists are unordered), where the
+// main launch of the same call screens it in full: no point changes cluster, is listed or records an event here, and
+// nothing is written to the caller's buffer, the library's copy of the assignment, the touched flags or the events.
+// 4 consecutive points per thread, 16-byte accesses, a step = 4 neighbouring lanes -- k_combine_screen's data movement.
+__global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict__ scr_m1, const float* __restrict__ scr_m2,
+                                                        const int* __restrict__ scr_k, long long n,
+                                                        const float* __restrict__ xnr, int fixed_s,
+                                                        const unsigned long long* __restrict__ cmax_bits,
+                                                        float* __restrict__ bnd, long long npad, int K,
+                                                        const int* __restrict__ todo_m, int* __restrict__ todo,
+                                                        unsigned* __restrict__ counters,
+                                                        const double* __restrict__ cum_in_p, const double* __restrict__ cum_now_p)
+{
+    constexpr int PPT = 4, WGP = 256 * PPT;
+    const long long total = (long long)counters[NL_TODO_M] * 16;
+    if ((long long)blockIdx.x * WGP >= total) return; // (whole workgroup; an empty list: every workgroup)
+    __shared__ float s_dk[SPKM_MOVER_KMAX];
+    __shared__ int s_slot[SPKM_MOVER_KMAX];
+    __shared__ int s_send[WGP / 16];
+    __shared__ unsigned s_nsend, s_pos, s_ncert;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        s_dk[k] = bnd[hb_delta(npad) + k];
+        s_slot[k] = reinterpret_cast<const int*>(bnd)[hb_mslot(npad) + k];
+    }
+    if (threadIdx.x == 0) { s_nsend = 0u; s_ncert = 0u; }
+    const double cum_in = *cum_in_p, cum_now = *cum_now_p;
+    const double cr = cum_in + (double)bnd[hb_mdr(npad)] * (1.0 + 1e-12);
+    const double cum_r = cr + fabs(cr) * 0x1p-52;
+    const double cmax = __builtin_bit_cast(double, *cmax_bits);
+    const double u = 0x1p-24;
+    const double eu = (2.0 * u + u * u) * (1.0 + 1e-9);
+    const double gacc = (double)(fixed_s + 1) * u * (1.0 + 1e-4);
+    const double sqrt_s = sqrt((double)fixed_s) * (1.0 + 1e-15);
+    const double nu = 0x1p-45;
+    const double inf = __builtin_inf();
+    float* lbp = bnd + npad;
+    const int* alib = reinterpret_cast<const int*>(bnd) + hb_assign(npad);
+    const bool al_pl = (n & 3) == 0 &&
+                       ((reinterpret_cast<size_t>(scr_m1) | reinterpret_cast<size_t>(scr_m2) | reinterpret_cast<size_t>(scr_k)) & 15) == 0;
+    const bool al_lib = (npad & 3) == 0 && ((reinterpret_cast<size_t>(bnd) | reinterpret_cast<size_t>(xnr)) & 15) == 0;
+    const int ln = threadIdx.x & 63;
+    constexpr int LPS = 16 / PPT;
+    unsigned ncert = 0;
+    __syncthreads();
+    for (long long q0 = (long long)blockIdx.x * WGP; q0 < total; q0 += (long long)gridDim.x * WGP) { // (uniform trip count)
+        const long long q = q0 + (long long)threadIdx.x * PPT;
+        const int step = q < total ? todo_m[q >> 4] : -1;
+        const long long i0 = step >= 0 ? (long long)step * 16 + (q & 15) : n;
+        bool in[PPT];
+#pragma unroll
+        for (int c = 0; c < PPT; c++) in[c] = i0 + c < n;
+        const bool wide = __all(i0 + 3 < n);
+        float xn[PPT], ub[PPT], lb[PPT], m1[PPT], m2[PPT];
+        int a[PPT], sl[PPT];
+        ld_points<PPT>(xnr, (size_t)i0, wide && al_lib, in, 0.f, xn);
+        ld_points<PPT>((const float*)bnd, (size_t)i0, wide && al_lib, in, 0.f, ub);
+        ld_points<PPT>((const float*)lbp, (size_t)i0, wide && al_lib, in, 0.f, lb);
+        ld_points<PPT>(alib, (size_t)i0, wide && al_lib, in, 0, a);
+        ld_points<PPT>(scr_m1, (size_t)i0, wide && al_pl, in, 0.f, m1);
+        ld_points<PPT>(scr_m2, (size_t)i0, wide && al_pl, in, 0.f, m2);
+        ld_points<PPT>(scr_k, (size_t)i0, wide && al_pl, in, -1, sl);
+        bool ok = true, st_ub[PPT], st_lb[PPT];
+        float ubn[PPT], lbn[PPT];
+#pragma unroll
+        for (int c = 0; c < PPT; c++) {
+            st_ub[c] = st_lb[c] = false;
+            ubn[c] = 0.f; lbn[c] = 0.f;
+            if (!in[c]) continue;
+            const int ac = ((unsigned)a[c] < (unsigned)K) ? a[c] : 0; // (the library's copy lies in [0, K) whenever the bounds are valid)
+            const float da = s_dk[ac];
+            const int sa = s_slot[ac];
+            const double E = eu * ((double)xn[c] + sqrt_s * cmax) * (1.0 + 1e-9) * (1.0 + 1e-9);
+            const double r1 = sqrt((double)m1[c]), r2 = sqrt((double)m2[c]);
+            const double e1 = E + gacc * r1 + 1e-20, e2 = E + gacc * r2 + 1e-20;
+            const bool have = sl[c] >= 0 && sl[c] < SPKM_MOVERS && r1 < inf && r2 < inf; // false for NaN
+            double lr = (double)lb[c] - cum_r;
+            lr = lr > 0.0 ? lr * (1.0 - 0x1p-50) : lr * (1.0 + 0x1p-50); // (rounded down)
+            bool good;
+            double un, ln_;
+            if (sa < 0) {
+                const double U = da > 0.f ? (double)__double2float_ru((double)ub[c] + (double)da) : (double)ub[c];
+                const double lm = fmax(0.0, fmin(r1 - e1, r2 - e2));
+                ln_ = fmin(lr, lm);
+                good = have && U * (1.0 + nu) < ln_ * (1.0 - nu);
+                un = U;
+                st_ub[c] = da > 0.f;
+                ubn[c] = (float)U;
+            } else {
+                ln_ = fmin(r2 - e2, lr);
+                un = (r1 + e1) * (1.0 + nu);
+                good = have && sl[c] == sa && un < ln_ * (1.0 - nu);
+                st_ub[c] = true;
+                ubn[c] = __double2float_ru(un * (1.0 + 1e-12));
+            }
+            st_lb[c] = true;
+            lbn[c] = __double2float_rd(fmax(0.0, ln_ * (1.0 - nu)) + cum_now);
+            ok = ok && good; // (false for NaN in any term)
+        }
+        const unsigned long long bq = __ballot(ok);
+        const bool whole = ((unsigned)(bq >> (ln & ~(LPS - 1))) & ((1u << LPS) - 1u)) == (1u << LPS) - 1u;
+        const bool lead_lane = (ln & (LPS - 1)) == 0 && step >= 0;
+#pragma unroll
+        for (int c = 0; c < PPT; c++) { st_ub[c] = st_ub[c] && whole; st_lb[c] = st_lb[c] && whole; }
+        st_points<PPT>(bnd, (size_t)i0, wide && al_lib, st_ub, ubn);
+        st_points<PPT>(lbp, (size_t)i0, wide && al_lib, st_lb, lbn);
+        ncert += (unsigned)__popcll(__ballot(lead_lane && whole));
+        const unsigned long long sm = __ballot(lead_lane && !whole);
+        if (sm) {
+            unsigned bp = 0;
+            if (ln == 0) bp = atomicAdd(&s_nsend, (unsigned)__popcll(sm));
+            bp = __builtin_amdgcn_readfirstlane(bp);
+            if (lead_lane && !whole) s_send[bp + __popcll(sm & ((1ull << ln) - 1ull))] = step;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_pos = s_nsend ? atomicAdd(counters + NL_TODO, s_nsend) : 0u;
+        __syncthreads();
+        for (unsigned j = threadIdx.x; j < s_nsend; j += blockDim.x) todo[s_pos + j] = s_send[j];
+        __syncthreads();
+        if (threadIdx.x == 0) { if (s_nsend) atomicAdd(counters + NL_MSENT, s_nsend); s_nsend = 0u; }
+        __syncthreads();
+    }
+    if (ln == 0 && ncert) atomicAdd(&s_ncert, ncert);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_ncert) atomicAdd(counters + NL_MCERT, s_ncert);
 }
 
 // Listed points: exact reference arithmetic over all K centroids (row-major scaled centres Cs in

@@ -356,12 +356,13 @@ __global__ __launch_bounds__(1024) void k_screen_quad(
     const float* __restrict__ hint, float hint_c, unsigned* __restrict__ counters, const int* __restrict__ todo,
     int todo_points, // todo_points != 0 (the PTS instantiation): the list holds point ids (counters[NL_TODO] of them), not 16-point steps
     const char* __restrict__ rec, int rec_R, // record layout for the listed points (PTS; may be null)
-    const int* __restrict__ recmap)          // ... and which record a point of this shard's order is (null: its own)
+    const int* __restrict__ recmap,          // ... and which record a point of this shard's order is (null: its own)
+    int todo_slot) // the counter that holds the list's length: NL_TODO, or NL_TODO_M for the mover tile's launch over todo_m[] (its early finishes: NL_MEARLY)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const spkm_blockmap bm = bmap[blockIdx.x];
     if (bm.tile < 0) return;
-    if (todo != nullptr && counters[NL_TODO] == 0u) return; // an empty list: not even the tile is loaded
+    if (todo != nullptr && counters[todo_slot] == 0u) return; // an empty list: not even the tile is loaded
     const int tid = threadIdx.x;
     const int pl = (bm.pad >> 16) & 0xff; // centroid pairs per lane in this workgroup's tile (5: 4 + one extra centroid)
     const size_t tile_bytes = (size_t)(p + 1) * SCREEN_KT * 4;
@@ -385,9 +386,9 @@ __global__ __launch_bounds__(1024) void k_screen_quad(
     const int eb = (int)tile_bytes, ek = extra_tile * SCREEN_KT;
     constexpr int A = TWO == 0 ? NR : (TWO == 2 && quad_split_late(NR, PTS) > 0 ? quad_split_late(NR, PTS) : quad_split(NR, PTS));
     int nv = n, chunk_v = chunk_points, tp = 0;
-    if (todo != nullptr) { // counters[NL_TODO] = length of the list; chunks small enough that every workgroup gets several
-        if (PTS) { tp = (int)counters[NL_TODO]; nv = (tp + 15) & ~15; }
-        else nv = (int)counters[NL_TODO] * 16;
+    if (todo != nullptr) { // counters[todo_slot] = length of the list; chunks small enough that every workgroup gets several
+        if (PTS) { tp = (int)counters[todo_slot]; nv = (tp + 15) & ~15; }
+        else nv = (int)counters[todo_slot] * 16;
         chunk_v = max(256, min(chunk_points, (nv / (int)(gridDim.x * 2)) & ~255));
     }
     if (pl == 4) screen_quad_body<NR, IR, 4, A, PTS>(ir, xval, p, n, nv, fixed_s, K, bm, chunk_v, m1o, m2o, ko, smem, ticket, eb, ek, hint, hint_c, counters, todo, tp, rec, rec_R, recmap);
@@ -396,7 +397,7 @@ __global__ __launch_bounds__(1024) void k_screen_quad(
     else screen_quad_body<NR, IR, 1, A, PTS>(ir, xval, p, n, nv, fixed_s, K, bm, chunk_v, m1o, m2o, ko, smem, ticket, eb, ek, hint, hint_c, counters, todo, tp, rec, rec_R, recmap);
     if (counters != nullptr) {
         __syncthreads();
-        if (tid == 0 && ticket[1]) atomicAdd(counters + NL_EARLY, ticket[1]);
+        if (tid == 0 && ticket[1]) atomicAdd(counters + (todo_slot == NL_TODO_M ? NL_MEARLY : NL_EARLY), ticket[1]);
     }
 }
 

@@ -1093,14 +1093,18 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
                             const double* __restrict__ cache_c = nullptr, size_t pk = 0, double* __restrict__ sums = nullptr,
                             double* __restrict__ counts = nullptr, unsigned* __restrict__ host_out = nullptr, unsigned seq = 0u,
                             unsigned long long work_steps = 0ull, int work_tiles = 0, int work_nr = 0, int work_a = 0,
-                            int work_flags = 0, unsigned long long screen_n = 0ull)
+                            int work_flags = 0, unsigned long long screen_n = 0ull, int mover_on = 0)
 {
+    // mover_on: the call listed steps for the mover tile (k_bounds_steps, MOV): the points of the steps certified there
+    // (counters[NL_MCERT], 16 each) count as screened, and the mover launch's rounds -- counters[NL_TODO_M] steps on one tile,
+    // less its early finishes, counters[NL_MEARLY] -- go into counters[NL_ROUNDS_DONE]; NL_ROUNDS_FULL and NL_EARLY stay the main launch's.
     // screen_n: the shard's points -- what this call's screen evaluated: all of them, or (work_flags & 2) the points of its
     // list, 16 per listed step -- into counters[NL_SCREENED], and added to the running total at counters[NL_SCREENED_TOTAL]
     // (spkm_last_screen_points)
     if (screen_n > 0ull && blockIdx.x == 0 && threadIdx.x == 0) {
         unsigned long long v = screen_n;
         if (work_flags & 2) v = (work_flags & 4) ? (unsigned long long)counters[NL_TODO] : (unsigned long long)counters[NL_TODO] * 16ull;
+        if (mover_on) v += (unsigned long long)counters[NL_MCERT] * 16ull;
         if (v > screen_n) v = screen_n;
         counters[NL_SCREENED] = (unsigned)v;
         *reinterpret_cast<unsigned long long*>(counters + NL_SCREENED_TOTAL) += v;
@@ -1118,6 +1122,14 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
         if (!(work_flags & 1) && work_a < work_nr) {
             const unsigned long long saved = (unsigned long long)counters[NL_EARLY] * (unsigned long long)(work_nr - work_a);
             r -= saved < r ? saved : r;
+        }
+        if (mover_on) {
+            unsigned long long rm = (unsigned long long)counters[NL_TODO_M] * (unsigned long long)((work_flags & 1) ? work_a : work_nr);
+            if (!(work_flags & 1) && work_a < work_nr) {
+                const unsigned long long saved = (unsigned long long)counters[NL_MEARLY] * (unsigned long long)(work_nr - work_a);
+                rm -= saved < rm ? saved : rm;
+            }
+            r += rm;
         }
         *reinterpret_cast<unsigned long long*>(counters + NL_ROUNDS_DONE) += r;
         *reinterpret_cast<unsigned long long*>(counters + NL_ROUNDS_FULL) += work_steps * (unsigned long long)work_tiles * (unsigned long long)work_nr;
