@@ -239,6 +239,22 @@ int spkm_shard_set_far_events(spkm_shard *s, int on);
  * state, like spkm_shard_reset_policy.  SPKM_FAR_RAGGED=1 opts every shard of a context in (read with the other switches:
  * spkm_ctx_reload_switches); the far screen's own opt-in is still needed. */
 int spkm_shard_set_far_ragged(spkm_shard *s, int on);
+/* Ragged shards on the LDS-tile screen (on != 0; default off).  The same RAGGED shard at a p that still has a 32-centroid
+ * f32 tile ((p + 1) * 128 + 16 bytes: p <= 1278 with 160 KB -- the p at which spkm_shard_set_far_ragged stops applying, so
+ * the two never compete) runs k_assign_tile over every point and a full accumulation in every call.  A shard that opts in
+ * here is screened instead by a form of the narrow-tile kernel that reads each point's column bounds from jc, on tiles of
+ * 8 centroids for K <= 8, 16 for K <= 16 and 32 beyond, in front of the pipeline the far screen runs: the same estimates and
+ * certificate -- with the shard's longest column where it takes a column length -- and the same exact list behind it.  An
+ * empty column goes to centroid 0 at distance 0 without a load and is never listed.  Carried bounds and incremental sums
+ * follow the shard's spkm_shard_set_far_bounds / spkm_shard_set_far_events opt-ins, as on a ragged far shard;
+ * spkm_last_path_info reports 1, spkm_last_screen_tile the tile width and the tiles, spkm_last_screen_mode and
+ * spkm_last_screen_points as on the far path.  K >= 2, 48 entries of slack behind ir / x, a workgroup per tile at least.
+ * Every output is what the all-exact kernels give.  A switch of its own: no other opt-in implies it, and it needs none.
+ * Opting in measures the shard's longest column once, as spkm_shard_set_far_ragged does.  On a fixed-stride shard, and on a
+ * ragged one past the last p with a 32-centroid tile, the setting changes nothing.  Turning it on or off forgets the
+ * shard's policy state, like spkm_shard_reset_policy.  SPKM_TILE_RAGGED=1 opts every shard of a context in (read with the
+ * other switches: spkm_ctx_reload_switches). */
+int spkm_shard_set_tile_ragged(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by

@@ -163,6 +163,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         check(spkm_shard_set_far_bounds(g_shard, 1));            /* carried bounds where a shard takes the far screen, as in the Python driver (profiles/far_bounds_ab.txt) */
         check(spkm_shard_set_far_events(g_shard, 1));            /* ... and incremental sums there for lazy calls with few movers, as in the Python driver (profiles/far_events_ab.txt) */
         check(spkm_shard_set_far_ragged(g_shard, 0));            /* a ragged shard on the far screen: off, as in the Python driver, until profiles/far_ragged_ab.txt holds a measurement */
+        check(spkm_shard_set_tile_ragged(g_shard, 0));           /* a ragged shard on the LDS-tile screen: off, as in the Python driver (profiles/tile_ragged_ab.txt: one winning series, the default waits for a second) */
         g_p = mxGetM(X);
         g_n = mxGetN(X);
         return;
@@ -223,6 +224,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         check(spkm_shard_set_far_bounds(g_shard, 1));            /* carried bounds where a shard takes the far screen, as in the Python driver (profiles/far_bounds_ab.txt) */
         check(spkm_shard_set_far_events(g_shard, 1));            /* ... and incremental sums there for lazy calls with few movers, as in the Python driver (profiles/far_events_ab.txt) */
         check(spkm_shard_set_far_ragged(g_shard, 0));            /* a ragged shard on the far screen: off, as in the Python driver, until profiles/far_ragged_ab.txt holds a measurement */
+        check(spkm_shard_set_tile_ragged(g_shard, 0));           /* a ragged shard on the LDS-tile screen: off, as in the Python driver (profiles/tile_ragged_ab.txt: one winning series, the default waits for a second) */
         hipFree(d_chunk);
         hipFree(d_sign);
         g_p = p2; g_n = n; g_s = s;

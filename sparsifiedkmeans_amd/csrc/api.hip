@@ -42,6 +42,7 @@ static spkm_switches read_switches()
     w.far_bounds = on("SPKM_FAR_BOUNDS");
     w.far_events = on("SPKM_FAR_EVENTS");
     w.far_ragged = on("SPKM_FAR_RAGGED");
+    w.tile_ragged = on("SPKM_TILE_RAGGED");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
@@ -441,6 +442,17 @@ extern "C" int spkm_shard_set_far_ragged(spkm_shard* s, int on)
     if (s->far_ragged && s->ctx) {
         spkm_ctx* ctx = s->ctx;
         const int rc = ensure_max_s(ctx, s); // (here, so that no fused call waits for it)
+        if (rc) return rc;
+    }
+    return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
+}
+
+extern "C" int spkm_shard_set_tile_ragged(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->tile_ragged = on != 0;
+    if (s->tile_ragged && s->ctx) {
+        const int rc = ensure_max_s(s->ctx, s); // (here, so that no fused call waits for it)
         if (rc) return rc;
     }
     return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)

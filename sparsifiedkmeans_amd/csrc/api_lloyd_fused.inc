@@ -35,7 +35,14 @@ static int far_screen_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
     return spkm_far_screen((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
                            s->wide || ctx->sw.wide_screen, s->far || ctx->sw.far_screen);
 }
-
+// ... and where both are 0 on a RAGGED shard, the tile width of k_screen_wide's RAGGED form (policy.h,
+// spkm_tile_screen_ragged): 8, 16 or 32 centroids for a shard or a context that opted in (spkm_shard_set_tile_ragged,
+// SPKM_TILE_RAGGED=1) at a p whose 32-centroid f32 tile fits; 0: the all-exact kernels.
+static int tile_ragged_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
+{
+    return spkm_tile_screen_ragged((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
+                                   s->tile_ragged || ctx->sw.tile_ragged);
+}
 
 static_assert(spkm_movers == SPKM_MOVERS && spkm_movers == SCREEN_KT && spkm_mover_kmin == SPKM_MOVER_KMIN && spkm_mover_kmax == SPKM_MOVER_KMAX &&
               SPKM_MOVER_KMAX <= BOUNDS_KTAB, "the mover tile is one full screen tile; policy.h and layout.h agree on its limits");
@@ -102,9 +109,9 @@ struct screen_call : spkm_call_in {
         zj.n = 0;
     }
     int* cl(int row) const { return pl.cl_on ? sm->cl_flags + (size_t)row * K : nullptr; } // row: CL_* (layout.h)
-    // the column length the certificate and the support-aware drift take: the stride, or a ragged far shard's longest column
+    // the column length the certificate and the support-aware drift take: the stride, or a ragged shard's longest column
     int col_s() const { return sm->fixed_s > 0 ? sm->fixed_s : sm->max_s; }
-    bool ragged() const { return sm->fixed_s <= 0; } // (only the far screen takes such a shard)
+    bool ragged() const { return sm->fixed_s <= 0; } // (only the far screen and the ragged tile screen take such a shard)
     // Buffers: the screen's inputs and scratch, the shard's carried bounds and cluster cache; a regrouping asked for.
     template <typename IR> int buffers()
     {
@@ -400,7 +407,8 @@ struct screen_call : spkm_call_in {
         }
         rep.movers = mv.on;
         // (k_screen_wide: the first twelve, then the list and the counters)
-        void* args_w[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt};
+        const long long* a_jc = nullptr; // (the RAGGED forms' column bounds: screen_tile_ragged)
+        void* args_w[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
         const bool wide_args = !quad && (wlist || kt != SCREEN_KT);
         HIP_TRY(hipLaunchKernel(kern, dim3(quad ? ctx->bmapq_blocks : ctx->bmap_blocks), dim3(1024), wide_args ? args_w : args, lds,
                                 ctx->stream));
@@ -452,6 +460,48 @@ struct screen_call : spkm_call_in {
         //  end return at once)
         const unsigned gx = (unsigned)std::min<long long>((n + 3) / 4, (long long)std::max(1, num_cus) * 32);
         HIP_TRY(hipLaunchKernel(kern, dim3(gx, (unsigned)pl.G), dim3(256), args, 0, ctx->stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(timing_end(ctx));
+        rep.skipping = pl.skip_enabled;
+        rep.pt_mode = pl.pt_mode;
+        return SPKM_OK;
+    }
+    // The LDS-tile screen of a RAGGED shard (screen_wide.hip, the RAGGED forms of k_screen_wide; policy.h,
+    // spkm_tile_screen_ragged) in the far screen's place: the tiles of kt = 8 / 16 / 32 centroids by k_prep_tiles_wide, with what
+    // that launch also leaves for the certificate, the exact list and the next call's drift, then a workgroup per blockmap
+    // entry over every point, or (a shard that skips on its bounds) the LIST form over the points of todo[].
+    template <typename IR> int screen_tile_ragged()
+    {
+        zero_flush();
+        const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
+        hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256), 0,
+                           ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p, (unsigned long long*)ctx->cmax.p,
+                           (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
+        rep.pl_last = pl.pl_last;
+        rep.kt = kt;
+        rep.tiles = pl.Gs;
+        rep.rounds_all = rep.rounds = 0;
+        rep.mode = 0;
+        const bool wlist = pl.skip_enabled;
+        const void* kern = wlist ? (kt == 32 ? (const void*)k_screen_wide<IR, 32, true, true>
+                                             : (kt == 16 ? (const void*)k_screen_wide<IR, 16, true, true> : (const void*)k_screen_wide<IR, 8, true, true>))
+                                 : (kt == 32 ? (const void*)k_screen_wide<IR, 32, false, true>
+                                             : (kt == 16 ? (const void*)k_screen_wide<IR, 16, false, true> : (const void*)k_screen_wide<IR, 8, false, true>));
+        const size_t lds = (size_t)(p + 1) * kt * 4 + 16;
+        HIP_TRY(allow_lds(ctx, kern, lds));
+        HIP_TRY(timing_begin(ctx));
+        const IR* a_ir = (const IR*)sm->ir;
+        const float* a_xf = (const float*)sm->xf;
+        const float* a_t = (const float*)ctx->t32.p;
+        int a_p = p, a_n = (int)n, a_s = 0, a_K = K, a_chunk = (int)pl.chunk;
+        const spkm_blockmap* a_bm = (const spkm_blockmap*)ctx->bmap.p;
+        float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
+        int* a_k = (int*)ctx->scr_k.p;
+        const int* a_todo = wlist ? (const int*)ctx->todo.p : (const int*)nullptr;
+        const unsigned* a_cnt = (const unsigned*)ctx->nlist.p;
+        const long long* a_jc = (const long long*)sm->jc;
+        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
+        HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmap_blocks), dim3(1024), args, lds, ctx->stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(timing_end(ctx));
         rep.skipping = pl.skip_enabled;
@@ -898,9 +948,14 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
 // call to call, point by point: the bounds stage settles the points it can, the LIST form of k_screen_far screens the others,
 // and the certify stage leaves every screened point's bounds behind (policy.h: the far case of the carry_bounds branch);
 // without the opt-in every call screens every point and leaves nothing behind for the next one.
+// tile: a RAGGED shard at a p with a 32-centroid LDS tile (spkm_shard_set_tile_ragged; kp = the tile width, 8 / 16 / 32): the
+// same stages with screen_tile_ragged in screen_far's place -- buffers() builds the blockmap and the plain f32 copy for any
+// shard that is not on the 4-lanes-per-point screen, the plan is the far case as it stands (policy.h), and the accumulation
+// behind it is form 1 (k_accumulate_sorted) at these p.
 template <typename IR>
 static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_centers, double gamma, int32_t* d_assign,
-                   double* d_mind, double* d_reduce, double* d_stats, uint64_t* d_nk_u64, int kp, spkm_screen_report* report)
+                   double* d_mind, double* d_reduce, double* d_stats, uint64_t* d_nk_u64, int kp, spkm_screen_report* report,
+                   bool tile = false)
 {
     screen_call c;
     c.kt = kp;
@@ -923,7 +978,9 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     // stays on the global atomics there is no slab, and a call with too many movers for the direct form takes the full pass
     const spkm_acc_plan ap = spkm_accumulate_form((long long)s->p, ctx->lds_max, s->sliced || ctx->sw.sliced_sums, ctx->sw.x_slab_rows);
     if (c.pl.ev_path && !c.pl.direct && ap.form == 2) c.pl.lose_events();
-    if ((rc = c.resources()) || (rc = c.bounds()) || (rc = c.screen_far<IR>()) || (rc = c.certify<IR>())) return rc;
+    if ((rc = c.resources()) || (rc = c.bounds()) || (rc = tile ? c.screen_tile_ragged<IR>() : c.screen_far<IR>()) ||
+        (rc = c.certify<IR>()))
+        return rc;
     bool no_stats = c.pl.ev_path; // (an event call is a lazy call without distances: NaN statistics)
     if ((rc = c.pl.ev_path ? c.far_events_apply<IR>(ap) : c.far_sums(&no_stats)) || (rc = c.tail(d_stats, d_nk_u64, no_stats))) return rc;
     *report = c.rep;
@@ -972,7 +1029,9 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
     }
     const bool cooling = ch.exact;
     const int kt = screen_width(ctx, s, (int)K64);
-    const int kp = kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64); // (the far screen: only where no tile serves, policy.h)
+    int kp = kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64); // (the far screen: only where no tile serves, policy.h)
+    // (a ragged shard that both turned away: the RAGGED tile screen in front of run_far's pipeline, where it opted in)
+    const bool tile_ragged = kt == 0 && kp == 0 && (kp = tile_ragged_width(ctx, s, (int)K64)) > 0;
     if (s->n > 0 && !cooling && (kt > 0 || kp > 0)) {
         ctx->ev_valid = false;
         // Hinted two-phase screen: when the unconditional two-phase form is not chosen and hints are not paused, the
@@ -982,8 +1041,8 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         const bool want_hint = ch.want_hint;
         spkm_screen_report rep;
         if (kp > 0)
-            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep)
-                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep);
+            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged)
+                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged);
         else
             rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep)
                                     : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep);

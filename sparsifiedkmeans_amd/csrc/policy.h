@@ -362,6 +362,29 @@ inline int spkm_far_screen_ragged(long long p, int K, int fixed_s, unsigned long
     if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (k_hist, as above)
     return kp;
 }
+// ... and BELOW that p, where a ragged shard ran k_assign_tile over every point and a full accumulation in every call: the
+// RAGGED form of k_screen_wide on an LDS tile (screen_wide.hip), in front of the pipeline the far screen runs -- bounds,
+// certificate, exact list, the any-p sums or the events.  Returns the tile width kt, or 0: not opted in (tile_ragged: the
+// shard, spkm_shard_set_tile_ragged, or the context, SPKM_TILE_RAGGED=1 -- a switch of its own); SPKM_NO_SCREEN; a
+// fixed-stride shard (spkm_screen_width answers for it); K < 2, an empty shard, less than 48 entries of slack; a p whose
+// 32-centroid f32 tile does not fit, (p + 1) 128 + 16 > lds_max -- the very p at which spkm_exact_tile_fits turns false (16
+// centroids of f64 are 32 of f32), so this form and spkm_far_screen_ragged never compete for a shard; more tiles than
+// workgroups, the cap of the other screens; K counters of k_hist beyond the LDS.
+// kt: the narrowest tile that holds all K in one, as the far screen chooses its plane -- 8 for K <= 8 (2 lanes per point, 32
+// points per wave), 16 for K <= 16, 32 beyond, in ceil(K / 32) tiles.
+inline int spkm_tile_ragged_kt(int K) { return K <= 8 ? 8 : (K <= 16 ? 16 : spkm_plan_kt); }
+inline int spkm_tile_screen_ragged(long long p, int K, int fixed_s, unsigned long long slack, unsigned long long nnz, size_t lds_max,
+                                   int num_cus, bool no_screen, bool tile_ragged)
+{
+    if (!tile_ragged || no_screen) return 0;
+    if (fixed_s > 0 || slack < 48 || nnz == 0 || K < 2) return 0;
+    if ((unsigned long long)(p + 1) * (unsigned)spkm_plan_kt * 4ull + 16ull > (unsigned long long)lds_max) return 0;
+    const int nb = num_cus > 0 ? num_cus : 256;
+    const int kt = spkm_tile_ragged_kt(K);
+    if ((K + kt - 1) / kt > nb) return 0;
+    if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (k_hist, as above)
+    return kt;
+}
 // Which kernel spkm_accumulate_dev runs (update.hip), from the rows, the device's LDS and the opt-in alone -- the form that
 // spkm_last_assign_tile reports in info[4]:
 //  1  k_accumulate_sorted: a cluster's sums and counts, 12 B per row, in one LDS slab of at most 64 KB (p <= 5461) --
@@ -610,7 +633,8 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
             // (ii) No refresh schedule: an eroded bound only loosens, until the point fails the test; the next screen then
             // gives it a fresh one -- the looseness of a bound costs a screened point, never a wrong answer, and mends itself.
             // A RAGGED far shard (fixed_s = 0, spkm_far_screen_ragged) takes this branch and the events below as they are:
-            // nothing here depends on the stride (the point-mode test reads bounds, the events name points).
+            // nothing here depends on the stride (the point-mode test reads bounds, the events name points).  So does a
+            // ragged shard on an LDS tile (spkm_tile_screen_ragged): its screen stage differs, its plan does not.
             pl.erode = pl.drift;
             pl.lazy_ub = true;
             // INCREMENTAL SUMS at these widths (spkm_shard_set_far_events; a plan made without the flag is the plan above in

@@ -6,7 +6,8 @@
 // (a shard that carries bounds, spkm_shard_set_wide_bounds: the points that k_bounds_steps could not settle) screens the
 // points of todo[] and writes its result planes BY LIST SLOT, as k_screen_quad's point lists do.  The LIST form also
 // exists at KT = 32, 8 lanes per point, for the columns of more than 64 entries that the 4-lanes-per-point kernel does not
-// take: a call over all their points stays with k_screen_tile.
+// take: a call over all their points stays with k_screen_tile.  A fourth template argument, RAGGED, gives every width a form
+// for shards whose columns have different lengths (below, in front of the kernel).
 //
 // Arithmetic, as the proof assumes: t = fl32(x~ + T) with T = -fl32(c), acc = fmaf(t, t, acc), one accumulator per
 // (point, centroid), over the column's s entries in storage order: s roundings of the FMA, none anywhere else.  A slot
@@ -86,7 +87,8 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // row id, 4 + sizeof(IR) bytes per lane) and hand them round inside the quad by DPP; four rounds are fetched ahead of their
 // use.  KT = 32: a point is TWO quads, and both fetch the same 4 entries, e = 4 r + (sub & 3) -- the second quad's loads hit
 // the lines the first one brought, the hand-round stays the quad_perm DPP, and nothing but the ds_read_b128 stream that
-// bounds this kernel goes through the LDS pipe (a ds_swizzle / ds_bpermute broadcast over 8 lanes would compete with it).
+// bounds this kernel goes through the LDS pipe (a ds_swizzle / ds_bpermute broadcast over 8 lanes would compete with it;
+// the RAGGED forms spend six ds_bpermute per STEP on the wave's longest column, against hundreds of ds_read_b128).
 // Nothing past a column's own s entries is read: a slot beyond the end takes x = 0 and row p without a load, and a point
 // past n reads point n - 1 and stores nothing.
 // LIST: the points are todo[0 .. counters[NL_TODO]) (k_bounds_steps in point mode; the length is read on the device, no host
@@ -106,14 +108,42 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // 2.7 (of 2 on 2: 1.5): the read is that many passes instead of one -- the price of the plain layout, kept because the rows
 // stay 16-byte aligned 128- / 64- / 32-byte runs that one b128 per lane covers.  Slots on the zero row all read one address
 // (a broadcast).
-template <typename IR, int KT, bool LIST = false>
+//
+// RAGGED (fourth template argument; a ragged shard at a p with a 32-centroid tile that opted in: spkm_shard_set_tile_ragged,
+// policy.h spkm_tile_screen_ragged; KT = 8, 16 and 32, plain and LIST -- the plain form at KT = 32 exists for RAGGED only):
+// point pt owns entries [jc[pt], jc[pt + 1]) of ir / xval instead of [pt s, (pt + 1) s); fixed_s is not read.  The
+// arithmetic, the entry order, the zero slot past a column's own end, the tie rule and the outputs are the ones above, and
+// every ragged statement sits behind `if constexpr (RAGGED)`: the fixed-stride instantiations compile to what they were.
+// A wave holds 64 / LG points with their own lengths and runs the rounds of the LONGEST of them (a wave-uniform count from
+// one reduction per step, not the shard's max_s); the shorter columns ride along on zero slots, without loads.  A point
+// past n, or a slot past the list, computes on the last valid one and stores nothing.
+// Prefetch: four rounds ahead inside a column, as before.  The addresses of a step's FIRST group of entries depend on
+// jc[pt] and jc[pt + 1], and in the LIST form those on todo[]; a step is only known once its ticket is drawn.  So the RAGGED
+// forms draw their tickets AHEAD: while step t runs, the wave holds the tickets of steps t + 1 and t + 2; jc of step t + 1
+// is read at the top of step t -- one step ahead -- and, LIST, the point id of step t + 2 there as well -- two steps ahead --
+// so that neither read waits for another one of its own step.  What remains is the one round trip the fixed-stride form
+// has too: the first group is fetched at the top of its own step (LIST, fixed stride: two, its id first).  A wave past its
+// last step has drawn two tickets nobody runs: tickets past T.  Measured (profiles/tile_ragged_ab.txt, p = 1024, K = 100,
+// N = 1e7): a call over every point 9.0 - 10.0 ms with the bounds read at the top of their own step, 8.7 - 9.5 ms drawn
+// ahead -- the reads of jc were never the larger part.  jc is read at [pt, pt + 1] for 0 <= pt < n, todo inside the list only,
+// ir / xval inside a column's own entries only.
+// EMPTY COLUMN (length 0): the far kernel's rule (screen_far.hip) -- distance 0 to every centre, the lowest index wins, now
+// and in every later call.  Answered without a load: tile 0 stores (m1 = 0, k = 0, m2 = the largest finite f32), every other
+// tile (+inf, -1, +inf); k_combine_screen certifies centroid 0 and the point is never listed (+inf as the runner-up would
+// turn the certificate's margin into a NaN).  Without the rule every blank point ties in every tile and is listed.
+// Resources of the RAGGED forms (-Rpass-analysis=kernel-resource-usage, gfx950; 16- / 32-bit row ids), beside the unchanged
+// fixed-stride ones above: <32> 110 / 110 VGPRs plain and 112 / 112 LIST, <16> 108 / 108 and 110 / 110, <8> 78 / 80 and 78 / 78; 58 SGPRs; no
+// scratch in all twelve; occupancy by registers 4 / 4 / 6 waves per SIMD, where the tile in LDS admits one workgroup per
+// CU, 4 waves per SIMD, anyway.  (Fixed stride, for comparison: <32> LIST 98 / 98, <16> 100 / 96, <8> 72 / 72, 65 / 60 SGPRs.)
+template <typename IR, int KT, bool LIST = false, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void k_screen_wide(
     const IR* __restrict__ ir, const float* __restrict__ xval, const float* __restrict__ Twt, int p, int n,
     int fixed_s, int K, const spkm_blockmap* __restrict__ bmap, int chunk_points, float* __restrict__ scr_m1,
     float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo = nullptr,
-    const unsigned* __restrict__ counters = nullptr)
+    const unsigned* __restrict__ counters = nullptr, const long long* __restrict__ jc = nullptr)
 {
-    static_assert(KT == 16 || KT == 8 || (KT == 32 && LIST), "tiles of 16 or 8 centroids; 32 for lists only");
+    static_assert(KT == 16 || KT == 8 || (KT == 32 && (LIST || RAGGED)), "tiles of 16 or 8 centroids; 32 for lists and ragged shards only");
+    constexpr float BLANK_M2 = 0x1.fffffep+127f; // an empty column's runner-up: the largest finite f32 (the header)
     constexpr int LG = KT / 4, PPW = 64 / LG, ROWB = KT * 4, UN = 4;
     constexpr int EPR = LG < 4 ? LG : 4; // entries per round: the lanes of a quad that belong to one point
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -141,7 +171,7 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
     const int esub = sub & (EPR - 1);
     const char* mytile = smem + sub * 16;
     const int s = fixed_s;
-    const int nr = (s + EPR - 1) / EPR; // rounds of EPR entries
+    int nr = (s + EPR - 1) / EPR; // rounds of EPR entries (RAGGED: of the wave's longest column, set per step)
     const int zero_off = p * ROWB;
     // (LIST: chunks small enough that every workgroup of the tile gets several, whatever the length)
     const int nv = LIST ? tp : n;
@@ -161,13 +191,68 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
         if (lane == 0) v = atomicAdd(ticket, 1u);
         return (int)__builtin_amdgcn_readfirstlane(v);
     };
-    for (int u = draw(); u < T; u = draw()) {
+    // RAGGED: the tickets are drawn AHEAD, so that a step's column bounds are on their way while the step before it runs (the
+    // header): ra.u1 / ra.u2 are the tickets after this one; s1 / s2 their first slots, -1 for none (past the tickets, or the
+    // last chunk's steps past the shard / the list); p1 / p2 this lane's points there (LIST: read from the list), clamped to
+    // points that exist; a0 / b0 and a1 / b1 = jc[pt], jc[pt + 1] of this step and of the next.  (Fixed stride: all of it unused.)
+    struct { int u1, s1, p1, u2, s2, p2; long long a0, b0, a1, b1; } ra = {0, -1, 0, 0, -1, 0, 0, 0, 0, 0};
+    auto first_slot = [&](int u) {
+        if (u >= T) return -1;
+        const int ci = u / R;
+        const int base = (bm.stream + ci * bm.nstreams) * chunk_v + (u - ci * R) * PPW;
+        return base < nv ? base : -1;
+    };
+    auto point_of = [&](int base) {
+        if (base < 0) return 0;
+        const int i = base + ps;
+        const int pt = LIST ? todo[i < nv ? i : nv - 1] : (i < n ? i : n - 1);
+        return min(max(pt, 0), n - 1);
+    };
+    int u_first = draw();
+    if constexpr (RAGGED) {
+        ra.u1 = draw();
+        ra.s1 = first_slot(ra.u1);
+        ra.p1 = point_of(ra.s1);
+        const int s0 = first_slot(u_first);
+        if (s0 >= 0) {
+            const int p0 = point_of(s0);
+            ra.a0 = jc[p0];
+            ra.b0 = jc[p0 + 1];
+        }
+    }
+    auto advance = [&](int& u) {
+        if constexpr (RAGGED) {
+            u = ra.u1; ra.a0 = ra.a1; ra.b0 = ra.b1;
+            ra.u1 = ra.u2; ra.s1 = ra.s2; ra.p1 = ra.p2;
+        } else
+            u = draw();
+    };
+    for (int u = u_first; u < T; advance(u)) {
+        if constexpr (RAGGED) {
+            if (ra.s1 >= 0) { // the next step's bounds (LIST: from an id read a step ago), in flight over this step
+                ra.a1 = jc[ra.p1];
+                ra.b1 = jc[ra.p1 + 1];
+            }
+            ra.u2 = draw();
+            ra.s2 = first_slot(ra.u2);
+            ra.p2 = point_of(ra.s2); // (LIST: the id of the step after the next)
+        }
         const int ci = u / R;
         const int base = (bm.stream + ci * bm.nstreams) * chunk_v + (u - ci * R) * PPW;
         if (base >= nv) continue; // (the last chunk's steps past the shard / the list)
         const int i = base + ps;  // the point; LIST: the list slot
-        const int pt = LIST ? todo[i < nv ? i : nv - 1] : (i < n ? i : n - 1);
-        const size_t col = (size_t)pt * (size_t)s;
+        int pt = 0;
+        if constexpr (!RAGGED) pt = LIST ? todo[i < nv ? i : nv - 1] : (i < n ? i : n - 1);
+        size_t col = (size_t)pt * (size_t)s;
+        int len = s; // this point's entries (RAGGED: its own column's)
+        if constexpr (RAGGED) {
+            col = (size_t)ra.a0;
+            len = max((int)(ra.b0 - ra.a0), 0); // (a jc that does not ascend counts as an empty column)
+            int w = (len + EPR - 1) / EPR;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) w = max(w, __shfl_xor(w, o));
+            nr = __builtin_amdgcn_readfirstlane(w);
+        }
         const float* xp = xval + col;
         const IR* rp = ir + col;
         int xv[UN], ro[UN];
@@ -175,7 +260,7 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
 #pragma unroll
             for (int c = 0; c < UN; c++) {
                 const int e = (r0 + c) * EPR + esub;
-                const bool in = e < s;
+                const bool in = RAGGED ? e < len : e < s;
                 xo[c] = in ? __builtin_bit_cast(int, xp[e]) : 0;
                 oo[c] = in ? (int)rp[e] * ROWB : zero_off;
             }
@@ -221,6 +306,16 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
 #pragma unroll
         for (int o = 1; o < LG; o <<= 1) m2 = fminf(m2, __shfl_xor(m2, o));
         const bool none = first == LG;
+        if constexpr (RAGGED) {
+            if (len == 0) { // an EMPTY column (the header): the rule, whatever the accumulators hold
+                if (sub == 0 && i < nv) {
+                    m1o[i] = g == 0 ? 0.f : __builtin_inff();
+                    m2o[i] = g == 0 ? BLANK_M2 : __builtin_inff();
+                    ko[i] = g == 0 ? 0 : -1;
+                }
+                continue;
+            }
+        }
         if (sub == (none ? 0 : first) && i < nv) {
             m1o[i] = none ? __builtin_inff() : m1;
             m2o[i] = none ? __builtin_inff() : m2;

@@ -137,6 +137,15 @@ class Shard:
         depend on it; the shard's policy state is forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_far_ragged(self.handle, 1 if on else 0), "spkm_shard_set_far_ragged")
 
+    def set_tile_ragged(self, on: bool = True):
+        """Let this shard, when it is RAGGED (columns of different lengths: a sample whose exact zeros were dropped) at a p
+        that still has a 32-centroid LDS tile (p <= 1278 with 160 KB), be screened on such a tile by the form of the
+        narrow-tile kernel that reads each point's column bounds, instead of running the all-exact tile kernel over every
+        point (spkm_shard_set_tile_ragged; off by default at the C interface; a switch of its own).  set_far_bounds() and
+        set_far_events() apply to it as to a far shard; an empty column goes to centroid 0 at distance 0 and is never
+        listed.  Outputs never depend on it; the shard's policy state is forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_tile_ragged(self.handle, 1 if on else 0), "spkm_shard_set_tile_ragged")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""

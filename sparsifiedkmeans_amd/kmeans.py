@@ -71,6 +71,10 @@ _DEFAULTS = dict(
 # exact LDS tile (p2 > 1278 with 160 KB), instead of the generic all-exact kernel (Shard.set_far_ragged).  Off by default: the
 # decision shapes of profiles/far_ragged_ab.txt have not been measured yet (record runs at small N gain 3-6x), and the
 # default goes on only once every pair of every shape wins.
+# tileRagged: the same RAGGED shard at p2 <= 1278, where every BASELINE configuration lives, is screened on an LDS tile of 8, 16
+# or 32 centroids by the ragged form of the narrow-tile kernel, with the far path's bounds and events behind it, instead of
+# the all-exact tile kernel over every point in every iteration (Shard.set_tile_ragged).  Off by default: the decision shapes
+# of profiles/tile_ragged_ab.txt were run once (every pair wins, 1.8x to 8x), and the default waits for a second series.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
 # seedTogether: the k-means++ starts of ALL replicates are drawn in one library call that shares each round's read of the
@@ -78,7 +82,7 @@ _DEFAULTS = dict(
 # than 'drop' (a drop shrinks K for the later replicates); False: replicate by replicate (_arthur).  Outputs never depend on
 # it: OUTPUT["seedPoints"] records the picks of either path.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
-              slicedSums=True, farBounds=True, farEvents=True, farRagged=False, seedTogether=True)
+              slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -428,6 +432,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_wide_bounds(bool(o["wideBounds"]))
     shard.set_far_screen(bool(o["farScreen"]))
     shard.set_far_ragged(bool(o["farRagged"]))
+    shard.set_tile_ragged(bool(o["tileRagged"]))
     shard.set_far_bounds(bool(o["farBounds"]))
     shard.set_far_events(bool(o["farEvents"]))
     shard.set_sliced_sums(bool(o["slicedSums"]))
