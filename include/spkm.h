@@ -430,6 +430,15 @@ int spkm_last_screen_points(spkm_ctx *ctx, int64_t info[2]);
  * call that took no screen or is not of this kind.  SPKM_MOVER_TILE=1 turns the form on for a context, SPKM_NO_MOVER_TILE=1
  * off (read with the other switches; DESIGN.md section 6.1 states the default).  Blocks on the stream. */
 int spkm_last_mover_steps(spkm_ctx *ctx, uint64_t out[3]);
+/* The second level: two mover tiles.  Where the mover tile is eligible and K >= 96, the pick goes on to the 64 centroids of
+ * largest drift (the 32 above are the first half) and every step is tested a third time against the largest drift outside
+ * those 64: a step that fails the first two tests but passes this one is screened against the two tiles that hold the 64 and
+ * certified against both, or sent on to the main launch of the same call.  No output changes.  out[0] = steps that passed
+ * the third test but not the second (counted on every such call, whether or not the form runs), out[1] = steps certified on
+ * the two tiles, out[2] = steps sent on; all 0 for a call that took no screen or is not of this kind.  SPKM_MOVER_TILE2=1
+ * turns the second level on for a context (it runs only where the first level does), SPKM_NO_MOVER_TILE2=1 off (read with
+ * the other switches; DESIGN.md section 6.1 states the default).  Blocks on the stream. */
+int spkm_last_mover_steps2(spkm_ctx *ctx, uint64_t out[3]);
 
 /* Unchanged-cluster shortcut of the fused call's exact pass.  A cluster (i) whose centroid is BITWISE the one the
  * previous fused call on this shard was given and (ii) that no point left or entered is not streamed again: every

@@ -150,6 +150,7 @@ def lib():
     L.spkm_last_screen_tile.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_screen_points.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_mover_steps.argtypes = [_vp, C.POINTER(C.c_uint64)]
+    L.spkm_last_mover_steps2.argtypes = [_vp, C.POINTER(C.c_uint64)]
     L.spkm_dense_assign_dev.argtypes = [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp]
     L.spkm_dense_accumulate_dev.argtypes = [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp]
     L.spkm_dense_assign_src_dev.argtypes = [_vp, _u64, _u64, C.c_int, _vp, _u64, _vp, _vp, _vp]

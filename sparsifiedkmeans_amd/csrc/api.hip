@@ -36,6 +36,7 @@ static spkm_switches read_switches()
     w.no_regroup = on("SPKM_NO_REGROUP");
     w.force_point_list = on("SPKM_FORCE_POINT_LIST");
     w.mover_tile = on("SPKM_NO_MOVER_TILE") ? -1 : (on("SPKM_MOVER_TILE") ? 1 : 0);
+    w.mover_tile2 = on("SPKM_NO_MOVER_TILE2") ? -1 : (on("SPKM_MOVER_TILE2") ? 1 : 0);
     w.wide_screen = on("SPKM_WIDE_SCREEN");
     w.wide_bounds = on("SPKM_WIDE_BOUNDS");
     w.far_screen = on("SPKM_FAR_SCREEN");
@@ -152,7 +153,7 @@ extern "C" void spkm_ctx_destroy(spkm_ctx* ctx)
     devbuf* all[] = {&ctx->tiles, &ctx->part_acc, &ctx->part_k, &ctx->blk_obj, &ctx->blk_max, &ctx->blk_imax,
                      &ctx->nk, &ctx->stats, &ctx->perm, &ctx->offs, &ctx->cursor, &ctx->items, &ctx->nitems,
                      &ctx->bmap, &ctx->blk_dff, &ctx->ct, &ctx->tmp_assign, &ctx->tmp_mind, &ctx->mscr, &ctx->dbg, &ctx->t32, &ctx->scr_m1, &ctx->scr_m2,
-                     &ctx->scr_k, &ctx->cmax, &ctx->list, &ctx->nlist, &ctx->dn_x, &ctx->dn_c, &ctx->dn_nk, &ctx->bmapq, &ctx->bmapm, &ctx->todo, &ctx->todo_m, &ctx->bstat, &ctx->nk_ev, &ctx->fin_ticket, &ctx->wgstat, &ctx->offs2, &ctx->cursor2, &ctx->hist2,
+                     &ctx->scr_k, &ctx->cmax, &ctx->list, &ctx->nlist, &ctx->dn_x, &ctx->dn_c, &ctx->dn_nk, &ctx->bmapq, &ctx->bmapm, &ctx->bmapm2, &ctx->todo, &ctx->todo_m, &ctx->todo_m2, &ctx->bstat, &ctx->nk_ev, &ctx->fin_ticket, &ctx->wgstat, &ctx->offs2, &ctx->cursor2, &ctx->hist2,
                      &ctx->items2, &ctx->perm_o, &ctx->mix_scr};
     for (devbuf* b : all) release(*b);
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);

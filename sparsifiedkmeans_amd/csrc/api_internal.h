@@ -64,6 +64,7 @@ struct spkm_switches {
     bool sliced_sums = false;     // SPKM_SLICED_SUMS: spkm_accumulate_dev on every shard of the context keeps its sums in LDS past the 64-KB slab too, a row slice at a time (k_accumulate_sliced; policy.h, spkm_accumulate_form), as if opted in (spkm_shard_set_sliced_sums)
     int x_slab_rows = 0;          // SPKM_X_SLAB_ROWS: at most this many rows per slab of k_accumulate_sliced, at any p and any number of slices (0: the default, what the LDS holds; experiments and tests)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
+    int mover_tile2 = 0;           // SPKM_NO_MOVER_TILE2: -1 / SPKM_MOVER_TILE2: +1, the second level -- steps that only the 64 largest movers unsettle, on two tiles of those (policy.h, spkm_plan_movers2); 0: the default
     int mover_tile = 0;            // SPKM_NO_MOVER_TILE: -1, steps that only the largest movers unsettle are screened like any other; SPKM_MOVER_TILE: +1, on one tile of those (policy.h, spkm_plan_movers); 0: the default
 };
 // What one fused call did on the screen path: written by the stages of that call (screen_call, api_lloyd_fused.inc), read
@@ -85,6 +86,7 @@ struct spkm_screen_report {
     bool direct_events = false;   // ... applied one by one (k_events_direct)
     bool pair_events = false;     // ... one event per mover (pair events)
     bool sums_only = false;       // the full pass left the distances out (lazy statistics)
+    bool movers2 = false;         // ... and the second level ran (spkm_plan_movers2)
     bool movers = false;          // steps that only the largest movers unsettle went to the mover tile (policy.h, spkm_plan_movers)
     bool dual = false;            // both forms were queued; the device chose (counters[NL_GATE_FULL]: the full pass)
 };
@@ -97,7 +99,7 @@ struct spkm_ctx {
     size_t mem_bytes = 0;
     // grow-only device scratch
     devbuf tiles, part_acc, part_k, blk_obj, blk_max, blk_imax, nk, stats, perm, offs, cursor, items, nitems,
-        bmap, blk_dff, ct, tmp_assign, tmp_mind, mscr, dbg, t32, scr_m1, scr_m2, scr_k, cmax, list, nlist, dn_x, dn_c, dn_nk, bmapq, bmapm, todo, todo_m, bstat, nk_ev, fin_ticket, wgstat, offs2, cursor2, hist2, items2, perm_o;
+        bmap, blk_dff, ct, tmp_assign, tmp_mind, mscr, dbg, t32, scr_m1, scr_m2, scr_k, cmax, list, nlist, dn_x, dn_c, dn_nk, bmapq, bmapm, bmapm2, todo, todo_m, todo_m2, bstat, nk_ev, fin_ticket, wgstat, offs2, cursor2, hist2, items2, perm_o;
     devbuf mix_scr; // mixed columns of the wide / short Hadamard sparsifier (at most SPKM_MIX_SCRATCH_BYTES)
     // results of an iteration handed to the host without a copy or a stream synchronisation (spkm_lloyd_iter_host): pinned host
     // memory the device maps -- [sequence number | dff^2 | obj^2 | cluster sizes], written by k_finalize_centers' last workgroup
@@ -110,6 +112,7 @@ struct spkm_ctx {
     int bmap_G = -1, bmap_blocks = 0, bmap_streams = 0;
     int bmapq_key = -1, bmapq_blocks = 0;
     int bmapm_key = -1, bmapm_blocks = 0; // ... and of the mover tile's launch (one full tile)
+    int bmapm2_key = -1, bmapm2_blocks = 0; // ... and of the launch over two mover tiles
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
     // optional per-launch timing log of the dominant assignment kernel (bench.py)

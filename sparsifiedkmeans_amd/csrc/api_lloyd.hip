@@ -312,11 +312,13 @@ static int build_blockmap(spkm_ctx* ctx, int G)
 //   entry: tile, stream = index among the tile's workgroups on this XCD, nstreams = their number,
 //          pad = NX | xcd << 8 | pairs-per-lane << 16
 // mover: the second cached map, of the mover tile's launch (1 tile, pl 4: every workgroup its own team; policy.h, spkm_plan_movers)
+// ... and with G == 2 the third, of the launch over the two mover tiles (spkm_plan_movers2): a call builds both
 static int build_blockmap_quad(spkm_ctx* ctx, int G, int pl_last, int rounds, bool mover = false)
 {
-    devbuf& buf = mover ? ctx->bmapm : ctx->bmapq;
-    int& slot_key = mover ? ctx->bmapm_key : ctx->bmapq_key;
-    int& slot_blocks = mover ? ctx->bmapm_blocks : ctx->bmapq_blocks;
+    const bool second = mover && G == 2;
+    devbuf& buf = second ? ctx->bmapm2 : (mover ? ctx->bmapm : ctx->bmapq);
+    int& slot_key = second ? ctx->bmapm2_key : (mover ? ctx->bmapm_key : ctx->bmapq_key);
+    int& slot_blocks = second ? ctx->bmapm2_blocks : (mover ? ctx->bmapm_blocks : ctx->bmapq_blocks);
     const int NB = ctx->num_cus > 0 ? ctx->num_cus : 256;
     const int key = G * 64 + pl_last * 8 + 1000003 * rounds + (ctx->sw.no_teams ? 7 : 0);
     if (slot_key == key && slot_blocks == NB) return SPKM_OK;
@@ -951,6 +953,22 @@ extern "C" int spkm_last_mover_steps(spkm_ctx* ctx, uint64_t out[3])
         unsigned v[SPKM_REPORT_WORDS] = {0};
         HIP_TRY(hipMemcpy(v, ctx->nlist.p, sizeof(v), hipMemcpyDeviceToHost));
         out[0] = v[NL_MSTEPS]; out[1] = v[NL_MCERT]; out[2] = v[NL_MSENT];
+    }
+    return SPKM_OK;
+}
+
+// The second level in the last fused call: steps that passed test B2 but not test B (counted on every eligible call, form
+// on or off), steps certified on the two mover tiles, steps they sent on to the main list.  Blocks on the stream.
+extern "C" int spkm_last_mover_steps2(spkm_ctx* ctx, uint64_t out[3])
+{
+    if (!ctx || !out) return SPKM_ERR_NULL_ARG;
+    out[0] = out[1] = out[2] = 0;
+    if (ctx->last.path == 1 && ctx->nlist.p) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        unsigned v[SPKM_REPORT_WORDS] = {0};
+        HIP_TRY(hipMemcpy(v, ctx->nlist.p, sizeof(v), hipMemcpyDeviceToHost));
+        out[0] = v[NL_MSTEPS2]; out[1] = v[NL_MCERT2]; out[2] = v[NL_MSENT2];
     }
     return SPKM_OK;
 }

@@ -46,6 +46,8 @@ static int tile_ragged_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
 
 static_assert(spkm_movers == SPKM_MOVERS && spkm_movers == SCREEN_KT && spkm_mover_kmin == SPKM_MOVER_KMIN && spkm_mover_kmax == SPKM_MOVER_KMAX &&
               SPKM_MOVER_KMAX <= BOUNDS_KTAB, "the mover tile is one full screen tile; policy.h and layout.h agree on its limits");
+static_assert(spkm_movers2 == SPKM_MOVERS2 && spkm_movers2 == 2 * SCREEN_KT && spkm_mover2_kmin == SPKM_MOVER2_KMIN,
+              "the second level is two full screen tiles; policy.h and layout.h agree on its limits");
 static_assert(spkm_plan_kt == SCREEN_KT && spkm_plan_span == BOUNDS_SPAN && spkm_plan_span_pt == BOUNDS_SPAN_PT &&
               spkm_plan_seg == SEG_POINTS, "policy.h sizes the kernels with these constants");
 
@@ -92,6 +94,7 @@ struct screen_call : spkm_call_in {
     size_t pk;
     spkm_call_plan pl;
     spkm_mover_plan mv;     // the mover tile (policy.h, spkm_plan_movers): decided after the plan, in run_screen
+    spkm_mover2_plan mv2;   // ... and its second level, two tiles (spkm_plan_movers2)
     spkm_screen_report rep; // what this call did, as its stages decide it (stored in the context when the call has gone through)
     spkm_zero_jobs zj;
     int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
@@ -136,8 +139,8 @@ struct screen_call : spkm_call_in {
         if (quad) rc = build_blockmap_quad(ctx, Gs, pl.pl_last, pl.nr);
         else rc = build_blockmap(ctx, pl.G);
         if (rc) return rc;
-        // (one tile more than the plan's where the mover tile may follow: k_prep_tiles_f32 gathers it behind the others)
-        if ((rc = ensure(ctx, ctx->t32, (size_t)(pl.G + (quad ? 1 : 0)) * (p + 1) * kt * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
+        // (two tiles more than the plan's where the mover tiles may follow: k_prep_tiles_f32 gathers them behind the others)
+        if ((rc = ensure(ctx, ctx->t32, (size_t)(pl.G + (quad ? 2 : 0)) * (p + 1) * kt * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
             (rc = ensure(ctx, ctx->scr_m1, (size_t)Gs * n * 4)) || (rc = ensure(ctx, ctx->scr_m2, (size_t)Gs * n * 4)) ||
             (rc = ensure(ctx, ctx->scr_k, (size_t)Gs * n * 4)) || (rc = ensure(ctx, ctx->list, (size_t)n * 4)))
             return rc;
@@ -267,7 +270,10 @@ struct screen_call : spkm_call_in {
         if (!mv.on) return SPKM_OK;
         int rc;
         if ((rc = build_blockmap_quad(ctx, mv.tiles, mv.pl, mv.nr, true))) return rc;
-        return ensure(ctx, ctx->todo_m, (size_t)mv.cap * 4);
+        if ((rc = ensure(ctx, ctx->todo_m, (size_t)mv.cap * 4))) return rc;
+        if (!mv2.on) return SPKM_OK;
+        if ((rc = build_blockmap_quad(ctx, mv2.tiles, mv2.pl, mv2.nr, true))) return rc;
+        return ensure(ctx, ctx->todo_m2, (size_t)mv2.cap * 4);
     }
     // The bounds test: the centroids' drift, then the steps (points) the bounds certify settled, the others listed, hints written.
     int bounds()
@@ -323,7 +329,8 @@ struct screen_call : spkm_call_in {
                                (unsigned*)ctx->nlist.p, pl.hinted ? sm->hintu : (float*)nullptr, pl.skip_enabled ? 1 : 0,
                                pl.pt_mode ? 1 : 0, (const double*)(sm->hb_cum + sm->cum_par), sm->hb_cum + (sm->cum_par ^ 1),
                                (int)pl.span, (unsigned*)ctx->bstat.p, pl.erode ? 1 : 0, sp_slack, sp_mask, sp_valid, pl.sp_reset ? 1 : 0,
-                               (const int*)same, (const int*)sm->map, mv.on ? (int*)ctx->todo_m.p : (int*)nullptr);
+                               (const int*)same, (const int*)sm->map, mv.on ? (int*)ctx->todo_m.p : (int*)nullptr,
+                               mv2.on ? (int*)ctx->todo_m2.p : (int*)nullptr);
             bstat_n = (int)blocks;
             if (pl.skip_enabled) sm->cum_par ^= 1; // the drift has been added
         }
@@ -344,7 +351,7 @@ struct screen_call : spkm_call_in {
                                0, ctx->stream, C, p, K, pl.G, gamma, (float*)ctx->t32.p,
                                (unsigned long long*)ctx->cmax.p, pl.pl_last, quad ? 1 : 0, (double*)ctx->ct.p,
                                carry ? sm->hb_centers : (double*)nullptr,
-                               mv.on ? reinterpret_cast<const int*>(sm->hb + hb_mlist(pl.npad)) : (const int*)nullptr);
+                               mv.on ? reinterpret_cast<const int*>(sm->hb + hb_mlist(pl.npad)) : (const int*)nullptr, mv2.on ? 2 : 1);
         else
             hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
                                0, ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p,
@@ -399,13 +406,33 @@ struct screen_call : spkm_call_in {
                              &a_hint, &a_hc, &a_cnt, &m_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &m_slot};
             HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmapm_blocks), dim3(1024), margs, lds, ctx->stream));
             HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_certify_movers, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
+            // The second level: the same instantiation over todo_m2[] against BOTH tiles behind the plan's (K = SPKM_MOVERS2 for
+            // the kernel: no carried remainder), results into planes 0 and 1; certified after the first level's launch and in
+            // front of the main one, like the first.
+            const int* m2_todo = (const int*)ctx->todo_m2.p;
+            if (mv2.on) {
+                const spkm_blockmap* m2_bm = (const spkm_blockmap*)ctx->bmapm2.p;
+                int m2_K = SPKM_MOVERS2, m2_slot = NL_TODO_M2;
+                void* m2args[] = {&a_ir, &a_xf, &m_t, &a_p, &a_n, &a_s, &m2_K, &m2_bm, &a_chunk, &a_m1, &a_m2, &a_k, &m_extra,
+                                  &a_hint, &a_hc, &a_cnt, &m2_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &m2_slot};
+                HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmapm2_blocks), dim3(1024), m2args, lds, ctx->stream));
+                HIP_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_certify_movers<1>, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
                                (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, (const float*)sm->xnr,
                                col_s(), (const unsigned long long*)ctx->cmax.p, sm->hb, pl.npad, K, m_todo, (int*)ctx->todo.p,
                                (unsigned*)ctx->nlist.p, (const double*)(sm->hb_cum + (sm->cum_par ^ 1)), (const double*)(sm->hb_cum + sm->cum_par));
             HIP_TRY(hipGetLastError());
+            if (mv2.on) {
+                hipLaunchKernelGGL(k_certify_movers<2>, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
+                                   (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, (const float*)sm->xnr,
+                                   col_s(), (const unsigned long long*)ctx->cmax.p, sm->hb, pl.npad, K, m2_todo, (int*)ctx->todo.p,
+                                   (unsigned*)ctx->nlist.p, (const double*)(sm->hb_cum + (sm->cum_par ^ 1)), (const double*)(sm->hb_cum + sm->cum_par));
+                HIP_TRY(hipGetLastError());
+            }
         }
         rep.movers = mv.on;
+        rep.movers2 = mv2.on;
         // (k_screen_wide: the first twelve, then the list and the counters)
         const long long* a_jc = nullptr; // (the RAGGED forms' column bounds: screen_tile_ragged)
         void* args_w[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
@@ -883,7 +910,7 @@ struct screen_call : spkm_call_in {
                            ev ? (const double*)(sm->cl_cache + cc_counts(pk)) : (const double*)nullptr, ev ? pk : (size_t)0,
                            ev ? sums : (double*)nullptr, ev ? counts : (double*)nullptr,
                            sm->nlist_pending ? (unsigned*)nullptr : sm->h_nlist_dev, sm->nlist_seq + 1u,
-                           work_steps, work_tiles, pl.nr, rep.rounds_all, work_flags, (unsigned long long)n, mv.on ? 1 : 0);
+                           work_steps, work_tiles, pl.nr, rep.rounds_all, work_flags, (unsigned long long)n, (mv.on ? 1 : 0) | (mv2.on ? 2 : 0));
         HIP_TRY(hipGetLastError());
         if (carry) { // the bounds now describe this call: its centroids are what the next call's drift is measured from
             sm->hb_K = K; sm->hb_gamma = gamma; sm->hb_valid = true;
@@ -919,6 +946,7 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
     c.plan_input(prune_a, want_hint);
     spkm_plan_call(c.pl, c, c.sm->pol);
     c.mv = spkm_plan_movers(c, c.pl, K, ctx->sw.mover_tile);
+    c.mv2 = spkm_plan_movers2(c.mv, c.pl, K, ctx->sw.mover_tile2);
     if ((rc = c.resources()) || (rc = c.mover_resources()) || (rc = c.bounds()) || (rc = c.screen<IR>())) return rc;
     // the sort buffers: at the events' sizes (2 per point, 2 K keys, SEG_EVENTS-event segments) from the start where there may be events
     const int ev = c.pl.ev_possible ? 2 : 1, max_items_ev_all = ev == 2 ? (int)((2 * c.n) / SEG_EVENTS) + 2 * K + 1 : 0;
@@ -1014,7 +1042,9 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         spkm_policy_counters c;
         c.listed = h[NL_LISTED]; c.ambig = h[NL_AMBIG]; c.early = h[NL_EARLY]; c.skipped = h[NL_SKIPPED];
         c.kept = h[NL_KEPT]; c.movers = h[NL_MOVERS];
-        c.msteps = h[NL_MCERT]; // (the steps settled on the mover tile never reached the main launch; 0 with the form off)
+        c.msteps = (double)h[NL_MCERT] + (double)h[NL_MCERT2]; // (the steps settled on the mover tiles never reached the main launch; 0 with the forms off)
+        c.pairs2 = 2.0 * ((double)h[NL_MCERT2] + (double)h[NL_MSENT2]); // (the launch over two mover tiles: every listed step on both)
+        c.early2 = h[NL_MEARLY2];
         c.full_opened = h[NL_GATE_FULL] != 0u;
         c.one_cluster_steps = h[NL_ONE_CLUSTER];
         c.may_regroup = sm->pend_full && sm->lazy && !sm->regroup_done;

@@ -29,6 +29,11 @@ enum spkm_counter_slot : int {
     NL_CHECK_DIFF = 20,    // places where d_assign differs from the library's copy (count_assign_diff)
     NL_ONE_CLUSTER = 21,   // 16-point steps whose points share one cluster
     NL_MEARLY = 22,        // steps the hinted mover launch finished early (NL_EARLY stays the main launch's)
+    NL_MSTEPS2 = 23,       // steps that only the SPKM_MOVERS2 largest movers unsettle: test B2 passed, test B did not (k_bounds_steps)
+    NL_TODO_M2 = 24,       // length of todo_m2[]: those steps, listed for the two mover tiles (0 with the second level off)
+    NL_MCERT2 = 25,        // steps certified on the two mover tiles (k_certify_movers<2>) ...
+    NL_MSENT2 = 26,        // ... and steps it sent on to todo[] instead
+    NL_MEARLY2 = 27,       // (step, tile) pairs the hinted launch over todo_m2[] finished early (moved here from NL_EARLY by k_certify_movers<2>)
     NL_PER_CALL_END = 32,
     NL_EXACT_TOTAL = 32,    // u64, running: points the exact passes processed
     NL_ROUNDS_DONE = 34,    // u64, running: screen rounds executed for all centroids of a tile
@@ -37,7 +42,7 @@ enum spkm_counter_slot : int {
     NL_SCREENED = 40,       // points this call screened (written by every call's tail, never zeroed)
     NL_WORDS = 64           // the buffer
 };
-constexpr int SPKM_REPORT_WORDS = 24;     // counters a fused call reports to the host, followed by the report's number ...
+constexpr int SPKM_REPORT_WORDS = 28;     // counters a fused call reports to the host, followed by the report's number ...
 constexpr int SPKM_REPORT_BUF_WORDS = 32; // ... in this much pinned host memory (spkm_shard::h_nlist)
 // the two ranges zeroed at the top of a call: the per-call words on either side of NL_SKIPPED_TOTAL
 constexpr int NL_ZERO_A = 0, NL_ZERO_A_END = NL_SKIPPED_TOTAL;
@@ -54,6 +59,9 @@ static_assert(NL_SCREENED < NL_WORDS && NL_ONE_CLUSTER < NL_PER_CALL_END, "every
 static_assert(nl_reported(NL_MSTEPS) && nl_reported(NL_MCERT) && nl_reported(NL_MSENT) && nl_zeroed(NL_MSTEPS) && nl_zeroed(NL_TODO_M) &&
               nl_zeroed(NL_MCERT) && nl_zeroed(NL_MSENT) && nl_zeroed(NL_MEARLY) && NL_MEARLY < SPKM_REPORT_WORDS,
               "the mover tile's counters are per-call words of the report");
+static_assert(nl_reported(NL_MSTEPS2) && nl_reported(NL_MCERT2) && nl_reported(NL_MSENT2) && nl_reported(NL_MEARLY2) && nl_zeroed(NL_MSTEPS2) &&
+              nl_zeroed(NL_TODO_M2) && nl_zeroed(NL_MCERT2) && nl_zeroed(NL_MSENT2) && nl_zeroed(NL_MEARLY2),
+              "... and so are the second level's");
 static_assert(nl_total_ok(NL_SKIPPED_TOTAL) && nl_total_ok(NL_EXACT_TOTAL) && nl_total_ok(NL_ROUNDS_DONE) &&
               nl_total_ok(NL_ROUNDS_FULL) && nl_total_ok(NL_SCREENED_TOTAL),
               "a running total is an aligned 64-bit pair that the per-call zeroing leaves alone");
@@ -72,17 +80,22 @@ enum { NI_FULL = 0, NI_EVENTS = 1, NI_PAIR_CHUNKS = 2, NI_REGROUP = 4, NI_WORDS 
 //   ub[npad] | lb[npad] | assignment[npad] (int32) | delta[K] | dmax | ... | hterm[K] at HB_HTERM | ... | movers at HB_MOVERS
 //   delta[k], dmax   drift of every centroid on a point's support (k_center_drift) and its maximum
 //   hterm[k]         hint_w x (full 2-norm drift)^2 per centroid: the hints' estimate, not a bound
-//   movers           the SPKM_MOVERS centroids of largest drift, picked by k_center_drift's last workgroup (K <= SPKM_MOVER_KMAX):
-//                    ticket (unsigned) | d_R = the largest drift among the OTHER centroids (float) | ... | list[SPKM_MOVERS]
-//                    (int, by rank) | slot[K] (int: a centroid's place in the list, -1: not a mover)
+//   movers           the SPKM_MOVERS2 centroids of largest drift, picked by k_center_drift's last workgroup (K <= SPKM_MOVER_KMAX):
+//                    ticket (unsigned) | d_R, d_R2 = the largest drift among the centroids outside the first SPKM_MOVERS /
+//                    outside all SPKM_MOVERS2 (two floats) | ... | list[SPKM_MOVERS2] (int, by rank: the first SPKM_MOVERS
+//                    are the first level's M) | slot[K] (int: a centroid's place in the list, -1: not among them)
 constexpr int HB_KMAX = 65536;           // the largest K a fused call takes
 constexpr int HB_HTERM = HB_KMAX + 16;   // within the tail
 constexpr int SPKM_MOVERS = 32;          // centroids on the mover tile: one full tile of the 4-lanes-per-point screen
+constexpr int SPKM_MOVERS2 = 64;         // ... and on the second level's two tiles (policy.h, spkm_plan_movers2)
 constexpr int SPKM_MOVER_KMIN = 64, SPKM_MOVER_KMAX = 1024; // (policy.h, spkm_plan_movers)
+constexpr int SPKM_MOVER2_KMIN = 96;                        // (policy.h, spkm_plan_movers2)
 constexpr int HB_MOVERS = 2 * HB_KMAX + 32;                 // behind hterm
-constexpr int HB_MTICKET = HB_MOVERS, HB_MDR = HB_MOVERS + 1, HB_MLIST = HB_MOVERS + 16, HB_MSLOT = HB_MLIST + SPKM_MOVERS;
+constexpr int HB_MTICKET = HB_MOVERS, HB_MDR = HB_MOVERS + 1, HB_MLIST = HB_MOVERS + 16, HB_MDR2 = HB_MDR + 1, HB_MSLOT = HB_MLIST + SPKM_MOVERS2;
 constexpr int HB_TAIL = HB_MSLOT + SPKM_MOVER_KMAX + 16; // floats behind the three per-point arrays
 static_assert(HB_HTERM + HB_KMAX <= HB_MOVERS && HB_MLIST % 4 == 0, "the movers lie behind hterm[], the list 16-byte aligned");
+static_assert(HB_MDR2 < HB_MLIST && HB_MLIST + SPKM_MOVERS2 <= HB_MSLOT && SPKM_MOVERS2 == 2 * SPKM_MOVERS,
+              "both drifts lie in front of the list, the list of two tiles in front of the slots");
 constexpr long long hb_lb(long long npad) { return npad; }
 constexpr long long hb_assign(long long npad) { return 2 * npad; }
 constexpr long long hb_delta(long long npad) { return 3 * npad; }
@@ -90,6 +103,7 @@ constexpr long long hb_dmax(long long npad, int K) { return 3 * npad + K; }
 constexpr long long hb_hterm(long long npad) { return 3 * npad + HB_HTERM; }
 constexpr long long hb_mticket(long long npad) { return 3 * npad + HB_MTICKET; }
 constexpr long long hb_mdr(long long npad) { return 3 * npad + HB_MDR; }
+constexpr long long hb_mdr2(long long npad) { return 3 * npad + HB_MDR2; }
 constexpr long long hb_mlist(long long npad) { return 3 * npad + HB_MLIST; }
 constexpr long long hb_mslot(long long npad) { return 3 * npad + HB_MSLOT; }
 constexpr size_t hb_floats(long long npad) { return (size_t)3 * npad + HB_TAIL; }

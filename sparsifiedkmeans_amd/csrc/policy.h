@@ -49,6 +49,7 @@ SPKM_HD constexpr int quad_split(int nr, bool pts = false)
 struct spkm_policy_counters {
     double listed = 0, ambig = 0, early = 0, skipped = 0, kept = 0, movers = 0;
     double msteps = 0;        // steps that went to the mover tile's list and not to the main launch (0: no such list)
+    double pairs2 = 0, early2 = 0; // the second level's launch (spkm_plan_movers2): its (step, tile) pairs and those it finished early (0: it did not run)
     bool full_opened = false; // a call that queued both accumulation forms: the device opened the full pass (k_pick_form)
     double one_cluster_steps = 0; // 16-point steps whose points all sit in one cluster (counted by a call over every point)
     bool may_regroup = false;     // that call screened every point of a lazy shard not yet regrouped (pend_full, lazy, !regroup_done)
@@ -143,12 +144,17 @@ struct spkm_policy {
             // hinted call: worth it only if a fair share of the (step, tile) pairs was finished early, and only while the
             // hints do not mislead (many listed points).  Steps skipped on the carried bounds never got as far as their hints.
             // ... and the steps certified on the mover tile never reached the main launch, whose pairs `early` counts.
-            const double steps = std::max(0.0, n / 16.0 - c.skipped - c.msteps) * t;
+            // The second level's launch is the same hinted instantiation over the steps it took from the main launch -- the
+            // easy ones, which finish early: its pairs and early finishes are judged with the main launch's (without them a
+            // main launch left with the hard third of the steps looked poor in iterations 5-6 of the headline run, and the
+            // hints were paused for iteration 7: +3.8 ms).  The first level's launch stays out, as before.
+            const double steps = std::max(0.0, n / 16.0 - c.skipped - c.msteps) * t + c.pairs2;
+            const double early = c.early + c.early2;
             // early or late split: a run's first three hinted calls use the late one, then the early one; an early call
             // that finishes fewer than 15 % of its pairs early sends the next two back to the late split.  (The late
             // split's own early-finish share says little about when to leave it -- it moves from 0.37 to 0.44 over the
             // iterations in which the early split's goes from 0.1 to 0.4 -- so the way back is a fixed count.)
-            const double share = steps > 0.0 ? c.early / steps : 1.0;
+            const double share = steps > 0.0 ? early / steps : 1.0;
             const bool was_late = hint_late_pending;
             // (only while a good part of the data is on the screen: with most steps settled by the carried bounds the few
             //  that are left are the hard ones, and the late split just costs more rounds on them)
@@ -156,7 +162,7 @@ struct spkm_policy {
             if (!was_late && share < 0.15 && steps > 0.25 * all_pairs && hint_late_left == 0) hint_late_left = 2;
             hint_late = hint_late_left > 0;
             const bool fallback_to_late = !was_late && hint_late && quad_split_late(nr) > quad_split(nr);
-            const bool poor = c.early < 0.05 * steps && steps > 0.01 * n / 16.0;
+            const bool poor = early < 0.05 * steps && steps > 0.01 * n / 16.0;
             if (c.listed > 0.005 * n || (poor && !fallback_to_late)) {
                 hint_fail_streak = std::min(hint_fail_streak + 1, 4);
                 hint_cooldown = 1 << hint_fail_streak; // early iterations mislead briefly, not for 16 calls
@@ -765,6 +771,52 @@ inline spkm_mover_plan spkm_plan_movers(const spkm_call_in& in, const spkm_call_
     m.eligible = in.quad && K >= spkm_mover_kmin && K <= spkm_mover_kmax && pl.drift && pl.skip_enabled && !pl.pt_mode &&
                  !pl.sp_on && pl.erode && !in.has_map;
     m.on = m.eligible && (sw > 0 || (sw == 0 && spkm_mover_default_on));
+    m.cap = m.on ? pl.npad / 16 + 1 : 0;
+    return m;
+}
+// ---- the second level: two mover tiles ----
+// While more than spkm_movers centroids still migrate, the drift of rank spkm_movers is as large as every slack and d_R spoils
+// test B.  So the pick goes on to M2, the spkm_movers2 centroids of largest drift by the same key -- M is its first half,
+// list[0..spkm_movers) is the first level's list -- and d_R2, the largest drift among the centroids outside M2.
+// k_bounds_steps tests every point a third time with d_R2 (test B2); a step that passes B2 but neither A nor B is screened
+// against the TWO tiles that hold M2 and certified against both planes by k_certify_movers<2>, or sent on to the main list.
+// A step chooses one tile or two by its own bounds: no threshold on the drifts.
+// rank < spkm_movers2: at list[rank], slot = rank; rank == spkm_movers: its drift is d_R; rank == spkm_movers2: d_R2
+// K < spkm_mover2_kmin (no second level there, spkm_plan_movers2): d_R2 is infinite, nothing passes B2 and nothing is counted.
+constexpr int spkm_movers2 = 64, spkm_mover2_kmin = 96;
+// The whole pick on the host: list[spkm_movers2], slot[K] (0 .. spkm_movers2 - 1, or -1), dr[2] = d_R, d_R2.
+inline void spkm_pick_movers2(const float* delta, int K, int* list, int* slot, float* dr)
+{
+    float dmax = 0.f, dn = __builtin_inff(), dn2 = __builtin_inff();
+    bool bad = false;
+    for (int k = 0; k < K; k++) {
+        const int r = spkm_mover_rank(delta, K, k);
+        slot[k] = r < spkm_movers2 ? r : -1;
+        if (r < spkm_movers2) list[r] = k;
+        if (r == spkm_movers) dn = delta[k];
+        if (r == spkm_movers2 && K >= spkm_mover2_kmin) dn2 = delta[k];
+        if (!(delta[k] >= 0.f)) bad = true; else dmax = std::max(dmax, delta[k]);
+    }
+    dr[0] = spkm_mover_dr(dn, bad ? __builtin_inff() : dmax);
+    dr[1] = spkm_mover_dr(dn2, bad ? __builtin_inff() : dmax);
+}
+// Which calls take the second level.  eligible: where the first level is, and K >= spkm_mover2_kmin -- below that two tiles
+// are more than half of the main launch's tile visits.  Eligible calls count the steps that pass B2 only (NL_MSTEPS2), form
+// on or off; `on` (the first level runs and the switch allows it) lists them and runs the launch over two tiles and its
+// certificate.  sw: -1 SPKM_NO_MOVER_TILE2=1, +1 SPKM_MOVER_TILE2=1, 0 the default (spkm_mover2_default_on: DESIGN section 7,
+// the mover tile's own decision rule; profiles/mover_tiles2_ab.txt holds the pairs).
+constexpr bool spkm_mover2_default_on = true;
+struct spkm_mover2_plan {
+    bool eligible = false, on = false;
+    long long cap = 0;            // entries of the third list
+    int tiles = 2, pl = 4, nr = 0; // its launch's blockmap: two full tiles, the call's rounds
+};
+inline spkm_mover2_plan spkm_plan_movers2(const spkm_mover_plan& first, const spkm_call_plan& pl, int K, int sw)
+{
+    spkm_mover2_plan m;
+    m.nr = pl.nr;
+    m.eligible = first.eligible && K >= spkm_mover2_kmin;
+    m.on = m.eligible && first.on && (sw > 0 || (sw == 0 && spkm_mover2_default_on));
     m.cap = m.on ? pl.npad / 16 + 1 : 0;
     return m;
 }

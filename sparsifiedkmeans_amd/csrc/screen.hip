@@ -49,10 +49,11 @@
 __global__ void k_prep_tiles_f32(const double* __restrict__ C, int p, int K, int G, double gamma,
                                  float* __restrict__ T32, unsigned long long* __restrict__ cmax_bits, int pl_last,
                                  int swz, double* __restrict__ Cs, double* __restrict__ keep,
-                                 const int* __restrict__ mlist = nullptr)
+                                 const int* __restrict__ mlist = nullptr, int mtiles = 1)
 {
     // mlist != nullptr (the mover tile; policy.h, spkm_plan_movers): one more full tile, tile G, whose slot kk holds centroid
-    // mlist[kk] -- the SPKM_MOVERS centroids of largest drift, as k_center_drift's last workgroup picked them in this call
+    // mlist[kk] -- the SPKM_MOVERS centroids of largest drift, as k_center_drift's last workgroup picked them in this call;
+    // mtiles == 2 (the second level, spkm_plan_movers2): a second one behind it, tile G + 1, through mlist[SPKM_MOVERS + kk]
     // Two more views of the same centres ride along (they were launches of their own: a small shard's settled iteration is
     // a chain of ~5-us kernels): Cs[r*K + k] = C[k*p + r] / gamma, row-major for the exact list kernel (k_assign_list),
     // and keep = C itself, the library's copy that the NEXT call's drift is measured from (k_center_drift has already
@@ -70,7 +71,7 @@ __global__ void k_prep_tiles_f32(const double* __restrict__ C, int p, int K, int
             }
         }
     }
-    const size_t total = (size_t)(G + (mlist != nullptr ? 1 : 0)) * (p + 1) * SCREEN_KT;
+    const size_t total = (size_t)(G + (mlist != nullptr ? mtiles : 0)) * (p + 1) * SCREEN_KT;
     double mx = 0.0;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         int kk = (int)(t % SCREEN_KT);
@@ -79,7 +80,7 @@ __global__ void k_prep_tiles_f32(const double* __restrict__ C, int p, int K, int
         const int g = (int)(rest / (p + 1));
         if (swz) kk ^= ((r >> 1) & 3) << 2; // physical -> logical position
         int k = g * SCREEN_KT + kk;
-        if (g == G) k = mlist[kk];
+        if (g >= G) k = mlist[(g - G) * SCREEN_KT + kk];
         else if (g == G - 1 && pl_last == 5) {
             const size_t local = t - (size_t)g * (p + 1) * SCREEN_KT; // compact (p+1) x 4 table first, rest unused
             r = (int)(local >> 2);
@@ -567,9 +568,10 @@ __global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__
                                                       int* __restrict__ mslot = nullptr)
 {
     // mticket != nullptr (SPKM_MOVER_KMIN <= K <= SPKM_MOVER_KMAX; policy.h, spkm_plan_movers): the workgroup that finishes
-    // last picks the movers -- mlist[r] = the centroid of rank r < SPKM_MOVERS by (drift descending, index ascending),
-    // mslot[k] = centroid k's rank or -1, *mdr = the drift of rank SPKM_MOVERS, i.e. the largest among the others (infinite
-    // when any drift is) -- and leaves the ticket at 0 for the next call.  No launch of its own: the settled iteration is launch-bound.
+    // last picks the movers -- mlist[r] = the centroid of rank r < SPKM_MOVERS2 by (drift descending, index ascending: the
+    // first SPKM_MOVERS are the first level's), mslot[k] = centroid k's rank or -1, mdr[0] = the drift of rank SPKM_MOVERS, i.e.
+    // the largest among the others, mdr[1] = the drift of rank SPKM_MOVERS2 (infinite below SPKM_MOVER2_KMIN centroids; both infinite when any drift is; policy.h,
+    // spkm_pick_movers2) -- and leaves the ticket at 0 for the next call.  No launch of its own: the settled iteration is launch-bound.
     __shared__ double sh[4][4];
     __shared__ int s_diff;
     __shared__ unsigned s_hist[256];
@@ -674,10 +676,12 @@ __global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__
             __syncthreads();
             for (int j = threadIdx.x; j < K; j += blockDim.x) {
                 const int r = spkm_mover_rank(s_dl, K, j);
-                mslot[j] = r < SPKM_MOVERS ? r : -1;
-                if (r < SPKM_MOVERS) mlist[r] = j;
-                if (r == SPKM_MOVERS) *mdr = spkm_mover_dr(s_dl[j], dmx);
+                mslot[j] = r < SPKM_MOVERS2 ? r : -1;
+                if (r < SPKM_MOVERS2) mlist[r] = j;
+                if (r == SPKM_MOVERS) mdr[0] = spkm_mover_dr(s_dl[j], dmx);
+                if (r == SPKM_MOVERS2 && K >= SPKM_MOVER2_KMIN) mdr[1] = spkm_mover_dr(s_dl[j], dmx);
             }
+            if (threadIdx.x == 0 && K < SPKM_MOVER2_KMIN) mdr[1] = __builtin_inff(); // (no second level there: spkm_pick_movers2)
             if (threadIdx.x == 0) *mticket = 0u;
         }
     }
@@ -743,6 +747,10 @@ __device__ __forceinline__ void st_points(T* __restrict__ p, size_t at, bool wid
 // counters[NL_TODO_M]) INSTEAD of todo[], its points' upper bounds are left as they are (k_certify_movers moves them, or
 // the step goes on to todo[] and k_combine_screen / k_assign_list write them) and the caller's buffer is repaired as for a
 // settled step.  cum_out, NL_SKIPPED, NL_KEPT and the hints are test A's, as without MOV.
+// The second level (policy.h, spkm_plan_movers2): a third comparison per point, test B2, the same with d_R2 -- the largest
+// drift among the centroids outside the SPKM_MOVERS2 largest movers -- in place of d_R.  A step whose 16 points all pass B2
+// but pass neither A nor B as a step is counted in counters[NL_MSTEPS2]; with todo_m2 != nullptr it is appended to todo_m2[]
+// (length counters[NL_TODO_M2]) instead of todo[] and treated like a step of todo_m[] in everything else.
 template <bool MAPPED, bool MOV = false> // MAPPED: a regrouped shard (map != nullptr) -- a compile-time flag: with the choice made at run time the
 // compiler puts the caller-buffer load behind a branch, apart from the other loads of its group (44 -> 113 us per settled call)
 __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, long long npad, long long n, int K,
@@ -756,7 +764,8 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
                                                       int* __restrict__ sp_valid = nullptr, int sp_reset = 0,
                                                       const int* __restrict__ same = nullptr,
                                                       const int* __restrict__ map = nullptr,
-                                                      int* __restrict__ todo_m = nullptr)
+                                                      int* __restrict__ todo_m = nullptr,
+                                                      int* __restrict__ todo_m2 = nullptr)
 {
     // assign == nullptr: the caller's buffer is known to hold the library's copy already (lazy statistics, the same buffer as
     // in the previous call: spkm.h) -- it is neither read nor restored.  map != nullptr (a regrouped shard, api_lloyd.hip): point i of
@@ -810,14 +819,21 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
         const double cr = *cum_in + (double)bnd[hb_mdr(npad)] * (1.0 + 1e-12);
         cum_r = cr + fabs(cr) * 0x1p-52;
     }
-    static_assert(BOUNDS_SPAN / 16 <= BOUNDS_SPAN_PT / 2, "both step lists of a span fit s_todo[]");
+    double cum_r2 = __builtin_inf();
+    if constexpr (MOV) {
+        const double cr = *cum_in + (double)bnd[hb_mdr2(npad)] * (1.0 + 1e-12);
+        cum_r2 = cr + fabs(cr) * 0x1p-52;
+    }
+    static_assert(BOUNDS_SPAN / 16 <= BOUNDS_SPAN_PT / 4, "the three step lists of a span fit s_todo[]");
     int* const s_todo_m = s_todo + BOUNDS_SPAN_PT / 2;
-    __shared__ unsigned s_cnt_m, s_pos_m, s_mst;
+    int* const s_todo_m2 = s_todo + 3 * (BOUNDS_SPAN_PT / 4);
+    __shared__ unsigned s_cnt_m, s_pos_m, s_mst, s_cnt_m2, s_pos_m2, s_mst2;
     const bool list_m = MOV && todo_m != nullptr;
-    unsigned nmst = 0;
+    const bool list_m2 = MOV && todo_m2 != nullptr;
+    unsigned nmst = 0, nmst2 = 0;
     const int lane = threadIdx.x & 63;
     unsigned nskip = 0, nkept = 0;
-    if (threadIdx.x == 0) { s_cnt = 0; s_skip = 0; s_kept = 0; s_cnt_m = 0; s_mst = 0; }
+    if (threadIdx.x == 0) { s_cnt = 0; s_skip = 0; s_kept = 0; s_cnt_m = 0; s_mst = 0; s_cnt_m2 = 0; s_mst2 = 0; }
     __syncthreads();
     constexpr int UN = 4; // consecutive points per thread
     // delta[k] and hterm[k], gathered by every point's assignment: from LDS (K <= BOUNDS_KTAB), else from global memory
@@ -956,12 +972,17 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
         if (!skip_enabled) continue;
         bool keep[UN], st_er[UN];
         bool keep_b = true; // MOV: this thread's points all pass test B (or test A: cum_r <= cum_now, spelt out for the roundings)
+        bool keep_b2 = true; // ... all pass test B2 (or A, or B)
         float ubn[UN];
         unsigned long long b[UN];
 #pragma unroll
         for (int c = 0; c < UN; c++) {
             keep[c] = !in[c] || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_now) * 0.999999; // false for NaN
-            if constexpr (MOV) keep_b = keep_b && (keep[c] || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_r) * 0.999999);
+            if constexpr (MOV) {
+                const bool kb = keep[c] || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_r) * 0.999999;
+                keep_b = keep_b && kb;
+                keep_b2 = keep_b2 && (kb || (double)(ubv[c] + dav[c]) * 1.000001 < ((double)lbv[c] - cum_r2) * 0.999999);
+            }
             b[c] = __ballot(keep[c]);
             nkept += (unsigned)__popcll(__ballot(keep[c] && in[c]));
             ubn[c] = (erode && dav[c] > 0.f) ? __double2float_ru((double)ubv[c] + (double)dav[c]) : ubv[c]; // Hamerly's update
@@ -982,14 +1003,19 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
         const bool live_step = (i0 - UN * (lane & (LPS - 1))) < n; // the step has at least one point
         const bool lead_lane = (lane & (LPS - 1)) == 0 && live_step;
         bool mstep = false; // MOV: all 16 points pass B, not all pass A
+        bool mstep2 = false; // ... all 16 pass B2, not all pass B
         if constexpr (MOV) {
             const unsigned long long bqb = __ballot(keep_b);
             mstep = !whole && ((unsigned)(bqb >> (lane & ~(LPS - 1))) & ((1u << LPS) - 1u)) == (1u << LPS) - 1u;
             nmst += (unsigned)__popcll(__ballot(lead_lane && mstep));
+            const unsigned long long bqb2 = __ballot(keep_b2);
+            mstep2 = !whole && !mstep && ((unsigned)(bqb2 >> (lane & ~(LPS - 1))) & ((1u << LPS) - 1u)) == (1u << LPS) - 1u;
+            nmst2 += (unsigned)__popcll(__ballot(lead_lane && mstep2));
             mstep = mstep && list_m; // (from here on: the step goes to the second list)
-            if (erode) { // (the eroded bounds of a step on the second list are k_certify_movers' to store)
+            mstep2 = mstep2 && list_m2; // (... to the third)
+            if (erode) { // (the eroded bounds of a step on the second or third list are k_certify_movers' to store)
 #pragma unroll
-                for (int c = 0; c < UN; c++) st_er[c] = st_er[c] && !mstep;
+                for (int c = 0; c < UN; c++) st_er[c] = st_er[c] && !mstep && !mstep2;
                 st_points<UN>(bnd, (size_t)i0, wide, st_er, ubn);
             }
         }
@@ -1022,7 +1048,7 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
             for (int c = 0; c < UN; c++) {
                 // a caller that passes the same buffer call after call already holds this value: a 4-B read instead of a
                 // 4-B store (a gigabyte of stores costs as much as several of loads here)
-                if ((skip || mstep) && in[c] && have_cur && curv[c] != apv[c]) assign[MAPPED ? (long long)map[i0 + c] : i0 + c] = apv[c];
+                if ((skip || mstep || mstep2) && in[c] && have_cur && curv[c] != apv[c]) assign[MAPPED ? (long long)map[i0 + c] : i0 + c] = apv[c];
                 st_h[c] = !skip && in[c] && hintu != nullptr;
             }
             if (hintu != nullptr) st_points<UN>(hintu, (size_t)i0, wide, st_h, hv);
@@ -1034,8 +1060,15 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
                     bp = __builtin_amdgcn_readfirstlane(bp);
                     if (lead_lane && mstep) s_todo_m[bp + __popcll(lmm & ((1ull << lane) - 1ull))] = (int)(i0 >> 4);
                 }
+                const unsigned long long lmm2 = __ballot(lead_lane && mstep2);
+                if (lmm2) {
+                    unsigned bp = 0;
+                    if (lane == 0) bp = atomicAdd(&s_cnt_m2, (unsigned)__popcll(lmm2));
+                    bp = __builtin_amdgcn_readfirstlane(bp);
+                    if (lead_lane && mstep2) s_todo_m2[bp + __popcll(lmm2 & ((1ull << lane) - 1ull))] = (int)(i0 >> 4);
+                }
             }
-            const bool lead = lead_lane && !skip && !mstep;
+            const bool lead = lead_lane && !skip && !mstep && !mstep2;
             const unsigned long long lm = __ballot(lead);
             if (lm) {
                 unsigned basepos = 0;
@@ -1079,17 +1112,24 @@ __global__ __launch_bounds__(256) void k_bounds_steps(float* __restrict__ bnd, l
             __syncthreads();
             for (unsigned j = threadIdx.x; j < s_cnt_m; j += 256) todo_m[s_pos_m + j] = s_todo_m[j];
         }
+        if (list_m2) { // (uniform) ... and the third
+            if (threadIdx.x == 0) s_pos_m2 = s_cnt_m2 ? atomicAdd(counters + NL_TODO_M2, s_cnt_m2) : 0u;
+            __syncthreads();
+            for (unsigned j = threadIdx.x; j < s_cnt_m2; j += 256) todo_m2[s_pos_m2 + j] = s_todo_m2[j];
+        }
     }
     __syncthreads();
-    if (threadIdx.x == 0) { s_cnt = 0; s_cnt_m = 0; }
+    if (threadIdx.x == 0) { s_cnt = 0; s_cnt_m = 0; s_cnt_m2 = 0; }
     __syncthreads();
     }
     }
     if (lane == 0 && nskip) atomicAdd(&s_skip, nskip);
     if (lane == 0 && nkept) atomicAdd(&s_kept, nkept);
     if (MOV && lane == 0 && nmst) atomicAdd(&s_mst, nmst);
+    if (MOV && lane == 0 && nmst2) atomicAdd(&s_mst2, nmst2);
     __syncthreads();
     if (MOV && threadIdx.x == 0 && s_mst) atomicAdd(counters + NL_MSTEPS, s_mst); // (one per workgroup that saw such a step)
+    if (MOV && threadIdx.x == 0 && s_mst2) atomicAdd(counters + NL_MSTEPS2, s_mst2);
     if (threadIdx.x == 0) { // points that passed the test (either mode), steps whose 16 points all passed: k_call_tail adds them up
         blkstat[BS_STRIDE * blockIdx.x + BS_KEPT] = s_kept;
         blkstat[BS_STRIDE * blockIdx.x + BS_SKIPPED] = s_skip;
@@ -1618,6 +1658,17 @@ __global__ __launch_bounds__(256) void k_combine_screen(const float* __restrict_
 // main launch of the same call screens it in full: no point changes cluster, is listed or records an event here, and
 // nothing is written to the caller's buffer, the library's copy of the assignment, the touched flags or the events.
 // 4 consecutive points per thread, 16-byte accesses, a step = 4 neighbouring lanes -- k_combine_screen's data movement.
+// PLANES == 2 (the second level; policy.h, spkm_plan_movers2): the steps of todo_m2[] -- the list passed as todo_m, its length
+// counters[NL_TODO_M2] -- after the launch over the TWO tiles of M2: plane t holds the leader of tile t (slots 32 t .. 32 t + 31),
+// its estimate and the lower bound of that tile's others.  With L_R2 = lb_stored - cum_R2 (d_R2 in place of d_R) and, per
+// plane, L_t = min(sqrt m1_t - eps, sqrt m2_t - eps) floored at 0:
+//   a not in M2:   U (1 + 2^-45) < min(L_R2, L_0, L_1) (1 - 2^-45);  ub as above, lb_stored <- that minimum + cum_now.
+//   a in plane t:  plane t's leader is a and (sqrt m1_t + eps)(1 + 2^-45) < min(sqrt m2_t - eps, L_other, L_R2)(1 - 2^-45);
+//                  ub <- sqrt m1_t + eps rounded up, lb_stored <- that minimum + cum_now.
+// Both planes must hold finite estimates.  Certified and sent-on steps: counters[NL_MCERT2] / counters[NL_MSENT2].  Its first
+// thread also moves the early finishes that the launch over todo_m2[] counted -- k_screen_quad knows two lists, so they
+// arrive in counters[NL_EARLY], which the main launch has not touched yet -- to counters[NL_MEARLY2].
+template <int PLANES = 1>
 __global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict__ scr_m1, const float* __restrict__ scr_m2,
                                                         const int* __restrict__ scr_k, long long n,
                                                         const float* __restrict__ xnr, int fixed_s,
@@ -1628,7 +1679,13 @@ __global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict_
                                                         const double* __restrict__ cum_in_p, const double* __restrict__ cum_now_p)
 {
     constexpr int PPT = 4, WGP = 256 * PPT;
-    const long long total = (long long)counters[NL_TODO_M] * 16;
+    static_assert(PLANES == 1 || PLANES == 2, "one mover tile or two");
+    constexpr int NL_LEN = PLANES == 2 ? NL_TODO_M2 : NL_TODO_M, NL_CERT = PLANES == 2 ? NL_MCERT2 : NL_MCERT,
+                  NL_SENT = PLANES == 2 ? NL_MSENT2 : NL_MSENT;
+    const long long total = (long long)counters[NL_LEN] * 16;
+    if constexpr (PLANES == 2) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { counters[NL_MEARLY2] = counters[NL_EARLY]; counters[NL_EARLY] = 0u; }
+    }
     if ((long long)blockIdx.x * WGP >= total) return; // (whole workgroup; an empty list: every workgroup)
     __shared__ float s_dk[SPKM_MOVER_KMAX];
     __shared__ int s_slot[SPKM_MOVER_KMAX];
@@ -1636,11 +1693,12 @@ __global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict_
     __shared__ unsigned s_nsend, s_pos, s_ncert;
     for (int k = threadIdx.x; k < K; k += blockDim.x) {
         s_dk[k] = bnd[hb_delta(npad) + k];
-        s_slot[k] = reinterpret_cast<const int*>(bnd)[hb_mslot(npad) + k];
+        const int sk = reinterpret_cast<const int*>(bnd)[hb_mslot(npad) + k];
+        s_slot[k] = sk < PLANES * SPKM_MOVERS ? sk : -1; // (one plane: the second half of M2 are not movers here)
     }
     if (threadIdx.x == 0) { s_nsend = 0u; s_ncert = 0u; }
     const double cum_in = *cum_in_p, cum_now = *cum_now_p;
-    const double cr = cum_in + (double)bnd[hb_mdr(npad)] * (1.0 + 1e-12);
+    const double cr = cum_in + (double)bnd[PLANES == 2 ? hb_mdr2(npad) : hb_mdr(npad)] * (1.0 + 1e-12);
     const double cum_r = cr + fabs(cr) * 0x1p-52;
     const double cmax = __builtin_bit_cast(double, *cmax_bits);
     const double u = 0x1p-24;
@@ -1675,6 +1733,13 @@ __global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict_
         ld_points<PPT>(scr_m1, (size_t)i0, wide && al_pl, in, 0.f, m1);
         ld_points<PPT>(scr_m2, (size_t)i0, wide && al_pl, in, 0.f, m2);
         ld_points<PPT>(scr_k, (size_t)i0, wide && al_pl, in, -1, sl);
+        float m1b[PPT], m2b[PPT]; // (PLANES == 2: plane 1)
+        int slb[PPT];
+        if constexpr (PLANES == 2) {
+            ld_points<PPT>(scr_m1 + n, (size_t)i0, wide && al_pl, in, 0.f, m1b);
+            ld_points<PPT>(scr_m2 + n, (size_t)i0, wide && al_pl, in, 0.f, m2b);
+            ld_points<PPT>(scr_k + n, (size_t)i0, wide && al_pl, in, -1, slb);
+        }
         bool ok = true, st_ub[PPT], st_lb[PPT];
         float ubn[PPT], lbn[PPT];
 #pragma unroll
@@ -1693,6 +1758,27 @@ __global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict_
             lr = lr > 0.0 ? lr * (1.0 - 0x1p-50) : lr * (1.0 + 0x1p-50); // (rounded down)
             bool good;
             double un, ln_;
+            if constexpr (PLANES == 2) {
+                const double q1 = sqrt((double)m1b[c]), q2 = sqrt((double)m2b[c]);
+                const double f1 = E + gacc * q1 + 1e-20, f2 = E + gacc * q2 + 1e-20;
+                const bool have2 = have && slb[c] >= SPKM_MOVERS && slb[c] < SPKM_MOVERS2 && q1 < inf && q2 < inf; // false for NaN
+                const double l0 = fmax(0.0, fmin(r1 - e1, r2 - e2)), l1 = fmax(0.0, fmin(q1 - f1, q2 - f2));
+                if (sa < 0) {
+                    const double U = da > 0.f ? (double)__double2float_ru((double)ub[c] + (double)da) : (double)ub[c];
+                    ln_ = fmin(lr, fmin(l0, l1));
+                    good = have2 && U * (1.0 + nu) < ln_ * (1.0 - nu);
+                    st_ub[c] = da > 0.f;
+                    ubn[c] = (float)U;
+                } else {
+                    const bool p1 = sa >= SPKM_MOVERS; // the plane of a
+                    const double w1 = p1 ? q1 : r1, g1 = p1 ? f1 : e1;
+                    ln_ = fmin(fmin(p1 ? q2 - f2 : r2 - e2, p1 ? l0 : l1), lr);
+                    un = (w1 + g1) * (1.0 + nu);
+                    good = have2 && (p1 ? slb[c] : sl[c]) == sa && un < ln_ * (1.0 - nu);
+                    st_ub[c] = true;
+                    ubn[c] = __double2float_ru(un * (1.0 + 1e-12));
+                }
+            } else
             if (sa < 0) {
                 const double U = da > 0.f ? (double)__double2float_ru((double)ub[c] + (double)da) : (double)ub[c];
                 const double lm = fmax(0.0, fmin(r1 - e1, r2 - e2));
@@ -1732,12 +1818,12 @@ __global__ __launch_bounds__(256) void k_certify_movers(const float* __restrict_
         __syncthreads();
         for (unsigned j = threadIdx.x; j < s_nsend; j += blockDim.x) todo[s_pos + j] = s_send[j];
         __syncthreads();
-        if (threadIdx.x == 0) { if (s_nsend) atomicAdd(counters + NL_MSENT, s_nsend); s_nsend = 0u; }
+        if (threadIdx.x == 0) { if (s_nsend) atomicAdd(counters + NL_SENT, s_nsend); s_nsend = 0u; }
         __syncthreads();
     }
     if (ln == 0 && ncert) atomicAdd(&s_ncert, ncert);
     __syncthreads();
-    if (threadIdx.x == 0 && s_ncert) atomicAdd(counters + NL_MCERT, s_ncert);
+    if (threadIdx.x == 0 && s_ncert) atomicAdd(counters + NL_CERT, s_ncert);
 }
 
 // Listed points: exact reference arithmetic over all K centroids (row-major scaled centres Cs in

@@ -1098,6 +1098,8 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
     // mover_on: the call listed steps for the mover tile (k_bounds_steps, MOV): the points of the steps certified there
     // (counters[NL_MCERT], 16 each) count as screened, and the mover launch's rounds -- counters[NL_TODO_M] steps on one tile,
     // less its early finishes, counters[NL_MEARLY] -- go into counters[NL_ROUNDS_DONE]; NL_ROUNDS_FULL and NL_EARLY stay the main launch's.
+    // mover_on & 2: the second level ran as well (spkm_plan_movers2): the same with counters[NL_MCERT2], and counters[NL_TODO_M2]
+    // steps on TWO tiles less the (step, tile) pairs finished early, counters[NL_MEARLY2].
     // screen_n: the shard's points -- what this call's screen evaluated: all of them, or (work_flags & 2) the points of its
     // list, 16 per listed step -- into counters[NL_SCREENED], and added to the running total at counters[NL_SCREENED_TOTAL]
     // (spkm_last_screen_points)
@@ -1105,6 +1107,7 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
         unsigned long long v = screen_n;
         if (work_flags & 2) v = (work_flags & 4) ? (unsigned long long)counters[NL_TODO] : (unsigned long long)counters[NL_TODO] * 16ull;
         if (mover_on) v += (unsigned long long)counters[NL_MCERT] * 16ull;
+        if (mover_on & 2) v += (unsigned long long)counters[NL_MCERT2] * 16ull;
         if (v > screen_n) v = screen_n;
         counters[NL_SCREENED] = (unsigned)v;
         *reinterpret_cast<unsigned long long*>(counters + NL_SCREENED_TOTAL) += v;
@@ -1127,6 +1130,14 @@ __global__ void k_call_tail(const unsigned long long* __restrict__ nk, int K, do
             unsigned long long rm = (unsigned long long)counters[NL_TODO_M] * (unsigned long long)((work_flags & 1) ? work_a : work_nr);
             if (!(work_flags & 1) && work_a < work_nr) {
                 const unsigned long long saved = (unsigned long long)counters[NL_MEARLY] * (unsigned long long)(work_nr - work_a);
+                rm -= saved < rm ? saved : rm;
+            }
+            r += rm;
+        }
+        if (mover_on & 2) {
+            unsigned long long rm = (unsigned long long)counters[NL_TODO_M2] * 2ull * (unsigned long long)((work_flags & 1) ? work_a : work_nr);
+            if (!(work_flags & 1) && work_a < work_nr) {
+                const unsigned long long saved = (unsigned long long)counters[NL_MEARLY2] * (unsigned long long)(work_nr - work_a);
                 rm -= saved < rm ? saved : rm;
             }
             r += rm;

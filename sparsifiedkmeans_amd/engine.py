@@ -476,6 +476,13 @@ class LloydEngine:
         _lib.check(_lib.lib().spkm_last_mover_steps(self.ctx.handle, a))
         return int(a[0]), int(a[1]), int(a[2])
 
+    def last_mover_steps2(self) -> tuple[int, int, int]:
+        """(16-point steps of the last fused call that only the 64 largest movers unsettled and the 32 largest alone did not,
+        steps certified on the two mover tiles, steps they sent on to the main launch; blocks) -- spkm_last_mover_steps2."""
+        a = (C.c_uint64 * 3)()
+        _lib.check(_lib.lib().spkm_last_mover_steps2(self.ctx.handle, a))
+        return int(a[0]), int(a[1]), int(a[2])
+
     def iterate(self, centers: torch.Tensor, want_mind: bool = True):
         """One full Lloyd iteration in place on ``centers``; returns the device tensor
         [dff^2, obj^2] (no host sync).  One library call (spkm_lloyd_iter: fused assignment + accumulation, the
