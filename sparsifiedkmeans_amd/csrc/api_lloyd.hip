@@ -10,16 +10,12 @@
 #include "dense.hip"
 
 #include "api_internal.h"
+#include "launch.h" // spkm_launch, the screen kernels' pointer types, k_screen_quad's dispatchers (screen_quad.hip)
 
-// k_screen_quad lives in its own translation units (screen_quad.hip, one per row-id width and list granularity)
-const void* spkm_sq_kernel_16_0(int rounds, int a_rounds);
-const void* spkm_sq_kernel_16_1(int rounds, int a_rounds);
-const void* spkm_sq_kernel_32_0(int rounds, int a_rounds);
-const void* spkm_sq_kernel_32_1(int rounds, int a_rounds);
-template <typename IR> static const void* screen_quad_kernel(int rounds, int a_rounds, bool pts = false)
+template <typename IR> static screen_quad_fn<IR> screen_quad_kernel(int rounds, int a_rounds, bool pts = false)
 {
-    if (sizeof(IR) == 2) return pts ? spkm_sq_kernel_16_1(rounds, a_rounds) : spkm_sq_kernel_16_0(rounds, a_rounds);
-    return pts ? spkm_sq_kernel_32_1(rounds, a_rounds) : spkm_sq_kernel_32_0(rounds, a_rounds);
+    if constexpr (sizeof(IR) == 2) return pts ? spkm_sq_kernel_16_1(rounds, a_rounds) : spkm_sq_kernel_16_0(rounds, a_rounds);
+    else return pts ? spkm_sq_kernel_32_1(rounds, a_rounds) : spkm_sq_kernel_32_0(rounds, a_rounds);
 }
 
 // A shard over RECORDS the caller holds on the device (spkm_mix_sample_rec_dev's output): n points of exactly s entries.
@@ -820,27 +816,17 @@ static int run_distances(spkm_ctx* ctx, const spkm_shard* s, int K, const double
             launch_scatter(ctx, sb, sc_lds, (const int*)d_assign, n, K, (const unsigned*)nullptr, (const int*)nullptr);
             ctx->sort_partial = false;
         }
-        const void* k3 = (const void*)k_exact_accumulate_rec<IR, 4, false>; // (distance-only variant: no sums / counts)
+        const auto k3 = k_exact_accumulate_rec<IR, 4, false>; // (distance-only variant: no sums / counts)
         const size_t lds3 = fixed_lds + (size_t)nw * 16 * per_pt;
-        HIP_TRY(allow_lds(ctx, k3, lds3));
+        HIP_TRY(allow_lds(ctx, (const void*)k3, lds3));
         const int ab = std::min(max_items, std::max(1, ctx->num_cus));
         // scratch for the per-item statistics: the plan above emits at most n / seg + K + 1 items for THIS segment length
         if ((rc = ensure(ctx, ctx->blk_dff, (size_t)std::max(max_items, FIN_BLOCKS_MAX) * 24))) return rc;
-        const char* a_rec = s->rec;
-        int a_R = s->rec_R, a_p = p, a_s = s->fixed_s;
-        const int* a_perm = (const int*)ctx->perm.p;
-        const long long* a_offs = (const long long*)ctx->offs.p;
-        const int4* a_items = (const int4*)ctx->items.p;
-        const int* a_nitems = (const int*)ctx->nitems.p;
-        const double* a_C = d_centers;
-        double a_gamma = gamma;
-        double* a_mind = d_mind;
-        float* a_ub = nullptr;
-        double *a_sums = nullptr, *a_counts = nullptr, *a_bo = (double*)ctx->blk_dff.p, *a_bm = a_bo + max_items;
+        double *a_bo = (double*)ctx->blk_dff.p, *a_bm = a_bo + max_items;
         long long* a_bi = (long long*)(a_bm + max_items);
-        void* args[] = {&a_rec, &a_R, &a_perm, &a_offs, &a_items, &a_nitems, &a_C, &a_gamma, &a_p, &a_s,
-                        &a_mind, &a_ub, &a_sums, &a_counts, &a_bo, &a_bm, &a_bi};
-        HIP_TRY(hipLaunchKernel(k3, dim3(ab), dim3(threads), args, lds3, ctx->stream));
+        HIP_TRY(spkm_launch(k3, dim3(ab), dim3(threads), lds3, ctx->stream, (const char*)s->rec, s->rec_R, (const int*)ctx->perm.p,
+                            (const long long*)ctx->offs.p, (const int4*)ctx->items.p, (const int*)ctx->nitems.p, d_centers, gamma,
+                            p, s->fixed_s, d_mind, nullptr, nullptr, nullptr, a_bo, a_bm, a_bi));
         if (d_stats) {
             hipLaunchKernelGGL(k_reduce_stats_n, dim3(1), dim3(64), 0, ctx->stream, (const double*)a_bo, (const double*)a_bm,
                                (const long long*)a_bi, (const int*)ctx->nitems.p, (double*)ctx->stats.p);

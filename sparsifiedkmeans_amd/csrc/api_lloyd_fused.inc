@@ -51,6 +51,42 @@ static_assert(spkm_movers2 == SPKM_MOVERS2 && spkm_movers2 == 2 * SCREEN_KT && s
 static_assert(spkm_plan_kt == SCREEN_KT && spkm_plan_span == BOUNDS_SPAN && spkm_plan_span_pt == BOUNDS_SPAN_PT &&
               spkm_plan_seg == SEG_POINTS, "policy.h sizes the kernels with these constants");
 
+// The kernels a call picks among at run time, by table: the instantiations that exist, each under its pointer type (launch.h);
+// null = no such kernel, which the caller answers with SPKM_ERR_UNSUPPORTED and never launches.  k_screen_wide by tile width
+// (8 / 16 / 32), LIST, RAGGED -- no <32, false, false>: k_screen_tile serves that case -- and k_screen_far by planes (1 / 2 / 4).
+template <typename IR> static screen_wide_fn<IR> pick_screen_wide(int kt, bool list, bool ragged)
+{
+    static constexpr screen_wide_fn<IR> tab[2][2][3] = {
+        {{k_screen_wide<IR, 8>, k_screen_wide<IR, 16>, nullptr}, {k_screen_wide<IR, 8, true>, k_screen_wide<IR, 16, true>, k_screen_wide<IR, 32, true>}},
+        {{k_screen_wide<IR, 8, false, true>, k_screen_wide<IR, 16, false, true>, k_screen_wide<IR, 32, false, true>},
+         {k_screen_wide<IR, 8, true, true>, k_screen_wide<IR, 16, true, true>, k_screen_wide<IR, 32, true, true>}}};
+    return (kt == 8 || kt == 16 || kt == 32) ? tab[ragged][list][kt / 16] : nullptr;
+}
+template <typename IR> static screen_far_fn<IR> pick_screen_far(int planes, bool list, bool ragged)
+{
+    static constexpr screen_far_fn<IR> tab[2][2][3] = {
+        {{k_screen_far<IR, 1>, k_screen_far<IR, 2>, k_screen_far<IR, 4>}, {k_screen_far<IR, 1, true>, k_screen_far<IR, 2, true>, k_screen_far<IR, 4, true>}},
+        {{k_screen_far<IR, 1, false, true>, k_screen_far<IR, 2, false, true>, k_screen_far<IR, 4, false, true>},
+         {k_screen_far<IR, 1, true, true>, k_screen_far<IR, 2, true, true>, k_screen_far<IR, 4, true, true>}}};
+    return (planes == 1 || planes == 2 || planes == 4) ? tab[ragged][list][planes / 2] : nullptr;
+}
+// ... and the two-way picks, [0] / [1]: the far shards' event kernels fixed-stride / RAGGED, k_exact_accumulate_rec sums-only / full
+template <typename IR> static auto pick_events_direct(bool ragged)
+{
+    static constexpr decltype(&k_events_direct<IR>) tab[2] = {k_events_direct<IR>, k_events_direct<IR, true>};
+    return tab[ragged];
+}
+template <typename IR> static auto pick_events_sliced(bool ragged)
+{
+    static constexpr decltype(&k_accumulate_events_sliced<IR>) tab[2] = {k_accumulate_events_sliced<IR>, k_accumulate_events_sliced<IR, true>};
+    return tab[ragged];
+}
+template <typename IR> static auto pick_exact_rec(bool dist)
+{
+    static constexpr decltype(&k_exact_accumulate_rec<IR, 4>) tab[2] = {k_exact_accumulate_rec<IR, 4, true, false>, k_exact_accumulate_rec<IR, 4>};
+    return tab[dist];
+}
+
 // A shard-owned device buffer that has to be (re)allocated: the old one is freed and `valid` -- the flag that vouches for
 // its contents, if any -- is cleared first.  Returns the allocation's status (the buffer is null when it failed).
 template <typename T>
@@ -340,6 +376,68 @@ struct screen_call : spkm_call_in {
         sm->hb_valid = false;     // until this call has gone through
         return SPKM_OK;
     }
+    // The table in tiles (planes) of kt centroids by k_prep_tiles_wide -- with cmax, the row-major f64 centres of the exact list
+    // and, for a shard that carries bounds, the library's copy of the centres that the next call's drift is measured from.
+    void prep_tiles_wide()
+    {
+        const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
+        hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256), 0,
+                           ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p, (unsigned long long*)ctx->cmax.p,
+                           (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
+    }
+    // What every screen stage reports: its tiles, its rounds (0 off the 4-lanes-per-point screen), the plan's list form.
+    void report_screen(int rounds_all, int rounds)
+    {
+        rep.pl_last = pl.pl_last; rep.kt = kt; rep.tiles = pl.Gs;
+        rep.rounds_all = rounds_all; rep.rounds = rounds; rep.mode = 0;
+        rep.skipping = pl.skip_enabled; rep.pt_mode = pl.pt_mode;
+    }
+    // The cluster sizes of `assign` into ctx->nk, zeroed first, both gated.  big_k: the far paths, which raise the LDS allowance for K * 4 B.
+    int hist(const unsigned* gate, bool big_k)
+    {
+        hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long*)ctx->nk.p, K, gate);
+        if (big_k && (size_t)K * 4 > 48 * 1024) HIP_TRY(allow_lds(ctx, (const void*)k_hist, (size_t)K * 4));
+        hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
+                           ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, gate);
+        return SPKM_OK;
+    }
+    // A mover list's steps settled on its PLANES tiles, or sent on to todo[] (k_certify_movers).
+    template <int PLANES> hipError_t certify_movers(const int* todo_m)
+    {
+        hipLaunchKernelGGL(k_certify_movers<PLANES>, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
+                           (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, (const float*)sm->xnr,
+                           col_s(), (const unsigned long long*)ctx->cmax.p, sm->hb, pl.npad, K, todo_m, (int*)ctx->todo.p,
+                           (unsigned*)ctx->nlist.p, (const double*)(sm->hb_cum + (sm->cum_par ^ 1)), (const double*)(sm->hb_cum + sm->cum_par));
+        return hipGetLastError();
+    }
+    // The single-level sort plan of the events by their 2 K keys (the histogram was collected by k_combine_screen / k_assign_list
+    // as they appended the events): segments of pl.seg_ev events, then the placement.  ev_est: the caller's estimate of the
+    // events -- the grid is sized by what usually moves, not by the worst case: every kernel strides over the device-side count.
+    void sort_events(long long ev_est, int* nitems_ev, const unsigned* gate_ev)
+    {
+        const int K2 = 2 * K;
+        const int hb_ = (int)std::min<long long>(1024, (ev_est + 1023) / 1024);
+        hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk_ev.p, K2,
+                           pl.seg_ev, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
+                           nitems_ev, gate_ev, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
+        launch_scatter(ctx, hb_, (size_t)((K2 + 1) & ~1) * 4 + (size_t)K2 * 12, (const int*)sm->ev_k, 0, K2, gate_ev, (const int*)nullptr,
+                       (const unsigned*)ctx->nlist.p + NL_EVENTS, (const int*)sm->ev_pt);
+    }
+    const int* todo_list() const { return pl.skip_enabled ? (const int*)ctx->todo.p : nullptr; } // the main launch's list, if it has one
+    // The timed launch of an LDS-tile screen over ctx->bmap: k_screen_tile, or k_screen_wide with its three further arguments in
+    // more... -- the twelve they share are spelled out here; s: the stride (0: a RAGGED form).  A null kern: no such kernel.
+    template <typename IR, typename KERN, typename... MORE> int launch_tiles(KERN kern, size_t lds, int s, MORE... more)
+    {
+        if (!kern) return SPKM_ERR_UNSUPPORTED;
+        HIP_TRY(allow_lds(ctx, (const void*)kern, lds));
+        HIP_TRY(timing_begin(ctx));
+        HIP_TRY(spkm_launch(kern, dim3(ctx->bmap_blocks), dim3(1024), lds, ctx->stream, (const IR*)sm->ir, (const float*)sm->xf,
+                            (const float*)ctx->t32.p, p, (int)n, s, K, (const spkm_blockmap*)ctx->bmap.p, (int)pl.chunk,
+                            (float*)ctx->scr_m1.p, (float*)ctx->scr_m2.p, (int*)ctx->scr_k.p, more...));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(timing_end(ctx));
+        return SPKM_OK;
+    }
     // The screen: f32 tiles of the centroids, then the 4-lanes-per-point (or 16-lanes-per-point, or narrow-tile) screen launch.
     template <typename IR> int screen()
     {
@@ -353,187 +451,85 @@ struct screen_call : spkm_call_in {
                                carry ? sm->hb_centers : (double*)nullptr,
                                mv.on ? reinterpret_cast<const int*>(sm->hb + hb_mlist(pl.npad)) : (const int*)nullptr, mv2.on ? 2 : 1);
         else
-            hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256),
-                               0, ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p,
-                               (unsigned long long*)ctx->cmax.p, (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
-        rep.pl_last = pl.pl_last;
-        rep.kt = kt;
-        rep.tiles = pl.Gs;
+            prep_tiles_wide();
+        report_screen(quad ? pl.rounds_all : 0, quad ? pl.nr : 0);
         const size_t lds = (size_t)(p + 1) * (kt * 4 + (pl.pl_last == 5 ? 16 : 0)) + 16;
-        // (a non-quad shard that skips on its bounds: the LIST form of k_screen_wide at its width, over the points of todo[])
-        const bool wlist = !quad && pl.skip_enabled;
-        const void* kern = quad ? screen_quad_kernel<IR>(pl.nr, pl.prune_a > 0 ? pl.prune_a : pl.nr, pl.pt_mode)
-                           : wlist ? (kt == SCREEN_KT ? (const void*)k_screen_wide<IR, 32, true>
-                                                      : (kt == 16 ? (const void*)k_screen_wide<IR, 16, true> : (const void*)k_screen_wide<IR, 8, true>))
-                                   : (kt == SCREEN_KT ? (const void*)k_screen_tile<IR>
-                                                      : (kt == 16 ? (const void*)k_screen_wide<IR, 16> : (const void*)k_screen_wide<IR, 8>));
-        HIP_TRY(allow_lds(ctx, kern, lds));
-        HIP_TRY(timing_begin(ctx));
-        const IR* a_ir = quad ? (const IR*)sm->irs : (const IR*)sm->ir;
-        const float* a_xf = quad ? (const float*)sm->xfs : (const float*)sm->xf;
-        const float* a_t = (const float*)ctx->t32.p;
-        int a_p = p, a_n = (int)n, a_s = sm->fixed_s, a_K = K, a_chunk = (int)pl.chunk;
-        const spkm_blockmap* a_bm = (const spkm_blockmap*)(quad ? ctx->bmapq.p : ctx->bmap.p);
-        float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
-        int* a_k = (int*)ctx->scr_k.p;
-        int a_extra = pl.G - 1; // buffer / centroid block of the carried remainder (pl 5)
-        rep.rounds_all = quad ? pl.rounds_all : 0;
-        rep.rounds = quad ? pl.nr : 0;
-        const float* a_hint = (pl.hinted && pl.rounds_all < pl.nr) ? sm->hintu : nullptr; // nullptr: every step is finished for the leaders only
-        float a_hc = 1.5f; // the other centroids' partial sums must exceed 1.5 x the hinted distance squared
-        rep.hinted = a_hint != nullptr;
+        const float* hint = (pl.hinted && pl.rounds_all < pl.nr) ? sm->hintu : nullptr; // nullptr: every step is finished for the leaders only
+        rep.hinted = hint != nullptr;
         rep.mode = rep.hinted ? 2 : (rep.rounds_all < rep.rounds ? 1 : 0);
-        unsigned* a_cnt = (unsigned*)ctx->nlist.p;
-        const int* a_todo = pl.skip_enabled ? (const int*)ctx->todo.p : nullptr;
-        // point lists: the listed points' entries come from the record layout of the exact pass when this shard has one
-        // (built in an earlier call: point lists only appear once most points pass the bounds)
-        const char* a_rec = (pl.pt_mode && sm->rec) ? sm->rec : (const char*)nullptr;
-        int a_recR = sm->rec_R, a_tp = pl.pt_mode ? 1 : 0;
-        const int* a_recmap = sm->map;
-        int a_slot = NL_TODO; // (k_screen_quad only: the counter that holds its list's length)
-        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_extra,
-                        &a_hint, &a_hc, &a_cnt, &a_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &a_slot};
-        if (mv.on) {
-            // The mover tile: the call's own instantiation over todo_m[] against the ONE tile behind the plan's (slot kk =
-            // centroid mlist[kk]: K = SPKM_MOVERS for the kernel), results into plane 0 -- the main launch runs afterwards and
-            // rewrites the entries of its own steps only.  Then k_certify_movers settles those steps or sends them on to todo[].
-            // An empty list: both return at once, the screen before its tile load.
-            const float* m_t = a_t + (size_t)pl.G * (p + 1) * SCREEN_KT;
-            const spkm_blockmap* m_bm = (const spkm_blockmap*)ctx->bmapm.p;
-            const int* m_todo = (const int*)ctx->todo_m.p;
-            int m_K = SPKM_MOVERS, m_extra = 0, m_slot = NL_TODO_M;
-            void* margs[] = {&a_ir, &a_xf, &m_t, &a_p, &a_n, &a_s, &m_K, &m_bm, &a_chunk, &a_m1, &a_m2, &a_k, &m_extra,
-                             &a_hint, &a_hc, &a_cnt, &m_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &m_slot};
-            HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmapm_blocks), dim3(1024), margs, lds, ctx->stream));
-            HIP_TRY(hipGetLastError());
-            // The second level: the same instantiation over todo_m2[] against BOTH tiles behind the plan's (K = SPKM_MOVERS2 for
-            // the kernel: no carried remainder), results into planes 0 and 1; certified after the first level's launch and in
-            // front of the main one, like the first.
-            const int* m2_todo = (const int*)ctx->todo_m2.p;
-            if (mv2.on) {
-                const spkm_blockmap* m2_bm = (const spkm_blockmap*)ctx->bmapm2.p;
-                int m2_K = SPKM_MOVERS2, m2_slot = NL_TODO_M2;
-                void* m2args[] = {&a_ir, &a_xf, &m_t, &a_p, &a_n, &a_s, &m2_K, &m2_bm, &a_chunk, &a_m1, &a_m2, &a_k, &m_extra,
-                                  &a_hint, &a_hc, &a_cnt, &m2_todo, &a_tp, &a_rec, &a_recR, &a_recmap, &m2_slot};
-                HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmapm2_blocks), dim3(1024), m2args, lds, ctx->stream));
-                HIP_TRY(hipGetLastError());
+        rep.movers = mv.on; rep.movers2 = mv2.on;
+        if (quad) {
+            const screen_quad_fn<IR> kern = screen_quad_kernel<IR>(pl.nr, pl.prune_a > 0 ? pl.prune_a : pl.nr, pl.pt_mode);
+            if (!kern) return SPKM_ERR_UNSUPPORTED;
+            HIP_TRY(allow_lds(ctx, (const void*)kern, lds));
+            HIP_TRY(timing_begin(ctx));
+            // point lists: the listed points' entries come from the record layout of the exact pass when this shard has one
+            // (built in an earlier call: point lists only appear once most points pass the bounds)
+            const char* rec = (pl.pt_mode && sm->rec) ? sm->rec : (const char*)nullptr;
+            // One launch of the call's instantiation: over the K_ centroids of the tiles from tile0 on, by blockmap bm; extra: buffer /
+            // centroid block of the carried remainder (pl 5); list, slot: the list and the counter that holds its length.
+            // (1.5f: the other centroids' partial sums must exceed 1.5 x the hinted distance squared)
+            auto launch = [&](int tile0, const devbuf& bm, int blocks, int K_, int extra, const int* list, int slot) {
+                const hipError_t e = spkm_launch(kern, dim3(blocks), dim3(1024), lds, ctx->stream, (const IR*)sm->irs, (const float*)sm->xfs,
+                                                 (const float*)ctx->t32.p + (size_t)tile0 * (p + 1) * SCREEN_KT, p, (int)n, sm->fixed_s, K_,
+                                                 (const spkm_blockmap*)bm.p, (int)pl.chunk, (float*)ctx->scr_m1.p, (float*)ctx->scr_m2.p,
+                                                 (int*)ctx->scr_k.p, extra, hint, 1.5f, (unsigned*)ctx->nlist.p, list, pl.pt_mode ? 1 : 0, rec,
+                                                 sm->rec_R, (const int*)sm->map, slot);
+                return e != hipSuccess ? e : hipGetLastError();
+            };
+            if (mv.on) {
+                // The mover tile: the call's own instantiation over todo_m[] against the ONE tile behind the plan's (slot kk =
+                // centroid mlist[kk]: K = SPKM_MOVERS for the kernel), results into plane 0 -- the main launch runs afterwards and
+                // rewrites the entries of its own steps only.  Then k_certify_movers settles those steps or sends them on to todo[].
+                // An empty list: both return at once, the screen before its tile load.
+                HIP_TRY(launch(pl.G, ctx->bmapm, ctx->bmapm_blocks, SPKM_MOVERS, 0, (const int*)ctx->todo_m.p, NL_TODO_M));
+                // The second level: the same instantiation over todo_m2[] against BOTH tiles behind the plan's (K = SPKM_MOVERS2 for
+                // the kernel: no carried remainder), results into planes 0 and 1; certified after the first level's launch and in
+                // front of the main one, like the first.
+                if (mv2.on) HIP_TRY(launch(pl.G, ctx->bmapm2, ctx->bmapm2_blocks, SPKM_MOVERS2, 0, (const int*)ctx->todo_m2.p, NL_TODO_M2));
+                HIP_TRY(certify_movers<1>((const int*)ctx->todo_m.p));
+                if (mv2.on) HIP_TRY(certify_movers<2>((const int*)ctx->todo_m2.p));
             }
-            hipLaunchKernelGGL(k_certify_movers<1>, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
-                               (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, (const float*)sm->xnr,
-                               col_s(), (const unsigned long long*)ctx->cmax.p, sm->hb, pl.npad, K, m_todo, (int*)ctx->todo.p,
-                               (unsigned*)ctx->nlist.p, (const double*)(sm->hb_cum + (sm->cum_par ^ 1)), (const double*)(sm->hb_cum + sm->cum_par));
-            HIP_TRY(hipGetLastError());
-            if (mv2.on) {
-                hipLaunchKernelGGL(k_certify_movers<2>, dim3((unsigned)std::min<long long>(4096, (n + 1023) / 1024)), dim3(256), 0, ctx->stream,
-                                   (const float*)ctx->scr_m1.p, (const float*)ctx->scr_m2.p, (const int*)ctx->scr_k.p, n, (const float*)sm->xnr,
-                                   col_s(), (const unsigned long long*)ctx->cmax.p, sm->hb, pl.npad, K, m2_todo, (int*)ctx->todo.p,
-                                   (unsigned*)ctx->nlist.p, (const double*)(sm->hb_cum + (sm->cum_par ^ 1)), (const double*)(sm->hb_cum + sm->cum_par));
-                HIP_TRY(hipGetLastError());
-            }
+            HIP_TRY(launch(0, ctx->bmapq, ctx->bmapq_blocks, K, pl.G - 1, todo_list(), NL_TODO));
+            HIP_TRY(timing_end(ctx));
+            return SPKM_OK;
         }
-        rep.movers = mv.on;
-        rep.movers2 = mv2.on;
-        // (k_screen_wide: the first twelve, then the list and the counters)
-        const long long* a_jc = nullptr; // (the RAGGED forms' column bounds: screen_tile_ragged)
-        void* args_w[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
-        const bool wide_args = !quad && (wlist || kt != SCREEN_KT);
-        HIP_TRY(hipLaunchKernel(kern, dim3(quad ? ctx->bmapq_blocks : ctx->bmap_blocks), dim3(1024), wide_args ? args_w : args, lds,
-                                ctx->stream));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(timing_end(ctx));
-        rep.skipping = pl.skip_enabled;
-        rep.pt_mode = pl.pt_mode;
-        return SPKM_OK;
+        if (kt == SCREEN_KT && !pl.skip_enabled) return launch_tiles<IR>(k_screen_tile<IR>, lds, sm->fixed_s);
+        // (narrow tiles, or a shard that skips on its bounds: the LIST form of k_screen_wide at its width, over the points of todo[])
+        return launch_tiles<IR>(pick_screen_wide<IR>(kt, pl.skip_enabled, false), lds, sm->fixed_s, todo_list(), (const unsigned*)ctx->nlist.p, nullptr);
     }
-    // The far screen (screen_far.hip): the table in planes of kt = 64 / 128 / 256 centroids by k_prep_tiles_wide -- with cmax and
-    // the row-major f64 centres of the exact list and, for a shard that carries bounds, the library's copy of the centres that
-    // the next call's drift is measured from, in one launch -- then one wave per (point, plane): over every point, or (a shard
-    // that skips on its bounds) the LIST form over the points of todo[].
+    // The far screen (screen_far.hip): the table in planes of kt = 64 / 128 / 256 centroids by k_prep_tiles_wide, then one wave
+    // per (point, plane): over every point, or (a shard that skips on its bounds) the LIST form over the points of todo[].
     template <typename IR> int screen_far()
     {
         zero_flush();
-        const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
-        hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256), 0,
-                           ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p, (unsigned long long*)ctx->cmax.p,
-                           (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
-        rep.pl_last = pl.pl_last;
-        rep.kt = kt;
-        rep.tiles = pl.Gs;
-        rep.rounds_all = rep.rounds = 0;
-        rep.mode = 0;
-        const int npl = kt / 64;
-        const bool flist = pl.skip_enabled;
-        const void* kern = flist ? (npl == 1 ? (const void*)k_screen_far<IR, 1, true>
-                                             : (npl == 2 ? (const void*)k_screen_far<IR, 2, true> : (const void*)k_screen_far<IR, 4, true>))
-                                 : (npl == 1 ? (const void*)k_screen_far<IR, 1> : (npl == 2 ? (const void*)k_screen_far<IR, 2> : (const void*)k_screen_far<IR, 4>));
-        if (ragged()) // (columns [jc[pt], jc[pt + 1]): the RAGGED forms, which read jc and not the stride)
-            kern = flist ? (npl == 1 ? (const void*)k_screen_far<IR, 1, true, true>
-                                     : (npl == 2 ? (const void*)k_screen_far<IR, 2, true, true> : (const void*)k_screen_far<IR, 4, true, true>))
-                         : (npl == 1 ? (const void*)k_screen_far<IR, 1, false, true>
-                                     : (npl == 2 ? (const void*)k_screen_far<IR, 2, false, true> : (const void*)k_screen_far<IR, 4, false, true>));
+        prep_tiles_wide();
+        report_screen(0, 0);
+        // (a ragged shard's columns are [jc[pt], jc[pt + 1]): the RAGGED forms, which read jc and not the stride)
+        const screen_far_fn<IR> kern = pick_screen_far<IR>(kt / 64, pl.skip_enabled, ragged());
+        if (!kern) return SPKM_ERR_UNSUPPORTED;
         HIP_TRY(timing_begin(ctx));
-        const IR* a_ir = (const IR*)sm->ir;
-        const float* a_xf = (const float*)sm->xf;
-        const float* a_t = (const float*)ctx->t32.p;
-        int a_p = p, a_n = (int)n, a_s = sm->fixed_s, a_K = K;
-        float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
-        int* a_k = (int*)ctx->scr_k.p;
-        const int* a_todo = flist ? (const int*)ctx->todo.p : (const int*)nullptr;
-        const unsigned* a_cnt = (const unsigned*)ctx->nlist.p;
-        const long long* a_jc = (const long long*)sm->jc;
-        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
         // (4 waves per workgroup, a wave per point; 32 workgroups per CU and plane at most: the waves stride over the points --
         //  the LIST form over the slots of a list whose length only the device knows: the same grid, and the waves past its
         //  end return at once)
         const unsigned gx = (unsigned)std::min<long long>((n + 3) / 4, (long long)std::max(1, num_cus) * 32);
-        HIP_TRY(hipLaunchKernel(kern, dim3(gx, (unsigned)pl.G), dim3(256), args, 0, ctx->stream));
+        HIP_TRY(spkm_launch(kern, dim3(gx, (unsigned)pl.G), dim3(256), 0, ctx->stream, (const IR*)sm->ir, (const float*)sm->xf,
+                            (const float*)ctx->t32.p, p, (int)n, sm->fixed_s, K, (float*)ctx->scr_m1.p, (float*)ctx->scr_m2.p,
+                            (int*)ctx->scr_k.p, todo_list(), (const unsigned*)ctx->nlist.p, (const long long*)sm->jc));
         HIP_TRY(hipGetLastError());
         HIP_TRY(timing_end(ctx));
-        rep.skipping = pl.skip_enabled;
-        rep.pt_mode = pl.pt_mode;
         return SPKM_OK;
     }
     // The LDS-tile screen of a RAGGED shard (screen_wide.hip, the RAGGED forms of k_screen_wide; policy.h,
-    // spkm_tile_screen_ragged) in the far screen's place: the tiles of kt = 8 / 16 / 32 centroids by k_prep_tiles_wide, with what
-    // that launch also leaves for the certificate, the exact list and the next call's drift, then a workgroup per blockmap
-    // entry over every point, or (a shard that skips on its bounds) the LIST form over the points of todo[].
+    // spkm_tile_screen_ragged) in the far screen's place: the tiles of kt = 8 / 16 / 32 centroids by k_prep_tiles_wide, then a
+    // workgroup per blockmap entry over every point, or (a shard that skips on its bounds) the LIST form over the points of todo[].
     template <typename IR> int screen_tile_ragged()
     {
         zero_flush();
-        const size_t tile_floats = (size_t)pl.G * (p + 1) * kt;
-        hipLaunchKernelGGL(k_prep_tiles_wide, dim3((unsigned)std::min<size_t>((tile_floats + 255) / 256, 2048)), dim3(256), 0,
-                           ctx->stream, C, p, K, pl.G, kt, gamma, (float*)ctx->t32.p, (unsigned long long*)ctx->cmax.p,
-                           (double*)ctx->ct.p, carry ? sm->hb_centers : (double*)nullptr);
-        rep.pl_last = pl.pl_last;
-        rep.kt = kt;
-        rep.tiles = pl.Gs;
-        rep.rounds_all = rep.rounds = 0;
-        rep.mode = 0;
-        const bool wlist = pl.skip_enabled;
-        const void* kern = wlist ? (kt == 32 ? (const void*)k_screen_wide<IR, 32, true, true>
-                                             : (kt == 16 ? (const void*)k_screen_wide<IR, 16, true, true> : (const void*)k_screen_wide<IR, 8, true, true>))
-                                 : (kt == 32 ? (const void*)k_screen_wide<IR, 32, false, true>
-                                             : (kt == 16 ? (const void*)k_screen_wide<IR, 16, false, true> : (const void*)k_screen_wide<IR, 8, false, true>));
-        const size_t lds = (size_t)(p + 1) * kt * 4 + 16;
-        HIP_TRY(allow_lds(ctx, kern, lds));
-        HIP_TRY(timing_begin(ctx));
-        const IR* a_ir = (const IR*)sm->ir;
-        const float* a_xf = (const float*)sm->xf;
-        const float* a_t = (const float*)ctx->t32.p;
-        int a_p = p, a_n = (int)n, a_s = 0, a_K = K, a_chunk = (int)pl.chunk;
-        const spkm_blockmap* a_bm = (const spkm_blockmap*)ctx->bmap.p;
-        float *a_m1 = (float*)ctx->scr_m1.p, *a_m2 = (float*)ctx->scr_m2.p;
-        int* a_k = (int*)ctx->scr_k.p;
-        const int* a_todo = wlist ? (const int*)ctx->todo.p : (const int*)nullptr;
-        const unsigned* a_cnt = (const unsigned*)ctx->nlist.p;
-        const long long* a_jc = (const long long*)sm->jc;
-        void* args[] = {&a_ir, &a_xf, &a_t, &a_p, &a_n, &a_s, &a_K, &a_bm, &a_chunk, &a_m1, &a_m2, &a_k, &a_todo, &a_cnt, &a_jc};
-        HIP_TRY(hipLaunchKernel(kern, dim3(ctx->bmap_blocks), dim3(1024), args, lds, ctx->stream));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(timing_end(ctx));
-        rep.skipping = pl.skip_enabled;
-        rep.pt_mode = pl.pt_mode;
-        return SPKM_OK;
+        prep_tiles_wide();
+        report_screen(0, 0);
+        return launch_tiles<IR>(pick_screen_wide<IR>(kt, pl.skip_enabled, true), (size_t)(p + 1) * kt * 4 + 16, 0, todo_list(),
+                                (const unsigned*)ctx->nlist.p, (const long long*)sm->jc);
     }
     // The sums behind the far screen, by the kernels that work at any p: the cluster sizes (k_hist), the distances and the
     // three statistics when the call wants them (the route of spkm_distances_stats_dev), sums and counts (the route of
@@ -542,11 +538,7 @@ struct screen_call : spkm_call_in {
     int far_sums(bool* no_stats)
     {
         int rc;
-        hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long*)ctx->nk.p, K,
-                           (const unsigned*)nullptr);
-        if ((size_t)K * 4 > 48 * 1024) HIP_TRY(allow_lds(ctx, (const void*)k_hist, (size_t)K * 4));
-        hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
-                           ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, (const unsigned*)nullptr);
+        if ((rc = hist(nullptr, true))) return rc;
         HIP_TRY(hipGetLastError());
         *no_stats = sm->lazy && mind == nullptr;
         if (!*no_stats) {
@@ -583,64 +575,41 @@ struct screen_call : spkm_call_in {
     template <typename IR> int far_events_apply(const spkm_acc_plan& ap)
     {
         int rc;
-        hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long*)ctx->nk.p, K,
-                           (const unsigned*)nullptr);
-        if ((size_t)K * 4 > 48 * 1024) HIP_TRY(allow_lds(ctx, (const void*)k_hist, (size_t)K * 4));
-        hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
-                           ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, (const unsigned*)nullptr);
+        if ((rc = hist(nullptr, true))) return rc;
         HIP_TRY(hipGetLastError());
         sm->cl_stats_valid = false;
         sm->sp_clean = false;
         const int K2 = 2 * K;
-        const unsigned* ev_n = (const unsigned*)ctx->nlist.p + NL_EVENTS;
         double *cache_s = sm->cl_cache, *cache_c = cache_s + cc_counts(pk);
         rep.direct_events = pl.direct;
         const bool timed = ctx->tlog_on && ctx->tlog_both;
+        // (a ragged shard: the RAGGED forms, which read jc and not the stride)
+        const int s = ragged() ? 0 : sm->fixed_s;
+        const long long* jc = ragged() ? (const long long*)sm->jc : (const long long*)nullptr;
         if (pl.direct) {
             if (timed) HIP_TRY(timing_begin(ctx));
-            if (ragged())
-                hipLaunchKernelGGL((k_events_direct<IR, true>), dim3(1024), dim3(256), 0, ctx->stream, (const char*)nullptr, 0,
-                                   (const IR*)sm->ir, (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k, ev_n, p,
-                                   0, K, cache_s, cache_c, (const int*)nullptr, (const long long*)sm->jc);
-            else
-                hipLaunchKernelGGL((k_events_direct<IR>), dim3(1024), dim3(256), 0, ctx->stream, (const char*)nullptr, 0,
-                                   (const IR*)sm->ir, (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k, ev_n, p,
-                                   sm->fixed_s, K, cache_s, cache_c, (const int*)nullptr);
+            HIP_TRY(spkm_launch(pick_events_direct<IR>(ragged()), dim3(1024), dim3(256), 0, ctx->stream, nullptr, 0, (const IR*)sm->ir,
+                                (const double*)sm->x, (const int*)sm->ev_pt, (const int*)sm->ev_k,
+                                (const unsigned*)ctx->nlist.p + NL_EVENTS, p, s, K, cache_s, cache_c, nullptr, jc));
         } else {
-            const int seg_ev = pl.seg_ev;
-            const int max_items_ev = (int)((2 * n) / seg_ev) + K2 + 1;
+            const int max_items_ev = (int)((2 * n) / pl.seg_ev) + K2 + 1;
             if ((rc = ensure(ctx, ctx->perm, (size_t)2 * n * 4)) || (rc = ensure(ctx, ctx->offs, (size_t)(K2 + 1) * 8)) ||
                 (rc = ensure(ctx, ctx->cursor, (size_t)K2 * 8)) || (rc = ensure(ctx, ctx->items, (size_t)max_items_ev * 16)) ||
                 (rc = ensure(ctx, ctx->nitems, NI_WORDS * 4)))
                 return rc;
             ctx->sort_owner = nullptr; // (the sort buffers hold this call's events now)
-            // (sized by what usually moves, not by the worst case: every kernel strides over the device-side count)
-            const long long ev_est = std::max<long long>(4096, (long long)std::min<unsigned long long>(4 * sm->pol.last_movers + 4096, (unsigned long long)2 * n));
-            const int hb_ = (int)std::min<long long>(1024, (ev_est + 1023) / 1024);
-            // (the histogram over the 2 K keys was collected by k_combine_screen / k_assign_list as they appended the events)
-            hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk_ev.p, K2,
-                               seg_ev, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
-                               (int*)ctx->nitems.p + NI_FULL, (const unsigned*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
-            const size_t sc_lds_ev = (size_t)((K2 + 1) & ~1) * 4 + (size_t)K2 * 12;
-            launch_scatter(ctx, hb_, sc_lds_ev, (const int*)sm->ev_k, 0, K2, (const unsigned*)nullptr, (const int*)nullptr, ev_n,
-                           (const int*)sm->ev_pt);
+            sort_events(std::max<long long>(4096, (long long)std::min<unsigned long long>(4 * sm->pol.last_movers + 4096, (unsigned long long)2 * n)),
+                        (int*)ctx->nitems.p + NI_FULL, nullptr);
             const size_t slab = (size_t)ap.R * spkm_acc_row_bytes;
-            const void* kern = ragged() ? (const void*)k_accumulate_events_sliced<IR, true> : (const void*)k_accumulate_events_sliced<IR>;
-            HIP_TRY(allow_lds(ctx, kern, slab));
+            const auto kern = pick_events_sliced<IR>(ragged());
+            HIP_TRY(allow_lds(ctx, (const void*)kern, slab));
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_max / std::max<size_t>(slab, 1)));
             const long long units = (long long)max_items_ev * ap.slices;
             const int ab = (int)std::max<long long>(1, std::min<long long>(units, (long long)std::max(1, ctx->num_cus) * per_cu));
             if (timed) HIP_TRY(timing_begin(ctx));
-            if (ragged())
-                hipLaunchKernelGGL((k_accumulate_events_sliced<IR, true>), dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream,
-                                   (const IR*)sm->ir, (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
-                                   (const int4*)ctx->items.p, (const int*)ctx->nitems.p + NI_FULL, p, 0, K, ap.R, ap.slices,
-                                   cache_s, cache_c, (const long long*)sm->jc);
-            else
-                hipLaunchKernelGGL((k_accumulate_events_sliced<IR>), dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream, (const IR*)sm->ir,
-                                   (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
-                                   (const int4*)ctx->items.p, (const int*)ctx->nitems.p + NI_FULL, p, sm->fixed_s, K, ap.R, ap.slices,
-                                   cache_s, cache_c);
+            HIP_TRY(spkm_launch(kern, dim3(ab), dim3(spkm_acc_wg), slab, ctx->stream, (const IR*)sm->ir, (const double*)sm->x,
+                                (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
+                                (const int*)ctx->nitems.p + NI_FULL, p, s, K, ap.R, ap.slices, cache_s, cache_c, jc));
         }
         HIP_TRY(hipGetLastError());
         if (timed) HIP_TRY(timing_end(ctx));
@@ -688,13 +657,12 @@ struct screen_call : spkm_call_in {
     // The software-pipelined record kernel (k_exact_accumulate_rec); dist = false: its sums-only variant.
     template <typename IR> int exact_rec(bool dist, double* dmind, float* ub, int grid)
     {
-        const void* k3 = dist ? (const void*)k_exact_accumulate_rec<IR, 4> : (const void*)k_exact_accumulate_rec<IR, 4, true, false>;
+        const auto k3 = pick_exact_rec<IR>(dist);
         const size_t lds3 = (size_t)p * 20 + 16 + (size_t)16 * 16 * ((size_t)(sm->fixed_s | 1) * 8);
-        HIP_TRY(allow_lds(ctx, k3, lds3));
-        hipLaunchKernelGGL((dist ? k_exact_accumulate_rec<IR, 4> : k_exact_accumulate_rec<IR, 4, true, false>), dim3(grid), dim3(1024),
-                           lds3, ctx->stream, (const char*)sm->rec, sm->rec_R, (const int*)ctx->perm.p, (const long long*)ctx->offs.p,
-                           (const int4*)ctx->items.p, (const int*)ctx->nitems.p, C, gamma, p, sm->fixed_s, dmind, ub, sums,
-                           counts, (double*)ctx->blk_obj.p, (double*)ctx->blk_max.p, (long long*)ctx->blk_imax.p);
+        HIP_TRY(allow_lds(ctx, (const void*)k3, lds3));
+        HIP_TRY(spkm_launch(k3, dim3(grid), dim3(1024), lds3, ctx->stream, (const char*)sm->rec, sm->rec_R, (const int*)ctx->perm.p,
+                            (const long long*)ctx->offs.p, (const int4*)ctx->items.p, (const int*)ctx->nitems.p, C, gamma, p, sm->fixed_s,
+                            dmind, ub, sums, counts, (double*)ctx->blk_obj.p, (double*)ctx->blk_max.p, (long long*)ctx->blk_imax.p));
         return SPKM_OK;
     }
     // Incremental sums: the per-cluster sums move by the events (point, key) of the points that changed cluster, sorted by key
@@ -771,15 +739,8 @@ struct screen_call : spkm_call_in {
             perm = perm2;
             offs = (const long long*)ctx->offs2.p;
             items = (const int4*)ctx->items2.p;
-        } else {
-            // (the histogram over the 2 K keys was collected by k_combine_screen / k_assign_list as they appended the events)
-            hipLaunchKernelGGL(k_plan_segments, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->nk_ev.p, K2,
-                               seg_ev, (long long*)ctx->offs.p, (unsigned long long*)ctx->cursor.p, (int4*)ctx->items.p,
-                               nitems_ev, gate_ev, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
-            const size_t sc_lds_ev = (size_t)((K2 + 1) & ~1) * 4 + (size_t)K2 * 12;
-            launch_scatter(ctx, hb_, sc_lds_ev, (const int*)sm->ev_k, 0, K2, gate_ev, (const int*)nullptr, ev_n,
-                           (const int*)sm->ev_pt);
-        }
+        } else
+            sort_events(ev_est, nitems_ev, gate_ev);
         if (!pl.direct) {
             const int ab_ev = (int)std::min<long long>(max_items_acc, std::max<long long>(std::max(1, ctx->num_cus) * 8, 1));
             if (ctx->tlog_both) HIP_TRY(timing_begin(ctx));
@@ -813,12 +774,8 @@ struct screen_call : spkm_call_in {
     template <typename IR> int full_pass()
     {
         const unsigned* gate = pl.reuse ? (const unsigned*)ctx->nlist.p + NL_CHANGED : (const unsigned*)nullptr;
-        if (!pl.nk_incr) {
-            hipLaunchKernelGGL(k_zero_u64_gated, dim3((K + 255) / 256), dim3(256), 0, ctx->stream,
-                               (unsigned long long*)ctx->nk.p, K, gate);
-            hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min<long long>(1024, (n + 1023) / 1024)), dim3(256), (size_t)K * 4,
-                               ctx->stream, (const int*)assign, n, K, (unsigned long long*)ctx->nk.p, gate);
-        }
+        int rc;
+        if (!pl.nk_incr && (rc = hist(gate, false))) return rc;
         if (pl.cl_on)
             hipLaunchKernelGGL(k_cluster_need, dim3(1), dim3(256), 0, ctx->stream, cl(CL_TOUCHED), (const int*)cl(CL_SAME),
                                pl.cl_skip ? 0 : 1, K, (const unsigned long long*)ctx->nk.p, cl(CL_NEED), (unsigned*)ctx->nlist.p);
@@ -847,10 +804,9 @@ struct screen_call : spkm_call_in {
         pts = std::max(8, pts & ~7);
         const size_t lds2 = fixed_lds + (size_t)nw * pts * per_pt;
         // 16 points' loads in flight per wave; 4 waves per SIMD (2 with 512-thread workgroups)
-        const void* k2 = pl.use_rec ? (const void*)k_exact_accumulate<IR, 16, 4, false, true> : (const void*)k_exact_accumulate<IR, 16, 4, false, false>;
+        const auto k2 = pl.use_rec ? k_exact_accumulate<IR, 16, 4, false, true> : k_exact_accumulate<IR, 16, 4, false, false>;
         HIP_TRY(allow_lds(ctx, (const void*)k2, lds2));
         const int ab = std::min(max_items, std::max(1, ctx->num_cus));
-        int rc;
         if ((rc = ensure_blk_stats(ctx, (size_t)std::max(ab, max_items)))) return rc;
         if (ctx->tlog_both) HIP_TRY(timing_begin(ctx));
         // (a regrouped shard: the certificate wrote them.  A non-quad shard that carries bounds gets EVERY point's fresh upper
@@ -860,8 +816,7 @@ struct screen_call : spkm_call_in {
         if (pl.pipe) {
             if ((rc = exact_rec<IR>(!pl.sums_only, mind, ub, ab))) return rc;
         } else {
-            hipLaunchKernelGGL((pl.use_rec ? k_exact_accumulate<IR, 16, 4, false, true> : k_exact_accumulate<IR, 16, 4, false, false>),
-                               dim3(ab), dim3(threads), lds2, ctx->stream, (const char*)sm->rec, sm->rec_R, (const IR*)sm->ir,
+            hipLaunchKernelGGL(k2, dim3(ab), dim3(threads), lds2, ctx->stream, (const char*)sm->rec, sm->rec_R, (const IR*)sm->ir,
                                (const double*)sm->x, (const int*)ctx->perm.p, (const long long*)ctx->offs.p, (const int4*)ctx->items.p,
                                (const int*)ctx->nitems.p, C, gamma, p, sm->fixed_s, pts, mind, ub, sums, counts,
                                (double*)ctx->blk_obj.p, (double*)ctx->blk_max.p, (long long*)ctx->blk_imax.p);

@@ -5,6 +5,7 @@
 //   -DSPKM_SQ_PTS=0|1        the list names 16-point steps / points
 // Each TU exports one dispatcher, spkm_sq_kernel_<bits>_<pts>(rounds, a_rounds) -> kernel (host stub address).
 #include "common.h"
+#include "launch.h" // screen_quad_fn and the dispatchers' declarations
 #include "quad_steps.inc"
 #include <type_traits>
 
@@ -412,7 +413,7 @@ typedef unsigned int sq_ir_t;
 
 // one kernel per round count (a switch inside one kernel makes the register allocator spill)
 // a_rounds: rounds evaluated for all centroids (>= rounds: the plain form; else one of the two compiled splits)
-const void* SPKM_SQ_CAT(spkm_sq_kernel_, SPKM_SQ_IRBITS, SPKM_SQ_PTS)(int rounds, int a_rounds)
+screen_quad_fn<sq_ir_t> SPKM_SQ_CAT(spkm_sq_kernel_, SPKM_SQ_IRBITS, SPKM_SQ_PTS)(int rounds, int a_rounds)
 {
     constexpr bool PTS = SPKM_SQ_PTS != 0;
     typedef sq_ir_t IR;
@@ -421,8 +422,8 @@ const void* SPKM_SQ_CAT(spkm_sq_kernel_, SPKM_SQ_IRBITS, SPKM_SQ_PTS)(int rounds
     switch (rounds) {
 #define SPKM_QUAD_CASE(N)                                                                                   \
     case N:                                                                                                 \
-        if (late) return (const void*)k_screen_quad<N, IR, (quad_split_late(N, PTS) > 0 ? 2 : 0), PTS>;     \
-        return two && quad_split(N, PTS) < N ? (const void*)k_screen_quad<N, IR, (quad_split(N, PTS) < N ? 1 : 0), PTS> : (const void*)k_screen_quad<N, IR, 0, PTS>;
+        if (late) return k_screen_quad<N, IR, (quad_split_late(N, PTS) > 0 ? 2 : 0), PTS>;                  \
+        return two && quad_split(N, PTS) < N ? k_screen_quad<N, IR, (quad_split(N, PTS) < N ? 1 : 0), PTS> : k_screen_quad<N, IR, 0, PTS>;
         SPKM_QUAD_CASE(1) SPKM_QUAD_CASE(2) SPKM_QUAD_CASE(3) SPKM_QUAD_CASE(4) SPKM_QUAD_CASE(5) SPKM_QUAD_CASE(6)
         SPKM_QUAD_CASE(7) SPKM_QUAD_CASE(8) SPKM_QUAD_CASE(9) SPKM_QUAD_CASE(10) SPKM_QUAD_CASE(11) SPKM_QUAD_CASE(12)
         SPKM_QUAD_CASE(13) SPKM_QUAD_CASE(14) SPKM_QUAD_CASE(15) SPKM_QUAD_CASE(16)
