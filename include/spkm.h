@@ -255,6 +255,19 @@ int spkm_shard_set_far_ragged(spkm_shard *s, int on);
  * shard's policy state, like spkm_shard_reset_policy.  SPKM_TILE_RAGGED=1 opts every shard of a context in (read with the
  * other switches: spkm_ctx_reload_switches). */
 int spkm_shard_set_tile_ragged(spkm_shard *s, int on);
+/* Ragged shards on the staged k-means++ round (on != 0; default off).  spkm_kpp_seed_dev on a RAGGED shard runs the generic
+ * round kernel: one lane per point walks its column in global memory and gathers every table row from L2.  A shard that
+ * opts in here is seeded by a form of the staged kernel that reads each point's column bounds from jc: the table of the RB
+ * newest centres in LDS, the entries of pts consecutive columns staged by coalesced loads at a per-point stride of
+ * max_s | 1 (max_s = the shard's longest column), 8 replicates sharing one read -- wherever the fixed-stride plan of a
+ * column of max_s entries has a staged table (csrc/policy.h, spkm_kpp_plan_ragged: RB, waves, points per wave and batches
+ * are that plan's); past that p, and on a shard without entries, the generic kernel as before.  No load reaches outside
+ * the nnz stored entries: the arrays need no slack.  Picks, statuses and running minima are the generic form's bit for
+ * bit; an empty column is at distance 0.  spkm_last_kpp_plan reports form 3.  Opting in measures the shard's longest
+ * column once, as spkm_shard_set_far_ragged does.  A fixed-stride shard never hears the setting.  A switch of its own: no
+ * other opt-in implies it, and it needs none.  SPKM_KPP_RAGGED=1 opts every shard of a context in (read with the other
+ * switches: spkm_ctx_reload_switches); such a shard's longest column is measured in its first seeding. */
+int spkm_shard_set_kpp_ragged(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by
@@ -490,15 +503,16 @@ int spkm_kpp_draw_dev(spkm_ctx *ctx, uint64_t n, const double *d_cum, double tar
  * first and the same uniform numbers, and d_run[r] the running minimum they hold after their last round, bit for bit, in
  * every form and at every RB: per (entry, replicate) one subtract, one multiply and one add, rounded separately, entries in
  * storage order; the prefix sums by the addition chains of spkm_kpp_update_dev.
- * The form -- the table of the RB newest centres in LDS over a fixed-stride shard, or in global memory over any CSC and
- * any p -- RB and the number of batches are planned in csrc/policy.h and read back by spkm_last_kpp_plan.  RB * n doubles of
+ * The form -- the table of the RB newest centres in LDS over a fixed-stride shard (or a ragged one that opted in,
+ * spkm_shard_set_kpp_ragged), or in global memory over any CSC and any p -- RB and the number of batches are planned in csrc/policy.h and read back by spkm_last_kpp_plan.  RB * n doubles of
  * scratch are held for the length of the call unless d_run is given.  CSC arrays that were released are brought back.
  * K = 1: chosen[r][0] = first[r], no launch.  SPKM_ERR_BAD_VALUE: K = 0, R = 0, gamma not > 0 (the sparse-centres form of
  * a seeding without gamma stays on the round-by-round calls), first[r] not in [0, n); SPKM_ERR_UNSUPPORTED: n > 0x7ff00000. */
 int spkm_kpp_seed_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, double gamma, uint32_t R, const int64_t *first,
                       const double *u, int64_t *chosen, int32_t *status, double *d_run);
-/* What the context's last spkm_kpp_seed_dev ran: info = { form (1 = table in LDS, 2 = table in global memory; 0 = none yet,
- * K = 1 or a failed call), RB, batches, points staged per wave (form 1) }.  Stored values; does not block. */
+/* What the context's last spkm_kpp_seed_dev ran: info = { form (1 = table in LDS, 2 = table in global memory, 3 = table in
+ * LDS over a ragged shard that opted in, spkm_shard_set_kpp_ragged; 0 = none yet, K = 1 or a failed call), RB, batches,
+ * points staged per wave (forms 1 and 3) }.  Stored values; does not block. */
 int spkm_last_kpp_plan(spkm_ctx *ctx, int info[4]);
 
 /* centers(:,k) = gamma*S(:,k) ./ (Cnt(:,k) + 1e-16) for clusters with nk > 0
@@ -719,7 +733,8 @@ int spkm_last_assign_kernel_ms(spkm_ctx *ctx, double *ms);
  * spkm_assign_dev records one event pair without any host sync; spkm_timing_read blocks on the
  * stream and returns up to cap durations (ms) and the number recorded.  enable=2: calls of
  * spkm_assign_accumulate_dev that take the screen path record two pairs each, the screen kernel and then the
- * exact accumulation kernel (k_exact_accumulate), alternating in the log. */
+ * exact accumulation kernel (k_exact_accumulate), alternating in the log.  enable=3: spkm_kpp_seed_dev records one pair per
+ * launch of its round kernel -- batches x (K - 1) pairs per call, in launch order -- beside what enable=1 records. */
 int spkm_timing_log(spkm_ctx *ctx, int enable);
 /* Developer aid: per-workgroup (start, end) wall-clock stamps (100 MHz) of the tiled assignment
  * kernel.  enable=1 arms it; enable=0 copies up to cap pairs into out and reports the grid size. */

@@ -146,6 +146,7 @@ def lib():
     L.spkm_shard_set_far_events.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_far_ragged.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_tile_ragged.argtypes = [_vp, C.c_int]
+    L.spkm_shard_set_kpp_ragged.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_sliced_sums.argtypes = [_vp, C.c_int]
     L.spkm_last_screen_tile.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_screen_points.argtypes = [_vp, C.POINTER(C.c_int64)]

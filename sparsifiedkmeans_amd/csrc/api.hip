@@ -44,6 +44,7 @@ static spkm_switches read_switches()
     w.far_events = on("SPKM_FAR_EVENTS");
     w.far_ragged = on("SPKM_FAR_RAGGED");
     w.tile_ragged = on("SPKM_TILE_RAGGED");
+    w.kpp_ragged = on("SPKM_KPP_RAGGED");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
@@ -459,6 +460,15 @@ extern "C" int spkm_shard_set_tile_ragged(spkm_shard* s, int on)
     return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
 }
 
+// (no policy state to forget: the seeding keeps nothing on the shard between calls)
+extern "C" int spkm_shard_set_kpp_ragged(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->kpp_ragged = on != 0;
+    if (s->kpp_ragged && s->ctx) return ensure_max_s(s->ctx, s); // (here, so that no seeding waits for it)
+    return SPKM_OK;
+}
+
 extern "C" int spkm_shard_order_info(const spkm_shard* s, int64_t info[2])
 {
     if (!s || !info) return SPKM_ERR_NULL_ARG;
@@ -555,6 +565,7 @@ extern "C" int spkm_timing_log(spkm_ctx* ctx, int enable)
     if (!ctx) return SPKM_ERR_NULL_ARG;
     ctx->tlog_on = enable != 0;
     ctx->tlog_both = enable == 2;
+    ctx->tlog_kpp = enable == 3;
     ctx->tlog_used = 0;
     return SPKM_OK;
 }

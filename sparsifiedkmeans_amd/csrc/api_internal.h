@@ -61,6 +61,7 @@ struct spkm_switches {
     bool far_events = false;      // SPKM_FAR_EVENTS: every shard of the context that takes the far screen, carries bounds there and has lazy statistics moves its sums by events once few points change cluster, as if opted in (spkm_shard_set_far_events)
     bool far_ragged = false;      // SPKM_FAR_RAGGED: every RAGGED shard of the context that no exact LDS tile serves either takes the far screen in its ragged form where it (or the context) opted in to the far screen, as if opted in (spkm_shard_set_far_ragged)
     bool tile_ragged = false;     // SPKM_TILE_RAGGED: every RAGGED shard of the context at a p with a 32-centroid f32 tile takes the RAGGED form of k_screen_wide on an LDS tile instead of k_assign_tile over every point, as if opted in (spkm_shard_set_tile_ragged); a switch of its own
+    bool kpp_ragged = false;      // SPKM_KPP_RAGGED: spkm_kpp_seed_dev on every RAGGED shard of the context whose longest column has a staged table takes k_kpp_round_ragged (the table in LDS, staged entries) instead of k_kpp_round_generic, as if opted in (spkm_shard_set_kpp_ragged); a switch of its own
     bool sliced_sums = false;     // SPKM_SLICED_SUMS: spkm_accumulate_dev on every shard of the context keeps its sums in LDS past the 64-KB slab too, a row slice at a time (k_accumulate_sliced; policy.h, spkm_accumulate_form), as if opted in (spkm_shard_set_sliced_sums)
     int x_slab_rows = 0;          // SPKM_X_SLAB_ROWS: at most this many rows per slab of k_accumulate_sliced, at any p and any number of slices (0: the default, what the LDS holds; experiments and tests)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
@@ -126,12 +127,13 @@ struct spkm_ctx {
     int sort_K = 0, sort_seg = 0;
     long long sort_n = 0;
     bool tlog_both = false; // fused screen path: log the exact accumulation kernel too (pairs alternate)
+    bool tlog_kpp = false;  // spkm_timing_log(ctx, 3): spkm_kpp_seed_dev logs one pair per launch of its round kernel
     int assign_KT = 0, assign_G = 0; // of the last assign call
     spkm_screen_report last;         // of the last spkm_assign_accumulate_dev
     int last_exact_pts = 0;          // points staged per wave by the last exact pass / K = 1 stream (16: the pipelined kernel)
     int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics, 3 LDS slabs over row slices
     int last_dist_form = 0;          // the last distances call: 1 streaming record kernel, 2 generic kernel
-    int last_kpp[4] = {0, 0, 0, 0};  // the last spkm_kpp_seed_dev: form (policy.h, spkm_kpp_plan; 0: none yet or K = 1), RB, batches, points staged per wave
+    int last_kpp[4] = {0, 0, 0, 0};  // the last spkm_kpp_seed_dev: form (policy.h, spkm_kpp_plan / spkm_kpp_plan_ragged; 0: none yet or K = 1), RB, batches, points staged per wave
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
     bool sort_perm_valid = false;    // ... and perm / offs / items really hold that call's counting sort (not after an incremental call)
     char errmsg[256] = {0};
@@ -158,8 +160,9 @@ struct spkm_shard {
     bool far_events = false; // spkm_shard_set_far_events: where this shard takes the far screen with carried bounds and lazy statistics, a call with few movers moves the kept sums (cl_cache's first two planes) by events instead of accumulating over every point
     bool far_ragged = false; // spkm_shard_set_far_ragged: a RAGGED shard (fixed_s = 0) that opted in to the far screen takes it, in k_screen_far's RAGGED form, where no exact LDS tile serves it either (policy.h, spkm_far_screen_ragged)
     bool tile_ragged = false; // spkm_shard_set_tile_ragged: a RAGGED shard (fixed_s = 0) at a p with a 32-centroid f32 tile takes k_screen_wide's RAGGED form there, in front of the far screen's pipeline (policy.h, spkm_tile_screen_ragged)
+    bool kpp_ragged = false; // spkm_shard_set_kpp_ragged: a RAGGED shard (fixed_s = 0) is seeded by k_kpp_round_ragged where its longest column has a staged table (policy.h, spkm_kpp_plan_ragged)
     int max_s = 0;           // the longest column: fixed_s on a fixed-stride shard; on a ragged one a reduction over jc, run once (ensure_max_s) ...
-    bool max_s_known = false; // ... when the shard opts in to a ragged screen (far or tile) or on its first call there
+    bool max_s_known = false; // ... when the shard opts in to a ragged screen (far or tile) or to the ragged seeding, or on its first call there
     bool sliced = false; // spkm_shard_set_sliced_sums: past the 64-KB slab spkm_accumulate_dev on this shard takes k_accumulate_sliced (policy.h, spkm_accumulate_form)
     float* xfs = nullptr;  // screen copy for the 4-lanes-per-point kernel: f32 values, columns partitioned by row parity
     void* irs = nullptr;   // ... and their row ids

@@ -1170,6 +1170,10 @@ static void kpp_launch_round(spkm_ctx* ctx, const spkm_shard* s, const spkm_kpp_
     if (pl.form == 1)
         hipLaunchKernelGGL((k_kpp_round<IR, RB>), dim3(nblocks), dim3(64 * pl.nw), lds, ctx->stream, (const IR*)s->ir,
                            (const double*)s->x, T, (int)s->p, n, s->fixed_s, pl.pts, live, first_round, run);
+    else if (pl.form == 3)
+        hipLaunchKernelGGL((k_kpp_round_ragged<IR, RB>), dim3(nblocks), dim3(64 * pl.nw), lds, ctx->stream, (const long long*)s->jc,
+                           (const IR*)s->ir, (const double*)s->x, T, (int)s->p, n, (long long)s->nnz, s->max_s, pl.pts, live,
+                           first_round, run);
     else
         hipLaunchKernelGGL((k_kpp_round_generic<IR, RB>), dim3(nblocks), dim3(256), 0, ctx->stream, (const long long*)s->jc,
                            (const IR*)s->ir, (const double*)s->x, T, n, live, first_round, run);
@@ -1209,10 +1213,11 @@ static int kpp_seed_run(spkm_ctx* ctx, const spkm_shard* s, int K, double gamma,
     HIP_TRY(hipMemsetAsync(dst, 0, (size_t)R * 4, ctx->stream));
     size_t lds = 0;
     int nblocks;
-    if (pl.form == 1) {
+    if (pl.form == 1 || pl.form == 3) {
+        // (form 3: the ragged shard's plan is the fixed-stride plan of its longest column -- the same sizes from max_s)
         const int nw = pl.nw;
-        lds = (size_t)p * RB * 8 + (size_t)nw * pl.pts * (s->fixed_s | 1) * 12;
-        HIP_TRY(allow_lds(ctx, (const void*)k_kpp_round<IR, RB>, lds));
+        lds = (size_t)p * RB * 8 + (size_t)nw * pl.pts * ((pl.form == 1 ? s->fixed_s : s->max_s) | 1) * 12;
+        HIP_TRY(allow_lds(ctx, pl.form == 1 ? (const void*)k_kpp_round<IR, RB> : (const void*)k_kpp_round_ragged<IR, RB>, lds));
         const long long per = (long long)nw * pl.pts;
         // (workgroups of fewer than 16 waves go several to a CU where their LDS allows)
         const long long per_cu = std::max<long long>(1, std::min<long long>(spkm_kpp_nw_max / nw, (long long)(ctx->lds_max / (lds + 1024))));
@@ -1225,7 +1230,9 @@ static int kpp_seed_run(spkm_ctx* ctx, const spkm_shard* s, int K, double gamma,
         HIP_TRY(hipMemsetAsync(T, 0, (size_t)p * RB * 8, ctx->stream));
         for (int k = 0; k < K; k++) {
             if (k > 0) {
+                if (ctx->tlog_kpp) HIP_TRY(timing_begin(ctx)); // (events on the stream: no round waits for the host)
                 kpp_launch_round<IR, RB>(ctx, s, pl, nblocks, lds, T, live, k == 1, run);
+                if (ctx->tlog_kpp) HIP_TRY(timing_end(ctx));
                 hipLaunchKernelGGL(k_kpp_totals, dim3(nb, live), dim3(256), 0, ctx->stream, (const double*)run, n, nb, tot);
             }
             hipLaunchKernelGGL((k_kpp_pick<IR>), dim3(live), dim3(256), 0, ctx->stream, (const long long*)s->jc, (const IR*)s->ir,
@@ -1274,8 +1281,12 @@ extern "C" int spkm_kpp_seed_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K6
         (void)hipGetLastError();
         free_b = ctx->mem_bytes;
     }
-    const spkm_kpp_plan_t pl = spkm_kpp_plan((long long)s->p, s->nnz > 0 ? s->fixed_s : 0, s->slack, R, (long long)s->n, ctx->lds_max,
-                                             (unsigned long long)free_b);
+    // a ragged shard opted in to the staged form (itself, or by the context's switch: its longest column is measured here then)
+    const bool kpp_ragged = s->fixed_s == 0 && s->nnz > 0 && (s->kpp_ragged || ctx->sw.kpp_ragged);
+    if (kpp_ragged)
+        if (int rcm = ensure_max_s(ctx, const_cast<spkm_shard*>(s))) return rcm;
+    const spkm_kpp_plan_t pl = spkm_kpp_plan_ragged((long long)s->p, s->nnz > 0 ? s->fixed_s : 0, kpp_ragged ? s->max_s : 0, s->nnz,
+                                                    s->slack, R, (long long)s->n, ctx->lds_max, (unsigned long long)free_b, kpp_ragged);
     const int rc = s->ir_bits == 16
         ? kpp_seed_dispatch<unsigned short>(ctx, s, (int)K64, gamma, (int)R, pl, first, u, chosen, status, d_run)
         : kpp_seed_dispatch<unsigned int>(ctx, s, (int)K64, gamma, (int)R, pl, first, u, chosen, status, d_run);
@@ -1284,7 +1295,8 @@ extern "C" int spkm_kpp_seed_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K6
     return SPKM_OK;
 }
 
-// What the context's last spkm_kpp_seed_dev ran: info = { form (1 staged, 2 generic; 0: none yet, K = 1 or a failed call),
+// What the context's last spkm_kpp_seed_dev ran: info = { form (1 staged, 2 generic, 3 staged over a ragged shard; 0: none
+// yet, K = 1 or a failed call),
 // replicates per batch, batches, points staged per wave }.  Stored values; does not block.
 extern "C" int spkm_last_kpp_plan(spkm_ctx* ctx, int info[4])
 {

@@ -116,6 +116,109 @@ __global__ __launch_bounds__(64 * KPP_WAVES) void k_kpp_round(const IR* __restri
     }
 }
 
+// Staged form over a RAGGED shard (policy.h, spkm_kpp_plan_ragged: form 3): k_kpp_round with the column bounds read from jc.
+// A trip's have <= pts <= 64 points: lane l reads jc[b0 + l] and jc[b0 + l + 1] once, coalesced, and keeps its point's
+// start relative to jc[b0] and its length; point pt's pair reaches the staging loop as wave-uniform values (v_readlane with
+// a uniform index), so the loads are k_kpp_round's -- lanes <-> entries of one column, U = 8 columns' loads issued before
+// the first LDS store, a column longer than 64 entries in further steps of 64.  Every load's index is clamped into
+// [0, nnz): the arrays have no slack behind them (spkm_kpp_slack = 0), an empty column's clamped load is not stored, and
+// nnz > 0 by the plan.  Then a lane owns a point and walks its own length; an empty column leaves sqrt(0) = 0.
+// Staging layout: point q of the trip at q * S1, S1 = max_s | 1 -- the fixed kernel's, and the one the plan sized (pts
+// points of max_s | 1 entries per wave).  A flat layout at jc[pt] - jc[b0] would pack more points into the same bytes, but
+// the plan would then need a capacity rule in entries, and lane l's walk would start at a data-dependent bank; the odd
+// stride spreads the 64 walks over the banks whatever the lengths are.
+// A length above max_s (a stale max_s: the caller changed jc behind the library's back) is cut to max_s, so that no LDS
+// store leaves the point's slot.
+// LDS: T f64[p * RB] | per wave vs f64[pts * S1] | per wave rs i32[pts * S1]
+template <typename IR, int RB>
+__global__ __launch_bounds__(64 * KPP_WAVES) void k_kpp_round_ragged(const long long* __restrict__ jc, const IR* __restrict__ ir,
+                                                                     const double* __restrict__ x, const double* __restrict__ Tg,
+                                                                     int p, long long n, long long nnz, int max_s, int pts, int live,
+                                                                     int first_round, double* __restrict__ run)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* T = reinterpret_cast<double*>(smem);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = blockDim.x >> 6;
+    const int S1 = max_s | 1;
+    double* vs = T + (size_t)p * RB + (size_t)wave * pts * S1;
+    int* rs = reinterpret_cast<int*>(T + (size_t)p * RB + (size_t)nwaves * pts * S1) + (size_t)wave * pts * S1;
+    for (int t = tid; t < p * RB; t += blockDim.x) T[t] = Tg[t];
+    __syncthreads();
+    constexpr int U = 8;
+    const long long stride = (long long)gridDim.x * nwaves * pts;
+    for (long long b0 = ((long long)blockIdx.x * nwaves + wave) * pts; b0 < n; b0 += stride) {
+        const int have = (n - b0 < pts) ? (int)(n - b0) : pts;
+        // column bounds: one coalesced read of jc per trip (lanes >= have: an empty column at the trip's start)
+        const long long j0 = jc[b0 + (lane < have ? lane : 0)];
+        const long long j1 = lane < have ? jc[b0 + lane + 1] : j0;
+        const long long base = ((long long)__builtin_amdgcn_readfirstlane((int)(j0 >> 32)) << 32) |
+                               (unsigned)__builtin_amdgcn_readfirstlane((int)j0); // jc[b0]: lane 0 is a point of the trip
+        const int rel = (int)(j0 - base);
+        const int len = (j1 - j0 < max_s) ? (int)(j1 - j0) : max_s;
+        for (int u = 0; u < have; u += U) {
+            double xv[U];
+            int rv[U];
+#pragma unroll
+            for (int v = 0; v < U; v++) {
+                const int pc = (u + v < have) ? u + v : have - 1;
+                const long long st = base + __builtin_amdgcn_readlane(rel, pc);
+                const int ln = __builtin_amdgcn_readlane(len, pc);
+                const int e = lane < ln ? lane : (ln > 0 ? ln - 1 : 0);
+                long long off = st + e;
+                off = off < nnz ? off : nnz - 1; // (only an empty column at the arrays' end is moved by this)
+                xv[v] = x[off];
+                rv[v] = (int)ir[off];
+            }
+#pragma unroll
+            for (int v = 0; v < U; v++) {
+                if (u + v < have) {
+                    const long long st = base + __builtin_amdgcn_readlane(rel, u + v);
+                    const int ln = __builtin_amdgcn_readlane(len, u + v);
+                    if (lane < ln) {
+                        vs[(size_t)(u + v) * S1 + lane] = xv[v];
+                        rs[(size_t)(u + v) * S1 + lane] = rv[v];
+                    }
+                    for (int e = 64 + lane; e < ln; e += 64) { // columns longer than one wave
+                        vs[(size_t)(u + v) * S1 + e] = x[st + e];
+                        rs[(size_t)(u + v) * S1 + e] = (int)ir[st + e];
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (lane < have) {
+            double acc[RB];
+#pragma unroll
+            for (int r = 0; r < RB; r++) acc[r] = 0.0;
+            const double* vq = vs + (size_t)lane * S1;
+            const int* rq = rs + (size_t)lane * S1;
+            for (int j = 0; j < len; j++) { // storage order
+                const double xj = vq[j];
+                double c[RB];
+                kpp_row<RB>::load(T + (size_t)rq[j] * RB, c);
+#pragma unroll
+                for (int r = 0; r < RB; r++) {
+                    const double d = xj + c[r]; // RN(x - c): the reference's subtraction
+                    acc[r] = acc[r] + d * d;
+                }
+            }
+            const long long i = b0 + lane;
+#pragma unroll
+            for (int r = 0; r < RB; r++) {
+                if (r < live) {
+                    double v = sqrt(acc[r]);
+                    double* dst = run + (size_t)r * n + i;
+                    if (!first_round) { const double o = *dst; v = o < v ? o : v; }
+                    *dst = v;
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // Generic form: any CSC (ragged, empty columns) and any p.  One lane per point walks its column; T is read from global
 // memory (L2).  The correctness floor, like k_assign_generic.
 template <typename IR, int RB>

@@ -461,11 +461,11 @@ constexpr int spkm_kpp_nw_max = 16, spkm_kpp_nw_min = 4, spkm_kpp_rb_max = 8, sp
 //  condition in this plan and in its tests, not in the launch code.)
 constexpr unsigned long long spkm_kpp_slack = 0;
 struct spkm_kpp_plan_t {
-    int form = 2;    // 1 staged (T in LDS), 2 generic
+    int form = 2;    // 1 staged (T in LDS), 2 generic, 3 staged over a ragged shard (spkm_kpp_plan_ragged)
     int RB = 1;      // replicates per batch
-    int pts = 0;     // points staged per wave (form 1)
+    int pts = 0;     // points staged per wave (forms 1 and 3)
     int batches = 1;
-    int nw = 0;      // waves per workgroup (form 1)
+    int nw = 0;      // waves per workgroup (forms 1 and 3)
 };
 // points staged per wave beside a table of RB replicates at nw waves per workgroup (0: does not fit)
 inline int spkm_kpp_pts(long long p, int fixed_s, int RB, int nw, size_t lds_max)
@@ -500,6 +500,23 @@ inline spkm_kpp_plan_t spkm_kpp_plan(long long p, int fixed_s, unsigned long lon
     }
     a.batches = (int)((R + a.RB - 1) / a.RB);
     return a;
+}
+//  3  k_kpp_round_ragged: a RAGGED shard (fixed_s = 0) that opted in (kpp_ragged: the shard, spkm_shard_set_kpp_ragged, or
+//     the context, SPKM_KPP_RAGGED=1 -- a switch of its own), with entries (nnz > 0, max_s > 0) and a p at which some RB of
+//     cap .. 1 has a staged table beside 16 points of max_s | 1 entries per wave.  The plan IS the fixed-stride plan of the
+//     shard's longest column, field for field -- RB, nw, pts, batches, the halving on free_bytes -- with form 3 in form 1's
+//     place: a staging area of nw * pts * (max_s | 1) entries holds any pts consecutive columns at a per-point stride of
+//     max_s | 1, so no second capacity rule exists.  slack: the kernel's loads are clamped to [0, nnz) (spkm_kpp_slack = 0).
+// Everything else is spkm_kpp_plan's answer: form 1 for a fixed-stride shard, which never hears the opt-in; form 2 for a
+// ragged shard that did not opt in, has no entries, or has a p too wide for one column of the table.
+inline spkm_kpp_plan_t spkm_kpp_plan_ragged(long long p, int fixed_s, int max_s, unsigned long long nnz, unsigned long long slack,
+                                            unsigned R, long long n, size_t lds_max, unsigned long long free_bytes, bool kpp_ragged)
+{
+    if (fixed_s <= 0 && kpp_ragged && nnz > 0 && max_s > 0) {
+        spkm_kpp_plan_t a = spkm_kpp_plan(p, max_s, slack, R, n, lds_max, free_bytes);
+        if (a.form == 1) { a.form = 3; return a; }
+    }
+    return spkm_kpp_plan(p, fixed_s, slack, R, n, lds_max, free_bytes);
 }
 // far shards with incremental sums: k_combine_screen keeps 2 K event counters (8 K bytes) in dynamic LDS beside 16 KB of
 // static stage -- 32 KB of counters (K <= 4096) stay inside the 64 KB every launch may use without asking

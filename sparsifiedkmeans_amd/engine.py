@@ -146,6 +146,15 @@ class Shard:
         listed.  Outputs never depend on it; the shard's policy state is forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_tile_ragged(self.handle, 1 if on else 0), "spkm_shard_set_tile_ragged")
 
+    def set_kpp_ragged(self, on: bool = True):
+        """Let ``kpp_seed`` on this shard, when it is RAGGED (columns of different lengths: a sample whose exact zeros were
+        dropped), run the staged round kernel in the form that reads each point's column bounds -- the newest centres'
+        table in LDS, the entries staged by coalesced loads, 8 replicates sharing one read -- wherever the fixed-stride plan
+        of its longest column has a staged table, instead of the generic kernel (spkm_shard_set_kpp_ragged; off by default;
+        a switch of its own).  Picks, statuses and running minima never depend on it; last_kpp_plan() reports
+        'staged-ragged'.  A fixed-stride shard never hears it."""
+        _lib.check(_lib.lib().spkm_shard_set_kpp_ragged(self.handle, 1 if on else 0), "spkm_shard_set_kpp_ragged")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""
@@ -214,12 +223,13 @@ def torch_context(device: int | None = None) -> Context:
     return Context(device, torch.cuda.current_stream(device).cuda_stream)
 
 
-KPP_FORMS = {0: "none", 1: "staged", 2: "generic"}   # spkm_last_kpp_plan's info[0]
+KPP_FORMS = {0: "none", 1: "staged", 2: "generic", 3: "staged-ragged"}   # spkm_last_kpp_plan's info[0]
 
 
 def last_kpp_plan(ctx: Context) -> tuple[str, int, int, int]:
     """(form, RB, batches, points staged per wave) of the context's last ``kpp_seed`` (spkm_last_kpp_plan): form
-    'staged' = the newest centres' table in LDS, 'generic' = in global memory, 'none' = no seeding yet or K = 1."""
+    'staged' = the newest centres' table in LDS, 'generic' = in global memory, 'staged-ragged' = in LDS over a ragged shard
+    that opted in (Shard.set_kpp_ragged), 'none' = no seeding yet or K = 1."""
     a = (C.c_int * 4)()
     _lib.check(_lib.lib().spkm_last_kpp_plan(ctx.handle, a), "spkm_last_kpp_plan")
     return KPP_FORMS[int(a[0])], int(a[1]), int(a[2]), int(a[3])

@@ -81,8 +81,14 @@ _DEFAULTS = dict(
 # shard between them (engine.kpp_seed) -- with 'Sparsify',true, unbiasedInitialization, one process and an EmptyAction other
 # than 'drop' (a drop shrinks K for the later replicates); False: replicate by replicate (_arthur).  Outputs never depend on
 # it: OUTPUT["seedPoints"] records the picks of either path.
+# kppRagged: on a RAGGED shard that one call runs the staged round kernel -- the newest centres' table in LDS, the entries
+# staged by coalesced loads -- in the form that reads each point's column bounds, instead of the generic kernel
+# (Shard.set_kpp_ragged; OUTPUT["seedPlan"][0] reads 'staged-ragged').  Picks never depend on it.  Off by default: the
+# shapes of profiles/kpp_ragged_ab.txt were run once (every pair wins: the start 1.1x to 6.6x faster), and the default waits
+# for a second series.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
-              slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True)
+              slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True,
+              kppRagged=False)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -433,6 +439,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_far_screen(bool(o["farScreen"]))
     shard.set_far_ragged(bool(o["farRagged"]))
     shard.set_tile_ragged(bool(o["tileRagged"]))
+    shard.set_kpp_ragged(bool(o["kppRagged"]))
     shard.set_far_bounds(bool(o["farBounds"]))
     shard.set_far_events(bool(o["farEvents"]))
     shard.set_sliced_sums(bool(o["slicedSums"]))
