@@ -1,5 +1,7 @@
 // Which form the next fused call takes -- the host-side policy of the screen path, on its own so that it can be read,
-// and tested (tests/test_policy.py drives it through tables on the CPU), apart from the launch code in api_lloyd.hip.
+// and tested on the CPU, apart from the launch code in api_lloyd.hip: tests/native/plan_harness.cpp is a C face on this
+// file that reaches every struct field by name, and tests/test_policy.py and tests/test_*plan*.py drive it through tables.
+// A field added to spkm_call_in or spkm_call_plan is named in that harness's table (its build fails until it is).
 //
 // Nothing here can change an output: every form computes the reference's assignment; the policy only chooses how much
 // work the next call does.  It sees the counters of a screen call ONE CALL LATE (copied back asynchronously: no host
@@ -524,6 +526,10 @@ constexpr size_t spkm_far_events_kmax_bytes = 32 * 1024;
 struct spkm_call_in {
     long long n = 0;
     int p = 0, K = 0, fixed_s = 0;
+    // the shard's LONGEST column: fixed_s on a fixed-stride shard; on a ragged one (fixed_s = 0: the RAGGED far screen,
+    // spkm_far_screen_ragged) the length a plan takes wherever it needs one
+    int max_s = 0;
+    // the screen kind
     bool quad = false;          // the 4-lanes-per-point screen (s <= 64)
     bool carry_bounds = false;  // this non-quad shard carries bounds (spkm_shard_set_wide_bounds; far: spkm_shard_set_far_bounds): point lists only
     bool far = false;           // the far screen (k_screen_far): no exact pass behind it
@@ -543,10 +549,6 @@ struct spkm_call_in {
     long long sp_blocks = 0;
     bool same_assign = false, assign_synced = false, sort_kept = false, sort_reusable = false;
     int prune_a = 0; bool want_hint = false; // the caller's choice (spkm_policy::next)
-    // the shard's LONGEST column: fixed_s on a fixed-stride shard; on a ragged one (fixed_s = 0: the RAGGED far screen,
-    // spkm_far_screen_ragged) the length a plan takes wherever it needs one.  (In the padding behind want_hint: the input
-    // keeps its size and the offsets tests/test_policy.py mirrors.)
-    int max_s = 0;
 };
 struct spkm_call_plan {
     // tiles of G x 32 centroids (G x 16 / G x 8: the narrow tiles of k_screen_wide, pl_last 4); pl_last = centroid pairs per lane of the last one (1, 2, 4; 5: its <= 4 centroids ride on

@@ -1,15 +1,14 @@
 """CPU: which kernel spkm_accumulate_dev takes (sparsifiedkmeans_amd/csrc/policy.h: spkm_accumulate_form) -- the 64-KB slab
 wherever it fits (form 1), the sliced slab only for a shard or context that opted in and only up to spkm_acc_max_slices
 slices (form 3), the atomics otherwise (form 2) -- and the slices it plans.  Every limit is restated here in plain integers
-and checked at the LDS size gfx950 reports (163840 B) and at 65536 B.  Compiled with g++ behind a small C harness
-(tests/native/acc_plan_harness.cpp)."""
+and checked at the LDS size gfx950 reports (163840 B) and at 65536 B.  Reached through tests/plan_harness.py
+(tests/native/plan_harness.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 LDS = (163840, 65536)
 ROW = 12                    # a double and a counter per row
 SLAB1 = 64 * 1024           # k_accumulate_sorted's slab stops here whatever the device holds
@@ -17,12 +16,8 @@ WG = 1024
 
 
 @pytest.fixture(scope="module")
-def ap(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("accplan") / "libaccplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "acc_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.acc_form.argtypes = [C.c_longlong, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    return L
+def ap():
+    return PH.lib()
 
 
 def plan(ap, L, p, sliced, x=0):
@@ -44,8 +39,8 @@ PS = [1, 2, 100, 5461, 5462, 5463, 8191, 8192, 13653, 13654, 16384, 27306, 27307
 
 
 def test_constants(ap):
-    assert ap.acc_row_bytes() == ROW and ap.acc_static_lds() == 0
-    assert 1 <= ap.acc_max_slices() <= 64
+    assert PH.const("spkm_acc_row_bytes") == ROW and PH.const("acc_static_lds") == 0
+    assert 1 <= PH.const("spkm_acc_max_slices") <= 64
 
 
 @pytest.mark.parametrize("L", LDS)
@@ -75,7 +70,7 @@ def test_never_form_3_without_the_opt_in(ap, L):
 def test_slices_cover_the_rows_once_and_fit_the_lds(ap, L):
     """opted in, past the 64-KB slab: R is what the LDS holds, the slices [j R, min(p, (j + 1) R)) cover [0, p) exactly once,
     the last may be short, R x 12 B plus the kernel's static LDS fits, and the count respects the cap"""
-    cap, rmax = ap.acc_max_slices(), (L - ap.acc_static_lds()) // ROW
+    cap, rmax = PH.const("spkm_acc_max_slices"), (L - PH.const("acc_static_lds")) // ROW
     assert rmax == {163840: 13653, 65536: 5461}[L]
     seen3 = 0
     for p in sorted(set(PS) | {rmax, rmax + 1, 2 * rmax, 2 * rmax + 1, cap * rmax, cap * rmax + 1}):
@@ -89,7 +84,7 @@ def test_slices_cover_the_rows_once_and_fit_the_lds(ap, L):
             continue
         seen3 += 1
         assert (f, R, sl, wg) == (3, min(p, rmax), want, WG), (p, L)
-        assert R * ROW + ap.acc_static_lds() <= L
+        assert R * ROW + PH.const("acc_static_lds") <= L
         cover = slices_of(p, R)
         assert len(cover) == sl and cover[0][0] == 0 and cover[-1][1] == p
         assert all(a[1] == b[0] for a, b in zip(cover, cover[1:])) and all(0 < hi - lo <= R for lo, hi in cover)
@@ -106,7 +101,7 @@ def test_slices_cover_the_rows_once_and_fit_the_lds(ap, L):
 @pytest.mark.parametrize("L", LDS)
 def test_the_widest_sketch_stays_on_the_atomics(ap, L):
     assert plan(ap, L, 1 << 24, 1) == (2, 0, 0, 256) and plan(ap, L, 1 << 24, 0) == (2, 0, 0, 256)
-    assert -(-(1 << 24) // (L // ROW)) > ap.acc_max_slices()
+    assert -(-(1 << 24) // (L // ROW)) > PH.const("spkm_acc_max_slices")
 
 
 def test_the_hadamard_widths(ap):

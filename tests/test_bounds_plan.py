@@ -1,51 +1,29 @@
 """CPU: the plan of a fused call on a shard that carries bounds beyond the 4-lanes-per-point screen
 (sparsifiedkmeans_amd/csrc/policy.h: spkm_call_in.carry_bounds, set for a shard with spkm_shard_set_wide_bounds that takes
 the narrow tiles or the 16-lanes-per-point kernel).  With the field set a non-quad plan tests its bounds point by point and
-nothing else; with it clear every plan -- quad plans with it at either value included -- is what it was.  Compiled with g++
-behind a small C harness (tests/native/bounds_plan_harness.cpp)."""
-import ctypes as C
+nothing else; with it clear every plan -- quad plans with it at either value included -- is what it was.  Planned through
+tests/plan_harness.py in run_screen's stages: spkm_plan_tiles at the call's width, spkm_plan_call, spkm_plan_sums."""
 import itertools
-import os
-import subprocess
 
 import pytest
 
-import test_policy
+import plan_harness as PH
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PLAN_FIELDS = ("G pl_last Gs nr bounds_ok kept ev_possible pair_capable ev_path pair_ev skip_enabled pt_mode hinted late prune_a "
-               "rounds_all drift erode sp_on sp_reset trusted npad span chunk bgrid use_rec pipe cl_on cl_skip sums_only lazy_ub dual "
-               "reuse nk_incr direct ev_cap seg_ev").split()
+# the input's flags, by their field names or the short spellings of plan_harness.ALIASES
 IN_FLAGS = ("quad carry bounds_valid no_bounds lazy want_dist sort_kept cl_valid cl_stats want_hint same_assign synced sp_clean "
             "sort_reusable force_pt has_map no_point_list").split()
 LDS, CUS = 163840, 256
 
 
 @pytest.fixture(scope="module")
-def bp(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("boundsplan") / "libboundsplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "bounds_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.bplan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
-                        C.c_uint64, C.c_int, C.POINTER(C.c_longlong)]
-    assert L.bplan_fields() == len(PLAN_FIELDS)
-    return L
+def bp():
+    return PH.lib()
 
 
 def plan(bp, n, p, K, s, kt, flags, prune_a=0, teams=32, pol=0, movers=0, rec=1, lds=LDS, cus=CUS):
-    bits = sum(1 << IN_FLAGS.index(f) for f in flags)
-    out = (C.c_longlong * len(PLAN_FIELDS))()
-    bp.bplan(n, p, K, s, kt, bits, prune_a, lds, cus, teams, pol, movers, rec, out)
-    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
-
-
-def test_the_new_field_lies_in_padding(bp):
-    """spkm_call_in keeps its size and the offsets tests/test_policy.py mirrors: carry_bounds takes a padding byte behind quad"""
-    out = (C.c_int * 4)()
-    bp.bplan_layout(out)
-    size, quad, carry, lds = out
-    assert size == C.sizeof(test_policy.CallIn) and quad == test_policy.CallIn.quad.offset and lds == test_policy.CallIn.lds_max.offset
-    assert quad < carry < lds
+    assert set(flags) <= set(IN_FLAGS)
+    inp = PH.call_in(flags, n=n, p=p, K=K, fixed_s=s, lds_max=lds, num_cus=cus, teams=teams, prune_a=prune_a)
+    return PH.plan(inp, PH.policy_bits(pol, movers), kt=kt, rec=rec)
 
 
 # shapes off the 4-lanes-per-point screen: (p, s, kt): narrow tiles of 16 and 8, long columns at 32
@@ -83,7 +61,7 @@ def test_non_quad_plan_with_the_field_set_and_clear(bp, p, s, kt):
             else:
                 assert (on["span"], on["bgrid"]) == (0, 0), tag
             # everything else: as with the field clear
-            for f in PLAN_FIELDS:
+            for f in PH.plan_fields():
                 if f not in ON + ("span", "bgrid"):
                     assert on[f] == off[f], (f, tag)
             # the tiles: plain ones at the call's width, every round for all centroids, the two-phase choice ignored
@@ -124,6 +102,6 @@ def test_quad_plans_do_not_see_the_field(bp, row):
     for rec in (0, 1):
         a = plan(bp, n, p, K, s, 32, fl + ["quad"], prune_a=prune_a, pol=pol, movers=movers, rec=rec, teams=48)
         b = plan(bp, n, p, K, s, 32, fl + ["quad", "carry"], prune_a=prune_a, pol=pol, movers=movers, rec=rec, teams=48)
-        assert a == b, {f: (a[f], b[f]) for f in PLAN_FIELDS if a[f] != b[f]}
+        assert a == b, {f: (a[f], b[f]) for f in PH.plan_fields() if a[f] != b[f]}
     if "bounds_valid" in fl:
         assert a["bounds_ok"] == 1                            # (the table does reach the bounds branch of the quad plan)

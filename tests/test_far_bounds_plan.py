@@ -3,21 +3,15 @@ with carry_bounds, set by run_far for a shard with spkm_shard_set_far_bounds or 
 takes the carry_bounds branch of the narrow tiles -- points only, the same span shortening -- with the two differences the
 branch states: no exact pass writes upper bounds behind the far screen, so every test erodes and the certify stage writes the
 upper bounds in every call (lazy_ub, set where the plan is made: a far call never reaches spkm_plan_sums).  No hints, events,
-block summaries or cluster shortcut.  Compiled with g++ behind a small C harness (tests/native/far_bounds_plan_harness.cpp),
-which plans as run_far does."""
-import ctypes as C
+block summaries or cluster shortcut.  Planned through tests/plan_harness.py as run_far does: spkm_plan_tiles at the plane
+width, then spkm_plan_call."""
 import itertools
-import os
-import subprocess
 
 import pytest
 
-import test_policy
+import plan_harness as PH
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PLAN_FIELDS = ("G pl_last Gs nr bounds_ok kept ev_possible pair_capable ev_path pair_ev skip_enabled pt_mode hinted late prune_a "
-               "rounds_all drift erode sp_on sp_reset trusted npad span chunk bgrid use_rec pipe cl_on cl_skip sums_only lazy_ub dual "
-               "reuse nk_incr direct ev_cap seg_ev").split()
+# the input's flags, by their field names or the short spellings of plan_harness.ALIASES
 IN_FLAGS = ("far carry bounds_valid no_bounds lazy want_dist sort_kept cl_valid cl_stats want_hint same_assign synced sp_clean "
             "sort_reusable force_pt has_map no_point_list").split()
 LDS, CUS = 163840, 256
@@ -29,31 +23,14 @@ BAIT = ["sort_kept", "cl_valid", "cl_stats", "want_hint", "same_assign", "synced
 
 
 @pytest.fixture(scope="module")
-def fb(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("farboundsplan") / "libfarboundsplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "far_bounds_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.fbplan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
-                         C.c_uint64, C.POINTER(C.c_longlong)]
-    assert L.fbplan_fields() == len(PLAN_FIELDS)
-    return L
+def fb():
+    return PH.lib()
 
 
 def plan(fb, n, p, K, s, flags, prune_a=0, teams=32, pol=0, movers=0, lds=LDS, cus=CUS):
-    kp = 64 if K <= 64 else (128 if K <= 128 else 256)
-    bits = sum(1 << IN_FLAGS.index(f) for f in flags)
-    out = (C.c_longlong * len(PLAN_FIELDS))()
-    fb.fbplan(n, p, K, s, kp, bits, prune_a, lds, cus, teams, pol, movers, out)
-    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
-
-
-def test_the_new_field_lies_in_padding(fb):
-    """spkm_call_in keeps its size and the offsets tests/test_policy.py mirrors: far takes a padding byte behind carry_bounds"""
-    out = (C.c_int * 5)()
-    fb.fbplan_layout(out)
-    size, quad, carry, far, lds = out
-    assert size == C.sizeof(test_policy.CallIn) and quad == test_policy.CallIn.quad.offset and lds == test_policy.CallIn.lds_max.offset
-    assert quad < carry < far < lds
+    assert set(flags) <= set(IN_FLAGS)
+    inp = PH.call_in(flags, n=n, p=p, K=K, fixed_s=s, lds_max=lds, num_cus=cus, teams=teams, prune_a=prune_a)
+    return PH.plan(inp, PH.policy_bits(pol, movers), kt=PH.far_plane_of(K))
 
 
 # shapes of the far screen: (p, s): past the narrowest tile (16- and 32-bit row ids) and the phase-2 case

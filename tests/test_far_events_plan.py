@@ -1,68 +1,45 @@
 """CPU: the plan of a FAR screen call on a shard that opted in to incremental sums (sparsifiedkmeans_amd/csrc/policy.h:
 spkm_call_in.far_events, set by run_far for a shard with spkm_shard_set_far_events or a context with SPKM_FAR_EVENTS=1 that
-carries bounds).  Compiled with g++ behind a small C harness (tests/native/far_events_plan_harness.cpp), which plans as
-run_far does.
+carries bounds).  Planned through tests/plan_harness.py as run_far does: spkm_plan_tiles at the plane width, then
+spkm_plan_call.
 
- * the input keeps its size and offsets; the flag lies in the padding byte in front of lds_max;
  * without the flag every field of the plan equals the plan of the policy.h BEFORE the flag existed, over the grid of
-   tests/test_far_bounds_plan.py -- recorded from that file by this module run as a script
-   (tests/golden/far_events_parent_plans.npy.gz, one row of PLAN_FIELDS per case: `python tests/test_far_events_plan.py
-   <that policy.h>` writes it);
+   tests/test_far_bounds_plan.py (tests/golden/far_events_parent_plans.npy.gz: one row per case, one column per field of
+   spkm_call_plan in declaration order, recorded from the policy.h of commit badf8a1, "Seed all replicates' k-means++
+   starts in one pass over the shard", the last one without the flag);
  * with the flag, ev_path is set exactly when the call is lazy and wants no distances, the bounds and the kept sums are
    valid, SPKM_NO_INCREMENTAL is off, a mover count is known and at most a third of the points, and no refresh is due -- and
    (a limit of the event stage, not a policy: k_combine_screen's 2 K counters in LDS) K <= 4096;
  * direct exactly below 2048 known movers; nothing else of the 4-lanes-per-point screen's machinery is ever set; a
    carry_bounds plan that is not far does not see the flag."""
-import ctypes as C
 import gzip
 import itertools
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import test_policy  # noqa: E402
-from test_far_bounds_plan import BAIT, CUS, LDS, PLAN_FIELDS, SHAPES, SIZES  # noqa: E402
-from test_far_bounds_plan import IN_FLAGS as FB_FLAGS  # noqa: E402
+import plan_harness as PH
+from test_far_bounds_plan import BAIT, CUS, LDS, SHAPES, SIZES
+from test_far_bounds_plan import IN_FLAGS as FB_FLAGS
 
 IN_FLAGS = list(FB_FLAGS) + ["events", "no_incremental", "no_direct"]
-GOLDEN = os.path.join(HERE, "golden", "far_events_parent_plans.npy.gz")
-HARNESS = os.path.join(HERE, "native", "far_events_plan_harness.cpp")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "far_events_parent_plans.npy.gz")
 # what the flag may switch on, and the segment length that goes with it
 MAY = ("ev_possible", "ev_path", "direct", "seg_ev")
 NEVER = ("kept", "pair_capable", "pair_ev", "hinted", "late", "sp_on", "trusted", "use_rec", "pipe", "cl_on", "cl_skip", "sums_only",
          "dual", "reuse", "nk_incr")
 
 
-def load(so):
-    L = C.CDLL(so)
-    L.feplan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int,
-                         C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_longlong)]
-    assert L.feplan_fields() == len(PLAN_FIELDS)
-    return L
-
-
 @pytest.fixture(scope="module")
-def fe(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("fareventsplan") / "libfareventsplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", HARNESS, "-o", so])
-    return load(so)
+def fe():
+    return PH.lib()
 
 
 def plan(fe, n, p, K, s, flags, prune_a=0, teams=32, pol=0, movers=0, ev_calls=0, ev_cum=0, lds=LDS, cus=CUS):
-    kp = 64 if K <= 64 else (128 if K <= 128 else 256)
-    bits = sum(1 << IN_FLAGS.index(f) for f in set(flags))      # (a flag named twice -- ON and BAIT share one -- counts once)
-    out = (C.c_longlong * len(PLAN_FIELDS))()
-    fe.feplan(n, p, K, s, kp, bits, prune_a, lds, cus, teams, pol, movers, ev_calls, ev_cum, out)
-    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+    assert set(flags) <= set(IN_FLAGS)                          # (a flag named twice -- ON and BAIT share one -- counts once)
+    inp = PH.call_in(flags, n=n, p=p, K=K, fixed_s=s, lds_max=lds, num_cus=cus, teams=teams, prune_a=prune_a)
+    return PH.plan(inp, PH.policy_bits(pol, movers, ev_calls, ev_cum), kt=PH.far_plane_of(K))
 
 
 def grid():
@@ -78,17 +55,8 @@ def grid_plans(fe):
     for p, s, n, K, fl, pol in grid():
         for carry in ([], ["carry"]):
             q = plan(fe, n, p, K, s, fl + carry, pol=pol, movers=5, prune_a=2)
-            rows.append([q[f] for f in PLAN_FIELDS])
+            rows.append([q[f] for f in PH.plan_fields()])
     return np.array(rows, np.int64)
-
-
-def test_the_new_flag_lies_in_padding(fe):
-    out = (C.c_int * 7)()
-    fe.feplan_layout(out)
-    size, quad, carry, far, lds, flag, cus = out
-    CI = test_policy.CallIn
-    assert size == C.sizeof(CI) and quad == CI.quad.offset and lds == CI.lds_max.offset and cus == CI.num_cus.offset
-    assert quad < carry < far < flag == lds - 1 == 23
 
 
 def test_without_the_flag_the_plan_is_the_one_before(fe):
@@ -97,9 +65,9 @@ def test_without_the_flag_the_plan_is_the_one_before(fe):
     with gzip.open(GOLDEN, "rb") as f:
         want = np.load(f)
     got = grid_plans(fe)
-    assert got.shape == want.shape and want.shape[1] == len(PLAN_FIELDS)
+    assert got.shape == want.shape and want.shape[1] == len(PH.plan_fields())
     bad = np.argwhere(got != want)
-    assert bad.size == 0, [(int(r), PLAN_FIELDS[int(c)]) for r, c in bad[:10]]
+    assert bad.size == 0, [(int(r), PH.plan_fields()[int(c)]) for r, c in bad[:10]]
 
 
 ON = ["far", "carry", "bounds_valid", "lazy", "cl_valid", "events"]
@@ -168,7 +136,7 @@ def test_nothing_else_is_ever_set_and_nothing_else_changes(fe, p, s):
             tag = (n, K, fl, pol, movers)
             for f in NEVER:
                 assert on[f] == 0, (f, tag)
-            for f in PLAN_FIELDS:
+            for f in PH.plan_fields():
                 if f not in MAY:
                     assert on[f] == off[f], (f, tag)
             for f in MAY[:3]:
@@ -185,19 +153,3 @@ def test_a_carrying_shard_that_is_not_far_does_not_see_the_flag(fe):
     assert plan(fe, 3001, 8192, 100, 82, ["far", "lazy", "cl_valid", "bounds_valid", "events"], pol=KNOWN, movers=5) == \
         plan(fe, 3001, 8192, 100, 82, ["far", "lazy", "cl_valid", "bounds_valid"], pol=KNOWN, movers=5)
 
-
-if __name__ == "__main__":
-    # record the plans of a policy.h that has no far_events field: python tests/test_far_events_plan.py path/to/that/policy.h
-    src = os.path.abspath(sys.argv[1])
-    with tempfile.TemporaryDirectory() as tmp:
-        os.makedirs(os.path.join(tmp, "tests", "native"))
-        os.makedirs(os.path.join(tmp, "sparsifiedkmeans_amd", "csrc"))
-        shutil.copy(HARNESS, os.path.join(tmp, "tests", "native"))
-        shutil.copy(src, os.path.join(tmp, "sparsifiedkmeans_amd", "csrc", "policy.h"))
-        so = os.path.join(tmp, "libparent.so")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-DFE_NO_FLAG",
-                               os.path.join(tmp, "tests", "native", "far_events_plan_harness.cpp"), "-o", so])
-        plans = grid_plans(load(so))
-    with gzip.GzipFile(GOLDEN, "wb", mtime=0) as f:
-        np.save(f, plans)
-    print(f"{GOLDEN}: {plans.shape[0]} plans of {plans.shape[1]} fields")

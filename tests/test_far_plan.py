@@ -1,28 +1,18 @@
 """CPU: where a fused call takes the far screen (sparsifiedkmeans_amd/csrc/policy.h: spkm_far_screen) -- only where
 spkm_screen_width finds no screen for want of LDS, only for a shard or context that opted in -- and the planes it plans.
 Every limit is restated here in plain integers and checked at the LDS size gfx950 reports (163840 B) and at 65536 B.
-Compiled with g++ behind a small C harness (tests/native/far_plan_harness.cpp)."""
-import ctypes as C
-import os
-import subprocess
-
+Reached through tests/plan_harness.py (tests/native/plan_harness.cpp)."""
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 LDS = (163840, 65536)
 CUS = 256
 
 
 @pytest.fixture(scope="module")
-def fp(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("farplan") / "libfarplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "far_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.screen_width.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
-    L.far_screen.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.far_planes.argtypes = [C.c_int, C.c_int]
-    L.far_table_max.restype = C.c_uint64
-    return L
+def fp():
+    return PH.lib()
 
 
 def last_p(L, kt):
@@ -136,7 +126,7 @@ def test_plane_cap(fp):
 def test_table_cap(fp):
     """G planes of p + 1 rows of KP floats stay within the 256 MB that the Infinity Cache holds"""
     L, cap = 163840, 256 << 20
-    assert fp.far_table_max() == cap
+    assert PH.const("spkm_far_table_max") == cap
     for K, kp in ((2, 64), (100, 128), (200, 256), (600, 256)):
         G = -(-K // kp)
         p_last = cap // (G * kp * 4) - 1

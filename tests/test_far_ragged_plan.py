@@ -4,19 +4,15 @@ AND to its ragged form, only where no exact LDS tile serves p either (pick_kt's 
 plans of such a shard's calls.  spkm_far_screen itself answers what it always answered: it is held, over the grids of
 tests/test_far_plan.py with fixed_s > 0 and with fixed_s = 0, to a restatement in plain integers of the function as it stood
 before the ragged form existed.  Every limit is restated here and checked at the LDS size gfx950 reports (163840 B) and at
-65536 B.  Compiled with g++ behind a small C harness (tests/native/far_ragged_plan_harness.cpp), which plans as run_far does."""
-import ctypes as C
+65536 B.  Planned through tests/plan_harness.py as run_far does: spkm_plan_tiles at the plane width, then spkm_plan_call."""
 import itertools
-import os
-import subprocess
 
 import pytest
 
-import test_policy
-from test_far_bounds_plan import BAIT, PLAN_FIELDS
+import plan_harness as PH
+from test_far_bounds_plan import BAIT
 from test_far_bounds_plan import IN_FLAGS as FB_FLAGS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 LDS = (163840, 65536)
 CUS = 256
 TABLE_MAX = 256 << 20
@@ -24,20 +20,8 @@ IN_FLAGS = list(FB_FLAGS) + ["events", "no_incremental", "no_direct"]
 
 
 @pytest.fixture(scope="module")
-def rg(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("farraggedplan") / "libfarraggedplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "far_ragged_plan_harness.cpp"),
-                           "-o", so])
-    L = C.CDLL(so)
-    L.screen_width.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
-    L.far_screen.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.far_screen_ragged.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.far_planes.argtypes = [C.c_int, C.c_int]
-    L.far_table_max.restype = C.c_uint64
-    L.rgplan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.c_int, C.c_int, C.c_int,
-                         C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_longlong)]
-    assert L.rgplan_fields() == len(PLAN_FIELDS)
-    return L
+def rg():
+    return PH.lib()
 
 
 # ---- the limits, restated ----
@@ -144,7 +128,7 @@ def test_around_the_last_p_with_an_exact_tile(rg, L, K):
 
 def test_the_table_cap_and_the_plane_cap(rg):
     L = 163840
-    assert rg.far_table_max() == TABLE_MAX
+    assert PH.const("spkm_far_table_max") == TABLE_MAX
     for K, kp in ((2, 64), (100, 128), (200, 256), (600, 256)):
         G = -(-K // kp)
         p_last = TABLE_MAX // (G * kp * 4) - 1
@@ -187,19 +171,9 @@ def test_the_fixed_stride_policies_are_what_they_were(rg, L):
 
 # ---- 3. the plans of a ragged far shard ----
 def plan(rg, n, p, K, flags, max_s=150, s=0, teams=32, pol=0, movers=0, ev_calls=0, ev_cum=0, lds=163840, cus=CUS):
-    bits = sum(1 << IN_FLAGS.index(f) for f in set(flags))
-    out = (C.c_longlong * len(PLAN_FIELDS))()
-    rg.rgplan(n, p, K, s, max_s, plane(K), bits, lds, cus, teams, pol, movers, ev_calls, ev_cum, out)
-    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
-
-
-def test_the_new_field_lies_in_padding(rg):
-    out = (C.c_int * 4)()
-    rg.rgplan_layout(out)
-    size, want_hint, max_s, fixed_s = out
-    CI = test_policy.CallIn
-    assert size == C.sizeof(CI) and want_hint == CI.want_hint.offset and fixed_s == CI.fixed_s.offset
-    assert want_hint < max_s and max_s + 4 <= size
+    assert set(flags) <= set(IN_FLAGS)
+    inp = PH.call_in(flags, n=n, p=p, K=K, fixed_s=s, max_s=max_s, lds_max=lds, num_cus=cus, teams=teams)
+    return PH.plan(inp, PH.policy_bits(pol, movers, ev_calls, ev_cum), kt=PH.far_plane_of(K))
 
 
 SHAPES = [(1279, 150), (2048, 41), (5119, 51), (8192, 82), (16384, 164), (70000, 150)]

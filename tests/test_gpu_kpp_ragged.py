@@ -7,7 +7,7 @@ longest column has a table.
 Every case compares three things: picks, statuses and running minima bit for bit with the host replay (tests/kpp_replay.py);
 the same with the oracle's distances to the picked centres (test_gpu_kpp_seed.check_against_replay does both); and the same
 -- every replicate, whatever its status -- with the same shard seeded with the opt-in off (the generic form).  Every case
-asserts spkm_last_kpp_plan against the plan harness (tests/native/kpp_ragged_plan_harness.cpp) at the LDS size the device
+asserts spkm_last_kpp_plan against the plan harness (tests/plan_harness.py: spkm_kpp_plan_ragged) at the LDS size the device
 reports: those assertions fail where the library has no such form.
 
 Inputs: tests/kpp_ragged_cases.py -- column lengths 0, 1, 7, 8, 9, 63, 64, 65, 127, 128, 129 and 150 in one shard.  Condition on
@@ -23,8 +23,8 @@ import torch
 
 import kpp_ragged_cases as RC
 import kpp_replay as KR
+import plan_harness as PH
 from test_gpu_kpp_seed import check_against_replay
-from test_kpp_ragged_plan import load as load_plan
 from util import mnist_like_pixels, replay_driver_products, set_switch
 
 pytestmark = pytest.mark.gpu
@@ -33,8 +33,8 @@ FORMS = ("none", "staged", "generic", "staged-ragged")
 
 
 @pytest.fixture(scope="module")
-def plan_lib(tmp_path_factory):
-    return load_plan(str(tmp_path_factory.mktemp("kppragged_gpu") / "libkppragged.so"))
+def plan_lib():
+    return PH.lib()
 
 
 def lds_of(ctx):

@@ -3,8 +3,6 @@ tests/kpp_replay.py: the picks of every replicate that reports status 0, the sta
 bit for bit against the oracle's distances to the picked centres -- at every batch width, in the staged and the generic
 form, on both sides of the plan's LDS edges, and against the round-by-round calls the driver has used so far."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,11 +10,11 @@ import scipy.sparse as sp
 import torch
 
 import kpp_replay as KR
+import plan_harness as PH
 from util import parts
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 P, S, K, GAMMA = 256, 13, 6, 13 / 256
 # gamma of the wide shapes: with gamma = s / p there (0.001 ...) a chosen point lies 1 / gamma - 1 times its own norm from
 # itself and is drawn again at once -- every replicate would report a repeat and nothing would be compared.  gamma is an
@@ -25,13 +23,8 @@ WIDE_GAMMA = 0.5
 
 
 @pytest.fixture(scope="module")
-def plan_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("kppplan_gpu") / "libkppplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "kpp_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.kpp_plan.argtypes = [C.c_longlong, C.c_int, C.c_uint64, C.c_uint, C.c_longlong, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)]
-    L.kpp_plan.restype = None
-    return L
+def plan_lib():
+    return PH.lib()
 
 
 def planned(plan_lib, ctx, p, s, R, n):

@@ -1,14 +1,13 @@
 """CPU: how a batched k-means++ seeding is planned (sparsifiedkmeans_amd/csrc/policy.h: spkm_kpp_plan) -- the form, the
 replicates per batch RB, the waves per workgroup, the points staged per wave and the batches.  Every limit is restated
-here in plain integers and checked at the LDS size gfx950 reports (163840 B) and at 65536 B.  Compiled with g++ behind a
-small C harness (tests/native/kpp_plan_harness.cpp)."""
+here in plain integers and checked at the LDS size gfx950 reports (163840 B) and at 65536 B.  Reached through
+tests/plan_harness.py (tests/native/plan_harness.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 LDS = (163840, 65536)
 STAGED, GENERIC = 1, 2
 WAVES = (16, 8, 4)           # waves per workgroup of the staged kernel, the most that fit
@@ -16,13 +15,8 @@ FREE = 1 << 40               # "plenty": the memory cap is out of the way
 
 
 @pytest.fixture(scope="module")
-def kp(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("kppplan") / "libkppplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "kpp_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.kpp_plan.argtypes = [C.c_longlong, C.c_int, C.c_uint64, C.c_uint, C.c_longlong, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)]
-    L.kpp_plan.restype = None
-    return L
+def kp():
+    return PH.lib()
 
 
 def plan(kp, p, s=13, slack=0, R=8, n=100000, L=163840, free=FREE):
@@ -129,7 +123,7 @@ def test_replicates_per_batch(kp, R, rb, nbatch):
 @pytest.mark.parametrize("form_s", (13, 0))
 def test_memory_cap(kp, form_s):
     """RB * n * 8 bytes of running minima stay within a quarter of the free memory: RB is halved at that edge, down to 1"""
-    assert kp.kpp_mem_share() == 4
+    assert PH.const("spkm_kpp_mem_share") == 4
     n = 1000003
     for rb in (8, 4, 2):
         free = 4 * rb * n * 8          # exactly the share for rb replicates

@@ -47,11 +47,12 @@ def test_size_cases_keep_their_replicates(oracle, n):
             assert ok >= RC.needed(case) >= 1, (case["name"], status)
 
 
-def test_the_edges_are_the_plan_s(tmp_path):
+def test_the_edges_are_the_plan_s():
     """EDGES_160K against the plan harness at 163840 bytes: 8 replicates up to the first, any table up to the second"""
-    from test_kpp_ragged_plan import GENERIC, RAGGED, load, ragged
+    import plan_harness as PH
+    from test_kpp_ragged_plan import GENERIC, RAGGED, ragged
 
-    kp = load(str(tmp_path / "libkppragged.so"))
+    kp = PH.lib()
     p8, p1 = RC.EDGES_160K
     assert ragged(kp, p8, RC.MAX_S, 8, 163840)[:2] == (RAGGED, 8) and ragged(kp, p8 + 1, RC.MAX_S, 8, 163840)[:2] == (RAGGED, 4)
     assert ragged(kp, p1, RC.MAX_S, 8, 163840)[:2] == (RAGGED, 1) and ragged(kp, p1 + 1, RC.MAX_S, 8, 163840)[0] == GENERIC

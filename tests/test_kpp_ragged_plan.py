@@ -3,14 +3,13 @@ spkm_kpp_plan_ragged).  An opted-in ragged shard with entries takes the plan of 
 longest column, field for field, with form 3 in form 1's place; everything else -- not opted in, no entries, no longest
 column, a p too wide for one column of the table, a fixed-stride shard -- is spkm_kpp_plan's answer exactly.  spkm_kpp_plan
 itself is held to a restatement of its rule in plain integers on the same grid, so that "equal to spkm_kpp_plan" says
-something.  Compiled with g++ behind a small C harness (tests/native/kpp_ragged_plan_harness.cpp)."""
+something.  Reached through tests/plan_harness.py (tests/native/plan_harness.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 LDS = (163840, 65536)
 MAX_S = (1, 13, 51, 64, 65, 150)
 REPS = (1, 2, 3, 5, 8, 11, 20)
@@ -19,21 +18,9 @@ FREE = 1 << 40               # "plenty": the memory cap is out of the way
 N = 100000
 
 
-def load(path):
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "kpp_ragged_plan_harness.cpp"),
-                           "-o", path])
-    L = C.CDLL(path)
-    L.kpp_plan.argtypes = [C.c_longlong, C.c_int, C.c_uint64, C.c_uint, C.c_longlong, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)]
-    L.kpp_plan.restype = None
-    L.kpp_plan_ragged.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint, C.c_longlong, C.c_uint64, C.c_uint64,
-                                  C.c_int, C.POINTER(C.c_int)]
-    L.kpp_plan_ragged.restype = None
-    return L
-
-
 @pytest.fixture(scope="module")
-def kp(tmp_path_factory):
-    return load(str(tmp_path_factory.mktemp("kppragged") / "libkppragged.so"))
+def kp():
+    return PH.lib()
 
 
 def plan(kp, p, s, R, L, n=N, free=FREE, slack=0):

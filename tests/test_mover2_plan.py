@@ -3,73 +3,56 @@ The pick of the 64 movers, d_R and d_R2 against a restatement in numpy -- random
 fewer than 64 non-zero drifts, a NaN or infinite drift, K = 96 / 100 / 128 / 1024 -- by the host's loop and by the kernel's
 thread layout; list[0..31] and d_R equal to spkm_pick_movers' on every input; the eligibility table (K = 95 / 96, regrouped
 shards, point lists, block summaries, eager statistics, the three switch values); the first level's plan, field by field,
-what tests/native/mover_plan_harness.cpp makes of the same call with the second level on or off.
-Compiled with g++ behind a small C harness (tests/native/mover2_plan_harness.cpp)."""
+what spkm_plan_movers alone makes of the same call with the second level on or off.
+Reached through tests/plan_harness.py (tests/native/plan_harness.cpp)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 MOVERS, MOVERS2, KMIN2 = 32, 64, 96
 FP, IP = C.POINTER(C.c_float), C.POINTER(C.c_int)
 
 
-def _build(tmp, name):
-    so = str(tmp / f"lib{name}.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", f"{name}.cpp"), "-o", so])
-    return C.CDLL(so)
+@pytest.fixture(scope="module")
+def mp2():
+    return PH.lib()
 
 
 @pytest.fixture(scope="module")
-def mp2(tmp_path_factory):
-    L = _build(tmp_path_factory.mktemp("mover2plan"), "mover2_plan_harness")
-    L.mover2_plan.argtypes = [C.c_longlong] + [C.c_int] * 14 + [C.POINTER(C.c_longlong)]
-    L.pick_movers2.argtypes = [FP, C.c_int, IP, IP, FP]
-    L.pick_movers2.restype = None
-    L.pick_movers.argtypes = [FP, C.c_int, IP, IP]
-    L.pick_movers.restype = C.c_float
-    L.pick_movers2_threads.argtypes = [FP, C.c_int, C.c_int, C.c_float, IP, IP, FP]
-    L.pick_movers2_threads.restype = None
-    L.observe_hinted2.argtypes = [C.c_double] * 9 + [C.c_int] * 2 + [IP]
-    return L
-
-
-@pytest.fixture(scope="module")
-def mp1(tmp_path_factory):
-    """the first level's own harness: what its plan is today"""
-    L = _build(tmp_path_factory.mktemp("mover1plan"), "mover_plan_harness")
-    L.mover_plan.argtypes = [C.c_longlong] + [C.c_int] * 13 + [C.POINTER(C.c_longlong)]
-    return L
+def mp1():
+    """the first level alone: what its plan is without spkm_plan_movers2 behind it"""
+    return PH.lib()
 
 
 ARGS = dict(n=100000, p=1024, K=100, s=51, quad=1, lazy=1, want_dist=0, bounds_valid=1, has_map=0, no_bounds=0, pt_next=0,
             blocks_next=0, no_point_list=0)
 
 
-def plan2(mp2, sw=1, sw2=1, **kw):
+def first_level(sw, kw):
+    """the call of ARGS and kw through spkm_plan_tiles, spkm_plan_call and spkm_plan_movers: its input's K, plan and mover plan"""
     a = dict(ARGS, **kw)
-    out = (C.c_longlong * 13)()
-    mp2.mover2_plan(a["n"], a["p"], a["K"], a["s"], a["quad"], a["lazy"], a["want_dist"], a["bounds_valid"], a["has_map"],
-                    a["no_bounds"], a["pt_next"], a["blocks_next"], a["no_point_list"], sw, sw2, out)
-    v = [int(x) for x in out]
-    names = "eligible on cap tiles pl nr".split()
-    return dict(zip(names, v[:6])), dict(zip(names, v[6:12])), v[12]
+    pol = PH.policy(pt_next=a.pop("pt_next"), blocks_next=a.pop("blocks_next"))
+    s = a.pop("s")
+    inp = PH.call_in(fixed_s=s, max_s=s, **a, **PH.MOVER_DEFAULTS)
+    pl = PH.plan_struct(inp, pol)
+    return a["K"], pl, PH.movers(inp, pl, a["K"], sw)
+
+
+def plan2(mp2, sw=1, sw2=1, **kw):
+    K, pl, m = first_level(sw, kw)
+    return dict(m.read()), dict(PH.movers2(m, pl, K, sw2).read()), pl.get("npad")
 
 
 def plan1(mp1, sw=1, **kw):
-    a = dict(ARGS, **kw)
-    out = (C.c_longlong * 12)()
-    mp1.mover_plan(a["n"], a["p"], a["K"], a["s"], a["quad"], a["lazy"], a["want_dist"], a["bounds_valid"], a["has_map"],
-                   a["no_bounds"], a["pt_next"], a["blocks_next"], a["no_point_list"], sw, out)
-    return dict(zip("eligible on cap tiles pl nr".split(), [int(x) for x in out][:6]))
+    return dict(first_level(sw, kw)[2].read())
 
 
 def test_constants(mp2):
-    assert [mp2.mover2_const(i) for i in range(2)] == [MOVERS2, KMIN2]
+    assert [PH.const(c) for c in ("spkm_movers2", "spkm_mover2_kmin")] == [MOVERS2, KMIN2]
 
 
 def test_eligible_by_K(mp2):
@@ -102,7 +85,7 @@ def test_switches_and_shape(mp2):
     first does; an eligible call counts either way; the list holds every step, the launch is two full tiles at the call's rounds"""
     for n, s in ((3001, 51), (4096, 13), (100000, 51)):
         npad = (n + 63) // 64 * 64
-        for sw2, want in ((1, 1), (-1, 0), (0, mp2.mover2_default_on())):
+        for sw2, want in ((1, 1), (-1, 0), (0, PH.const("spkm_mover2_default_on"))):
             first, second, got_npad = plan2(mp2, n=n, s=s, sw=1, sw2=sw2)
             assert got_npad == npad
             assert (second["eligible"], second["on"]) == (1, want), (n, sw2)
@@ -111,7 +94,7 @@ def test_switches_and_shape(mp2):
         first, second, _ = plan2(mp2, n=n, s=s, sw=-1, sw2=1)      # the first level off: the second does not run
         assert (first["on"], second["eligible"], second["on"], second["cap"]) == (0, 1, 0, 0)
         first, second, _ = plan2(mp2, n=n, s=s, sw=0, sw2=1)
-        assert second["on"] == mp2.mover_default_on()
+        assert second["on"] == PH.const("spkm_mover_default_on")
     assert plan2(mp2, K=95, sw2=1)[1] == dict(eligible=0, on=0, cap=0, tiles=2, pl=4, nr=13)
 
 
@@ -224,8 +207,8 @@ def test_observe_counts_the_second_launch_with_the_main_one(mp2):
     n, tiles, nr = 1.0e8, 3, 13
     st = n / 16
     main_early = 0.056 * 0.4 * st * tiles
-    alone, both = (C.c_int * 5)(), (C.c_int * 5)()
-    mp2.observe_hinted2(1700, 0.5 * n, main_early, 0, 0.0, 0.6 * st, 0.0, 0.0, n, tiles, nr, alone)
-    mp2.observe_hinted2(1700, 0.5 * n, main_early, 0, 0.0, 0.6 * st, 2 * 0.6 * st, 0.9 * 2 * 0.6 * st, n, tiles, nr, both)
-    assert list(alone)[3:] == [1, 2]            # back to the late split for two calls
-    assert list(both) == [0, 0, 0, 0, 0]        # a good call: no pause, the early split stays
+    seen = dict(listed=1700, ambig=0.5 * n, early=main_early, skipped=0, kept=0.0, msteps=0.6 * st)
+    alone = PH.observe_hinted(n, tiles, nr, False, **seen, pairs2=0.0, early2=0.0)
+    both = PH.observe_hinted(n, tiles, nr, False, **seen, pairs2=2 * 0.6 * st, early2=0.9 * 2 * 0.6 * st)
+    assert alone[3:] == [1, 2]                  # back to the late split for two calls
+    assert both == [0, 0, 0, 0, 0]              # a good call: no pause, the early split stays

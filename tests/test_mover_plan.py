@@ -3,46 +3,36 @@ spkm_pick_movers) and spkm_policy::observe with the msteps counter.  Which calls
 call, behind a real spkm_plan_call -- and what the switch does; the pick of the 32 movers and of d_R on hand-made drift
 vectors, restated here in numpy (ties, fewer than 32 non-zero drifts, K = 64 / 100 / 200, a drift that is not a number), by
 the host's loop and by the kernel's thread layout; observe() with msteps = 0 against today's rule restated here.
-Compiled with g++ behind a small C harness (tests/native/mover_plan_harness.cpp)."""
+Reached through tests/plan_harness.py (tests/native/plan_harness.cpp)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 MOVERS, KMIN, KMAX = 32, 64, 1024
 
 
 @pytest.fixture(scope="module")
-def mp(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("moverplan") / "libmoverplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "mover_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.mover_plan.argtypes = [C.c_longlong] + [C.c_int] * 13 + [C.POINTER(C.c_longlong)]
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
-    L.pick_movers.argtypes = [fp, C.c_int, ip, ip]
-    L.pick_movers.restype = C.c_float
-    L.pick_movers_threads.argtypes = [fp, C.c_int, C.c_int, C.c_float, ip, ip]
-    L.pick_movers_threads.restype = C.c_float
-    L.mover_key.argtypes = [C.c_float, C.c_int]
-    L.mover_key.restype = C.c_uint64
-    L.observe_hinted.argtypes = [C.c_double] * 8 + [C.c_int] * 3 + [ip]
-    return L
+def mp():
+    return PH.lib()
 
 
 def plan(mp, n=100000, p=1024, K=100, s=51, quad=1, lazy=1, want_dist=0, bounds_valid=1, has_map=0, no_bounds=0, pt_next=0,
          blocks_next=0, no_point_list=0, sw=1):
-    out = (C.c_longlong * 12)()
-    mp.mover_plan(n, p, K, s, quad, lazy, want_dist, bounds_valid, has_map, no_bounds, pt_next, blocks_next, no_point_list, sw, out)
-    names = "eligible on cap tiles pl nr pt_mode sp_on erode skip_enabled drift npad".split()
-    return dict(zip(names, [int(v) for v in out]))
+    """spkm_plan_movers behind a real spkm_plan_tiles and spkm_plan_call; with the plan's own pt_mode ... npad"""
+    inp = PH.call_in(n=n, p=p, K=K, fixed_s=s, max_s=s, quad=quad, lazy=lazy, want_dist=want_dist, bounds_valid=bounds_valid,
+                     has_map=has_map, no_bounds=no_bounds, no_point_list=no_point_list, **PH.MOVER_DEFAULTS)
+    pl = PH.plan_struct(inp, PH.policy(pt_next=pt_next, blocks_next=blocks_next))
+    out = PH.movers(inp, pl, K, sw).read()
+    out.update((f, pl.get(f)) for f in "pt_mode sp_on erode skip_enabled drift npad".split())
+    return out
 
 
 def test_constants(mp):
-    assert [mp.mover_const(i) for i in range(3)] == [MOVERS, KMIN, KMAX]
+    assert [PH.const(c) for c in ("spkm_movers", "spkm_mover_kmin", "spkm_mover_kmax")] == [MOVERS, KMIN, KMAX]
 
 
 def test_eligible_by_K(mp):
@@ -80,7 +70,7 @@ def test_switch_and_shape(mp):
     for n, s in ((3001, 51), (4096, 13), (100000, 51), (20000, 64)):
         on, off, dflt = plan(mp, n=n, s=s, sw=1), plan(mp, n=n, s=s, sw=-1), plan(mp, n=n, s=s, sw=0)
         assert (on["eligible"], off["eligible"], dflt["eligible"]) == (1, 1, 1)
-        assert (on["on"], off["on"], dflt["on"]) == (1, 0, mp.mover_default_on())
+        assert (on["on"], off["on"], dflt["on"]) == (1, 0, PH.const("spkm_mover_default_on"))
         npad = (n + 63) // 64 * 64
         assert on["npad"] == npad and on["cap"] == npad // 16 + 1 and off["cap"] == 0
         assert (on["tiles"], on["pl"], on["nr"]) == (1, 4, (s + 3) // 4)
@@ -201,9 +191,9 @@ def test_observe_msteps_zero_is_today(mp):
     ]
     for listed, ambig, early, skipped, late in rows:
         for tiles, nr in ((3, 13), (7, 4), (2, 16)):
-            out = (C.c_int * 5)()
-            mp.observe_hinted(listed, ambig, early, skipped, 0.9 * n, 0, 0.0, n, tiles, nr, late, out)
-            assert list(out) == today_hinted(listed, ambig, early * 1.0, skipped, n, tiles, nr, late), (listed, ambig, early, skipped, late, tiles, nr)
+            out = PH.observe_hinted(n, tiles, nr, late, listed=listed, ambig=ambig, early=early, skipped=skipped, kept=0.9 * n, movers=0,
+                                    msteps=0.0)
+            assert out == today_hinted(listed, ambig, early * 1.0, skipped, n, tiles, nr, late), (listed, ambig, early, skipped, late, tiles, nr)
 
 
 def test_observe_msteps_leave_the_denominator(mp):
@@ -212,8 +202,7 @@ def test_observe_msteps_leave_the_denominator(mp):
     n, tiles, nr = 1.0e6, 3, 13
     steps_main = n / 16 * 0.2
     early = 0.10 * steps_main * tiles
-    a, b = (C.c_int * 5)(), (C.c_int * 5)()
-    mp.observe_hinted(0, 0.5 * n, early, 0, 0.9 * n, 0, 0.0, n, tiles, nr, 1, a)
-    mp.observe_hinted(0, 0.5 * n, early, 0, 0.9 * n, 0, n / 16 * 0.8, n, tiles, nr, 1, b)
-    assert list(a)[:2] == [2, 1] and list(b)[:2] == [0, 0]
-    assert list(b) == today_hinted(0, 0.5 * n, early, n / 16 * 0.8, n, tiles, nr, 1)
+    a = PH.observe_hinted(n, tiles, nr, 1, listed=0, ambig=0.5 * n, early=early, skipped=0, kept=0.9 * n, movers=0, msteps=0.0)
+    b = PH.observe_hinted(n, tiles, nr, 1, listed=0, ambig=0.5 * n, early=early, skipped=0, kept=0.9 * n, movers=0, msteps=n / 16 * 0.8)
+    assert a[:2] == [2, 1] and b[:2] == [0, 0]
+    assert b == today_hinted(0, 0.5 * n, early, n / 16 * 0.8, n, tiles, nr, 1)

@@ -2,86 +2,27 @@
 
 The policy decides how much work the next fused call does -- all-exact kernels, plain screen, unconditional or hinted
 two-phase form, early or late split, point or step lists, incremental or full sums -- from the counters of the previous
-screen call; it never decides a result.  Compiled here with g++ behind a small C harness (tests/native)."""
+screen call; it never decides a result.  Reached through tests/plan_harness.py (tests/native/plan_harness.cpp): the policy
+and the plan structs by field name, the plan in the library's stages."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import plan_harness as PH
+
 N, TILES, NR = 1_000_000.0, 3, 13          # a shard of 1e6 points, K = 100 (three tiles after the remainder is carried), s = 51
 
 
 @pytest.fixture(scope="module")
-def pol(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("policy") / "libpolicy.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "policy_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.pol_new.restype = C.c_void_p
-    for f in (L.pol_free, L.pol_reset):
-        f.argtypes = [C.c_void_p]
-    L.pol_observe.argtypes = [C.c_void_p] + [C.c_double] * 7 + [C.c_int, C.c_int]
-    L.pol_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    L.pol_take_hinted_split.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.pol_launched.argtypes = [C.c_void_p] + [C.c_int] * 8
-    L.pol_observe_full_opened.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int]
-    L.pol_pt_next.argtypes = [C.c_void_p]
-    L.pol_blocks_next.argtypes = [C.c_void_p]
-    L.pol_few_movers.argtypes = [C.c_void_p, C.c_double]
-    L.pol_few_movers_pair.argtypes = [C.c_void_p, C.c_double]
-    L.pol_form_on_device.argtypes = [C.c_void_p]
-    L.pol_events_direct.argtypes = [C.c_void_p]
-    L.pol_sums_by_events.argtypes = [C.c_void_p]
-    L.pol_sums_by_full_pass.argtypes = [C.c_void_p]
-    L.pol_refresh_due.argtypes = [C.c_void_p, C.c_double]
-    L.pol_event_cap.argtypes = [C.c_uint64]
-    L.pol_event_cap.restype = C.c_uint64
-    L.pol_event_cap_pair.argtypes = [C.c_uint64]
-    L.pol_event_cap_pair.restype = C.c_uint64
-    L.plan_call.argtypes = [C.POINTER(CallIn), C.c_void_p, C.POINTER(Plan)]
-    L.plan_lose_events.argtypes = L.plan_lose_pair.argtypes = [C.POINTER(Plan)]
-    L.plan_sums.argtypes = [C.POINTER(Plan), C.POINTER(CallIn), C.c_void_p, C.c_int]
-    L.pol_set.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int]
-    L.pol_regroup_wanted.argtypes = [C.c_void_p]
-    L.pol_observe_regroup.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double]
-    L.seg_const.argtypes = [C.c_char_p]
-    L.pol_seg_points.argtypes = [C.c_longlong, C.c_int]
-    sizes = (C.c_int * 2)()
-    L.plan_sizes(sizes)
-    assert (sizes[0], sizes[1]) == (C.sizeof(CallIn), C.sizeof(Plan)), "the ctypes mirror of policy.h's plan structs is stale"
-    L.plan_in_offset.argtypes = L.plan_offset.argtypes = [C.c_char_p]
-    for S, off in ((CallIn, L.plan_in_offset), (Plan, L.plan_offset)):          # ... field by field
-        for f, _ in S._fields_:
-            assert off(f.encode()) == getattr(S, f).offset, (S.__name__, f)
-    return L
-
-
-def _struct(name, spec):
-    """a ctypes mirror of a policy.h struct: spec = [(ctype, "field field ..."), ...] in declaration order"""
-    return type(name, (C.Structure,), {"_fields_": [(f, t) for t, names in spec for f in names.split()]})
-
-
-B = C.c_bool
-CallIn = _struct("CallIn", [(C.c_longlong, "n"), (C.c_int, "p K fixed_s"), (B, "quad"), (C.c_size_t, "lds_max"),
-                            (C.c_int, "num_cus teams"),
-                            (B, "no_bounds no_point_list force_point_list no_late_split no_incremental no_pair_events "
-                                "force_pair_events no_block_skip no_cluster_skip no_sums_only no_dual no_direct_events"),
-                            (C.c_int, "x_hint_chunk x_plain_chunk"),
-                            (B, "bounds_valid lazy want_dist has_map cl_valid cl_stats_valid sp_clean"), (C.c_longlong, "sp_blocks"),
-                            (B, "same_assign assign_synced sort_kept sort_reusable"), (C.c_int, "prune_a"), (B, "want_hint")])
-Plan = _struct("Plan", [(C.c_int, "G pl_last Gs nr"),
-                        (B, "bounds_ok kept ev_possible pair_capable ev_path pair_ev skip_enabled pt_mode hinted late"),
-                        (C.c_int, "prune_a rounds_all"), (B, "drift erode sp_on sp_reset trusted"), (C.c_longlong, "npad span chunk"),
-                        (C.c_int, "bgrid"), (B, "use_rec pipe cl_on cl_skip sums_only lazy_ub dual reuse nk_incr direct"),
-                        (C.c_uint, "ev_cap"), (C.c_int, "seg_ev")])
+def pol():
+    return PH.lib()
 
 
 class Walk:
     """one shard's policy: call() = 'a fused call is issued' (returns its form), seen() = 'its counters arrived'"""
 
     def __init__(self, L, no_prune=0, no_hint=0, no_late=0):
-        self.L, self.p = L, C.c_void_p(L.pol_new())
+        self.L, self.p = L, PH.policy()
         self.sw = (no_prune, no_hint, no_late)
         self.bounds = False                  # the library holds bounds from a previous screen call
 
@@ -96,32 +37,32 @@ class Walk:
             return "exact"
         hinted = bool(want_hint and self.bounds and prune_a == 0)
         late = bool(self.L.pol_take_hinted_split(self.p, NR, self.sw[2])) if hinted else False
-        rounds_all = (self.L.pol_quad_split_late(NR) if late else self.L.pol_quad_split(NR)) if hinted else (prune_a or NR)
+        rounds_all = (self.L.pol_quad_split_late(NR, 0) if late else self.L.pol_quad_split(NR, 0)) if hinted else (prune_a or NR)
         if sums == "events":
             self.L.pol_sums_by_events(self.p)
         elif sums == "full":
             self.L.pol_sums_by_full_pass(self.p)
-        self.L.pol_launched(self.p, rounds_all, NR, int(hinted), int(late), int(self.bounds), int(self.bounds),
-                            int(sums == "events"), int(both))
+        PH.launched(self.p, rounds_all, NR, hinted, late, self.bounds, self.bounds, sums == "events", both)
         self.bounds = True
         if hinted:
             return "hinted-late" if late else "hinted-early"
         return "two-phase" if prune_a else "plain"
 
     def seen(self, listed=0, ambig=0, early=0, skipped=0, kept=0, movers=0):
-        self.L.pol_observe(self.p, listed, ambig, early, skipped, kept, movers, N, TILES, NR)
+        PH.observe(self.p, N, TILES, NR, listed=listed, ambig=ambig, early=early, skipped=skipped, kept=kept, movers=movers)
 
 
 def test_compiled_splits(pol):
     # the step-major copy lists a point's entries by |x| descending: an eighth / a quarter of the rounds
-    assert [pol.pol_quad_split(nr) for nr in (1, 2, 3, 8, 13, 16)] == [1, 2, 1, 1, 1, 2]
-    assert [pol.pol_quad_split_late(nr) for nr in (5, 6, 10, 13, 16)] == [0, 2, 3, 3, 4]
+    assert [pol.pol_quad_split(nr, 0) for nr in (1, 2, 3, 8, 13, 16)] == [1, 2, 1, 1, 1, 2]
+    assert [pol.pol_quad_split_late(nr, 0) for nr in (5, 6, 10, 13, 16)] == [0, 2, 3, 3, 4]
     # the point-list kernels (entries possibly in storage order): a quarter / half of the rounds, as in round 4
-    assert [pol.pol_quad_split_pts(nr) for nr in (1, 2, 3, 8, 13, 16)] == [1, 2, 2, 2, 3, 4]
-    assert [pol.pol_quad_split_late_pts(nr) for nr in (9, 10, 13, 16)] == [0, 5, 7, 8]
+    assert [pol.pol_quad_split(nr, 1) for nr in (1, 2, 3, 8, 13, 16)] == [1, 2, 2, 2, 3, 4]
+    assert [pol.pol_quad_split_late(nr, 1) for nr in (9, 10, 13, 16)] == [0, 5, 7, 8]
     for nr in range(1, 17):                                   # a late split, where there is one, comes after the early one
-        for f, g in ((pol.pol_quad_split, pol.pol_quad_split_late), (pol.pol_quad_split_pts, pol.pol_quad_split_late_pts)):
-            assert g(nr) == 0 or f(nr) < g(nr) < nr
+        for pts in (0, 1):
+            f, g = pol.pol_quad_split(nr, pts), pol.pol_quad_split_late(nr, pts)
+            assert g == 0 or f < g < nr
 
 
 def test_first_call_is_plain_and_well_separated_data_goes_two_phase(pol):
@@ -196,7 +137,7 @@ def test_point_lists_enter_at_four_leave_below_two_and_a_half_and_lower_bars_for
 
     def after(kept_share, skipped_share):
         w.seen(ambig=0.3 * N, early=0.5 * N, kept=kept_share * N, skipped=skipped_share * steps)
-        r = pol.pol_pt_next(w.p)
+        r = w.p.get("pt_next")
         w.call()
         return r
 
@@ -242,7 +183,7 @@ def test_block_summaries_only_where_whole_blocks_settle(pol):
 
     def after(kept_share, skipped_share):
         w.seen(ambig=0.3 * N, early=0.5 * N, kept=kept_share * N, skipped=skipped_share * steps)
-        r = (pol.pol_blocks_next(w.p), pol.pol_pt_next(w.p))
+        r = (w.p.get("blocks_next"), w.p.get("pt_next"))
         w.call()
         return r
 
@@ -254,28 +195,28 @@ def test_block_summaries_only_where_whole_blocks_settle(pol):
     assert after(0.999, 0.99)[0] == 0                        # 0.1 % failing, scattered over 1 % of the steps (16x): no
     assert after(0.999, 0.9985)[0] == 1                      # ... sitting together: yes
     pol.pol_reset(w.p)
-    assert pol.pol_blocks_next(w.p) == 0
+    assert w.p.get("blocks_next") == 0
 
 
 def test_incremental_sums_while_at_most_a_third_of_the_points_move(pol):
     w = Walk(pol)
-    assert pol.pol_few_movers(w.p, N) == 1                   # no count yet (a run's second call): taken as few
+    assert pol.pol_few_movers(w.p, N, 0) == 1                   # no count yet (a run's second call): taken as few
     w.call(); w.seen()                                       # the first call cannot count movers (no previous assignment)
-    assert pol.pol_few_movers(w.p, N) == 1
+    assert pol.pol_few_movers(w.p, N, 0) == 1
     w.call(); w.seen(movers=0.4 * N)
-    assert pol.pol_few_movers(w.p, N) == 0
+    assert pol.pol_few_movers(w.p, N, 0) == 0
     w.call(); w.seen(movers=0.3 * N)
-    assert pol.pol_few_movers(w.p, N) == 1
+    assert pol.pol_few_movers(w.p, N, 0) == 1
     pol.pol_reset(w.p)
-    assert pol.pol_few_movers(w.p, N) == 1
+    assert pol.pol_few_movers(w.p, N, 0) == 1
     # pair events (one per mover, its record read once): the bar is half of the points, on the host and on the device
     w.call(); w.seen()
     w.call(); w.seen(movers=0.45 * N)
-    assert pol.pol_few_movers(w.p, N) == 0 and pol.pol_few_movers_pair(w.p, N) == 1
+    assert pol.pol_few_movers(w.p, N, 0) == 0 and pol.pol_few_movers(w.p, N, 1) == 1
     w.call(); w.seen(movers=0.55 * N)
-    assert pol.pol_few_movers_pair(w.p, N) == 0
+    assert pol.pol_few_movers(w.p, N, 1) == 0
     for n in (0, 1, 2, 3, 100, 10**8):
-        assert pol.pol_event_cap_pair(n) == n // 2
+        assert pol.pol_event_cap(n, 1) == n // 2
 
 
 def test_a_call_without_a_mover_count_lets_the_device_choose_the_form(pol):
@@ -290,14 +231,14 @@ def test_a_call_without_a_mover_count_lets_the_device_choose_the_form(pol):
     w.call()                                                 # ... its counters are not back yet:
     assert pol.pol_form_on_device(w.p) == 1                  # a third call issued now still lets the device decide
     w.seen(movers=0.9 * N)                                   # (from a random start nearly every point moves)
-    assert pol.pol_form_on_device(w.p) == 0 and pol.pol_few_movers(w.p, N) == 0   # known and many: the full pass, host-side
+    assert pol.pol_form_on_device(w.p) == 0 and pol.pol_few_movers(w.p, N, 0) == 0   # known and many: the full pass, host-side
     w.call(); w.seen(movers=0.1 * N)
-    assert pol.pol_form_on_device(w.p) == 0 and pol.pol_few_movers(w.p, N) == 1   # known and few: the events, host-side
+    assert pol.pol_form_on_device(w.p) == 0 and pol.pol_few_movers(w.p, N, 0) == 1   # known and few: the events, host-side
     pol.pol_reset(w.p)
     assert pol.pol_form_on_device(w.p) == 1                  # a new replicate starts over
     # the device's bar: events <= 2 * floor(n / 3)  <=>  movers <= n / 3 (every mover with a valid old cluster is 2 events)
     for n in (0, 1, 2, 3, 4, 100, 10**8, 125_000_000, 2**31):
-        cap = pol.pol_event_cap(n)
+        cap = pol.pol_event_cap(n, 0)
         assert cap == 2 * (n // 3) and cap <= 2 * n
         movers_ok, movers_too_many = n // 3, n // 3 + 1
         assert 2 * movers_ok <= cap < 2 * movers_too_many
@@ -358,7 +299,7 @@ def test_movers_are_credited_to_the_call_that_was_observed(pol):
     for _ in range(3):
         w2.call(sums="events"); w2.seen(movers=2.0 * N)
     w2.call(sums="events", both=True)                        # both forms queued; the device opened the full pass
-    pol.pol_observe_full_opened(w2.p, 3.0 * N, N, TILES, NR)
+    PH.observe(w2.p, N, TILES, NR, movers=3.0 * N, full_opened=True)
     assert pol.pol_refresh_due(w2.p, N) == 0                 # 6 N + a fresh summation: the count starts over
     w2.call(sums="events"); w2.seen(movers=2.0 * N)
     assert pol.pol_refresh_due(w2.p, N) == 0
@@ -371,15 +312,15 @@ def test_launch_kind_helper_matches_the_compiled_splits(pol):
     import screen_forms as F
 
     for nr in range(1, F.NR_MAX + 1):
-        assert F.split_early(nr) == pol.pol_quad_split(nr), nr
-        assert F.split_late(nr) == pol.pol_quad_split_late(nr), nr
-        assert F.split_early(nr, True) == pol.pol_quad_split_pts(nr), nr
-        assert F.split_late(nr, True) == pol.pol_quad_split_late_pts(nr), nr
+        assert F.split_early(nr) == pol.pol_quad_split(nr, 0), nr
+        assert F.split_late(nr) == pol.pol_quad_split_late(nr, 0), nr
+        assert F.split_early(nr, True) == pol.pol_quad_split(nr, 1), nr
+        assert F.split_late(nr, True) == pol.pol_quad_split_late(nr, 1), nr
         for pts in (False, True):
             kinds = F.expected_kinds(nr, pts)
             # the unconditional form as run_screen converts the policy's choice; hinted splits as take_hinted_split allows
-            late = pol.pol_quad_split_late_pts(nr) if pts else pol.pol_quad_split_late(nr)
-            early = pol.pol_quad_split_pts(nr) if pts else pol.pol_quad_split(nr)
+            late = pol.pol_quad_split_late(nr, pts)
+            early = pol.pol_quad_split(nr, pts)
             uncond = Call(pol, fixed_s=4 * nr, prune_a=1, force_point_list=pts, want_hint=False).plan().prune_a
             assert kinds["plain"] == (pts, nr, nr, False)
             assert kinds.get("two-phase") == ((pts, nr, uncond, False) if uncond < nr else None), (nr, pts)
@@ -398,26 +339,17 @@ class Call:
     (13 rounds), the previous call's bounds, sort, cluster cache and block summaries all held, few movers known"""
 
     def __init__(self, L, movers=1000, pt_next=False, blocks_next=True, ev_calls=0, known=True, **kw):
-        self.L, self.pol = L, C.c_void_p(L.pol_new())
-        L.pol_set(self.pol, int(known), int(movers), int(pt_next), int(blocks_next), ev_calls)
+        self.pol = PH.policy(movers_known=known, last_movers=movers, pt_next=pt_next, blocks_next=blocks_next, ev_calls=ev_calls)
         n = kw.get("n", 1_000_000)
-        self.inp = CallIn(n=n, p=1024, K=100, fixed_s=51, quad=True, lds_max=160 * 1024, num_cus=256, teams=192,
-                          bounds_valid=True, lazy=True, cl_valid=True, cl_stats_valid=True, sp_clean=True,
-                          sp_blocks=(n + 63) // 64 * 64 // 1024 + 1, same_assign=True, assign_synced=True, sort_kept=True,
-                          sort_reusable=True, want_hint=True)
-        for k, v in kw.items():
-            setattr(self.inp, k, v)
+        self.inp = PH.call_in(n=n, p=1024, K=100, fixed_s=51, quad=True, lds_max=160 * 1024, num_cus=256, teams=192,
+                              bounds_valid=True, lazy=True, cl_valid=True, cl_stats_valid=True, sp_clean=True,
+                              sp_blocks=PH.sp_blocks_of(n), same_assign=True, assign_synced=True, sort_kept=True,
+                              sort_reusable=True, want_hint=True)
+        self.inp.set(**kw)
 
     def plan(self, rec=True, lose=()):
-        """spkm_plan_call, the device's refusals in run_screen's order, then spkm_plan_sums"""
-        pl = Plan()
-        self.L.plan_call(C.byref(self.inp), self.pol, C.byref(pl))
-        if "events" in lose and pl.ev_possible:
-            self.L.plan_lose_events(C.byref(pl))
-        if ("pair_lds" in lose or "ev_o" in lose) and pl.pair_ev:
-            self.L.plan_lose_pair(C.byref(pl))
-        self.L.plan_sums(C.byref(pl), C.byref(self.inp), self.pol, int(rec))
-        return pl
+        """run_screen's stages: spkm_plan_tiles, spkm_plan_call, the device's refusals, then spkm_plan_sums"""
+        return PH.plan(self.inp, self.pol, lose=lose, rec=rec)
 
 
 def test_plan_takes_the_events_only_where_the_call_allows_them(pol):
@@ -478,7 +410,7 @@ def test_plan_hinted_split_early_late_and_the_unconditional_conversion(pol):
     # no hinted call, no late-split bookkeeping
     c3 = Call(pol, want_hint=False)
     assert not any(c3.plan().hinted for _ in range(3))
-    c3.inp.want_hint = True
+    c3.inp.set(want_hint=True)
     assert c3.plan().late
     # the unconditional form's compiled split, as tests/screen_forms.py restates it
     for nr in range(1, F.NR_MAX + 1):
@@ -495,6 +427,7 @@ def test_plan_block_summaries_and_the_trusted_buffer(pol):
     assert pl.erode and pl.sp_on and not pl.sp_reset and not pl.trusted
     for kw in (dict(lazy=False), dict(want_dist=True), dict(no_bounds=True), dict(K=129), dict(no_block_skip=True)):
         assert not Call(pol, **kw).plan().sp_on, kw
+    assert Call(pol, K=128).plan().sp_on                                 # (the last K with summaries)
     assert not Call(pol, blocks_next=False).plan().sp_on
     for kw in (dict(sp_clean=False), dict(same_assign=False), dict(sp_blocks=7)):
         pl = Call(pol, **kw).plan()
@@ -635,20 +568,20 @@ def test_regroup_is_wanted_after_a_full_call_over_mixed_steps(pol):
     steps = N / 16
 
     def wanted(ambig=0.3 * N, one=0.1 * steps, may=1, n=N):
-        p = C.c_void_p(pol.pol_new())
-        pol.pol_observe_regroup(p, ambig, one, may, n)
-        return pol.pol_regroup_wanted(p)
+        p = PH.policy()
+        PH.observe(p, n, 4, 13, ambig=ambig, one_cluster_steps=one, may_regroup=may)
+        return p.get("regroup_wanted")
 
     assert wanted() == 1
     assert wanted(one=0.125 * steps) == 0 and wanted(one=0.124 * steps) == 1
     assert wanted(ambig=0.9 * N) == 0 and wanted(may=0) == 0
     assert wanted(n=4095, one=0, ambig=0) == 0 and wanted(n=4096, one=0, ambig=0) == 1
-    p = C.c_void_p(pol.pol_new())
-    pol.pol_observe_regroup(p, 0.3 * N, 0.0, 1, N)
-    pol.pol_observe_regroup(p, 0.3 * N, steps, 1, N)                     # (a later report does not take it back)
-    assert pol.pol_regroup_wanted(p) == 1
+    p = PH.policy()
+    PH.observe(p, N, 4, 13, ambig=0.3 * N, one_cluster_steps=0.0, may_regroup=1)
+    PH.observe(p, N, 4, 13, ambig=0.3 * N, one_cluster_steps=steps, may_regroup=1)   # (a later report does not take it back)
+    assert p.get("regroup_wanted") == 1
     pol.pol_reset(p)
-    assert pol.pol_regroup_wanted(p) == 0
+    assert p.get("regroup_wanted") == 0
 
 
 def test_segment_lengths_are_the_ones_the_designed_size_fixture_is_built_around(pol):
@@ -657,11 +590,12 @@ def test_segment_lengths_are_the_ones_the_designed_size_fixture_is_built_around(
     either side of them: a change here must be made there as well."""
     import designed_sizes as D
 
-    assert [pol.seg_const(s.encode()) for s in ("SEG_POINTS", "SEG_POINTS_MAX", "SEG_EVENTS", "SEG_DENSE", "spkm_plan_seg")] == \
+    assert [PH.const(s) for s in ("SEG_POINTS", "SEG_POINTS_MAX", "SEG_EVENTS", "SEG_DENSE", "spkm_plan_seg")] == \
         [2048, 8192, 256, 256, 2048]
-    assert pol.seg_const(b"no_such_name") == -1
+    with pytest.raises(KeyError):
+        PH.const("no_such_name")
     for name in ("SEG_POINTS", "SEG_POINTS_MAX", "SEG_EVENTS", "SEG_DENSE"):
-        assert pol.seg_const(name.encode()) == getattr(D, name), name
+        assert PH.const(name) == getattr(D, name), name
     # seg_points: SEG_POINTS while a workgroup would get fewer than 16 longer segments, then n / (16 blocks), at most 8192
     assert [pol.pol_seg_points(n, 256) for n in (0, 1, 12_000, 2048 * 4096, 2049 * 4096, 5000 * 4096, 8192 * 4096, 10 ** 9)] == \
         [2048, 2048, 2048, 2048, 2049, 5000, 8192, 8192]

@@ -4,40 +4,25 @@ switch of its own, and only at a p whose 32-centroid f32 tile fits, which is the
 answering -- and the plans of such a shard's calls.  The new function is held to a restatement in plain integers at the LDS
 size gfx950 reports (163840 B) and at 65536 B; over a grid of (p, K, opt-ins) at most one of the four screen policies
 answers; spkm_screen_width, spkm_far_screen and spkm_far_screen_ragged are held to the restatements
-tests/test_far_ragged_plan.py carries.  Compiled with g++ behind a small C harness
-(tests/native/tile_ragged_plan_harness.cpp), which plans as run_far does."""
-import ctypes as C
+tests/test_far_ragged_plan.py carries.  Planned through tests/plan_harness.py as run_far does: spkm_plan_tiles at the TILE
+width, then spkm_plan_call."""
 import itertools
-import os
-import subprocess
 
 import pytest
 
-from test_far_bounds_plan import BAIT, PLAN_FIELDS
+import plan_harness as PH
+from test_far_bounds_plan import BAIT
 from test_far_ragged_plan import IN_FLAGS, KNOWN, exact_tile_fits, far_before, last_exact_p, width_before
 from test_far_ragged_plan import plane as far_plane
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 LDS = (163840, 65536)
 CUS = 256
 TABLE_MAX = 256 << 20
 
 
 @pytest.fixture(scope="module")
-def tr(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("tileraggedplan") / "libtileraggedplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "tile_ragged_plan_harness.cpp"),
-                           "-o", so])
-    L = C.CDLL(so)
-    L.screen_width.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
-    L.far_screen.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.far_screen_ragged.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.tile_screen_ragged.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
-    L.exact_tile_fits.argtypes = [C.c_longlong, C.c_uint64]
-    L.rgplan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.c_int, C.c_int, C.c_int,
-                         C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_longlong)]
-    assert L.rgplan_fields() == len(PLAN_FIELDS)
-    return L
+def tr():
+    return PH.lib()
 
 
 # ---- the limits, restated ----
@@ -154,10 +139,9 @@ def test_the_restatement_and_at_most_one_screen_answers(tr, L):
 
 # ---- 2. the plans of a ragged shard on the tile ----
 def plan(tr, n, p, K, flags, kt, max_s=150, s=0, teams=32, pol=0, movers=0, ev_calls=0, ev_cum=0, lds=163840, cus=CUS):
-    bits = sum(1 << IN_FLAGS.index(f) for f in set(flags))
-    out = (C.c_longlong * len(PLAN_FIELDS))()
-    tr.rgplan(n, p, K, s, max_s, kt, bits, lds, cus, teams, pol, movers, ev_calls, ev_cum, out)
-    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+    assert set(flags) <= set(IN_FLAGS)
+    inp = PH.call_in(flags, n=n, p=p, K=K, fixed_s=s, max_s=max_s, lds_max=lds, num_cus=cus, teams=teams)
+    return PH.plan(inp, PH.policy_bits(pol, movers, ev_calls, ev_cum), kt=kt)
 
 
 SHAPES = [(151, 150), (256, 41), (1024, 51), (1278, 150)]

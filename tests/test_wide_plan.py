@@ -1,29 +1,24 @@
 """CPU: which screen a fused call takes past the 32-centroid tile (sparsifiedkmeans_amd/csrc/policy.h: spkm_wide_kt,
 spkm_screen_width, the tile plan at a width).  Every limit is restated here in plain integers and checked at the LDS size
-gfx950 reports (163840 B) and at 65536 B.  Compiled with g++ behind a small C harness (tests/native/wide_plan_harness.cpp)."""
-import ctypes as C
-import os
-import subprocess
-
+gfx950 reports (163840 B) and at 65536 B.  Reached through tests/plan_harness.py (tests/native/plan_harness.cpp)."""
 import pytest
 
-import test_policy
+import plan_harness as PH
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 LDS = (163840, 65536)
 CUS = 256
 
 
 @pytest.fixture(scope="module")
-def wp(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("wideplan") / "libwideplan.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", os.path.join(HERE, "native", "wide_plan_harness.cpp"), "-o", so])
-    L = C.CDLL(so)
-    L.wide_kt.argtypes = [C.c_longlong, C.c_uint64]
-    L.screen_width.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
-    L.screen_quad.argtypes = [C.c_int, C.c_int]
-    L.plan_tiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_uint64, C.c_int, C.POINTER(C.c_int)]
-    return L
+def wp():
+    return PH.lib()
+
+
+def tiles(wp, p, K, s, n, lds, kt):
+    """G, pl_last, Gs, nr of the tile plan of a call that takes tiles of kt centroids"""
+    inp = PH.call_in(p=p, K=K, fixed_s=s, n=n, lds_max=lds, quad=wp.screen_quad(kt, s), sp_blocks=0)
+    pl = PH.tile_plan(inp, kt)
+    return [pl[f] for f in ("G", "pl_last", "Gs", "nr")]
 
 
 def last_p(L, kt):
@@ -106,21 +101,9 @@ def test_quad_only_at_32(wp):
 
 @pytest.mark.parametrize("K,kt,G", [(2, 16, 1), (17, 16, 2), (17, 8, 3), (100, 16, 7), (130, 8, 17), (130, 16, 9), (33, 8, 5)])
 def test_tile_plan_at_a_narrow_width(wp, K, kt, G):
-    out = (C.c_int * 4)()
-    wp.plan_tiles(2000, K, 26, 3001, 163840, kt, out)
-    assert list(out) == [G, 4, G, 7]                          # G = Gs = ceil(K / kt), full-width body, ceil(26 / 4) rounds
+    assert tiles(wp, 2000, K, 26, 3001, 163840, kt) == [G, 4, G, 7]                          # G = Gs = ceil(K / kt), full-width body, ceil(26 / 4) rounds
 
 
 def test_tile_plan_at_32_is_unchanged(wp):
-    out = (C.c_int * 4)()
-    wp.plan_tiles(1000, 100, 51, 6007, 163840, 32, out)       # K = 100: the last 4 centroids ride on the tile before
-    assert list(out) == [4, 5, 3, 13]
-    wp.plan_tiles(1000, 100, 75, 6007, 163840, 32, out)       # the 16-lanes-per-point kernel: plain tiles
-    assert list(out) == [4, 4, 4, 19]
-
-
-def test_plan_structs_keep_their_layout(wp):
-    """spkm_call_in / spkm_call_plan are what tests/test_policy.py mirrors: the width travels beside them"""
-    sizes = (C.c_int * 2)()
-    wp.plan_sizes(sizes)
-    assert (sizes[0], sizes[1]) == (C.sizeof(test_policy.CallIn), C.sizeof(test_policy.Plan))
+    assert tiles(wp, 1000, 100, 51, 6007, 163840, 32) == [4, 5, 3, 13]   # K = 100: the last 4 centroids ride on the tile before
+    assert tiles(wp, 1000, 100, 75, 6007, 163840, 32) == [4, 4, 4, 19]   # the 16-lanes-per-point kernel: plain tiles
