@@ -255,6 +255,24 @@ int spkm_shard_set_far_ragged(spkm_shard *s, int on);
  * shard's policy state, like spkm_shard_reset_policy.  SPKM_TILE_RAGGED=1 opts every shard of a context in (read with the
  * other switches: spkm_ctx_reload_switches). */
 int spkm_shard_set_tile_ragged(spkm_shard *s, int on);
+/* Many centres on the LDS-tile screen (on != 0; default off).  The certified f32 screen gives every tile of 32 centroids a
+ * workgroup per XCD, which stops at 32 tiles on a 256-CU part: a fused call with K > 1024 on columns of up to 64 entries runs
+ * the all-exact kernels, K f64 terms per entry for every point in every call and nothing carried between calls.  A shard that
+ * opts in here is screened at those K by the narrow-tile kernel on 32-centroid tiles taken in PASSES of 32 tiles -- one launch
+ * per pass, ceil(ceil(K / 32) / 32) of them -- every pass folded into the same 32 result planes, so that the screen's scratch
+ * (3 x 32 x n x 4 bytes) and the certificate's reads are those of K = 1024 whatever K is; the pipeline behind it is the far
+ * screen's: the same estimates and certificate, the same exact list.  Carried bounds and incremental sums follow the shard's
+ * spkm_shard_set_far_bounds / spkm_shard_set_far_events opt-ins, as on a far shard; spkm_last_path_info reports 1,
+ * spkm_last_screen_tile (32, ceil(K / 32)) -- all the tiles --, spkm_last_screen_passes the passes and the planes,
+ * spkm_last_screen_mode and spkm_last_screen_points as on the far path.  Needs more than 32 tiles (K > 1024: at or below that
+ * the setting changes nothing, and the other screens answer as before), a p with a 32-centroid f32 tile ((p + 1) * 128 + 16
+ * bytes: p <= 1278 with 160 KB), 48 entries of slack behind ir / x, at least 32 workgroups, 4 K bytes of LDS for the cluster
+ * sizes (K <= 40960 with 160 KB); a RAGGED shard must have opted in to spkm_shard_set_tile_ragged as well.  Where it applies
+ * it comes first: a shard with columns of more than 64 entries, or a ragged one on the tile screen, with 1024 < K <= 8192
+ * leaves its one-plane-per-tile screen for this one.  Every output is what the all-exact kernels give.  A switch of its own:
+ * no other opt-in implies it.  Turning it on or off forgets the shard's policy state, like spkm_shard_reset_policy.
+ * SPKM_MANY_SCREEN=1 opts every shard of a context in (read with the other switches: spkm_ctx_reload_switches). */
+int spkm_shard_set_many_screen(spkm_shard *s, int on);
 /* Ragged shards on the staged k-means++ round (on != 0; default off).  spkm_kpp_seed_dev on a RAGGED shard runs the generic
  * round kernel: one lane per point walks its column in global memory and gathers every table row from L2.  A shard that
  * opts in here is seeded by a form of the staged kernel that reads each point's column bounds from jc: the table of the RB
@@ -430,6 +448,10 @@ int spkm_last_assign_tile(spkm_ctx *ctx, int64_t info[6]);
  * 256 (the planes of the far screen, spkm_shard_set_far_screen), 0 = that call took no screen; info[1] = its number of tiles
  * (result slots per point). */
 int spkm_last_screen_tile(spkm_ctx *ctx, int64_t info[2]);
+/* The many-centres screen of the last fused call (spkm_shard_set_many_screen; stored values; does not block): info[0] = its
+ * passes of 32 tiles, ceil(ceil(K / 32) / 32), info[1] = the result planes per point they were folded into (32); (0, 0) after
+ * a call that took any other screen, or none. */
+int spkm_last_screen_passes(spkm_ctx *ctx, int64_t info[2]);
 /* How many points the screen of the last fused call evaluated (any screen kernel): info[0] = n for a call over all points,
  * the length of the list for a call that skipped on its carried bounds (points; 16 per listed step for a step list), 0
  * when the call took no screen; info[1] = the running total over the context.  Blocks on the stream. */

@@ -44,6 +44,7 @@ static spkm_switches read_switches()
     w.far_events = on("SPKM_FAR_EVENTS");
     w.far_ragged = on("SPKM_FAR_RAGGED");
     w.tile_ragged = on("SPKM_TILE_RAGGED");
+    w.many_screen = on("SPKM_MANY_SCREEN");
     w.kpp_ragged = on("SPKM_KPP_RAGGED");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
@@ -455,6 +456,17 @@ extern "C" int spkm_shard_set_tile_ragged(spkm_shard* s, int on)
     s->tile_ragged = on != 0;
     if (s->tile_ragged && s->ctx) {
         const int rc = ensure_max_s(s->ctx, s); // (here, so that no fused call waits for it)
+        if (rc) return rc;
+    }
+    return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
+}
+
+extern "C" int spkm_shard_set_many_screen(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->many = on != 0;
+    if (s->many && s->ctx) {
+        const int rc = ensure_max_s(s->ctx, s); // (a ragged shard: here, so that no fused call waits for it)
         if (rc) return rc;
     }
     return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)

@@ -1024,6 +1024,16 @@ extern "C" int spkm_last_screen_tile(spkm_ctx* ctx, int64_t info[2])
     return SPKM_OK;
 }
 
+// The last fused call's many-centres screen: its passes and the result planes they were folded into; (0, 0): the call took
+// another screen or none.  Stored values; does not block.
+extern "C" int spkm_last_screen_passes(spkm_ctx* ctx, int64_t info[2])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    info[0] = ctx->last.passes;
+    info[1] = ctx->last.planes;
+    return SPKM_OK;
+}
+
 // [0] = path of the last spkm_assign_accumulate_dev (0 exact tiles, 1 f32 screen + exact confirmation),
 // [1] = number of points the screen could not certify (evaluated exactly over all K).  Blocks on the stream.
 extern "C" int spkm_debug_shard_bounds(spkm_ctx* ctx, const spkm_shard* s, float* ub, double* lb, int32_t* lib_assign)

@@ -43,6 +43,14 @@ static int tile_ragged_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
     return spkm_tile_screen_ragged((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
                                    s->tile_ragged || ctx->sw.tile_ragged);
 }
+// ... and, asked BEFORE all three: the passes of the many-centres screen (policy.h, spkm_many_screen) -- more than 32 tiles of 32
+// centroids, folded into 32 result planes -- for a shard or a context that opted in (spkm_shard_set_many_screen,
+// SPKM_MANY_SCREEN=1); 0: the dispatch above, untouched.
+static int many_screen_passes(const spkm_ctx* ctx, const spkm_shard* s, int K)
+{
+    return spkm_many_screen((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
+                            s->tile_ragged || ctx->sw.tile_ragged, s->many || ctx->sw.many_screen);
+}
 
 static_assert(spkm_movers == SPKM_MOVERS && spkm_movers == SCREEN_KT && spkm_mover_kmin == SPKM_MOVER_KMIN && spkm_mover_kmax == SPKM_MOVER_KMAX &&
               SPKM_MOVER_KMAX <= BOUNDS_KTAB, "the mover tile is one full screen tile; policy.h and layout.h agree on its limits");
@@ -61,6 +69,13 @@ template <typename IR> static screen_wide_fn<IR> pick_screen_wide(int kt, bool l
         {{k_screen_wide<IR, 8, false, true>, k_screen_wide<IR, 16, false, true>, k_screen_wide<IR, 32, false, true>},
          {k_screen_wide<IR, 8, true, true>, k_screen_wide<IR, 16, true, true>, k_screen_wide<IR, 32, true, true>}}};
     return (kt == 8 || kt == 16 || kt == 32) ? tab[ragged][list][kt / 16] : nullptr;
+}
+// ... and its FOLD forms, the passes of the many-centres screen: k_screen_wide_fold by LIST, RAGGED
+template <typename IR> static screen_wide_fold_fn<IR> pick_screen_many(bool list, bool ragged)
+{
+    static constexpr screen_wide_fold_fn<IR> tab[2][2] = {{k_screen_wide_fold<IR, false, false>, k_screen_wide_fold<IR, true, false>},
+                                                          {k_screen_wide_fold<IR, false, true>, k_screen_wide_fold<IR, true, true>}};
+    return tab[ragged][list];
 }
 template <typename IR> static screen_far_fn<IR> pick_screen_far(int planes, bool list, bool ragged)
 {
@@ -134,6 +149,7 @@ struct screen_call : spkm_call_in {
     spkm_screen_report rep; // what this call did, as its stages decide it (stored in the context when the call has gone through)
     spkm_zero_jobs zj;
     int kt = SCREEN_KT; // centroids per screen tile (screen_width): 16 / 8 = the narrow tiles of k_screen_wide, always !quad
+    int many = 0;       // passes of the many-centres screen (spkm_many_screen; 0: another screen): pl.Gs = 32 planes and a block map of 32 tiles, pl.G all the tiles
     bool carry = false; // this shard carries bounds between screen calls: quad, or carry_bounds (spkm_shard_set_wide_bounds; on the far screen spkm_shard_set_far_bounds)
     int bstat_n = 0, seg = 0, max_items = 0; // bstat_n: workgroups of k_bounds_steps whose statistics wait in ctx->bstat
     // everything this call needs zeroed, in one launch (flushed in front of the first kernel)
@@ -173,7 +189,7 @@ struct screen_call : spkm_call_in {
         }
         const int Gs = pl.Gs;
         if (quad) rc = build_blockmap_quad(ctx, Gs, pl.pl_last, pl.nr);
-        else rc = build_blockmap(ctx, pl.G);
+        else rc = build_blockmap(ctx, many > 0 ? spkm_many_slots : pl.G);
         if (rc) return rc;
         // (two tiles more than the plan's where the mover tiles may follow: k_prep_tiles_f32 gathers them behind the others)
         if ((rc = ensure(ctx, ctx->t32, (size_t)(pl.G + (quad ? 2 : 0)) * (p + 1) * kt * 4)) || (rc = ensure(ctx, ctx->cmax, 64)) ||
@@ -530,6 +546,32 @@ struct screen_call : spkm_call_in {
         report_screen(0, 0);
         return launch_tiles<IR>(pick_screen_wide<IR>(kt, pl.skip_enabled, true), (size_t)(p + 1) * kt * 4 + 16, 0, todo_list(),
                                 (const unsigned*)ctx->nlist.p, (const long long*)sm->jc);
+    }
+    // The MANY-CENTRES screen (screen_wide.hip, the FOLD forms; policy.h, spkm_many_screen) in the far screen's place: ALL the
+    // tiles of 32 centroids by k_prep_tiles_wide, then one launch per pass of spkm_many_slots tiles over the block map of
+    // that many -- on this stream, whose order is the read-after-write order the fold needs -- inside one timing pair: over
+    // every point, or (a shard that skips on its bounds) the LIST forms over the points of todo[], whose results lie by slot.
+    template <typename IR> int screen_many()
+    {
+        zero_flush();
+        prep_tiles_wide();
+        report_screen(0, 0);
+        rep.tiles = pl.G; // (every tile; the planes they were folded into: spkm_last_screen_passes)
+        rep.passes = many; rep.planes = pl.Gs;
+        const screen_wide_fold_fn<IR> kern = pick_screen_many<IR>(pl.skip_enabled, ragged());
+        const size_t lds = (size_t)(p + 1) * kt * 4 + 16;
+        HIP_TRY(allow_lds(ctx, (const void*)kern, lds));
+        HIP_TRY(timing_begin(ctx));
+        for (int tile0 = 0; tile0 < pl.G; tile0 += spkm_many_slots) {
+            HIP_TRY(spkm_launch(kern, dim3(ctx->bmap_blocks), dim3(1024), lds, ctx->stream, (const IR*)sm->ir, (const float*)sm->xf,
+                                (const float*)ctx->t32.p, p, (int)n, ragged() ? 0 : sm->fixed_s, K, (const spkm_blockmap*)ctx->bmap.p,
+                                (int)pl.chunk, (float*)ctx->scr_m1.p, (float*)ctx->scr_m2.p, (int*)ctx->scr_k.p, todo_list(),
+                                (const unsigned*)ctx->nlist.p, ragged() ? (const long long*)sm->jc : (const long long*)nullptr, tile0,
+                                tile0 > 0 ? 1 : 0));
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(timing_end(ctx));
+        return SPKM_OK;
     }
     // The sums behind the far screen, by the kernels that work at any p: the cluster sizes (k_hist), the distances and the
     // three statistics when the call wants them (the route of spkm_distances_stats_dev), sums and counts (the route of
@@ -935,10 +977,12 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
 // same stages with screen_tile_ragged in screen_far's place -- buffers() builds the blockmap and the plain f32 copy for any
 // shard that is not on the 4-lanes-per-point screen, the plan is the far case as it stands (policy.h), and the accumulation
 // behind it is form 1 (k_accumulate_sorted) at these p.
+// many: the passes of the many-centres screen (spkm_shard_set_many_screen; kp = 32, policy.h spkm_many_screen) -- the same stages
+// again with screen_many in screen_far's place, 32 result planes whatever K is, and a block map of 32 tiles.
 template <typename IR>
 static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_centers, double gamma, int32_t* d_assign,
                    double* d_mind, double* d_reduce, double* d_stats, uint64_t* d_nk_u64, int kp, spkm_screen_report* report,
-                   bool tile = false)
+                   bool tile = false, int many = 0)
 {
     screen_call c;
     c.kt = kp;
@@ -954,6 +998,7 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     if ((rc = ensure_max_s(ctx, c.sm))) return rc;
     c.max_s = c.sm->max_s;
     spkm_plan_tiles(c.pl, c, kp);
+    if (many > 0) { c.many = many; c.pl.Gs = spkm_many_slots; } // (pl.G keeps all the tiles: it sizes the f32 table)
     if ((rc = c.buffers<IR>())) return rc;
     c.plan_input(0, false);
     spkm_plan_call(c.pl, c, c.sm->pol);
@@ -961,7 +1006,8 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     // stays on the global atomics there is no slab, and a call with too many movers for the direct form takes the full pass
     const spkm_acc_plan ap = spkm_accumulate_form((long long)s->p, ctx->lds_max, s->sliced || ctx->sw.sliced_sums, ctx->sw.x_slab_rows);
     if (c.pl.ev_path && !c.pl.direct && ap.form == 2) c.pl.lose_events();
-    if ((rc = c.resources()) || (rc = c.bounds()) || (rc = tile ? c.screen_tile_ragged<IR>() : c.screen_far<IR>()) ||
+    if ((rc = c.resources()) || (rc = c.bounds()) ||
+        (rc = many > 0 ? c.screen_many<IR>() : (tile ? c.screen_tile_ragged<IR>() : c.screen_far<IR>())) ||
         (rc = c.certify<IR>()))
         return rc;
     bool no_stats = c.pl.ev_path; // (an event call is a lazy call without distances: NaN statistics)
@@ -1013,10 +1059,12 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         ch.want_hint = ctx->sw.force_form == 3 && screen_use_quad(ctx, s);
     }
     const bool cooling = ch.exact;
-    const int kt = screen_width(ctx, s, (int)K64);
-    int kp = kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64); // (the far screen: only where no tile serves, policy.h)
+    // (the many-centres screen is asked first: where it answers, no other screen is; where it does not, the dispatch below is untouched)
+    const int many = many_screen_passes(ctx, s, (int)K64);
+    const int kt = many > 0 ? 0 : screen_width(ctx, s, (int)K64);
+    int kp = many > 0 ? SCREEN_KT : (kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64)); // (the far screen: only where no tile serves, policy.h)
     // (a ragged shard that both turned away: the RAGGED tile screen in front of run_far's pipeline, where it opted in)
-    const bool tile_ragged = kt == 0 && kp == 0 && (kp = tile_ragged_width(ctx, s, (int)K64)) > 0;
+    const bool tile_ragged = many == 0 && kt == 0 && kp == 0 && (kp = tile_ragged_width(ctx, s, (int)K64)) > 0;
     if (s->n > 0 && !cooling && (kt > 0 || kp > 0)) {
         ctx->ev_valid = false;
         // Hinted two-phase screen: when the unconditional two-phase form is not chosen and hints are not paused, the
@@ -1026,8 +1074,8 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         const bool want_hint = ch.want_hint;
         spkm_screen_report rep;
         if (kp > 0)
-            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged)
-                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged);
+            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged, many)
+                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged, many);
         else
             rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep)
                                     : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep);

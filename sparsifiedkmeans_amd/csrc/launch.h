@@ -28,8 +28,12 @@ using screen_tile_fn = void (*)(const IR*, const float*, const float*, int, int,
 template <typename IR>
 using screen_wide_fn = void (*)(const IR*, const float*, const float*, int, int, int, int, const spkm_blockmap*, int, float*, float*, int*,
                                 const int*, const unsigned*, const long long*);
+// ... and its FOLD forms, k_screen_wide_fold<IR, LIST, RAGGED>: the same fifteen, then the pass's first tile and whether it folds
 template <typename IR>
-using screen_far_fn = void (*)(const IR*, const float*, const float*, int, int, int, int, float*, float*, int*, const int*,
+using screen_wide_fold_fn = void (*)(const IR*, const float*, const float*, int, int, int, int, const spkm_blockmap*, int, float*, float*,
+                                     int*, const int*, const unsigned*, const long long*, int, int);
+template <typename IR>
+using screen_far_fn =void (*)(const IR*, const float*, const float*, int, int, int, int, float*, float*, int*, const int*,
                                const unsigned*, const long long*);
 // k_screen_quad's translation units (one per row-id width and list granularity) export one dispatcher each: (rounds, rounds
 // evaluated for all centroids) -> kernel, null for a round count that is not compiled

@@ -393,6 +393,33 @@ inline int spkm_tile_screen_ragged(long long p, int K, int fixed_s, unsigned lon
     if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (k_hist, as above)
     return kt;
 }
+// MANY CENTRES: the LDS-tile screen past the tile counts above -- ceil(K / 32) > 32 tiles, K > 1024 -- for a shard or a context
+// that opted in (many: spkm_shard_set_many_screen, SPKM_MANY_SCREEN=1; a switch of its own).  The FOLD forms of k_screen_wide
+// (screen_wide.hip) take the 32-centroid tiles in PASSES of spkm_many_slots and fold every pass into the same spkm_many_slots
+// result planes, so that the scratch (3 planes x 32 x n x 4 B) and the certificate's reads do not grow with K; the pipeline
+// behind it is the far screen's (run_far: point-mode bounds, certificate, exact list, k_hist, the any-p sums or the events).
+// Returns the number of passes, ceil(ceil(K / 32) / 32), or 0: not opted in; SPKM_NO_SCREEN; less than 48 entries of slack,
+// an empty shard; at most 32 tiles -- those K belong to the screens above, whose answers this function never changes; a p
+// whose 32-centroid f32 tile does not fit, (p + 1) 128 + 16 > lds_max; fewer than spkm_many_slots workgroups (one per plane
+// at least); K counters of k_hist beyond the LDS, the cap the far screens apply; a RAGGED shard (fixed_s <= 0) that has not
+// opted in to the ragged tile screen as well (tile_ragged) -- the RAGGED FOLD forms are that screen's.  Asked FIRST by
+// spkm_assign_accumulate_dev: where it answers, a shard with s > 64 or a ragged one with 1024 < K <= 8192 leaves k_screen_tile
+// / the ragged tile screen for it; where it does not, the dispatch is today's.  The policy's cool-down is the caller's to add.
+constexpr int spkm_many_slots = 32;
+inline int spkm_many_screen(long long p, int K, int fixed_s, unsigned long long slack, unsigned long long nnz, size_t lds_max,
+                            int num_cus, bool no_screen, bool tile_ragged, bool many)
+{
+    if (!many || no_screen) return 0;
+    if (slack < 48 || nnz == 0) return 0;
+    const int tiles = (K + spkm_plan_kt - 1) / spkm_plan_kt;
+    if (tiles <= spkm_many_slots) return 0;
+    if ((unsigned long long)(p + 1) * (unsigned)spkm_plan_kt * 4ull + 16ull > (unsigned long long)lds_max) return 0;
+    const int nb = num_cus > 0 ? num_cus : 256;
+    if (nb < spkm_many_slots) return 0;
+    if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (k_hist, as above)
+    if (fixed_s <= 0 && !tile_ragged) return 0;
+    return (tiles + spkm_many_slots - 1) / spkm_many_slots;
+}
 // Which kernel spkm_accumulate_dev runs (update.hip), from the rows, the device's LDS and the opt-in alone -- the form that
 // spkm_last_assign_tile reports in info[4]:
 //  1  k_accumulate_sorted: a cluster's sums and counts, 12 B per row, in one LDS slab of at most 64 KB (p <= 5461) --

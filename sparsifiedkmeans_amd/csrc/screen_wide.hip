@@ -135,14 +135,40 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // fixed-stride ones above: <32> 110 / 110 VGPRs plain and 112 / 112 LIST, <16> 108 / 108 and 110 / 110, <8> 78 / 80 and 78 / 78; 58 SGPRs; no
 // scratch in all twelve; occupancy by registers 4 / 4 / 6 waves per SIMD, where the tile in LDS admits one workgroup per
 // CU, 4 waves per SIMD, anyway.  (Fixed stride, for comparison: <32> LIST 98 / 98, <16> 100 / 96, <8> 72 / 72, 65 / 60 SGPRs.)
-template <typename IR, int KT, bool LIST = false, bool RAGGED = false>
-__global__ __launch_bounds__(1024) void k_screen_wide(
+//
+// FOLD (fifth template argument of the body, KT = 32 only; MANY CENTRES: more than 32 tiles, K > 1024, on a shard that opted in
+// -- spkm_shard_set_many_screen, policy.h spkm_many_screen; plain and LIST, fixed stride and RAGGED, the plain fixed-stride
+// <32> existing for FOLD only).  The tiles are taken in PASSES of 32, one launch per pass on the library's stream, and every
+// pass is folded into the same 32 result planes: a workgroup whose block-map tile is t loads tile g = tile0 + t (tile0: the
+// pass's first tile; past the last tile it returns before the load), runs the rounds above on it -- kfirst and the k >= K
+// mask are g's -- and writes PLANE t.  Scratch is 3 x 32 x n x 4 B and the certificate reads 32 planes, whatever K is.
+// Pass 0 (fold = 0) stores as every other form does.  A later pass MERGES at the point's index: the storing lane reads the
+// plane's (m1, k, m2); if new.m1 < old.m1, or the old entry names no centroid (k < 0), the new leader is stored with
+// m2 = min(new.m2, old.m1, old.m2); otherwise (m1, k) stay and m2 = min(old.m2, new.m1, new.m2).  Invariant (what the proof in
+// screen.hip needs of a plane): m1 is the estimate of centroid k, and m2 a lower bound of the estimate of every OTHER centroid
+// folded into the plane so far -- either branch takes the minimum over the old others, the new others and the loser of the
+// two leaders.  A tie between passes keeps the earlier pass's leader and leaves m2 == m1: the certificate fails, the exact
+// list decides, the lowest index wins.  An all-NaN tile arrives as (+inf, -1, +inf) and changes nothing (the minima are
+// fminf's; a stored value is never a NaN).  An EMPTY column keeps what pass 0 stored -- (0, 0, BLANK_M2) in plane 0 -- through
+// every later pass, which skips it.  The read-after-write order between passes is the stream's: no loop over tiles in the
+// kernel, no fence.  The chunk map (stream + ci nstreams) and the LIST form's length, read on the device from the same
+// counter, are the same in every pass, so a list slot meets the same plane entry each time, whichever workgroup holds it.
+// The two arguments travel in a kernel of their own, k_screen_wide_fold<IR, LIST, RAGGED> = the body at <IR, 32, LIST, RAGGED,
+// true>; k_screen_wide keeps its fifteen parameters, and every FOLD statement sits behind `if constexpr (FOLD)`: the twelve
+// instantiations above compile to what they were.
+// Resources of the FOLD forms (-Rpass-analysis=kernel-resource-usage, gfx950; 16- / 32-bit row ids): fixed stride
+// 98 / 98 VGPRs plain and 98 / 98 LIST, 72 / 66 SGPRs; RAGGED 110 / 110 plain and 112 / 112 LIST, 64 / 64 SGPRs -- the VGPRs of
+// the <32> forms they extend; scratch 0 in all eight; 4 waves per SIMD by registers, which the tile in LDS allows anyway.  The
+// resources of every kernel that existed before are the same numbers as before (compared kernel by kernel over the unit).
+template <typename IR, int KT, bool LIST, bool RAGGED, bool FOLD>
+__device__ __forceinline__ void screen_wide_body(
     const IR* __restrict__ ir, const float* __restrict__ xval, const float* __restrict__ Twt, int p, int n,
     int fixed_s, int K, const spkm_blockmap* __restrict__ bmap, int chunk_points, float* __restrict__ scr_m1,
-    float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo = nullptr,
-    const unsigned* __restrict__ counters = nullptr, const long long* __restrict__ jc = nullptr)
+    float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo, const unsigned* __restrict__ counters,
+    const long long* __restrict__ jc, int tile0, int fold)
 {
-    static_assert(KT == 16 || KT == 8 || (KT == 32 && (LIST || RAGGED)), "tiles of 16 or 8 centroids; 32 for lists and ragged shards only");
+    static_assert(KT == 16 || KT == 8 || (KT == 32 && (LIST || RAGGED || FOLD)), "tiles of 16 or 8 centroids; 32 for lists, ragged shards and folded passes only");
+    static_assert(!FOLD || KT == 32, "passes are folded on the 32-centroid tile only");
     constexpr float BLANK_M2 = 0x1.fffffep+127f; // an empty column's runner-up: the largest finite f32 (the header)
     constexpr int LG = KT / 4, PPW = 64 / LG, ROWB = KT * 4, UN = 4;
     constexpr int EPR = LG < 4 ? LG : 4; // entries per round: the lanes of a quad that belong to one point
@@ -155,7 +181,11 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
         if (tp <= 0) return; // an empty list: not even the tile is loaded
         if (tp > n) tp = n;
     }
-    const int g = bm.tile;
+    int g = bm.tile; // the tile in LDS; FOLD: the pass's first tile + the block map's, results into PLANE bm.tile
+    if constexpr (FOLD) {
+        g += tile0;
+        if ((long long)g * KT >= K) return; // (the last pass: past the last tile)
+    }
     const int tid = threadIdx.x;
     const size_t tile_bytes = (size_t)(p + 1) * ROWB;
     {
@@ -180,9 +210,11 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
     const int R = chunk_v / PPW;
     const int my_chunks = (nchunks > bm.stream) ? (nchunks - bm.stream + bm.nstreams - 1) / bm.nstreams : 0;
     const int T = my_chunks * R;
-    float* m1o = scr_m1 + (size_t)g * n;
-    float* m2o = scr_m2 + (size_t)g * n;
-    int* ko = scr_k + (size_t)g * n;
+    size_t plane = (size_t)g;
+    if constexpr (FOLD) plane = (size_t)bm.tile;
+    float* m1o = scr_m1 + plane * n;
+    float* m2o = scr_m2 + plane * n;
+    int* ko = scr_k + plane * n;
     const int kfirst = g * KT + sub * 4; // this lane's centroids: kfirst .. kfirst + 3
     const bool ragged_tile = g * KT + KT > K; // (block-uniform: only the last tile has slots k >= K)
     unsigned* ticket = reinterpret_cast<unsigned*>(smem + tile_bytes);
@@ -308,10 +340,29 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
         const bool none = first == LG;
         if constexpr (RAGGED) {
             if (len == 0) { // an EMPTY column (the header): the rule, whatever the accumulators hold
+                if constexpr (FOLD) {
+                    if (fold) continue; // (pass 0 stored the rule; a later pass leaves every plane as it is)
+                }
                 if (sub == 0 && i < nv) {
                     m1o[i] = g == 0 ? 0.f : __builtin_inff();
                     m2o[i] = g == 0 ? BLANK_M2 : __builtin_inff();
                     ko[i] = g == 0 ? 0 : -1;
+                }
+                continue;
+            }
+        }
+        if constexpr (FOLD) {
+            if (fold) { // a later pass: merged into what the passes before left at this index (the header)
+                if (sub == (none ? 0 : first) && i < nv) {
+                    const float n1 = none ? __builtin_inff() : m1, n2 = none ? __builtin_inff() : m2;
+                    const float o1 = m1o[i], o2 = m2o[i];
+                    const int ok = ko[i];
+                    if (n1 < o1 || ok < 0) { // a new leader: the old one joins the others
+                        m1o[i] = n1;
+                        ko[i] = none ? -1 : kfirst + li;
+                        m2o[i] = fminf(n2, fminf(o1, o2));
+                    } else // (a tie keeps the earlier pass's leader and leaves m2 == m1: no certificate, the exact list decides)
+                        m2o[i] = fminf(o2, fminf(n1, n2));
                 }
                 continue;
             }
@@ -322,4 +373,25 @@ __global__ __launch_bounds__(1024) void k_screen_wide(
             ko[i] = none ? -1 : kfirst + li;
         }
     }
+}
+template <typename IR, int KT, bool LIST = false, bool RAGGED = false>
+__global__ __launch_bounds__(1024) void k_screen_wide(
+    const IR* __restrict__ ir, const float* __restrict__ xval, const float* __restrict__ Twt, int p, int n,
+    int fixed_s, int K, const spkm_blockmap* __restrict__ bmap, int chunk_points, float* __restrict__ scr_m1,
+    float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo = nullptr,
+    const unsigned* __restrict__ counters = nullptr, const long long* __restrict__ jc = nullptr)
+{
+    screen_wide_body<IR, KT, LIST, RAGGED, false>(ir, xval, Twt, p, n, fixed_s, K, bmap, chunk_points, scr_m1, scr_m2, scr_k, todo,
+                                                  counters, jc, 0, 0);
+}
+// One pass of the MANY-CENTRES screen (the header: FOLD): tiles tile0 .. tile0 + 31 into planes 0 .. 31; fold = 0: the first pass
+template <typename IR, bool LIST, bool RAGGED>
+__global__ __launch_bounds__(1024) void k_screen_wide_fold(
+    const IR* __restrict__ ir, const float* __restrict__ xval, const float* __restrict__ Twt, int p, int n,
+    int fixed_s, int K, const spkm_blockmap* __restrict__ bmap, int chunk_points, float* __restrict__ scr_m1,
+    float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo, const unsigned* __restrict__ counters,
+    const long long* __restrict__ jc, int tile0, int fold)
+{
+    screen_wide_body<IR, 32, LIST, RAGGED, true>(ir, xval, Twt, p, n, fixed_s, K, bmap, chunk_points, scr_m1, scr_m2, scr_k, todo,
+                                                 counters, jc, tile0, fold);
 }

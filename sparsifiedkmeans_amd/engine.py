@@ -146,6 +146,17 @@ class Shard:
         listed.  Outputs never depend on it; the shard's policy state is forgotten as by reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_tile_ragged(self.handle, 1 if on else 0), "spkm_shard_set_tile_ragged")
 
+    def set_many_screen(self, on: bool = True):
+        """Let this shard's fused calls with more than 32 centroid tiles (K > 1024) at a p that has a 32-centroid LDS tile
+        (p <= 1278 with 160 KB) take the certified f32 screen in passes of 32 tiles, every pass folded into the same 32
+        result planes, in front of the far screen's pipeline, instead of the all-exact kernels -- or, with columns of more
+        than 64 entries or on a ragged shard with set_tile_ragged(), instead of a screen with one plane per tile
+        (spkm_shard_set_many_screen; off by default at the C interface; a switch of its own).  set_far_bounds() and
+        set_far_events() apply to it as to a far shard; a ragged shard needs set_tile_ragged() as well.  Outputs never
+        depend on it; last_screen_passes() reads back what a call did.  The shard's policy state is forgotten as by
+        reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_many_screen(self.handle, 1 if on else 0), "spkm_shard_set_many_screen")
+
     def set_kpp_ragged(self, on: bool = True):
         """Let ``kpp_seed`` on this shard, when it is RAGGED (columns of different lengths: a sample whose exact zeros were
         dropped), run the staged round kernel in the form that reads each point's column bounds -- the newest centres'
@@ -469,6 +480,13 @@ class LloydEngine:
         spkm_last_screen_tile."""
         a = (C.c_int64 * 2)()
         _lib.check(_lib.lib().spkm_last_screen_tile(self.ctx.handle, a))
+        return int(a[0]), int(a[1])
+
+    def last_screen_passes(self) -> tuple[int, int]:
+        """(passes of 32 tiles of the last fused call's many-centres screen, set_many_screen(); the result planes they were
+        folded into, 32) -- (0, 0) after a call that took another screen or none -- spkm_last_screen_passes."""
+        a = (C.c_int64 * 2)()
+        _lib.check(_lib.lib().spkm_last_screen_passes(self.ctx.handle, a))
         return int(a[0]), int(a[1])
 
     def last_screen_points(self) -> tuple[int, int]:

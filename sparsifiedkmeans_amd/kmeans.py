@@ -75,6 +75,11 @@ _DEFAULTS = dict(
 # or 32 centroids by the ragged form of the narrow-tile kernel, with the far path's bounds and events behind it, instead of
 # the all-exact tile kernel over every point in every iteration (Shard.set_tile_ragged).  Off by default: the decision shapes
 # of profiles/tile_ragged_ab.txt were run once (every pair wins, 1.8x to 8x), and the default waits for a second series.
+# manyCentres: with more than 1024 centres (more than 32 centroid tiles) at p2 <= 1278, where the screen's one-workgroup-per-tile-
+# and-XCD rule sends every call to the all-exact kernels, the shard is screened in passes of 32 tiles folded into 32 result
+# planes, with the far path's bounds and events behind it (Shard.set_many_screen; farBounds and farEvents apply to it; a
+# ragged shard needs tileRagged as well).  Off by default: of the decision shapes of profiles/many_centres_ab.txt a shortened
+# series ran two (every pair wins, 14x to 29x), and the default goes on only once every pair of every shape wins.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
 # seedTogether: the k-means++ starts of ALL replicates are drawn in one library call that shares each round's read of the
@@ -88,7 +93,7 @@ _DEFAULTS = dict(
 # for a second series.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
               slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True,
-              kppRagged=False)
+              kppRagged=False, manyCentres=False)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -439,6 +444,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_far_screen(bool(o["farScreen"]))
     shard.set_far_ragged(bool(o["farRagged"]))
     shard.set_tile_ragged(bool(o["tileRagged"]))
+    shard.set_many_screen(bool(o["manyCentres"]))
     shard.set_kpp_ragged(bool(o["kppRagged"]))
     shard.set_far_bounds(bool(o["farBounds"]))
     shard.set_far_events(bool(o["farEvents"]))
