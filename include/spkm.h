@@ -286,6 +286,19 @@ int spkm_shard_set_many_screen(spkm_shard *s, int on);
  * other opt-in implies it, and it needs none.  SPKM_KPP_RAGGED=1 opts every shard of a context in (read with the other
  * switches: spkm_ctx_reload_switches); such a shard's longest column is measured in its first seeding. */
 int spkm_shard_set_kpp_ragged(spkm_shard *s, int on);
+/* The sparse-centres assignment through a row index of the centres (on != 0; default off).  spkm_assign_sparse_centers_dev
+ * visits every (entry, centroid) pair of a point through a row-major K x p mask, although the reference's sum runs over
+ * supp(x_i) ∩ supp(c_k) only.  For a shard that opts in here the call first turns the centres round -- row r lists, in
+ * ascending k, the centres whose support holds r, with c / gamma beside each (p + 1 ints, p * K uint16 and p * K doubles
+ * of scratch at the most, no more than the call took before; built on the device, nothing read back) -- and a point
+ * then walks, for each of its entries, that row's list alone: P points per wave, 64 / P lanes per point, K f64
+ * accumulators per point in LDS (csrc/policy.h, spkm_sparse_plan: P = 8, 4, 2, 1 by K; past the K whose accumulators fit
+ * the LDS at P = 1 -- 5120 with 160 KB -- and for p * K >= 2^31 today's kernel).  Every centre receives its terms in the
+ * storage order of the point's column, both divides are true divides: d_assign, d_mind, d_stats and d_nk_u64 are
+ * today's bit for bit, fixed-stride or ragged shard, either row-id width.  spkm_last_sparse_form reads back what a call
+ * did.  A switch of its own: no other opt-in implies it, and it needs none.  SPKM_SPARSE_INDEX=1 opts every shard of a
+ * context in (read with the other switches: spkm_ctx_reload_switches). */
+int spkm_shard_set_sparse_index(spkm_shard *s, int on);
 /* Halve the resident footprint of a fixed-stride shard (every column has the same number of entries, at most 64): build
  * now what the fused call would build on its first use -- the record layout (a point's values and row ids side by side)
  * and the screen's f32 copy + norms -- and let go of the CSC value / row-id arrays.  A shard made by
@@ -452,6 +465,11 @@ int spkm_last_screen_tile(spkm_ctx *ctx, int64_t info[2]);
  * passes of 32 tiles, ceil(ceil(K / 32) / 32), info[1] = the result planes per point they were folded into (32); (0, 0) after
  * a call that took any other screen, or none. */
 int spkm_last_screen_passes(spkm_ctx *ctx, int64_t info[2]);
+/* The context's last spkm_assign_sparse_centers_dev (stored values; does not block): info[0] = its form -- 0 = one lane per
+ * centroid over the row-major mask, 1 = the row index of the centres (spkm_shard_set_sparse_index) --, info[1] = points per
+ * wave, info[2] = waves per workgroup, info[3] = bytes of LDS per workgroup (zeros for form 0: csrc/policy.h,
+ * spkm_sparse_plan); all zeros after spkm_assign_dev or spkm_assign_accumulate_dev, and before any call. */
+int spkm_last_sparse_form(spkm_ctx *ctx, int64_t info[4]);
 /* How many points the screen of the last fused call evaluated (any screen kernel): info[0] = n for a call over all points,
  * the length of the list for a call that skipped on its carried bounds (points; 16 per listed step for a step list), 0
  * when the call took no screen; info[1] = the running total over the context.  Blocks on the stream. */

@@ -148,6 +148,8 @@ def lib():
     L.spkm_shard_set_tile_ragged.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_many_screen.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_kpp_ragged.argtypes = [_vp, C.c_int]
+    L.spkm_shard_set_sparse_index.argtypes = [_vp, C.c_int]
+    L.spkm_last_sparse_form.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_shard_set_sliced_sums.argtypes = [_vp, C.c_int]
     L.spkm_last_screen_tile.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_screen_passes.argtypes = [_vp, C.POINTER(C.c_int64)]

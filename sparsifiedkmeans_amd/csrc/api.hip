@@ -46,6 +46,7 @@ static spkm_switches read_switches()
     w.tile_ragged = on("SPKM_TILE_RAGGED");
     w.many_screen = on("SPKM_MANY_SCREEN");
     w.kpp_ragged = on("SPKM_KPP_RAGGED");
+    w.sparse_index = on("SPKM_SPARSE_INDEX");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
@@ -156,7 +157,7 @@ extern "C" void spkm_ctx_destroy(spkm_ctx* ctx)
                      &ctx->nk, &ctx->stats, &ctx->perm, &ctx->offs, &ctx->cursor, &ctx->items, &ctx->nitems,
                      &ctx->bmap, &ctx->blk_dff, &ctx->ct, &ctx->tmp_assign, &ctx->tmp_mind, &ctx->mscr, &ctx->dbg, &ctx->t32, &ctx->scr_m1, &ctx->scr_m2,
                      &ctx->scr_k, &ctx->cmax, &ctx->list, &ctx->nlist, &ctx->dn_x, &ctx->dn_c, &ctx->dn_nk, &ctx->bmapq, &ctx->bmapm, &ctx->bmapm2, &ctx->todo, &ctx->todo_m, &ctx->todo_m2, &ctx->bstat, &ctx->nk_ev, &ctx->fin_ticket, &ctx->wgstat, &ctx->offs2, &ctx->cursor2, &ctx->hist2,
-                     &ctx->items2, &ctx->perm_o, &ctx->mix_scr};
+                     &ctx->items2, &ctx->perm_o, &ctx->mix_scr, &ctx->sp_rowptr, &ctx->sp_ck};
     for (devbuf* b : all) release(*b);
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
     for (auto& pr : ctx->tlog) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -478,6 +479,14 @@ extern "C" int spkm_shard_set_kpp_ragged(spkm_shard* s, int on)
     if (!s) return SPKM_ERR_NULL_ARG;
     s->kpp_ragged = on != 0;
     if (s->kpp_ragged && s->ctx) return ensure_max_s(s->ctx, s); // (here, so that no seeding waits for it)
+    return SPKM_OK;
+}
+
+// (no policy state to forget, nothing to measure: the sparse-centres call keeps nothing on the shard)
+extern "C" int spkm_shard_set_sparse_index(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->sparse_index = on != 0;
     return SPKM_OK;
 }
 

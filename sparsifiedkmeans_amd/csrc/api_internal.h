@@ -63,6 +63,7 @@ struct spkm_switches {
     bool tile_ragged = false;     // SPKM_TILE_RAGGED: every RAGGED shard of the context at a p with a 32-centroid f32 tile takes the RAGGED form of k_screen_wide on an LDS tile instead of k_assign_tile over every point, as if opted in (spkm_shard_set_tile_ragged); a switch of its own
     bool many_screen = false;     // SPKM_MANY_SCREEN: every shard of the context with more than 32 centroid tiles (K > 1024) at a p with a 32-centroid f32 tile takes the folded passes of k_screen_wide (policy.h, spkm_many_screen) in front of the far screen's pipeline, as if opted in (spkm_shard_set_many_screen); a switch of its own
     bool kpp_ragged = false;      // SPKM_KPP_RAGGED: spkm_kpp_seed_dev on every RAGGED shard of the context whose longest column has a staged table takes k_kpp_round_ragged (the table in LDS, staged entries) instead of k_kpp_round_generic, as if opted in (spkm_shard_set_kpp_ragged); a switch of its own
+    bool sparse_index = false;    // SPKM_SPARSE_INDEX: spkm_assign_sparse_centers_dev on every shard of the context walks a row index of the centres (k_assign_sparse_indexed; policy.h, spkm_sparse_plan) instead of k_assign_sparse_centers, as if opted in (spkm_shard_set_sparse_index); a switch of its own
     bool sliced_sums = false;     // SPKM_SLICED_SUMS: spkm_accumulate_dev on every shard of the context keeps its sums in LDS past the 64-KB slab too, a row slice at a time (k_accumulate_sliced; policy.h, spkm_accumulate_form), as if opted in (spkm_shard_set_sliced_sums)
     int x_slab_rows = 0;          // SPKM_X_SLAB_ROWS: at most this many rows per slab of k_accumulate_sliced, at any p and any number of slices (0: the default, what the LDS holds; experiments and tests)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
@@ -102,7 +103,8 @@ struct spkm_ctx {
     size_t mem_bytes = 0;
     // grow-only device scratch
     devbuf tiles, part_acc, part_k, blk_obj, blk_max, blk_imax, nk, stats, perm, offs, cursor, items, nitems,
-        bmap, blk_dff, ct, tmp_assign, tmp_mind, mscr, dbg, t32, scr_m1, scr_m2, scr_k, cmax, list, nlist, dn_x, dn_c, dn_nk, bmapq, bmapm, bmapm2, todo, todo_m, todo_m2, bstat, nk_ev, fin_ticket, wgstat, offs2, cursor2, hist2, items2, perm_o;
+        bmap, blk_dff, ct, tmp_assign, tmp_mind, mscr, dbg, t32, scr_m1, scr_m2, scr_k, cmax, list, nlist, dn_x, dn_c, dn_nk, bmapq, bmapm, bmapm2, todo, todo_m, todo_m2, bstat, nk_ev, fin_ticket, wgstat, offs2, cursor2, hist2, items2, perm_o,
+        sp_rowptr, sp_ck; // the row index of sparse centres (sparse_index.hip): p + 1 ints, p * K uint16 (its values: ct)
     devbuf mix_scr; // mixed columns of the wide / short Hadamard sparsifier (at most SPKM_MIX_SCRATCH_BYTES)
     // results of an iteration handed to the host without a copy or a stream synchronisation (spkm_lloyd_iter_host): pinned host
     // memory the device maps -- [sequence number | dff^2 | obj^2 | cluster sizes], written by k_finalize_centers' last workgroup
@@ -136,6 +138,7 @@ struct spkm_ctx {
     int last_acc_form = 0;           // spkm_accumulate_dev's last kernel: 1 LDS slab over a counting sort, 2 global atomics, 3 LDS slabs over row slices
     int last_dist_form = 0;          // the last distances call: 1 streaming record kernel, 2 generic kernel
     int last_kpp[4] = {0, 0, 0, 0};  // the last spkm_kpp_seed_dev: form (policy.h, spkm_kpp_plan / spkm_kpp_plan_ragged; 0: none yet or K = 1), RB, batches, points staged per wave
+    int last_sparse[4] = {0, 0, 0, 0}; // the last spkm_assign_sparse_centers_dev: form, points per wave, waves per workgroup, LDS bytes (policy.h, spkm_sparse_plan); zeros after any other assignment call
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
     bool sort_perm_valid = false;    // ... and perm / offs / items really hold that call's counting sort (not after an incremental call)
     char errmsg[256] = {0};
@@ -164,6 +167,7 @@ struct spkm_shard {
     bool tile_ragged = false; // spkm_shard_set_tile_ragged: a RAGGED shard (fixed_s = 0) at a p with a 32-centroid f32 tile takes k_screen_wide's RAGGED form there, in front of the far screen's pipeline (policy.h, spkm_tile_screen_ragged)
     bool many = false; // spkm_shard_set_many_screen: with more than 32 centroid tiles (K > 1024) at a p with a 32-centroid f32 tile this shard's fused calls take the folded passes of k_screen_wide (policy.h, spkm_many_screen)
     bool kpp_ragged = false; // spkm_shard_set_kpp_ragged: a RAGGED shard (fixed_s = 0) is seeded by k_kpp_round_ragged where its longest column has a staged table (policy.h, spkm_kpp_plan_ragged)
+    bool sparse_index = false; // spkm_shard_set_sparse_index: spkm_assign_sparse_centers_dev on this shard walks a row index of the centres (policy.h, spkm_sparse_plan)
     int max_s = 0;           // the longest column: fixed_s on a fixed-stride shard; on a ragged one a reduction over jc, run once (ensure_max_s) ...
     bool max_s_known = false; // ... when the shard opts in to a ragged screen (far or tile) or to the ragged seeding, or on its first call there
     bool sliced = false; // spkm_shard_set_sliced_sums: past the 64-KB slab spkm_accumulate_dev on this shard takes k_accumulate_sliced (policy.h, spkm_accumulate_form)

@@ -4,6 +4,7 @@
 #include "assign.hip"
 #include "update.hip"
 #include "kpp.hip"
+#include "sparse_index.hip"
 #include "screen.hip"
 #include "screen_wide.hip"
 #include "screen_far.hip"
@@ -473,6 +474,7 @@ extern "C" int spkm_assign_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64,
     if (!ctx || !s || !d_centers || !d_assign || !d_mind) return SPKM_ERR_NULL_ARG;
     if (K64 == 0 || K64 > 65536) return SPKM_ERR_UNSUPPORTED;
     ctx->sort_owner = nullptr; // this call overwrites (some of) the buffers a kept counting sort lives in
+    memset(ctx->last_sparse, 0, sizeof(ctx->last_sparse)); // (spkm_last_sparse_form: not a sparse-centres call)
     HIP_TRY(hipSetDevice(ctx->device));
     const_cast<spkm_shard*>(s)->sp_clean = false; // (this call writes d_assign: the block summaries' claim on that buffer ends)
     const_cast<spkm_shard*>(s)->assign_synced = false;
@@ -592,6 +594,41 @@ extern "C" int spkm_assign_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64,
     return combine_partials(ctx, n, G, K, d_assign, d_mind, d_stats, d_nk_u64);
 }
 
+// The sparse-centres call of a shard that opted in to the row index (sparse_index.hip; sp: policy.h, spkm_sparse_plan form 1):
+// the index from d_centers / d_mask -- rowptr, ck, cv (in ct) and gamma_c (in tmp_assign), sized for p * K entries so that
+// no count comes back to the host -- then k_assign_sparse_indexed into part_acc / part_k, for combine_partials.
+template <typename IR>
+static int assign_sparse_indexed(spkm_ctx* ctx, const spkm_shard* s, const spkm_sparse_plan_t& sp, int K, const double* d_centers,
+                                 const uint8_t* d_mask, double gamma)
+{
+    const int p = (int)s->p;
+    const long long n = (long long)s->n;
+    int rc;
+    if ((rc = ensure(ctx, ctx->ct, (size_t)p * K * 8))) return rc;        // cv
+    if ((rc = ensure(ctx, ctx->sp_ck, (size_t)p * K * 2))) return rc;
+    if ((rc = ensure(ctx, ctx->sp_rowptr, ((size_t)p + 1) * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->tmp_assign, (size_t)K * 8))) return rc;    // gamma_c per centre
+    if ((rc = ensure(ctx, ctx->part_acc, (size_t)n * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->part_k, (size_t)n * 4))) return rc;
+    int* rowptr = (int*)ctx->sp_rowptr.p;
+    const unsigned rb = ((unsigned)p + 255u) / 256u;
+    HIP_TRY(spkm_launch(k_sparse_index_gc, dim3(K), dim3(256), 0, ctx->stream, d_mask, p, K, (double*)ctx->tmp_assign.p));
+    HIP_TRY(spkm_launch(k_sparse_index_count, dim3(rb), dim3(256), 0, ctx->stream, d_mask, p, K, rowptr));
+    HIP_TRY(spkm_launch(k_sparse_index_scan, dim3(1), dim3(1024), 0, ctx->stream, rowptr, p));
+    HIP_TRY(spkm_launch(k_sparse_index_fill, dim3(rb), dim3(256), 0, ctx->stream, d_centers, d_mask, p, K, gamma, (const int*)rowptr,
+                        (unsigned short*)ctx->sp_ck.p, (double*)ctx->ct.p));
+    auto kern = sparse_indexed_kernel<IR>(sp.pts);
+    if (!kern || sp.nw != 4) return SPKM_ERR_UNSUPPORTED; // (a plan this build has no kernel for: an error, not another path)
+    const size_t lds = (size_t)sp.lds;
+    if (lds > 48 * 1024) HIP_TRY(allow_lds(ctx, (const void*)kern, lds));
+    const long long per_wg = (long long)sp.nw * sp.pts;
+    const int blocks = (int)std::max<long long>(1, std::min<long long>((n + per_wg - 1) / per_wg, (long long)std::max(1, ctx->num_cus) * 8));
+    HIP_TRY(spkm_launch(kern, dim3(blocks), dim3(sp.nw * 64), lds, ctx->stream, (const long long*)s->jc, (const IR*)s->ir,
+                        (const double*)s->x, (const int*)rowptr, (const unsigned short*)ctx->sp_ck.p, (const double*)ctx->ct.p,
+                        (const double*)ctx->tmp_assign.p, gamma > 0.0 ? 1 : 0, K, n, (double*)ctx->part_acc.p, (int*)ctx->part_k.p));
+    return SPKM_OK;
+}
+
 extern "C" int spkm_assign_sparse_centers_dev(spkm_ctx* ctx, const spkm_shard* s, uint64_t K64,
                                               const double* d_centers, const uint8_t* d_mask, double gamma,
                                               int32_t* d_assign, double* d_mind, double* d_stats,
@@ -611,11 +648,20 @@ extern "C" int spkm_assign_sparse_centers_dev(spkm_ctx* ctx, const spkm_shard* s
     if ((rc = ensure(ctx, ctx->stats, 4 * 8))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->nk.p, 0, (size_t)K * 8, ctx->stream));
     ctx->ev_valid = false;
+    // the form (policy.h, spkm_sparse_plan): today's kernel unless the shard or the context opted in to the row index
+    const spkm_sparse_plan_t sp = spkm_sparse_plan((long long)p, K, ctx->lds_max, s->sparse_index || ctx->sw.sparse_index);
+    ctx->last_sparse[0] = sp.form; ctx->last_sparse[1] = sp.pts; ctx->last_sparse[2] = sp.nw; ctx->last_sparse[3] = (int)sp.lds;
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(ctx->stats.p, 0, 4 * 8, ctx->stream));
         if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, 3 * 8, ctx->stream));
         if (d_nk_u64) HIP_TRY(hipMemsetAsync(d_nk_u64, 0, (size_t)K * 8, ctx->stream));
         return SPKM_OK;
+    }
+    if (sp.form == 1) {
+        if (s->ir_bits == 16) rc = assign_sparse_indexed<unsigned short>(ctx, s, sp, K, d_centers, d_mask, gamma);
+        else rc = assign_sparse_indexed<unsigned int>(ctx, s, sp, K, d_centers, d_mask, gamma);
+        if (rc) return rc;
+        return combine_partials(ctx, n, 1, K, d_assign, d_mind, d_stats, d_nk_u64);
     }
     if ((rc = ensure(ctx, ctx->ct, (size_t)p * K * 8))) return rc;
     if ((rc = ensure(ctx, ctx->tmp_mind, (size_t)p * K))) return rc;     // row-major mask
@@ -1031,6 +1077,15 @@ extern "C" int spkm_last_screen_passes(spkm_ctx* ctx, int64_t info[2])
     if (!ctx || !info) return SPKM_ERR_NULL_ARG;
     info[0] = ctx->last.passes;
     info[1] = ctx->last.planes;
+    return SPKM_OK;
+}
+
+// The context's last sparse-centres call: form (0 k_assign_sparse_centers, 1 the row index), points per wave, waves per
+// workgroup, LDS bytes -- policy.h, spkm_sparse_plan; zeros after any other assignment call.  Stored values; does not block.
+extern "C" int spkm_last_sparse_form(spkm_ctx* ctx, int64_t info[4])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    for (int j = 0; j < 4; j++) info[j] = ctx->last_sparse[j];
     return SPKM_OK;
 }
 

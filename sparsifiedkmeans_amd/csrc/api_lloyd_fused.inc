@@ -1022,6 +1022,7 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
 {
     if (!ctx || !s || !d_centers || !d_assign || !d_reduce) return SPKM_ERR_NULL_ARG; // d_mind may be NULL (spkm.h)
     if (K64 == 0 || K64 > 65536) return SPKM_ERR_UNSUPPORTED;
+    memset(ctx->last_sparse, 0, sizeof(ctx->last_sparse)); // (spkm_last_sparse_form: not a sparse-centres call)
     HIP_TRY(hipSetDevice(ctx->device));
     int rc;
     spkm_shard* sm = const_cast<spkm_shard*>(s);

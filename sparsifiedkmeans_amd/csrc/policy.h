@@ -547,6 +547,35 @@ inline spkm_kpp_plan_t spkm_kpp_plan_ragged(long long p, int fixed_s, int max_s,
     }
     return spkm_kpp_plan(p, fixed_s, slack, R, n, lds_max, free_bytes);
 }
+// The sparse-centres assignment (spkm_assign_sparse_centers_dev; findClusterAssignments.m:63-75).  Two forms:
+//  0  k_assign_sparse_centers: one wave per point, one lane per centroid, every (entry, centroid) pair visited through a
+//     row-major K x p mask -- today's kernel, for every shard that did not opt in.
+//  1  k_assign_sparse_indexed: a ROW INDEX of the centres (row r lists the centres whose support holds r, ascending) is
+//     walked over supp(x_i) ∩ supp(c_k) only; P points per wave, 64 / P lanes per point, K f64 accumulators per point in LDS.
+//     For a shard or a context that opted in (opted_in: spkm_shard_set_sparse_index, SPKM_SPARSE_INDEX=1; a switch of its own).
+// The rule: spkm_sparse_nw = 4 waves per workgroup (256 threads); P = the largest of 8, 4, 2, 1 whose accumulators,
+// nw * P * K * 8 bytes, fit HALF the LDS (two workgroups per CU); failing that P = 1 within the whole LDS (160 KB: K <= 5120).
+// Form 0 beyond that, without the opt-in, for K <= 0 or p <= 0, and for p * K >= 2^31 (the index counts its entries in an int).
+constexpr int spkm_sparse_nw = 4, spkm_sparse_pts_max = 8;
+struct spkm_sparse_plan_t {
+    int form = 0; // 0 k_assign_sparse_centers, 1 k_assign_sparse_indexed
+    int pts = 0;  // points per wave (form 1)
+    int nw = 0;   // waves per workgroup (form 1)
+    unsigned long long lds = 0; // bytes of dynamic LDS per workgroup (form 1)
+};
+inline spkm_sparse_plan_t spkm_sparse_plan(long long p, int K, size_t lds_max, bool opted_in)
+{
+    spkm_sparse_plan_t a;
+    if (!opted_in || K <= 0 || p <= 0 || (unsigned long long)p * (unsigned long long)K >= (1ull << 31)) return a;
+    const unsigned long long per_pt = (unsigned long long)spkm_sparse_nw * (unsigned long long)K * 8;
+    int P = 0;
+    for (int c = spkm_sparse_pts_max; c >= 1 && !P; c /= 2)
+        if (per_pt * c <= (unsigned long long)lds_max / 2) P = c;
+    if (!P && per_pt <= (unsigned long long)lds_max) P = 1;
+    if (!P) return a;
+    a.form = 1; a.pts = P; a.nw = spkm_sparse_nw; a.lds = per_pt * P;
+    return a;
+}
 // far shards with incremental sums: k_combine_screen keeps 2 K event counters (8 K bytes) in dynamic LDS beside 16 KB of
 // static stage -- 32 KB of counters (K <= 4096) stay inside the 64 KB every launch may use without asking
 constexpr size_t spkm_far_events_kmax_bytes = 32 * 1024;

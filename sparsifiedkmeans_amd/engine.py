@@ -166,6 +166,15 @@ class Shard:
         'staged-ragged'.  A fixed-stride shard never hears it."""
         _lib.check(_lib.lib().spkm_shard_set_kpp_ragged(self.handle, 1 if on else 0), "spkm_shard_set_kpp_ragged")
 
+    def set_sparse_index(self, on: bool = True):
+        """Let ``LloydEngine.assign_sparse_step`` on this shard walk a ROW INDEX of the centres -- row r lists the centres
+        whose support holds r -- so that a point meets only the (entry, centre) pairs of supp(x_i) ∩ supp(c_k), 8 points per
+        wave with their K accumulators in LDS, instead of visiting every pair through a row-major mask
+        (spkm_shard_set_sparse_index; off by default; a switch of its own).  Up to the K whose accumulators fit the LDS
+        (5120 with 160 KB); past it the call runs as before.  Assignments, distances, statistics and cluster sizes never
+        depend on it, bit for bit; LloydEngine.last_sparse_form() reads back what a call did."""
+        _lib.check(_lib.lib().spkm_shard_set_sparse_index(self.handle, 1 if on else 0), "spkm_shard_set_sparse_index")
+
     def column(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         """(row ids int64 ascending, values float64) of column ``i`` -- from the CSC arrays or, once they are released,
         from the record layout (spkm_shard_get_column_host)."""
@@ -488,6 +497,14 @@ class LloydEngine:
         a = (C.c_int64 * 2)()
         _lib.check(_lib.lib().spkm_last_screen_passes(self.ctx.handle, a))
         return int(a[0]), int(a[1])
+
+    def last_sparse_form(self) -> tuple[int, int, int, int]:
+        """(form, points per wave, waves per workgroup, LDS bytes) of the context's last assign_sparse_step: form 0 = one lane
+        per centroid over the row-major mask, 1 = the row index of the centres (Shard.set_sparse_index) -- all zeros after
+        assign_step / assign_accumulate_step -- spkm_last_sparse_form."""
+        a = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().spkm_last_sparse_form(self.ctx.handle, a), "spkm_last_sparse_form")
+        return int(a[0]), int(a[1]), int(a[2]), int(a[3])
 
     def last_screen_points(self) -> tuple[int, int]:
         """(points the last fused call's screen evaluated: n for a call over all points, the length of its list when it

@@ -91,9 +91,16 @@ _DEFAULTS = dict(
 # (Shard.set_kpp_ragged; OUTPUT["seedPlan"][0] reads 'staged-ragged').  Picks never depend on it.  Off by default: the
 # shapes of profiles/kpp_ragged_ab.txt were run once (every pair wins: the start 1.1x to 6.6x faster), and the default waits
 # for a second series.
+# sparseIndex: the iterations whose centres are still sparse (denseCenters=false: a replicate's first, and every further one
+# while fewer than 99 % of the centre entries are filled; the rounds of a start without unbiasedInitialization) assign through
+# a row index of the centres -- a point meets only the (entry, centre) pairs of supp(x) n supp(c), 8 points per wave, their K
+# accumulators in LDS -- instead of visiting every pair through a row-major mask (Shard.set_sparse_index;
+# OUTPUT["sparseForm"][0] reads 1, OUTPUT["sparseIterations"] counts such iterations whatever the form).  No output ever
+# depends on it.  Off by default: the shapes of profiles/sparse_centres_ab.txt were run once, in a shortened series (every
+# pair wins: that call 1.4x to 3.6x faster), and the default goes on only once every pair of shapes 1-3 wins in two series.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
               slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True,
-              kppRagged=False, manyCentres=False)
+              kppRagged=False, manyCentres=False, sparseIndex=False)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -446,6 +453,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_tile_ragged(bool(o["tileRagged"]))
     shard.set_many_screen(bool(o["manyCentres"]))
     shard.set_kpp_ragged(bool(o["kppRagged"]))
+    shard.set_sparse_index(bool(o["sparseIndex"]))
     shard.set_far_bounds(bool(o["farBounds"]))
     shard.set_far_events(bool(o["farEvents"]))
     shard.set_sliced_sums(bool(o["slicedSums"]))
@@ -520,6 +528,7 @@ def kmeans_sparsified(X, K, **options):
 
     best = dict(obj=np.inf)
     distances = None
+    OUTPUT["sparseForm"] = (0, 0, 0, 0)       # (not a reference field: LloydEngine.last_sparse_form() of the run's last sparse-centres iteration)
     K_start = K                               # K of a 'Start' matrix
     for trial in range(Replicates):
         t1 = time.time()
@@ -571,13 +580,15 @@ def kmeans_sparsified(X, K, **options):
         csc_released = False
         dist_t = eng.mind                     # min-distances of the latest iteration (survives a 'drop' re-build of eng)
         mind_pending, eng_used, centers_used = False, eng, centers
-        fused_iters = event_iters = 0
+        fused_iters = event_iters = sparse_iters = 0
         screened0 = eng.last_screen_points()[1]   # (the context's running total: this replicate's share is the difference)
         for its in range(1, int(o["MaxIter"]) + 1):
             # [assignments,distances] = findClusters(X,centers) (:420) and the per-cluster sums of :430-453
             host_res = None
             if mask_t is not None:
                 eng.assign_sparse_step(centers, mask_t)                          # findClusterAssignments.m:63-75
+                sparse_iters += 1
+                OUTPUT["sparseForm"] = eng.last_sparse_form()   # (a stored value of the call just queued: no synchronisation)
                 eng.accumulate_step()
             else:
                 # dense centres: the fused call -- the library's fast path (certified screen, carried bounds) when the
@@ -701,6 +712,8 @@ def kmeans_sparsified(X, K, **options):
         OUTPUT.setdefault("fusedIterations", np.zeros(Replicates, int))[trial] = fused_iters
         # ... and how many of them moved their sums by events instead of a full accumulation pass
         OUTPUT.setdefault("eventIterations", np.zeros(Replicates, int))[trial] = event_iters
+        # ... and how many iterations still had sparse centres (findClusterAssignments.m:63-75; OUTPUT["sparseForm"]: their kernel)
+        OUTPUT.setdefault("sparseIterations", np.zeros(Replicates, int))[trial] = sparse_iters
         # ... and how many points their screens evaluated in all: fusedIterations x n unless carried bounds settled some
         OUTPUT.setdefault("screenedPoints", np.zeros(Replicates, np.int64))[trial] = eng.last_screen_points()[1] - screened0
         OUTPUT.setdefault("lastPath", np.zeros(Replicates, int))[trial] = last_path
