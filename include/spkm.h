@@ -273,6 +273,23 @@ int spkm_shard_set_tile_ragged(spkm_shard *s, int on);
  * no other opt-in implies it.  Turning it on or off forgets the shard's policy state, like spkm_shard_reset_policy.
  * SPKM_MANY_SCREEN=1 opts every shard of a context in (read with the other switches: spkm_ctx_reload_switches). */
 int spkm_shard_set_many_screen(spkm_shard *s, int on);
+/* Narrow-tile and long-column shards on the far pipeline (on != 0; default off).  A FIXED-STRIDE shard whose fused call takes
+ * an LDS-tile screen other than the 4-lanes-per-point one -- rows past the 32-centroid tile on the narrow tiles of
+ * spkm_shard_set_wide_screen (1280 <= p <= 5118 with 160 KB), or columns of more than 64 entries (p <= 1278) -- runs, behind
+ * that screen, the exact pass over every point and a full accumulation in every call, bounds carried
+ * (spkm_shard_set_wide_bounds) or not.  A shard that opts in here runs the same tile screen, on the same tile width, in front
+ * of the far screen's pipeline instead: the certificate and the exact list cover the unsettled points only, the sums come from
+ * spkm_accumulate_dev's kernels, and carried bounds and incremental sums follow the shard's spkm_shard_set_far_bounds /
+ * spkm_shard_set_far_events opt-ins as on a far shard (spkm_shard_set_wide_bounds is not read on this route).  Needs a screen
+ * today (every condition of that screen: fixed stride, 48 entries of slack, K >= 2, K > 16 on the 32-centroid tile, the
+ * narrow-tile opt-in where only a narrow tile fits), at most 32 centroid tiles -- K <= 1024 / 512 / 256 at 32 / 16 / 8 centroids
+ * per tile; past that the dispatch is unchanged -- and 4 K bytes of LDS for the cluster sizes.  The 4-lanes-per-point screen
+ * (columns of up to 64 entries at p <= 1278), ragged shards and far shards never hear the setting.  spkm_last_path_info
+ * reports 1 and spkm_last_screen_tile the same (width, tiles) as without it; spkm_last_tile_far tells the routes apart.  Every
+ * output is what the all-exact kernels give, sums to rounding.  A switch of its own: no other opt-in implies it.  Turning it on
+ * or off forgets the shard's policy state, bounds and kept sums, like spkm_shard_reset_policy.  SPKM_TILE_FAR=1 opts every
+ * shard of a context in (read with the other switches: spkm_ctx_reload_switches). */
+int spkm_shard_set_tile_far(spkm_shard *s, int on);
 /* Ragged shards on the staged k-means++ round (on != 0; default off).  spkm_kpp_seed_dev on a RAGGED shard runs the generic
  * round kernel: one lane per point walks its column in global memory and gathers every table row from L2.  A shard that
  * opts in here is seeded by a form of the staged kernel that reads each point's column bounds from jc: the table of the RB
@@ -470,6 +487,10 @@ int spkm_last_screen_passes(spkm_ctx *ctx, int64_t info[2]);
  * wave, info[2] = waves per workgroup, info[3] = bytes of LDS per workgroup (zeros for form 0: csrc/policy.h,
  * spkm_sparse_plan); all zeros after spkm_assign_dev or spkm_assign_accumulate_dev, and before any call. */
 int spkm_last_sparse_form(spkm_ctx *ctx, int64_t info[4]);
+/* The tile-far route of the last fused call (spkm_shard_set_tile_far; stored values; does not block): info[0] = 1 if the call
+ * ran a fixed-stride shard's LDS-tile screen in front of the far screen's pipeline, info[1] = its centroids per tile (32, 16,
+ * 8); (0, 0) after any other call. */
+int spkm_last_tile_far(spkm_ctx *ctx, int64_t info[2]);
 /* How many points the screen of the last fused call evaluated (any screen kernel): info[0] = n for a call over all points,
  * the length of the list for a call that skipped on its carried bounds (points; 16 per listed step for a step list), 0
  * when the call took no screen; info[1] = the running total over the context.  Blocks on the stream. */

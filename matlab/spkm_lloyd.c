@@ -164,6 +164,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         check(spkm_shard_set_far_events(g_shard, 1));            /* ... and incremental sums there for lazy calls with few movers, as in the Python driver (profiles/far_events_ab.txt) */
         check(spkm_shard_set_far_ragged(g_shard, 0));            /* a ragged shard on the far screen: off, as in the Python driver, until profiles/far_ragged_ab.txt holds a measurement */
         check(spkm_shard_set_tile_ragged(g_shard, 0));           /* a ragged shard on the LDS-tile screen: off, as in the Python driver (profiles/tile_ragged_ab.txt: one winning series, the default waits for a second) */
+        check(spkm_shard_set_tile_far(g_shard, 0));              /* narrow-tile and long-column shards on the far pipeline: off, as in the Python driver (profiles/tile_far_ab.txt: the default waits for two winning series) */
         g_p = mxGetM(X);
         g_n = mxGetN(X);
         return;
@@ -225,6 +226,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         check(spkm_shard_set_far_events(g_shard, 1));            /* ... and incremental sums there for lazy calls with few movers, as in the Python driver (profiles/far_events_ab.txt) */
         check(spkm_shard_set_far_ragged(g_shard, 0));            /* a ragged shard on the far screen: off, as in the Python driver, until profiles/far_ragged_ab.txt holds a measurement */
         check(spkm_shard_set_tile_ragged(g_shard, 0));           /* a ragged shard on the LDS-tile screen: off, as in the Python driver (profiles/tile_ragged_ab.txt: one winning series, the default waits for a second) */
+        check(spkm_shard_set_tile_far(g_shard, 0));              /* narrow-tile and long-column shards on the far pipeline: off, as in the Python driver (profiles/tile_far_ab.txt: the default waits for two winning series) */
         hipFree(d_chunk);
         hipFree(d_sign);
         g_p = p2; g_n = n; g_s = s;

@@ -147,12 +147,14 @@ def lib():
     L.spkm_shard_set_far_ragged.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_tile_ragged.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_many_screen.argtypes = [_vp, C.c_int]
+    L.spkm_shard_set_tile_far.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_kpp_ragged.argtypes = [_vp, C.c_int]
     L.spkm_shard_set_sparse_index.argtypes = [_vp, C.c_int]
     L.spkm_last_sparse_form.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_shard_set_sliced_sums.argtypes = [_vp, C.c_int]
     L.spkm_last_screen_tile.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_screen_passes.argtypes = [_vp, C.POINTER(C.c_int64)]
+    L.spkm_last_tile_far.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_screen_points.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_last_mover_steps.argtypes = [_vp, C.POINTER(C.c_uint64)]
     L.spkm_last_mover_steps2.argtypes = [_vp, C.POINTER(C.c_uint64)]

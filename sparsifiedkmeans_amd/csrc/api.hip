@@ -45,6 +45,7 @@ static spkm_switches read_switches()
     w.far_ragged = on("SPKM_FAR_RAGGED");
     w.tile_ragged = on("SPKM_TILE_RAGGED");
     w.many_screen = on("SPKM_MANY_SCREEN");
+    w.tile_far = on("SPKM_TILE_FAR");
     w.kpp_ragged = on("SPKM_KPP_RAGGED");
     w.sparse_index = on("SPKM_SPARSE_INDEX");
     w.sliced_sums = on("SPKM_SLICED_SUMS");
@@ -471,6 +472,13 @@ extern "C" int spkm_shard_set_many_screen(spkm_shard* s, int on)
         if (rc) return rc;
     }
     return spkm_shard_reset_policy(s); // (what the policy learned belongs to the other path)
+}
+
+extern "C" int spkm_shard_set_tile_far(spkm_shard* s, int on)
+{
+    if (!s) return SPKM_ERR_NULL_ARG;
+    s->tile_far = on != 0;
+    return spkm_shard_reset_policy(s); // (the policy state, the bounds and the kept sums belong to the other route)
 }
 
 // (no policy state to forget: the seeding keeps nothing on the shard between calls)

@@ -62,6 +62,7 @@ struct spkm_switches {
     bool far_ragged = false;      // SPKM_FAR_RAGGED: every RAGGED shard of the context that no exact LDS tile serves either takes the far screen in its ragged form where it (or the context) opted in to the far screen, as if opted in (spkm_shard_set_far_ragged)
     bool tile_ragged = false;     // SPKM_TILE_RAGGED: every RAGGED shard of the context at a p with a 32-centroid f32 tile takes the RAGGED form of k_screen_wide on an LDS tile instead of k_assign_tile over every point, as if opted in (spkm_shard_set_tile_ragged); a switch of its own
     bool many_screen = false;     // SPKM_MANY_SCREEN: every shard of the context with more than 32 centroid tiles (K > 1024) at a p with a 32-centroid f32 tile takes the folded passes of k_screen_wide (policy.h, spkm_many_screen) in front of the far screen's pipeline, as if opted in (spkm_shard_set_many_screen); a switch of its own
+    bool tile_far = false;        // SPKM_TILE_FAR: every FIXED-STRIDE shard of the context whose fused call takes a non-quad LDS-tile screen on at most 32 tiles (policy.h, spkm_tile_far_screen) runs that screen in front of the far screen's pipeline instead of the exact pass over every point, as if opted in (spkm_shard_set_tile_far); a switch of its own
     bool kpp_ragged = false;      // SPKM_KPP_RAGGED: spkm_kpp_seed_dev on every RAGGED shard of the context whose longest column has a staged table takes k_kpp_round_ragged (the table in LDS, staged entries) instead of k_kpp_round_generic, as if opted in (spkm_shard_set_kpp_ragged); a switch of its own
     bool sparse_index = false;    // SPKM_SPARSE_INDEX: spkm_assign_sparse_centers_dev on every shard of the context walks a row index of the centres (k_assign_sparse_indexed; policy.h, spkm_sparse_plan) instead of k_assign_sparse_centers, as if opted in (spkm_shard_set_sparse_index); a switch of its own
     bool sliced_sums = false;     // SPKM_SLICED_SUMS: spkm_accumulate_dev on every shard of the context keeps its sums in LDS past the 64-KB slab too, a row slice at a time (k_accumulate_sliced; policy.h, spkm_accumulate_form), as if opted in (spkm_shard_set_sliced_sums)
@@ -78,6 +79,7 @@ struct spkm_screen_report {
     int path = 0;                 // 0 = exact tiled/generic, 1 = f32 screen + exact confirmation
     int kt = 0, tiles = 0;        // centroids per tile and tiles of the screen (the far screen: per plane, and planes)
     int passes = 0, planes = 0;   // the many-centres screen (policy.h, spkm_many_screen): its passes and the result planes they fold into; 0, 0: any other call
+    bool tile_far = false;        // the tile-far route (policy.h, spkm_tile_far_screen): a fixed-stride shard's non-quad LDS-tile screen in front of run_far's stages
     int pl_last = 0;              // the plan: centroid pairs per lane of its last tile (5: carried)
     int rounds_all = 0, rounds = 0; // rounds for all centroids / total rounds of a 4-lanes-per-point screen
     int mode = 0;                 // 0 plain screen, 1 two-phase, 2 hinted two-phase
@@ -166,6 +168,7 @@ struct spkm_shard {
     bool far_ragged = false; // spkm_shard_set_far_ragged: a RAGGED shard (fixed_s = 0) that opted in to the far screen takes it, in k_screen_far's RAGGED form, where no exact LDS tile serves it either (policy.h, spkm_far_screen_ragged)
     bool tile_ragged = false; // spkm_shard_set_tile_ragged: a RAGGED shard (fixed_s = 0) at a p with a 32-centroid f32 tile takes k_screen_wide's RAGGED form there, in front of the far screen's pipeline (policy.h, spkm_tile_screen_ragged)
     bool many = false; // spkm_shard_set_many_screen: with more than 32 centroid tiles (K > 1024) at a p with a 32-centroid f32 tile this shard's fused calls take the folded passes of k_screen_wide (policy.h, spkm_many_screen)
+    bool tile_far = false; // spkm_shard_set_tile_far: a fixed-stride shard whose fused call takes a non-quad LDS-tile screen on at most 32 tiles runs it in front of the far screen's pipeline (policy.h, spkm_tile_far_screen)
     bool kpp_ragged = false; // spkm_shard_set_kpp_ragged: a RAGGED shard (fixed_s = 0) is seeded by k_kpp_round_ragged where its longest column has a staged table (policy.h, spkm_kpp_plan_ragged)
     bool sparse_index = false; // spkm_shard_set_sparse_index: spkm_assign_sparse_centers_dev on this shard walks a row index of the centres (policy.h, spkm_sparse_plan)
     int max_s = 0;           // the longest column: fixed_s on a fixed-stride shard; on a ragged one a reduction over jc, run once (ensure_max_s) ...

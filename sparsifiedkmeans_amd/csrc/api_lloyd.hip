@@ -1089,6 +1089,16 @@ extern "C" int spkm_last_sparse_form(spkm_ctx* ctx, int64_t info[4])
     return SPKM_OK;
 }
 
+// The last fused call's tile-far route (spkm_shard_set_tile_far): (1, its tile width) when the call ran a fixed-stride shard's
+// LDS-tile screen in front of the far screen's stages; (0, 0) after any other call.  Stored values; does not block.
+extern "C" int spkm_last_tile_far(spkm_ctx* ctx, int64_t info[2])
+{
+    if (!ctx || !info) return SPKM_ERR_NULL_ARG;
+    info[0] = ctx->last.tile_far ? 1 : 0;
+    info[1] = ctx->last.tile_far ? ctx->last.kt : 0;
+    return SPKM_OK;
+}
+
 // [0] = path of the last spkm_assign_accumulate_dev (0 exact tiles, 1 f32 screen + exact confirmation),
 // [1] = number of points the screen could not certify (evaluated exactly over all K).  Blocks on the stream.
 extern "C" int spkm_debug_shard_bounds(spkm_ctx* ctx, const spkm_shard* s, float* ub, double* lb, int32_t* lib_assign)

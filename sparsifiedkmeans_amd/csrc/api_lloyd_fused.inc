@@ -51,6 +51,14 @@ static int many_screen_passes(const spkm_ctx* ctx, const spkm_shard* s, int K)
     return spkm_many_screen((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
                             s->tile_ragged || ctx->sw.tile_ragged, s->many || ctx->sw.many_screen);
 }
+// ... and, asked after it and BEFORE the others: the tile width of the tile-far route (policy.h, spkm_tile_far_screen) -- a
+// fixed-stride shard whose fused call takes a non-quad LDS-tile screen, at most 32 tiles -- for a shard or a context that opted
+// in (spkm_shard_set_tile_far, SPKM_TILE_FAR=1): that screen in front of run_far's stages; 0: the dispatch above, untouched.
+static int tile_far_width(const spkm_ctx* ctx, const spkm_shard* s, int K)
+{
+    return spkm_tile_far_screen((long long)s->p, K, s->fixed_s, s->slack, s->nnz, ctx->lds_max, ctx->num_cus, ctx->sw.no_screen,
+                                s->wide || ctx->sw.wide_screen, s->tile_far || ctx->sw.tile_far);
+}
 
 static_assert(spkm_movers == SPKM_MOVERS && spkm_movers == SCREEN_KT && spkm_mover_kmin == SPKM_MOVER_KMIN && spkm_mover_kmax == SPKM_MOVER_KMAX &&
               SPKM_MOVER_KMAX <= BOUNDS_KTAB, "the mover tile is one full screen tile; policy.h and layout.h agree on its limits");
@@ -61,11 +69,12 @@ static_assert(spkm_plan_kt == SCREEN_KT && spkm_plan_span == BOUNDS_SPAN && spkm
 
 // The kernels a call picks among at run time, by table: the instantiations that exist, each under its pointer type (launch.h);
 // null = no such kernel, which the caller answers with SPKM_ERR_UNSUPPORTED and never launches.  k_screen_wide by tile width
-// (8 / 16 / 32), LIST, RAGGED -- no <32, false, false>: k_screen_tile serves that case -- and k_screen_far by planes (1 / 2 / 4).
+// (8 / 16 / 32), LIST, RAGGED -- <32, false, false> is the tile-far route's (screen_tile): run_screen keeps k_screen_tile for that
+// case -- and k_screen_far by planes (1 / 2 / 4).
 template <typename IR> static screen_wide_fn<IR> pick_screen_wide(int kt, bool list, bool ragged)
 {
     static constexpr screen_wide_fn<IR> tab[2][2][3] = {
-        {{k_screen_wide<IR, 8>, k_screen_wide<IR, 16>, nullptr}, {k_screen_wide<IR, 8, true>, k_screen_wide<IR, 16, true>, k_screen_wide<IR, 32, true>}},
+        {{k_screen_wide<IR, 8>, k_screen_wide<IR, 16>, k_screen_wide<IR, 32>}, {k_screen_wide<IR, 8, true>, k_screen_wide<IR, 16, true>, k_screen_wide<IR, 32, true>}},
         {{k_screen_wide<IR, 8, false, true>, k_screen_wide<IR, 16, false, true>, k_screen_wide<IR, 32, false, true>},
          {k_screen_wide<IR, 8, true, true>, k_screen_wide<IR, 16, true, true>, k_screen_wide<IR, 32, true, true>}}};
     return (kt == 8 || kt == 16 || kt == 32) ? tab[ragged][list][kt / 16] : nullptr;
@@ -539,13 +548,16 @@ struct screen_call : spkm_call_in {
     // The LDS-tile screen of a RAGGED shard (screen_wide.hip, the RAGGED forms of k_screen_wide; policy.h,
     // spkm_tile_screen_ragged) in the far screen's place: the tiles of kt = 8 / 16 / 32 centroids by k_prep_tiles_wide, then a
     // workgroup per blockmap entry over every point, or (a shard that skips on its bounds) the LIST form over the points of todo[].
-    template <typename IR> int screen_tile_ragged()
+    // A FIXED-STRIDE shard on the tile-far route (policy.h, spkm_tile_far_screen) takes the same stage with the fixed-stride
+    // forms of its width: the stride in jc's place, several tiles at kt = 8 / 16 as well (plane g = tile g, as run_screen has them).
+    template <typename IR> int screen_tile()
     {
         zero_flush();
         prep_tiles_wide();
         report_screen(0, 0);
-        return launch_tiles<IR>(pick_screen_wide<IR>(kt, pl.skip_enabled, true), (size_t)(p + 1) * kt * 4 + 16, 0, todo_list(),
-                                (const unsigned*)ctx->nlist.p, (const long long*)sm->jc);
+        rep.tile_far = !ragged();
+        return launch_tiles<IR>(pick_screen_wide<IR>(kt, pl.skip_enabled, ragged()), (size_t)(p + 1) * kt * 4 + 16, ragged() ? 0 : sm->fixed_s,
+                                todo_list(), (const unsigned*)ctx->nlist.p, ragged() ? (const long long*)sm->jc : (const long long*)nullptr);
     }
     // The MANY-CENTRES screen (screen_wide.hip, the FOLD forms; policy.h, spkm_many_screen) in the far screen's place: ALL the
     // tiles of 32 centroids by k_prep_tiles_wide, then one launch per pass of spkm_many_slots tiles over the block map of
@@ -974,9 +986,11 @@ static int run_screen(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d
 // and the certify stage leaves every screened point's bounds behind (policy.h: the far case of the carry_bounds branch);
 // without the opt-in every call screens every point and leaves nothing behind for the next one.
 // tile: a RAGGED shard at a p with a 32-centroid LDS tile (spkm_shard_set_tile_ragged; kp = the tile width, 8 / 16 / 32): the
-// same stages with screen_tile_ragged in screen_far's place -- buffers() builds the blockmap and the plain f32 copy for any
+// same stages with screen_tile in screen_far's place -- buffers() builds the blockmap and the plain f32 copy for any
 // shard that is not on the 4-lanes-per-point screen, the plan is the far case as it stands (policy.h), and the accumulation
-// behind it is form 1 (k_accumulate_sorted) at these p.
+// behind it is form 1 (k_accumulate_sorted) at these p.  ... or a FIXED-STRIDE shard on the tile-far route
+// (spkm_shard_set_tile_far; policy.h spkm_tile_far_screen; kp = 32 / 16 / 8, at most 32 tiles): the same stage with the
+// fixed-stride forms, p <= 5118 -- still the one-slab accumulation, and one slab for the sorted events.
 // many: the passes of the many-centres screen (spkm_shard_set_many_screen; kp = 32, policy.h spkm_many_screen) -- the same stages
 // again with screen_many in screen_far's place, 32 result planes whatever K is, and a block map of 32 tiles.
 template <typename IR>
@@ -1007,7 +1021,7 @@ static int run_far(spkm_ctx* ctx, const spkm_shard* s, int K, const double* d_ce
     const spkm_acc_plan ap = spkm_accumulate_form((long long)s->p, ctx->lds_max, s->sliced || ctx->sw.sliced_sums, ctx->sw.x_slab_rows);
     if (c.pl.ev_path && !c.pl.direct && ap.form == 2) c.pl.lose_events();
     if ((rc = c.resources()) || (rc = c.bounds()) ||
-        (rc = many > 0 ? c.screen_many<IR>() : (tile ? c.screen_tile_ragged<IR>() : c.screen_far<IR>())) ||
+        (rc = many > 0 ? c.screen_many<IR>() : (tile ? c.screen_tile<IR>() : c.screen_far<IR>())) ||
         (rc = c.certify<IR>()))
         return rc;
     bool no_stats = c.pl.ev_path; // (an event call is a lazy call without distances: NaN statistics)
@@ -1062,10 +1076,13 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
     const bool cooling = ch.exact;
     // (the many-centres screen is asked first: where it answers, no other screen is; where it does not, the dispatch below is untouched)
     const int many = many_screen_passes(ctx, s, (int)K64);
-    const int kt = many > 0 ? 0 : screen_width(ctx, s, (int)K64);
-    int kp = many > 0 ? SCREEN_KT : (kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64)); // (the far screen: only where no tile serves, policy.h)
+    // (then the tile-far route: a fixed-stride shard's non-quad LDS-tile screen in front of run_far's pipeline, where it opted in)
+    const int tile_far = many > 0 ? 0 : tile_far_width(ctx, s, (int)K64);
+    const int kt = (many > 0 || tile_far > 0) ? 0 : screen_width(ctx, s, (int)K64);
+    int kp = many > 0 ? SCREEN_KT : (tile_far > 0 ? tile_far : (kt > 0 ? 0 : far_screen_width(ctx, s, (int)K64))); // (the far screen: only where no tile serves, policy.h)
     // (a ragged shard that both turned away: the RAGGED tile screen in front of run_far's pipeline, where it opted in)
-    const bool tile_ragged = many == 0 && kt == 0 && kp == 0 && (kp = tile_ragged_width(ctx, s, (int)K64)) > 0;
+    const bool tile_ragged = many == 0 && tile_far == 0 && kt == 0 && kp == 0 && (kp = tile_ragged_width(ctx, s, (int)K64)) > 0;
+    const bool tile = tile_ragged || tile_far > 0;
     if (s->n > 0 && !cooling && (kt > 0 || kp > 0)) {
         ctx->ev_valid = false;
         // Hinted two-phase screen: when the unconditional two-phase form is not chosen and hints are not paused, the
@@ -1075,8 +1092,8 @@ extern "C" int spkm_assign_accumulate_dev(spkm_ctx* ctx, const spkm_shard* s, ui
         const bool want_hint = ch.want_hint;
         spkm_screen_report rep;
         if (kp > 0)
-            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged, many)
-                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile_ragged, many);
+            rc = (s->ir_bits == 16) ? run_far<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile, many)
+                                    : run_far<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, d_stats, d_nk_u64, kp, &rep, tile, many);
         else
             rc = (s->ir_bits == 16) ? run_screen<unsigned short>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep)
                                     : run_screen<unsigned int>(ctx, s, (int)K64, d_centers, gamma, d_assign, d_mind, d_reduce, prune_a, want_hint, d_stats, d_nk_u64, kt, &rep);

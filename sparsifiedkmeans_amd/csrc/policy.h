@@ -420,6 +420,29 @@ inline int spkm_many_screen(long long p, int K, int fixed_s, unsigned long long 
     if (fixed_s <= 0 && !tile_ragged) return 0;
     return (tiles + spkm_many_slots - 1) / spkm_many_slots;
 }
+// TILE-FAR: the fixed-stride shards that spkm_screen_width sends to a NON-QUAD LDS-tile screen -- rows past the 32-centroid tile
+// on the narrow tiles of k_screen_wide (kt = 16 / 8), and columns of more than 64 entries at kt = 32 (k_screen_tile, or the LIST
+// form of k_screen_wide once bounds are carried) -- for a shard or a context that opted in (tile_far: spkm_shard_set_tile_far,
+// SPKM_TILE_FAR=1; a switch of its own).  run_screen's non-quad branch runs the exact pass and a full accumulation over every
+// point in every call; with the opt-in the same tile screen stands in front of the far screen's pipeline instead (run_far:
+// point-mode bounds that erode, certificate, exact list, k_hist, the any-p sums or the events), as the ragged tile screen and
+// the many-centres screen do.  Returns the tile width kt = spkm_screen_width's answer, or 0: not opted in; SPKM_NO_SCREEN; no
+// screen today (spkm_screen_width == 0: a ragged shard, no narrow-tile opt-in where only a narrow tile fits, K <= 16 at kt = 32,
+// the phase-2 formula, ...); the 4-lanes-per-point screen, which keeps everything it has; more than spkm_many_slots tiles --
+// K > 1024 / 512 / 256 at kt = 32 / 16 / 8: the certificate reads every plane per point and the scratch is 3 planes x tiles x n
+// x 4 B, the reason the many-centres form folds to 32 (past the cap the dispatch is today's); K counters of k_hist beyond the
+// LDS, the cap of the other far forms.  Asked by spkm_assign_accumulate_dev AFTER the many-centres screen and before today's
+// dispatch; no other plan function changes its answer.  The policy's cool-down is the caller's to add.
+inline int spkm_tile_far_screen(long long p, int K, int fixed_s, unsigned long long slack, unsigned long long nnz, size_t lds_max,
+                                int num_cus, bool no_screen, bool wide, bool tile_far)
+{
+    if (!tile_far || no_screen) return 0;
+    const int kt = spkm_screen_width(p, K, fixed_s, slack, nnz, lds_max, num_cus, no_screen, wide);
+    if (kt == 0 || spkm_screen_quad(kt, fixed_s)) return 0;
+    if ((K + kt - 1) / kt > spkm_many_slots) return 0;
+    if ((unsigned long long)K * 4ull > (unsigned long long)lds_max) return 0; // (k_hist, as above)
+    return kt;
+}
 // Which kernel spkm_accumulate_dev runs (update.hip), from the rows, the device's LDS and the opt-in alone -- the form that
 // spkm_last_assign_tile reports in info[4]:
 //  1  k_accumulate_sorted: a cluster's sums and counts, 12 B per row, in one LDS slab of at most 64 KB (p <= 5461) --
@@ -715,7 +738,9 @@ inline void spkm_plan_call(spkm_call_plan& pl, const spkm_call_in& in, spkm_poli
             // gives it a fresh one -- the looseness of a bound costs a screened point, never a wrong answer, and mends itself.
             // A RAGGED far shard (fixed_s = 0, spkm_far_screen_ragged) takes this branch and the events below as they are:
             // nothing here depends on the stride (the point-mode test reads bounds, the events name points).  So does a
-            // ragged shard on an LDS tile (spkm_tile_screen_ragged): its screen stage differs, its plan does not.
+            // ragged shard on an LDS tile (spkm_tile_screen_ragged): its screen stage differs, its plan does not.  And so does a
+            // FIXED-STRIDE shard on the tile-far route (spkm_tile_far_screen: the narrow tiles, or columns of more than 64
+            // entries, in front of run_far's stages): kt = 32 / 16 / 8, up to 32 tiles, every one a result plane.
             pl.erode = pl.drift;
             pl.lazy_ub = true;
             // INCREMENTAL SUMS at these widths (spkm_shard_set_far_events; a plan made without the flag is the plan above in

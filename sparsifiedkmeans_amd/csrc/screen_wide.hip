@@ -6,7 +6,10 @@
 // (a shard that carries bounds, spkm_shard_set_wide_bounds: the points that k_bounds_steps could not settle) screens the
 // points of todo[] and writes its result planes BY LIST SLOT, as k_screen_quad's point lists do.  The LIST form also
 // exists at KT = 32, 8 lanes per point, for the columns of more than 64 entries that the 4-lanes-per-point kernel does not
-// take: a call over all their points stays with k_screen_tile.  A fourth template argument, RAGGED, gives every width a form
+// take: a call over all their points stays with k_screen_tile on that route.  The PLAIN form at KT = 32 exists too, for the
+// tile-far route (spkm_shard_set_tile_far; policy.h, spkm_tile_far_screen: these same shards -- narrow tiles, or long columns
+// -- with this kernel in front of the far screen's stages instead of the exact pass over every point), whose call over all
+// points has no k_screen_tile to go to: the body below at <IR, 32, false, false>, which already ran under FOLD.  A fourth template argument, RAGGED, gives every width a form
 // for shards whose columns have different lengths (below, in front of the kernel).
 //
 // Arithmetic, as the proof assumes: t = fl32(x~ + T) with T = -fl32(c), acc = fmaf(t, t, acc), one accumulator per
@@ -98,6 +101,8 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // several even for a short list (k_screen_quad sizes chunk_v the same way).  Entries come from the same plain copy.
 // Resources (-Rpass-analysis=kernel-resource-usage, 16- / 32-bit row ids): plain <16> 100 / 96 and <8> 72 / 72 VGPRs, as
 // before the LIST form existed; LIST <32> 98 / 98, <16> 100 / 96, <8> 72 / 72 VGPRs; 65 / 60 SGPRs and no scratch in all.
+// Plain <32> (the tile-far route): 98 / 98 VGPRs, 65 / 60 SGPRs, no scratch, 4 waves per SIMD by registers -- its LIST twin's
+// numbers; every instantiation that existed before it keeps its own (compared kernel by kernel over the unit).
 // LDS banks.  A ds_read_b128 is served in four groups of 16 lanes, bank = (address / 4) % 64.  The LG lanes of a point
 // read the 16 * LG contiguous bytes of ONE row, so a 16-lane group holds 16 / LG points (2 at KT = 32, 4 at 16, 8 at 8) on
 // rows the DATA chooses: a 256-byte bank line holds 256 / (4 KT) rows (2 / 4 / 8), and two points of a group collide when
@@ -110,7 +115,7 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // (a broadcast).
 //
 // RAGGED (fourth template argument; a ragged shard at a p with a 32-centroid tile that opted in: spkm_shard_set_tile_ragged,
-// policy.h spkm_tile_screen_ragged; KT = 8, 16 and 32, plain and LIST -- the plain form at KT = 32 exists for RAGGED only):
+// policy.h spkm_tile_screen_ragged; KT = 8, 16 and 32, plain and LIST):
 // point pt owns entries [jc[pt], jc[pt + 1]) of ir / xval instead of [pt s, (pt + 1) s); fixed_s is not read.  The
 // arithmetic, the entry order, the zero slot past a column's own end, the tie rule and the outputs are the ones above, and
 // every ragged statement sits behind `if constexpr (RAGGED)`: the fixed-stride instantiations compile to what they were.
@@ -137,8 +142,7 @@ __device__ __forceinline__ void wide_entry(const char* __restrict__ tile, int xb
 // CU, 4 waves per SIMD, anyway.  (Fixed stride, for comparison: <32> LIST 98 / 98, <16> 100 / 96, <8> 72 / 72, 65 / 60 SGPRs.)
 //
 // FOLD (fifth template argument of the body, KT = 32 only; MANY CENTRES: more than 32 tiles, K > 1024, on a shard that opted in
-// -- spkm_shard_set_many_screen, policy.h spkm_many_screen; plain and LIST, fixed stride and RAGGED, the plain fixed-stride
-// <32> existing for FOLD only).  The tiles are taken in PASSES of 32, one launch per pass on the library's stream, and every
+// -- spkm_shard_set_many_screen, policy.h spkm_many_screen; plain and LIST, fixed stride and RAGGED).  The tiles are taken in PASSES of 32, one launch per pass on the library's stream, and every
 // pass is folded into the same 32 result planes: a workgroup whose block-map tile is t loads tile g = tile0 + t (tile0: the
 // pass's first tile; past the last tile it returns before the load), runs the rounds above on it -- kfirst and the k >= K
 // mask are g's -- and writes PLANE t.  Scratch is 3 x 32 x n x 4 B and the certificate reads 32 planes, whatever K is.
@@ -167,7 +171,7 @@ __device__ __forceinline__ void screen_wide_body(
     float* __restrict__ scr_m2, int* __restrict__ scr_k, const int* __restrict__ todo, const unsigned* __restrict__ counters,
     const long long* __restrict__ jc, int tile0, int fold)
 {
-    static_assert(KT == 16 || KT == 8 || (KT == 32 && (LIST || RAGGED || FOLD)), "tiles of 16 or 8 centroids; 32 for lists, ragged shards and folded passes only");
+    static_assert(KT == 32 || KT == 16 || KT == 8, "tiles of 32, 16 or 8 centroids");
     static_assert(!FOLD || KT == 32, "passes are folded on the 32-centroid tile only");
     constexpr float BLANK_M2 = 0x1.fffffep+127f; // an empty column's runner-up: the largest finite f32 (the header)
     constexpr int LG = KT / 4, PPW = 64 / LG, ROWB = KT * 4, UN = 4;

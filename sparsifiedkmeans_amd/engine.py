@@ -157,6 +157,17 @@ class Shard:
         reset_policy()."""
         _lib.check(_lib.lib().spkm_shard_set_many_screen(self.handle, 1 if on else 0), "spkm_shard_set_many_screen")
 
+    def set_tile_far(self, on: bool = True):
+        """Let this FIXED-STRIDE shard's fused calls that take a non-quad LDS-tile screen -- the narrow tiles of
+        set_wide_screen() at 1280 <= p <= 5118, or columns of more than 64 entries at p <= 1278 (160 KB of LDS) -- with at
+        most 32 centroid tiles (K <= 1024 / 512 / 256 at 32 / 16 / 8 centroids per tile) run that screen in front of the far
+        screen's pipeline instead of the exact pass and a full accumulation over every point in every call
+        (spkm_shard_set_tile_far; off by default at the C interface; a switch of its own).  set_far_bounds() and
+        set_far_events() apply to it as to a far shard; set_wide_bounds() does not.  Outputs never depend on it but for the
+        sums' rounding; LloydEngine.last_tile_far() reads back what a call did.  The shard's policy state, bounds and kept sums
+        are forgotten as by reset_policy()."""
+        _lib.check(_lib.lib().spkm_shard_set_tile_far(self.handle, 1 if on else 0), "spkm_shard_set_tile_far")
+
     def set_kpp_ragged(self, on: bool = True):
         """Let ``kpp_seed`` on this shard, when it is RAGGED (columns of different lengths: a sample whose exact zeros were
         dropped), run the staged round kernel in the form that reads each point's column bounds -- the newest centres'
@@ -505,6 +516,13 @@ class LloydEngine:
         a = (C.c_int64 * 4)()
         _lib.check(_lib.lib().spkm_last_sparse_form(self.ctx.handle, a), "spkm_last_sparse_form")
         return int(a[0]), int(a[1]), int(a[2]), int(a[3])
+
+    def last_tile_far(self) -> tuple[int, int]:
+        """(1 if the last fused call ran the tile-far route of set_tile_far(), its centroids per tile: 32 / 16 / 8) -- (0, 0)
+        after any other call -- spkm_last_tile_far.  Stored values: does not block."""
+        a = (C.c_int64 * 2)()
+        _lib.check(_lib.lib().spkm_last_tile_far(self.ctx.handle, a))
+        return int(a[0]), int(a[1])
 
     def last_screen_points(self) -> tuple[int, int]:
         """(points the last fused call's screen evaluated: n for a call over all points, the length of its list when it

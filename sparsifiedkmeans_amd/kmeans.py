@@ -80,6 +80,12 @@ _DEFAULTS = dict(
 # planes, with the far path's bounds and events behind it (Shard.set_many_screen; farBounds and farEvents apply to it; a
 # ragged shard needs tileRagged as well).  Off by default: of the decision shapes of profiles/many_centres_ab.txt a shortened
 # series ran two (every pair wins, 14x to 29x), and the default goes on only once every pair of every shape wins.
+# tileFar: a FIXED-STRIDE shard whose iterations take a non-quad LDS-tile screen -- 1280 <= p2 <= 5118 on the narrow tiles (the
+# Hadamard widths 2048 and 4096), or columns of more than 64 entries at p2 <= 1278 (SparsityLevel 0.1 at d = 1024) -- with at
+# most 32 centroid tiles (K <= 1024 / 512 / 256 at 32 / 16 / 8 centroids per tile) runs that screen in front of the far path's
+# pipeline: farBounds and farEvents apply to it, and a settled iteration no longer streams the shard for an exact pass and a
+# full accumulation (Shard.set_tile_far; OUTPUT["tileFarIterations"] counts such iterations).  No output depends on it but the
+# sums' rounding.  Off by default: the shapes of profiles/tile_far_ab.txt decide by DESIGN section 6's rule, in two series.
 # slicedSums: past the 64-KB slab of the sorted accumulation (p2 > 5461: the same widths) the per-cluster sums and counts stay
 # in LDS, a slice of the rows at a time, instead of two global atomics per entry (Shard.set_sliced_sums); False: off.
 # seedTogether: the k-means++ starts of ALL replicates are drawn in one library call that shares each round's read of the
@@ -100,7 +106,7 @@ _DEFAULTS = dict(
 # pair wins: that call 1.4x to 3.6x faster), and the default goes on only once every pair of shapes 1-3 wins in two series.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
               slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True,
-              kppRagged=False, manyCentres=False, sparseIndex=False)
+              kppRagged=False, manyCentres=False, sparseIndex=False, tileFar=False)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -452,6 +458,7 @@ def kmeans_sparsified(X, K, **options):
     shard.set_far_ragged(bool(o["farRagged"]))
     shard.set_tile_ragged(bool(o["tileRagged"]))
     shard.set_many_screen(bool(o["manyCentres"]))
+    shard.set_tile_far(bool(o["tileFar"]))
     shard.set_kpp_ragged(bool(o["kppRagged"]))
     shard.set_sparse_index(bool(o["sparseIndex"]))
     shard.set_far_bounds(bool(o["farBounds"]))
@@ -580,7 +587,7 @@ def kmeans_sparsified(X, K, **options):
         csc_released = False
         dist_t = eng.mind                     # min-distances of the latest iteration (survives a 'drop' re-build of eng)
         mind_pending, eng_used, centers_used = False, eng, centers
-        fused_iters = event_iters = sparse_iters = 0
+        fused_iters = event_iters = sparse_iters = tile_far_iters = 0
         screened0 = eng.last_screen_points()[1]   # (the context's running total: this replicate's share is the difference)
         for its in range(1, int(o["MaxIter"]) + 1):
             # [assignments,distances] = findClusters(X,centers) (:420) and the per-cluster sums of :430-453
@@ -607,6 +614,7 @@ def kmeans_sparsified(X, K, **options):
                     eng.assign_accumulate_step(centers, want_mind=False)
                 fused_iters += 1
                 event_iters += 1 if eng.last_events_form()[0] else 0   # (a stored value of the call just queued: no synchronisation)
+                tile_far_iters += eng.last_tile_far()[0]               # (a stored value as well)
                 if Y is None and not csc_released and fused_iters == 1:
                     # the first fused call has built the library's record layout and screen copy: the CSC value / row
                     # arrays of the device-built shard can go (spkm_shard_release_csc; an entry point that needs them
@@ -712,6 +720,8 @@ def kmeans_sparsified(X, K, **options):
         OUTPUT.setdefault("fusedIterations", np.zeros(Replicates, int))[trial] = fused_iters
         # ... and how many of them moved their sums by events instead of a full accumulation pass
         OUTPUT.setdefault("eventIterations", np.zeros(Replicates, int))[trial] = event_iters
+        # ... and how many took the tile-far route (tileFar: a fixed-stride shard's LDS-tile screen in front of the far pipeline)
+        OUTPUT.setdefault("tileFarIterations", np.zeros(Replicates, int))[trial] = tile_far_iters
         # ... and how many iterations still had sparse centres (findClusterAssignments.m:63-75; OUTPUT["sparseForm"]: their kernel)
         OUTPUT.setdefault("sparseIterations", np.zeros(Replicates, int))[trial] = sparse_iters
         # ... and how many points their screens evaluated in all: fusedIterations x n unless carried bounds settled some
