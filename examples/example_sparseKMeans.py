@@ -40,6 +40,27 @@ def main():
     print(f"max |centre - planted centre| = {err:.3f} one pass, {err2:.3f} after the second pass over the unsampled "
           f"data (noise level 0.1); the dense re-assignment moves {int(np.sum(IDX2 != IDX))} of {n} points")
 
+    # Sparsify once, cluster many times: the ingest on its own, a sweep over K on the resident shard, and the shard kept
+    # on disk for the next process (a directory of .npy files and a meta.json: sparsifiedkmeans_amd/shardfile.py)
+    import tempfile
+
+    from sparsifiedkmeans_amd import SparsifiedData, sparsify
+
+    data = sparsify(X.T, SparsityLevel=0.05, rng=1)
+    for kk in (3, 5, 8):
+        t0 = time.time()
+        OUTk = kmeans_sparsified(data, kk, Replicates=5)[4]
+        print(f"K = {kk}: objective {OUTk['objectives'].min():.3e} in {time.time() - t0:.2f} s "
+              f"(the ingest, {OUTk['TimeToSketch']:.2f} s, was paid once)")
+    with tempfile.TemporaryDirectory() as d:
+        info = data.save(os.path.join(d, "shard"))
+        again = SparsifiedData.load(os.path.join(d, "shard"), rng=2)
+        IDXl = kmeans_sparsified(again, k, Replicates=5)[0]
+        print(f"saved {info['bytes'] / 1e6:.1f} MB in {info['seconds']:.2f} s; the loaded shard clusters {again.n} points "
+              f"into sizes {np.bincount(IDXl - 1, minlength=k).tolist()}")
+        again.close()
+    data.close()
+
 
 if __name__ == "__main__":
     main()

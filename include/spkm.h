@@ -344,6 +344,34 @@ int spkm_shard_info(const spkm_shard *s, uint64_t *p, uint64_t *n, uint64_t *nnz
  * SPKM_NO_REGROUP=1: A/B switch.  info[0] = 1 if the shard's own order differs from the caller's, info[1] = 1 if it was
  * regrouped since the last spkm_shard_reset_policy. */
 int spkm_shard_order_info(const spkm_shard *s, int64_t info[2]);
+/* Which layouts hold the shard's entries now: info[0] = 1 if the CSC value / row-id arrays are resident, info[1] = 1 if the
+ * record layout exists, info[2] = the fixed column length (0: ragged).  {0, 1, s}: records only -- a shard made by
+ * spkm_shard_create_rec_dev, or one whose arrays spkm_shard_release_csc let go and no CSC entry point brought back. */
+int spkm_shard_layout_info(const spkm_shard *s, int64_t info[3]);
+/* Columns [col0, col0 + ncols) of a resident shard as CSC on the device, in the caller's point order: what a save of the
+ * shard streams chunk by chunk.  d_jc: ncols + 1 int64, RELATIVE to the first exported entry (d_jc[0] = 0); d_ir: the
+ * shard's own row-id width (ir_bits must name it: spkm_shard_info); d_x: float64; cap = room in d_ir / d_x, in entries.
+ * Serves every state of a shard: CSC arrays resident, fixed stride or ragged (a rebased jc and two device-to-device
+ * copies), and records only, either id width (k_unpack_records_range reads records col0 .. and writes the chunk in whole
+ * 16-byte pieces where d_ir / d_x are 16-byte aligned, element by element where not).  A records-only shard STAYS records
+ * only: no array of the shard's size is allocated.  A shard the library regrouped (spkm_shard_order_info) exports the
+ * caller's order all the same: neither the records nor the CSC arrays ever move, and the call does not read the index map.
+ * d_ir == NULL AND d_x == NULL asks for d_jc alone: the column starts are written, cap is not looked at, SPKM_OK -- the way
+ * to learn a ragged range's entry count (d_jc[ncols]) before allocating for it; only one of the two NULL with entries to
+ * write is SPKM_ERR_NULL_ARG.
+ * SPKM_ERR_BAD_VALUE: col0 + ncols > n, ir_bits not the shard's, cap below the range's entry count (d_jc is written all
+ * the same).  Asynchronous on the context's stream; only where entries of a RAGGED shard are asked for is the range's entry
+ * count read back first, for the test of cap (that call blocks once; the d_jc-alone form never does). */
+int spkm_shard_export_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t col0, uint64_t ncols, int64_t *d_jc, void *d_ir,
+                          int ir_bits, double *d_x, uint64_t cap);
+/* The inverse for fixed-stride chunks: ncols columns of exactly s entries (1 <= s <= 64, s <= p; d_ir / d_x hold
+ * ncols * s entries in column order, ids of ir_bits = 16 or 32 bits) become ncols records at d_rec_out (16-byte aligned;
+ * ncols * spkm_record_bytes(s, ir_bits) bytes are written, nothing behind them): the layout of spkm_mix_sample_rec_dev,
+ * with the padding bytes behind a record's last row id written as ZEROS, so that two loads of one file give identical
+ * buffers.  A load assembles the buffer chunk by chunk and adopts it with spkm_shard_create_rec_dev (which asks for 256
+ * bytes of slack behind the last record).  Asynchronous on the context's stream. */
+int spkm_pack_records_dev(spkm_ctx *ctx, uint64_t p, uint64_t s, int ir_bits, uint64_t ncols, const void *d_ir,
+                          const double *d_x, void *d_rec_out);
 
 /* Length (in doubles) of the per-iteration reduce buffer for (p, K):
  *   [ sums p*K | counts p*K | nk K | obj2 1 ]      -- one SUM all-reduce covers all of it. */

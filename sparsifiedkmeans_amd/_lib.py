@@ -174,6 +174,9 @@ def lib():
     L.spkm_shard_set_lazy_stats.argtypes = [_vp, C.c_int]
     L.spkm_shard_release_csc.argtypes = [_vp, _vp]
     L.spkm_shard_get_column_host.argtypes = [_vp, _vp, _u64, _u64, _vp, _vp, C.POINTER(C.c_uint64)]
+    L.spkm_shard_layout_info.argtypes = [_vp, C.POINTER(C.c_int64)]
+    L.spkm_shard_export_dev.argtypes = [_vp, _vp, _u64, _u64, _vp, _vp, C.c_int, _vp, _u64]
+    L.spkm_pack_records_dev.argtypes = [_vp, _u64, _u64, C.c_int, _u64, _vp, _vp, _vp]
     L.spkm_kpp_update_dev.argtypes = [_vp, _u64, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_double)]
     L.spkm_kpp_draw_dev.argtypes = [_vp, _u64, _vp, C.c_double, C.POINTER(C.c_int64)]
     L.spkm_kpp_seed_dev.argtypes = [_vp, _vp, _u64, C.c_double, C.c_uint32, _vp, _vp, _vp, _vp, _vp]

@@ -9,6 +9,7 @@
 #include "screen_wide.hip"
 #include "screen_far.hip"
 #include "dense.hip"
+#include "shard_io.hip"
 
 #include "api_internal.h"
 #include "launch.h" // spkm_launch, the screen kernels' pointer types, k_screen_quad's dispatchers (screen_quad.hip)
@@ -1510,3 +1511,5 @@ extern "C" int spkm_dense_accumulate_src_dev(spkm_ctx* ctx, uint64_t p64, uint64
     default: return dense_accumulate_launch(ctx, p, n, (const unsigned short*)d_X, K, d_assign, d_sums, d_counts);
     }
 }
+
+#include "api_shard_io.inc" // spkm_shard_export_dev, spkm_pack_records_dev: a shard out as CSC chunks, chunks in as records

@@ -202,6 +202,51 @@ class Shard:
             _lib.check(st, "spkm_shard_get_column_host")
             return ir[: cnt.value].astype(np.int64), x[: cnt.value].copy()
 
+    def layout_info(self) -> tuple[bool, bool, int]:
+        """(the CSC value / row-id arrays are resident, the record layout exists, the fixed column length or 0 for a ragged
+        shard) -- spkm_shard_layout_info.  (False, True, s): records only, as after from_records() or release_csc()."""
+        a = (C.c_int64 * 3)()
+        _lib.check(_lib.lib().spkm_shard_layout_info(self.handle, a), "spkm_shard_layout_info")
+        return bool(a[0]), bool(a[1]), int(a[2])
+
+    def _ir_dtype(self):
+        return torch.int16 if self.ir_bits == 16 else torch.int32
+
+    def _export_jc(self, col0: int, ncols: int, jc: torch.Tensor) -> None:
+        """jc[0 .. ncols] <- the relative column starts of [col0, col0 + ncols), nothing else: spkm_shard_export_dev's form
+        without d_ir and d_x (asynchronous, nothing read back)"""
+        _lib.check(_lib.lib().spkm_shard_export_dev(self.ctx.handle, self.handle, int(col0), int(ncols), _p(jc), None,
+                                                    self.ir_bits, None, 0), "spkm_shard_export_dev")
+
+    def export_into(self, col0: int, ncols: int, jc: torch.Tensor, ir: torch.Tensor, x: torch.Tensor) -> None:
+        """spkm_shard_export_dev into the caller's device tensors (jc int64 [>= ncols + 1], ir of the shard's id width, x
+        float64, both with room for the range's entries); asynchronous on the context's stream."""
+        assert jc.is_cuda and jc.dtype == torch.int64 and jc.is_contiguous() and jc.numel() >= ncols + 1
+        assert ir.is_cuda and ir.is_contiguous() and ir.element_size() * 8 == self.ir_bits
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float64
+        _lib.check(_lib.lib().spkm_shard_export_dev(self.ctx.handle, self.handle, int(col0), int(ncols), _p(jc), _p(ir),
+                                                    self.ir_bits, _p(x), min(ir.numel(), x.numel())), "spkm_shard_export_dev")
+
+    def export(self, col0: int, ncols: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Columns [col0, col0 + ncols) as CSC device tensors (jc int64 [ncols + 1] relative to the first exported entry, ir
+        int16 -- the bits of uint16 ids -- or int32, x float64), in the order of the points, from whichever layout holds the
+        entries (spkm_shard_export_dev).  A records-only shard stays records-only: only the chunk is allocated."""
+        col0, ncols = int(col0), int(ncols)
+        if not (0 <= col0 and ncols >= 0 and col0 + ncols <= self.n):
+            raise _lib.SpkmError(_lib.ERR_BAD_VALUE, f"Shard.export: columns [{col0}, {col0 + ncols}) of {self.n}")
+        dev = torch.device("cuda", self.ctx.device)
+        jc = torch.empty(ncols + 1, dtype=torch.int64, device=dev)
+        s = self.layout_info()[2]
+        if s > 0 or self.nnz == 0:
+            cnt = ncols * s
+        else:
+            self._export_jc(col0, ncols, jc)                # (a ragged range: its entry count comes with its jc)
+            cnt = int(jc[-1].item())
+        ir = torch.empty(max(cnt, 1), dtype=self._ir_dtype(), device=dev)[:cnt]
+        x = torch.empty(max(cnt, 1), dtype=torch.float64, device=dev)[:cnt]
+        self.export_into(col0, ncols, jc, ir, x)
+        return jc, ir, x
+
     def release_csc(self) -> bool:
         """Let go of the CSC value / row-id arrays once the record layout and the screen copy exist
         (spkm_shard_release_csc): the tensors an adopted shard was built from are dropped here, so that their memory
@@ -813,6 +858,200 @@ def mix_sample_source_device(ctx: Context, src: torch.Tensor, src_kind: int, p2:
         return False
     _lib.check(rc, where)
     return True
+
+
+def pack_records_device(ctx: Context, p: int, s: int, ir: torch.Tensor, x: torch.Tensor, rec_out: torch.Tensor,
+                        ncols: int | None = None) -> None:
+    """``ncols`` fixed-stride columns of s <= 64 entries (ir int16 / int32 and x float64, ncols * s entries in column order)
+    -> ncols records at the start of ``rec_out`` (uint8; mix_sample_records_device's layout, padding bytes zeroed):
+    spkm_pack_records_dev, the inverse of Shard.export for such chunks."""
+    ncols = x.numel() // s if ncols is None else int(ncols)
+    bits = ir.element_size() * 8
+    assert x.dtype == torch.float64 and x.is_contiguous() and ir.is_contiguous() and x.is_cuda and ir.is_cuda
+    assert x.numel() >= ncols * s and ir.numel() >= ncols * s
+    assert rec_out.dtype == torch.uint8 and rec_out.is_contiguous() and rec_out.numel() >= ncols * record_bytes(s, bits)
+    _lib.check(_lib.lib().spkm_pack_records_dev(ctx.handle, int(p), int(s), bits, ncols, _p(ir), _p(x), _p(rec_out)),
+               "spkm_pack_records_dev")
+
+
+def _ctx_stream(ctx: Context, dev):
+    # the stream the library launches on (the context's), not whatever torch's current stream happens to be now
+    return torch.cuda.ExternalStream(ctx.stream, device=dev) if ctx.stream else torch.cuda.default_stream(dev)
+
+
+def _host_tensor(a: np.ndarray) -> torch.Tensor:
+    """a numpy array (a slice of a memory map, read-only or not) as a host tensor over the same memory"""
+    if a.flags.writeable:
+        return torch.from_numpy(a)
+    with warnings.catch_warnings():                 # (a read-only map: torch only warns about memory it may not write; it is only read)
+        warnings.simplefilter("ignore")
+        return torch.from_numpy(a)
+
+
+def _column_chunks(n: int, nnz: int, s: int, jc, entry_bytes: int, chunk_bytes: int):
+    """[(c0, c1, j0, j1)]: consecutive column ranges of at most ``chunk_bytes`` of entries each (one column at the least),
+    with their entry ranges; ``jc`` (host, n + 1) for a ragged shard"""
+    per = max(1, int(chunk_bytes) // entry_bytes)                 # entries per chunk
+    out, c0 = [], 0
+    while c0 < n:
+        if s > 0:
+            c1 = min(n, c0 + max(1, per // s))
+            j0, j1 = c0 * s, c1 * s
+        else:
+            j0 = int(jc[c0])
+            c1 = int(np.searchsorted(jc, j0 + per, side="right")) - 1
+            c1 = min(n, max(c1, c0 + 1))
+            j1 = int(jc[c1])
+        out.append((c0, c1, j0, j1))
+        c0 = c1
+    return out
+
+
+SHARD_CHUNK_BYTES = 256 << 20     # save_shard / load_shard: bytes of entries per chunk (two pinned buffers of this size)
+
+
+def save_shard(shard: Shard, path: str, meta: dict, sign=None, chunk_bytes: int = SHARD_CHUNK_BYTES) -> dict:
+    """Write ``shard`` to the directory ``path`` in the format of ``shardfile`` (version 1), chunk by chunk: columns are
+    exported on the context's stream (Shard.export_into: from the records or the CSC arrays, whichever the shard holds),
+    copied into one of two PINNED host buffers on a copy stream, and written into the memory-mapped .npy files from there --
+    the device-to-host copy of chunk c runs under the export of chunk c + 1 and the host's write of chunk c - 1.  ``meta``:
+    the settings shardfile.META_FIELDS names beyond the shard's own (p2, n, nnz, s, ir_bits come from the shard).  Returns
+    {"bytes": entry bytes written, "seconds": wall time}."""
+    from . import shardfile
+
+    t0 = time.time()
+    ctx, dev = shard.ctx, torch.device("cuda", shard.ctx.device)
+    s = shard.layout_info()[2] if shard.nnz else 0
+    n, nnz, irb = shard.n, shard.nnz, shard.ir_bits // 8
+    w = shardfile.ShardWriter(path, dict(meta, p2=int(shard.p), n=int(n), nnz=int(nnz), s=int(s), ir_bits=int(shard.ir_bits)),
+                              sign)
+    main = _ctx_stream(ctx, dev)
+    jc_h = None
+    if s == 0:
+        # a ragged shard's jc first (8 bytes per point): the chunks below are cut by it
+        step = max(1, int(chunk_bytes) // 8)
+        base = 0
+        jc_d = torch.empty(min(n, step) + 1, dtype=torch.int64, device=dev)
+        for c0 in range(0, max(n, 1), step):
+            m = min(step, n - c0)
+            shard._export_jc(c0, m, jc_d)
+            w.jc[c0:c0 + m + 1] = jc_d[:m + 1].cpu().numpy() + base
+            base = int(w.jc[c0 + m])
+        jc_h = w.jc
+    chunks = _column_chunks(n, nnz, s, jc_h, 8 + irb, chunk_bytes) if nnz else []
+    cap = max((j1 - j0 for _, _, j0, j1 in chunks), default=0)
+    mcols = max((c1 - c0 for c0, c1, _, _ in chunks), default=0)
+    if chunks:
+        copy = torch.cuda.Stream(device=dev)
+        d_x = [torch.empty(cap, dtype=torch.float64, device=dev) for _ in range(2)]
+        d_ir = [torch.empty(cap, dtype=shard._ir_dtype(), device=dev) for _ in range(2)]
+        d_jc = torch.empty(mcols + 1, dtype=torch.int64, device=dev)       # (the host has jc already)
+        h_x = [torch.empty(cap, dtype=torch.float64, pin_memory=True) for _ in range(2)]
+        h_ir = [torch.empty(cap, dtype=shard._ir_dtype(), pin_memory=True) for _ in range(2)]
+        ev_exp = [torch.cuda.Event(), torch.cuda.Event()]
+        ev_copied = [torch.cuda.Event(), torch.cuda.Event()]
+        ir_np = np.int16 if irb == 2 else np.int32     # (torch has the signed types: the same bytes)
+
+        def drain(k):
+            b, (_, _, j0, j1) = k & 1, chunks[k]
+            ev_copied[b].synchronize()
+            # (the host's write into the mapped files, with the bounded thread count of every staging copy here)
+            _parallel_host_copy(_host_tensor(w.x[j0:j1]), h_x[b][: j1 - j0])
+            _parallel_host_copy(_host_tensor(w.ir[j0:j1].view(ir_np)), h_ir[b][: j1 - j0])
+
+        for k, (c0, c1, j0, j1) in enumerate(chunks):
+            b = k & 1
+            # (device buffers b: chunk k - 2 left them before drain(k - 2) returned)
+            shard.export_into(c0, c1 - c0, d_jc, d_ir[b], d_x[b])
+            ev_exp[b].record(main)
+            with torch.cuda.stream(copy):
+                copy.wait_event(ev_exp[b])
+                h_x[b][: j1 - j0].copy_(d_x[b][: j1 - j0], non_blocking=True)
+                h_ir[b][: j1 - j0].copy_(d_ir[b][: j1 - j0], non_blocking=True)
+                ev_copied[b].record(copy)
+            if k:
+                drain(k - 1)
+        drain(len(chunks) - 1)
+    w.close()
+    return {"bytes": nnz * (8 + irb), "seconds": time.time() - t0}
+
+
+def load_shard(ctx: Context, path: str, chunk_bytes: int = SHARD_CHUNK_BYTES, check: bool = True):
+    """Read a shard directory written by save_shard back onto the device; returns (Shard, shardfile.ShardFile).  The layout
+    is the one the streaming sparsifier would have chosen: a fixed stride of s <= 64 entries becomes RECORDS -- chunks go
+    through two pinned host buffers and a copy stream into two device staging buffers, spkm_pack_records_dev packs chunk c
+    under the transfer of chunk c + 1, and the buffer is adopted by Shard.from_records: the entries exist once, from the
+    start -- anything else (longer columns, a ragged shard) CSC arrays with the 48 entries of slack the screens ask for.
+    ``check``: run shardfile.validate (one scan of jc and ir on the host) first."""
+    from . import shardfile
+
+    sf = shardfile.open_shard(path, check=check)
+    m = sf.meta
+    dev = torch.device("cuda", ctx.device)
+    torch.cuda.set_device(ctx.device)
+    n, nnz, s, p2, bits = m["n"], m["nnz"], m["s"], m["p2"], m["ir_bits"]
+    irb = bits // 8
+    ir_t = torch.int16 if bits == 16 else torch.int32
+    ir_np = np.int16 if bits == 16 else np.int32
+    records = 0 < s <= 64 and n > 0
+    main = _ctx_stream(ctx, dev)
+    chunks = _column_chunks(n, nnz, s, sf.jc, 8 + irb, chunk_bytes) if nnz else []
+    cap = max((j1 - j0 for _, _, j0, j1 in chunks), default=0)
+    if records:
+        R = record_bytes(s, bits)
+        rec = torch.empty(n * R + 256, dtype=torch.uint8, device=dev)
+        rec[n * R:].zero_()
+        d_x = [torch.empty(cap, dtype=torch.float64, device=dev) for _ in range(2)]
+        d_ir = [torch.empty(cap, dtype=ir_t, device=dev) for _ in range(2)]
+    else:
+        x = torch.empty(nnz + 48, dtype=torch.float64, device=dev)
+        ir = torch.empty(nnz + 48, dtype=ir_t, device=dev)
+        x[nnz:].zero_()
+        ir[nnz:].zero_()
+    if chunks:
+        copy = torch.cuda.Stream(device=dev)
+        copy.wait_stream(main)                                     # (the buffers above were prepared on these streams)
+        copy.wait_stream(torch.cuda.current_stream(dev))
+        h_x = [torch.empty(cap, dtype=torch.float64, pin_memory=True) for _ in range(2)]
+        h_ir = [torch.empty(cap, dtype=ir_t, pin_memory=True) for _ in range(2)]
+        ev_sent = [None, None]          # copy stream: the pinned pair has left the host
+        ev_copied = [torch.cuda.Event(), torch.cuda.Event()]
+        ev_free = [None, None]          # main stream: the pack kernel has read the staging pair
+        for k, (c0, c1, j0, j1) in enumerate(chunks):
+            b, cnt = k & 1, j1 - j0
+            if ev_sent[b] is not None:
+                ev_sent[b].synchronize()
+            _parallel_host_copy(h_x[b][:cnt], _host_tensor(sf.x[j0:j1]))            # the host-side read of the chunk
+            _parallel_host_copy(h_ir[b][:cnt], _host_tensor(sf.ir[j0:j1].view(ir_np)))
+            with torch.cuda.stream(copy):
+                if records:
+                    if ev_free[b] is not None:
+                        copy.wait_event(ev_free[b])
+                    d_x[b][:cnt].copy_(h_x[b][:cnt], non_blocking=True)
+                    d_ir[b][:cnt].copy_(h_ir[b][:cnt], non_blocking=True)
+                else:
+                    x[j0:j1].copy_(h_x[b][:cnt], non_blocking=True)
+                    ir[j0:j1].copy_(h_ir[b][:cnt], non_blocking=True)
+                ev_sent[b] = torch.cuda.Event()
+                ev_sent[b].record(copy)
+                ev_copied[b].record(copy)
+            main.wait_event(ev_copied[b])
+            if records:
+                pack_records_device(ctx, p2, s, d_ir[b], d_x[b], rec[c0 * R:], ncols=c1 - c0)
+                ev_free[b] = torch.cuda.Event()
+                ev_free[b].record(main)
+        for ev in ev_sent:
+            if ev is not None:
+                ev.synchronize()
+    if records:
+        main.synchronize()                                          # (the staging buffers go: their readers are done)
+        return Shard.from_records(ctx, p2, n, s, rec, bits), sf
+    if s > 0:
+        jc = torch.arange(0, (n + 1) * s, s, dtype=torch.int64, device=dev)
+    else:
+        jc = torch.from_numpy(np.array(sf.jc, dtype=np.int64)).to(dev)
+    main.synchronize()
+    return Shard.from_device(ctx, p2, jc, ir, x, nnz=nnz), sf
 
 
 def _copy_threads() -> int:

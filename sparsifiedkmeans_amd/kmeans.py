@@ -104,9 +104,11 @@ _DEFAULTS = dict(
 # OUTPUT["sparseForm"][0] reads 1, OUTPUT["sparseIterations"] counts such iterations whatever the form).  No output ever
 # depends on it.  Off by default: the shapes of profiles/sparse_centres_ab.txt were run once, in a shortened series (every
 # pair wins: that call 1.4x to 3.6x faster), and the default goes on only once every pair of shapes 1-3 wins in two series.
+# secondPassSource: with a SparsifiedData as X, the dense data the two-pass outputs (nargout > 5) read in their second pass --
+# an n x p array or tensor (p x n with the data's ColumnSamples) or the path of such a .npy file; the one-shot call reads X.
 _EXTRA = dict(rng=None, device=None, nargout=5, first=0, n_total=None, wideScreen=True, wideBounds=True, farScreen=True,
               slicedSums=True, farBounds=True, farEvents=True, farRagged=False, tileRagged=False, seedTogether=True,
-              kppRagged=False, manyCentres=False, sparseIndex=False, tileFar=False)
+              kppRagged=False, manyCentres=False, sparseIndex=False, tileFar=False, secondPassSource=None)
 _KPP_STARTS = ("arthur", "++", "kmeans++", "k-means++", "k-means-++")
 
 
@@ -280,30 +282,174 @@ def _tensor_source(X: torch.Tensor, ctx) -> torch.Tensor:
     return X.detach()
 
 
-def kmeans_sparsified(X, K, **options):
-    """[IDX, C, SUMD, D, OUTPUT] = kmeans_sparsified(X, K, 'Name', value, ...)   (kmeans_sparsified.m:1)
+class SparsifiedData:
+    """A dataset after the one pass the method rests on: the resident sparse shard and everything needed to cluster it again
+    -- the sketch (kind, sign, p, p2), small_p, gamma, n, first, n_total, the ingest timings and the generator, which stands
+    where the one-shot call's stands after its ingest.  ``sparsify`` makes one; ``kmeans_sparsified(data, K, ...)`` clusters it
+    as often as wanted (other K, more replicates, a start from the last centres) without touching the dense data;
+    ``save`` / ``load`` keep it across processes (shardfile: format version 1).  ``close()`` frees the shard."""
 
-    X: n x p numpy array or torch.Tensor (pageable, pinned, or on the run's device; points are rows, 'ColumnSamples',True
-    for p x n).  float32 / float16 / bfloat16 / uint8 / int8 / int16 / uint16 data is streamed in its own width.  Returns the tuple
-    (IDX, C, SUMD, D, OUTPUT); IDX is 1-based.  With nargout=6..9 the two-pass outputs follow:
-    (..., C_twoPass, IDX_twoPass, D_twoPass, SUMD_twoPass)[:nargout].  See module docstring for scope."""
-    t0 = time.time()
+    def __init__(self, ctx, shard, sketch, *, small_p, gamma, n, nnz, first, n_total, timings, rng, SparsityLevel,
+                 ColumnSamples, FORCE_BUG, sample_seed, LoadFromDisk=False, Y=None, sk_name=None):
+        self.ctx, self.shard, self.sketch = ctx, shard, sketch
+        self.small_p, self.gamma, self.n, self.nnz = int(small_p), float(gamma), int(n), int(nnz)
+        self.first, self.n_total = int(first), int(n_total)
+        self.timings, self.rng = dict(timings), rng
+        self.SparsityLevel, self.ColumnSamples, self.FORCE_BUG = SparsityLevel, bool(ColumnSamples), bool(FORCE_BUG)
+        self.sample_seed, self.LoadFromDisk = int(sample_seed), bool(LoadFromDisk)
+        self.Y = Y               # the host's copy of a shard sampled on the host (Hadamard past 2^24 rows, p = 1); else None
+        self.sk_name = sk_name or sketch.kind   # the sketch as the ingesting call spelled it (its Display line)
+
+    p = property(lambda self: self.sketch.p)
+    p2 = property(lambda self: self.sketch.p2)
+    kind = property(lambda self: self.sketch.kind)
+
+    def value_range(self) -> tuple[float, float]:
+        """(min, max) over the stored values, 0 included when there are none (the 'uniform' start, kmeans_sparsified.m:390)"""
+        mn = mx = 0.0
+        step = max(1, (1 << 24) // max(1, self.small_p))
+        for c0 in range(0, self.n, step):
+            x = self.shard.export(c0, min(step, self.n - c0))[2]
+            if x.numel():
+                mn, mx = min(mn, float(x.min().item())), max(mx, float(x.max().item()))
+        return mn, mx
+
+    def save(self, path, chunk_bytes: int | None = None) -> dict:
+        """Write the shard and its settings to the directory ``path`` (engine.save_shard; in a distributed run every rank
+        saves its own block to its own directory).  Returns {"bytes", "seconds"}."""
+        from .engine import SHARD_CHUNK_BYTES, save_shard
+
+        meta = dict(p=int(self.p), sketch=self.kind, SparsityLevel=float(self.SparsityLevel), small_p=self.small_p,
+                    gamma=self.gamma, sample_seed=self.sample_seed, first=self.first, n_total=self.n_total,
+                    ColumnSamples=self.ColumnSamples, FORCE_BUG=self.FORCE_BUG)
+        sign = None if self.sketch.sign is None else self.sketch.sign.cpu().numpy()
+        return save_shard(self.shard, str(path), meta, sign, chunk_bytes or SHARD_CHUNK_BYTES)
+
+    @classmethod
+    def load(cls, path, device=None, rng=None, first=None, n_total=None, chunk_bytes: int | None = None) -> "SparsifiedData":
+        """Read a directory written by save() back onto ``device``.  The generator of the saving process is not part of
+        the file: ``rng`` (a numpy Generator or a seed) takes its place.  Neither are the ingest's timings (meta.json holds
+        settings only): ``timings`` of a loaded object holds the time and bytes of the LOAD instead -- TimeToLoad,
+        loadBytes -- and TimeToSketch = TimeToSample = 0.0, ingestBytes = 0 (this process sketched nothing), so that
+        OUTPUT of a run on it has the fields of any other run.  ``first`` / ``n_total``: what this rank expects its
+        block to be -- a mismatch with the file is refused."""
+        from .engine import SHARD_CHUNK_BYTES, load_shard
+
+        ctx = torch_context(device)
+        t1 = time.time()
+        shard, sf = load_shard(ctx, str(path), chunk_bytes or SHARD_CHUNK_BYTES)
+        m = sf.meta
+        timings = dict(TimeToSketch=0.0, TimeToSample=0.0, ingestBytes=0, TimeToLoad=time.time() - t1,
+                       loadBytes=m["nnz"] * (8 + m["ir_bits"] // 8))
+        for name, want in (("first", first), ("n_total", n_total)):
+            if want is not None and int(want) != m[name]:
+                shard.close()
+                raise ValueError(f"{name} = {int(want)}, but {path} holds a block saved with {name} = {m[name]}")
+        sketch = _Sketch(ctx, m["sketch"], m["p"], None if sf.sign is None else np.array(sf.sign))
+        rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+        return cls(ctx, shard, sketch, small_p=m["small_p"], gamma=m["gamma"], n=m["n"], nnz=m["nnz"], first=m["first"],
+                   n_total=m["n_total"], timings=timings, rng=rng, SparsityLevel=m["SparsityLevel"],
+                   ColumnSamples=m["ColumnSamples"], FORCE_BUG=m["FORCE_BUG"], sample_seed=m["sample_seed"])
+
+    def close(self) -> None:
+        if self.shard is not None:
+            self.shard.close()
+            self.shard = None
+        self.Y = None
+
+
+_INGEST_OPTIONS = ("SparsityLevel", "SketchType", "ColumnSamples", "MB_limit", "SparsityIgnoreUpsampling", "FORCE_BUG", "rng",
+                   "device", "first", "n_total", "DataFile", "DataFileVerbose")
+
+
+def sparsify(X, **options) -> SparsifiedData:
+    """The ingest half of ``kmeans_sparsified(X, K, 'Sparsify', True, ...)`` on its own: one pass over X (an array, a tensor
+    or a 'DataFile'), mixed, sampled and kept as a resident sparse shard.  Options are those of the ingest, under the same
+    names: SparsityLevel, SketchType, ColumnSamples, MB_limit, SparsityIgnoreUpsampling, FORCE_BUG, rng, device, first,
+    n_total (and DataFile / DataFileVerbose).  ``rng`` is drawn from exactly as the one-shot call draws -- the sign vector,
+    then the sampling seed -- and kept in ``data.rng``, so that sparsify + kmeans_sparsified(data, K) is the one-shot run."""
+    canon = {k.lower(): k for k in _INGEST_OPTIONS}
+    for k in options:
+        if k.lower() not in canon:
+            raise TypeError(f"'{k}' is not an option of sparsify (the ingest takes {', '.join(_INGEST_OPTIONS)})")
     o = _parse(options)
-    nargout = int(o["nargout"])
-    if not 1 <= nargout <= 9:
-        raise ValueError("nargout must be between 1 and 9")
     if isinstance(X, str):
-        o["DataFile"], X = X, None                                                # kmeans_sparsified.m:179-183
-    LoadFromDisk = o["DataFile"] is not None
-    if not o["Sparsify"]:
-        return _kmeans_dense(X, K, o, nargout, t0)
-    MLcorrection = bool(o["MLcorrection"]) and bool(o["Sparsify"])   # :171
+        o["DataFile"], X = X, None
     rng = o["rng"] if isinstance(o["rng"], np.random.Generator) else np.random.default_rng(o["rng"])
     ctx = torch_context(o["device"])
-    dev = f"cuda:{ctx.device}"
-    Display = o["Display"] if isinstance(o["Display"], str) else "off"
-    OUTPUT = dict(LoadFromDisk=LoadFromDisk, Options=dict(o), Sparsify=True)
+    return _ingest(X, o, ctx, rng, {})[0]                  # (nothing of the dense data is kept)
 
+
+def _device_index(device) -> int:
+    """the ordinal of ``device`` in any form torch.cuda.set_device takes: an int, 'cuda:1', 'cuda', a torch.device"""
+    if isinstance(device, (int, np.integer)) and not isinstance(device, bool):
+        return int(device)
+    d = torch.device(device)
+    if d.type != "cuda":
+        raise ValueError(f"device = {device!r}: the run needs a HIP device ('cuda:N')")
+    return torch.cuda.current_device() if d.index is None else int(d.index)
+
+
+def _second_pass_source(src, data: SparsifiedData):
+    """'secondPassSource' of a call on SparsifiedData as the second pass reads a source: (p x n array or tensor, None).  A
+    path names a .npy file, which is memory-mapped and read like an array in memory (chunks of MB_limit)."""
+    if isinstance(src, str):
+        fn = src if src.endswith(".npy") else src + ".npy"
+        try:
+            src = np.load(fn, mmap_mode="r")
+        except FileNotFoundError:
+            raise FileNotFoundError(f"secondPassSource: cannot find {fn}")
+    if isinstance(src, torch.Tensor):
+        src = _tensor_source(src, data.ctx)
+        if src.dtype not in _KEEP_NARROW_TORCH and src.dtype != torch.float64:
+            src = src.to(torch.float64)
+    else:
+        if np.iscomplexobj(src):
+            raise ValueError("Code and distance computations require real data")   # :312-314
+        if not isinstance(src, np.ndarray):
+            src = np.asarray(src)
+    if src.ndim != 2:
+        raise ValueError(f"secondPassSource must be a matrix, got {src.ndim} dimensions")
+    if not data.ColumnSamples:
+        src = src.T
+    if tuple(src.shape) != (data.p, data.n):
+        want = (data.p, data.n) if data.ColumnSamples else (data.n, data.p)
+        got = tuple(src.shape) if data.ColumnSamples else tuple(src.shape)[::-1]
+        raise ValueError(f"secondPassSource is {got[0]} x {got[1]}, the sparsified data came from {want[0]} x {want[1]}")
+    return src, None
+
+
+def _check_against_data(data: SparsifiedData, options: dict, o: dict) -> None:
+    """options of the ingest that a call passes beside a SparsifiedData must agree with it: ValueError names the option"""
+    given = {k.lower() for k in options}
+    if "sparsify" in given and not o["Sparsify"]:
+        raise ValueError("'Sparsify', false contradicts the SparsifiedData passed as X: it holds sparsified data only")
+    if "sparsitylevel" in given and o["SparsityLevel"] != data.SparsityLevel:
+        raise ValueError(f"SparsityLevel = {o['SparsityLevel']} contradicts the data, sparsified with {data.SparsityLevel}")
+    if "sketchtype" in given:
+        sk = o["SketchType"]
+        sk = str(sk).lower() if not isinstance(sk, (list, tuple)) else "function handle"
+        if sk == "auto":
+            sk = "hadamard" if data.p == _nextpow2(data.p) else "dct"
+        if sk == "nothing":
+            sk = "none"
+        if sk != data.kind:
+            raise ValueError(f"SketchType = {o['SketchType']!r} contradicts the data, sparsified with {data.kind!r}")
+    if "columnsamples" in given and bool(o["ColumnSamples"]) != data.ColumnSamples:
+        raise ValueError(f"ColumnSamples = {bool(o['ColumnSamples'])} contradicts the data, sparsified with {data.ColumnSamples}")
+    for name in ("first", "n_total"):
+        if name in given and o[name] is not None and int(o[name]) != getattr(data, name):
+            raise ValueError(f"{name} = {int(o[name])} contradicts the data, a block with {name} = {getattr(data, name)}")
+    if "datafile" in given and o["DataFile"] is not None:
+        raise ValueError("DataFile contradicts the SparsifiedData passed as X (secondPassSource names the dense data)")
+
+
+def _ingest(X, o, ctx, rng, OUTPUT, K=None):
+    """The ingest half of kmeans_sparsified (kmeans_sparsified.m:179-334): read the source, draw the sketch's signs and the
+    sampling seed from ``rng`` -- in this order, and nothing else -- and mix + sample the data into a resident shard.  Fills
+    the ingest fields of ``OUTPUT`` and returns (SparsifiedData, the dense source p x n or None, its memory map or None); both kmeans_sparsified and sparsify run exactly this."""
+    dev = f"cuda:{ctx.device}"
+    LoadFromDisk = o["DataFile"] is not None
     if LoadFromDisk:
         # the reference streams a MATLAB v7.3 (HDF5) file through matfile(); here: a .npy file, memory-mapped
         # and read MB_limit megabytes at a time (private/sampleAndMixFromLargeFile.m:79-129)
@@ -342,7 +488,7 @@ def kmeans_sparsified(X, K, **options):
     n_glob = int(o["n_total"]) if (dist_on and o["n_total"]) else n
     if dist_on and o["n_total"] is None:
         raise ValueError("distributed run: pass n_total (and first) so that all ranks agree on the dataset")
-    if n_glob < K:
+    if K is not None and n_glob < K:
         raise ValueError("X must have more samples than the number of clusters.")  # :219-221
 
     # ---- sketch (:224-296) ----
@@ -414,7 +560,7 @@ def kmeans_sparsified(X, K, **options):
             x2_[:nnz] = vals_[nzm_]
             ir2_[:nnz] = sp_.ir[: n * small_p][nzm_]
             shard = Shard.from_device(ctx, p2, jc_, ir2_, x2_, nnz=nnz)
-        del nzm_, vals_
+        del nzm_, vals_, sp_
         torch.cuda.synchronize()
         OUTPUT["TimeToSketch"] = OUTPUT["TimeToSample"] = time.time() - t1       # fused: one number for both
     else:
@@ -446,6 +592,77 @@ def kmeans_sparsified(X, K, **options):
             raise ValueError("X must be finite (Inf / NaN entries found)")
         shard = Shard.from_scipy(ctx, Y)
         nnz = Y.nnz
+    timings = {k: OUTPUT[k] for k in ("TimeToReadSizeOfFile", "SketchType", "SlowHadamard", "ingestBytes", "TimeToSketch",
+                                      "TimeToSample") if k in OUTPUT}
+    data = SparsifiedData(ctx, shard, sketch, small_p=small_p, gamma=gamma, n=n, nnz=nnz, first=first, n_total=n_glob,
+                          timings=timings, rng=rng, SparsityLevel=o["SparsityLevel"], ColumnSamples=bool(o["ColumnSamples"]),
+                          FORCE_BUG=bool(o["FORCE_BUG"]), sample_seed=sample_seed, LoadFromDisk=LoadFromDisk, Y=Y,
+                          sk_name=sk)
+    return data, X, (Xmm if LoadFromDisk else None)        # ... and the dense data, for the second pass of the same call
+
+
+def kmeans_sparsified(X, K, **options):
+    """[IDX, C, SUMD, D, OUTPUT] = kmeans_sparsified(X, K, 'Name', value, ...)   (kmeans_sparsified.m:1)
+
+    X: n x p numpy array or torch.Tensor (pageable, pinned, or on the run's device; points are rows, 'ColumnSamples',True
+    for p x n).  float32 / float16 / bfloat16 / uint8 / int8 / int16 / uint16 data is streamed in its own width.  Returns the tuple
+    (IDX, C, SUMD, D, OUTPUT); IDX is 1-based.  With nargout=6..9 the two-pass outputs follow:
+    (..., C_twoPass, IDX_twoPass, D_twoPass, SUMD_twoPass)[:nargout].  See module docstring for scope.
+
+    X may also be a SparsifiedData (``sparsify`` / ``SparsifiedData.load``): the ingest is skipped, 'Sparsify' is implied, the
+    run draws from ``data.rng`` unless ``rng`` is given, OUTPUT["fromSparsified"] is True and carries the stored ingest
+    timings.  Ingest options that contradict the data (SparsityLevel, SketchType, ColumnSamples, first, n_total) raise
+    ValueError; nargout > 5 reads the dense data from 'secondPassSource'."""
+    t0 = time.time()
+    o = _parse(options)
+    nargout = int(o["nargout"])
+    if not 1 <= nargout <= 9:
+        raise ValueError("nargout must be between 1 and 9")
+    data = X if isinstance(X, SparsifiedData) else None
+    if data is not None:
+        # sparsified earlier (sparsify / SparsifiedData.load): no ingest.  What the call says about the ingest must agree
+        # with the data; what it does not say is the data's.
+        _check_against_data(data, options, o)
+        if data.shard is None:
+            raise ValueError("the SparsifiedData passed as X has been closed")
+        o["Sparsify"], o["ColumnSamples"] = True, data.ColumnSamples
+        if nargout > 5 and o["secondPassSource"] is None:
+            raise ValueError("nargout > 5 needs the dense data for the second pass: pass it as 'secondPassSource' "
+                             "(an n x p array or tensor, or the path of a .npy file)")
+    elif o["secondPassSource"] is not None:
+        raise ValueError("'secondPassSource' belongs to a call on SparsifiedData; here the second pass reads X itself")
+    if isinstance(X, str):
+        o["DataFile"], X = X, None                                                # kmeans_sparsified.m:179-183
+    LoadFromDisk = o["DataFile"] is not None
+    if not o["Sparsify"]:
+        return _kmeans_dense(X, K, o, nargout, t0)
+    MLcorrection = bool(o["MLcorrection"]) and bool(o["Sparsify"])   # :171
+    if data is not None and o["rng"] is None:
+        rng = data.rng                                                # the run goes on where the ingest stopped drawing
+    else:
+        rng = o["rng"] if isinstance(o["rng"], np.random.Generator) else np.random.default_rng(o["rng"])
+    if data is not None and o["device"] is not None and _device_index(o["device"]) != int(data.ctx.device):
+        raise ValueError(f"device = {o['device']} contradicts the data, resident on cuda:{data.ctx.device}")
+    ctx = data.ctx if data is not None else torch_context(o["device"])
+    if data is not None:
+        torch.cuda.set_device(ctx.device)
+    dev = f"cuda:{ctx.device}"
+    Display = o["Display"] if isinstance(o["Display"], str) else "off"
+    OUTPUT = dict(LoadFromDisk=LoadFromDisk, Options=dict(o), Sparsify=True, fromSparsified=data is not None)
+
+    if data is None:
+        data, X, Xmm = _ingest(X, o, ctx, rng, OUTPUT, K)
+    else:
+        OUTPUT.update(data.timings)  # the ingest's own fields, as stored
+        OUTPUT["LoadFromDisk"] = LoadFromDisk = False
+        X, Xmm = _second_pass_source(o["secondPassSource"], data) if nargout > 5 else (None, None)
+        if data.n_total < K:
+            raise ValueError("X must have more samples than the number of clusters.")  # :219-221
+    shard, sketch, Y = data.shard, data.sketch, data.Y
+    p, p2, n, nnz, small_p, gamma = data.p, data.p2, data.n, data.nnz, data.small_p, data.gamma
+    dist_on = D_.is_distributed()
+    first, n_glob = data.first, data.n_total
+    sk = data.sk_name
     # obj = sqrt(sum(distances.^2)) is evaluated in every iteration (:471) but used only by Display='iter' (:472-475) and,
     # after the loop, for the iteration that turned out to be the last (:489-503): unless it is displayed per iteration
     # the library may leave it (and the exact pass that produces it) out of a fused call; it is then obtained on demand
@@ -496,8 +713,10 @@ def kmeans_sparsified(X, K, **options):
                   objectives=np.zeros(Replicates), replicateTimes=np.zeros(Replicates),
                   replicateTimesJustInitialization=np.zeros(Replicates))
     if isinstance(start, str) and start.lower() == "uniform":
-        vals = Y.data if Y is not None else sp_.x[: n * small_p].cpu().numpy()
-        mn, mx = float(vals.min(initial=0.0)), float(vals.max(initial=0.0))      # full(min(X(:))) incl. implicit zeros
+        if Y is not None:
+            mn, mx = float(Y.data.min(initial=0.0)), float(Y.data.max(initial=0.0))  # full(min(X(:))) incl. implicit zeros
+        else:
+            mn, mx = data.value_range()                                           # (the same over the resident shard)
         if nnz < p2 * n:
             mn, mx = min(mn, 0.0), max(mx, 0.0)
         if dist_on:
@@ -615,13 +834,14 @@ def kmeans_sparsified(X, K, **options):
                 fused_iters += 1
                 event_iters += 1 if eng.last_events_form()[0] else 0   # (a stored value of the call just queued: no synchronisation)
                 tile_far_iters += eng.last_tile_far()[0]               # (a stored value as well)
+                if Y is None and not csc_released and fused_iters == 1 and not shard.layout_info()[0]:
+                    csc_released = True                      # records only already (layout="records", a loaded shard, an earlier run)
                 if Y is None and not csc_released and fused_iters == 1:
                     # the first fused call has built the library's record layout and screen copy: the CSC value / row
                     # arrays of the device-built shard can go (spkm_shard_release_csc; an entry point that needs them
                     # -- the k-means++ rounds of the next replicate -- brings them back from the records)
                     torch.cuda.synchronize()
-                    if shard.release_csc():
-                        sp_.x = sp_.ir = None
+                    if shard.release_csc():             # (the shard drops the tensors it was built from)
                         torch.cuda.empty_cache()
                     csc_released = True
             if mask_t is not None:
