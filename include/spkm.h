@@ -604,6 +604,36 @@ int spkm_kpp_seed_dev(spkm_ctx *ctx, const spkm_shard *s, uint64_t K, double gam
  * points staged per wave (forms 1 and 3) }.  Stored values; does not block. */
 int spkm_last_kpp_plan(spkm_ctx *ctx, int info[4]);
 
+/* Gram sums of a chunk of sparse columns -- the hot loop of the covariance / PCA estimator on sparsified data:
+ *   G += sum_i v_i v_i^T,  sum += sum_i v_i   over the ncols columns v_i of a p2 x ncols CSC chunk in device memory,
+ * laid out as spkm_shard_export_dev writes one: d_jc int64 [ncols + 1], d_ir 16-bit row ids ascending within a column
+ * (ir_bits must be 16: they cover every accepted p2), d_x float64.  No shard is involved and none is touched.
+ * d_G: row-major float64 [p2][p2], ACCUMULATED into (the caller zeroes it once and may spread the points over any
+ * number of calls).  THE TRIANGLE RULE: only entries with row <= column are added to; the strict lower triangle is never
+ * read and never written -- the caller mirrors the upper triangle when it is done.  d_sum: float64 [p2], accumulated
+ * into as well; NULL: not wanted.
+ * Every addition is a float64 atomic add whose order is not fixed: two runs on the same input, the two forms below, or
+ * one call against two calls over halves of the columns agree only up to the rounding of a reordered sum.  THE LAST
+ * BITS ARE NOT REPRODUCIBLE; each entry stays within (m + 1) u |v_j|^T |v_k| of the exact sum over m columns.
+ * Two kernels (csrc/gram.hip), chosen by a byte model in csrc/policy.h (spkm_gram_plan there; its two rates come from
+ * profiles/gram_ab.txt): 1 = a T x T tile of G in LDS per workgroup, one workgroup per pair of row blocks and chunk of points;
+ * 2 = one wave per point, every product straight to G.  SPKM_X_GRAM_FORM=1|2 forces one, SPKM_X_GRAM_TILE=t caps T at t
+ * rounded down to a multiple of 16, at least 16 -- experiments and tests only; read with the other switches
+ * (spkm_ctx_reload_switches).
+ * The kernels run asynchronously on the context's stream.  The byte model needs the chunk's entry count, which lives on
+ * the device: spkm_gram_csc_nnz_dev takes it from the caller (nnz = d_jc[ncols]; only the choice of form depends on it, no
+ * access does) and never blocks; spkm_gram_csc_dev reads d_jc[ncols] back first (8 bytes: it waits once for the work
+ * queued in front of it) unless a form is forced, when it does not block either.
+ * SPKM_ERR_BAD_VALUE: p2 == 0, or d_jc / d_ir / d_x / d_G NULL with ncols > 0; SPKM_ERR_UNSUPPORTED: p2 > 32768 (G would
+ * pass 8 GiB) or ir_bits != 16.  ncols == 0: nothing is done, SPKM_OK. */
+int spkm_gram_csc_dev(spkm_ctx *ctx, uint64_t p2, uint64_t ncols, const int64_t *d_jc, const void *d_ir, int ir_bits,
+                      const double *d_x, double *d_G, double *d_sum);
+int spkm_gram_csc_nnz_dev(spkm_ctx *ctx, uint64_t p2, uint64_t ncols, uint64_t nnz, const int64_t *d_jc, const void *d_ir,
+                          int ir_bits, const double *d_x, double *d_G, double *d_sum);
+/* What the context's last spkm_gram_csc_dev / spkm_gram_csc_nnz_dev that launched a kernel ran: info = { form, T (form 2: 0), block pairs
+ * (form 2: 0), workgroups }; zeros before the first.  Stored values; does not block. */
+int spkm_last_gram_plan(spkm_ctx *ctx, int64_t info[4]);
+
 /* centers(:,k) = gamma*S(:,k) ./ (Cnt(:,k) + 1e-16) for clusters with nk > 0
  * (kmeans_sparsified.m:448); empty clusters keep their column.  d_centers is updated in place;
  * d_out double[2] (device) = { ||old-new||_F^2, obj2 } (kmeans_sparsified.m:470-471 before sqrt). */

@@ -181,6 +181,9 @@ def lib():
     L.spkm_kpp_draw_dev.argtypes = [_vp, _u64, _vp, C.c_double, C.POINTER(C.c_int64)]
     L.spkm_kpp_seed_dev.argtypes = [_vp, _vp, _u64, C.c_double, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
     L.spkm_last_kpp_plan.argtypes = [_vp, C.POINTER(C.c_int)]
+    L.spkm_gram_csc_dev.argtypes = [_vp, _u64, _u64, _vp, _vp, C.c_int, _vp, _vp, _vp]
+    L.spkm_gram_csc_nnz_dev.argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, C.c_int, _vp, _vp, _vp]
+    L.spkm_last_gram_plan.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_ctx_reload_switches.argtypes = [_vp]
     L.spkm_widen_f64_dev.argtypes = [_vp, C.c_int, _u64, _vp, _vp]
     L.spkm_comm_unique_id.argtypes = [_vp]

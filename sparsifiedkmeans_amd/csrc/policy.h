@@ -489,6 +489,72 @@ inline spkm_acc_plan spkm_accumulate_form(long long p, size_t lds_max, bool slic
     a.form = 3; a.R = (int)R; a.slices = (int)slices; a.wg = spkm_acc_wg;
     return a;
 }
+// ---- Gram sums of a chunk of sparse columns (spkm_gram_csc_dev; gram.hip) ----
+// G += sum_i v_i v_i^T over the upper triangle of a p2 x p2 f64 matrix.  form, as spkm_last_gram_plan reports it:
+//  1  k_gram_tiles: the rows cut into nb = ceil(p2 / T) blocks of T, a workgroup owning one block pair (I, J), I <= J, and
+//     one chunk of the points, its T x T tile of G in LDS.  T: the largest multiple of 16, at most p2 rounded up to one, whose
+//     tile, T doubles of the column sum and the staged runs of spkm_gram_waves waves -- two runs of up to T entries per
+//     wave, 10 B each -- fit the workgroup's LDS: 8 T^2 + 8 T + 20 T waves bytes (T = 128 with 160 KB, 80 with 64 KB).
+//     pairs = nb (nb + 1) / 2.  A workgroup zeroes and flushes T^2 doubles whatever it is given, so a chunk is as long as
+//     filling the device allows: about spkm_gram_wgs workgroups over all pairs, never fewer than spkm_gram_min_chunk
+//     points per chunk; grid = pairs x chunks.
+//  2  k_gram_direct: one wave per point, every product one f64 global atomic: any p2, no LDS.
+// The choice is a byte model with two fitted rates:
+//   form 1 streams the chunk once per pair -- pairs x nnz x (2 B of row ids + 8 B for the share of the entries that lies
+//     in the pair's two runs, min(1, 2 T / p2)) -- and flushes grid x T^2 x 8 B by atomics (an upper bound: zeros are skipped);
+//   form 2 issues sum_i s_i (s_i + 1) / 2 x 8 B of atomics, taken at the mean column length nnz / ncols (a lower bound
+//     for ragged columns, by convexity).
+// Each side is divided by a rate, both from profiles/gram_ab.txt (tools/gram_ab.py: N = 1e7, ONE run per form and shape, no
+// spread): spkm_gram_atomic_rate = 0.18 TB/s, what k_gram_direct's scattered f64 adds reach (0.166 / 0.193 / 0.185 TB/s at
+// p2 = 1024 s = 51, 1024 / 102, 8192 / 82; profiles/sliced_sums_ab.txt has 0.19 TB/s for the same kind of add);
+// spkm_gram_stream_rate = 0.30 TB/s, the rate at which k_gram_tiles works through the bytes of this model (0.31 / 0.36 /
+// 0.23 TB/s at the same shapes) -- an EFFECTIVE rate, far below HBM's: the kernel is not bound by the stream, and what
+// bounds it (its LDS adds, the per-point chain of loads, one workgroup per CU) has not been profiled.  Form 1 is 2.7x and
+// 5.4x ahead at p2 = 1024 (s = 51, 102), form 2 11x ahead at p2 = 8192, s = 82 (2080 pairs re-read the chunk).  The two
+// constants are fitted to those three points, so the model's agreeing with them says nothing about other shapes: where the
+// crossover lies between p2 = 1024 and 8192 has not been measured.
+// SPKM_X_GRAM_TILE=t (x_tile > 0: experiments and tests) caps T at t rounded down to a multiple of 16, at least 16;
+// SPKM_X_GRAM_FORM=1|2 (x_form) forces a form -- form 1 where no tile fits the LDS still answers form 2.
+constexpr int spkm_gram_waves = 8;            // waves per workgroup of k_gram_tiles (512 threads)
+constexpr long long spkm_gram_wgs = 1024;     // workgroups a launch of k_gram_tiles aims at
+constexpr long long spkm_gram_min_chunk = 1024; // points per chunk, at least
+constexpr long long spkm_gram_max_p2 = 32768; // G would pass 8 GiB beyond
+constexpr double spkm_gram_atomic_rate = 0.18e12; // B/s of scattered f64 global adds (profiles/gram_ab.txt)
+constexpr double spkm_gram_stream_rate = 0.30e12; // B/s of the model's form-1 bytes, effective (profiles/gram_ab.txt)
+constexpr long long spkm_gram_direct_max_grid = 65536; // workgroups of k_gram_direct (4 points each per trip), at most
+struct spkm_gram_geom {
+    int form = 2;          // 1 LDS tiles, 2 direct
+    int T = 0;             // rows per block (form 2: 0)
+    long long pairs = 0;   // block pairs (form 2: 0)
+    long long chunk = 0;   // points per workgroup chunk (form 2: 0)
+    long long grid = 0;    // workgroups (ncols == 0: 0)
+};
+inline size_t spkm_gram_lds(long long T) { return (size_t)(8 * T * T + 8 * T + 20 * T * spkm_gram_waves); }
+inline spkm_gram_geom spkm_gram_plan(long long p2, unsigned long long nnz, unsigned long long ncols, size_t lds_max, int x_tile,
+                                     int x_form)
+{
+    spkm_gram_geom g;
+    if (p2 <= 0 || p2 > spkm_gram_max_p2 || ncols == 0) return g;
+    const long long n = (long long)ncols;
+    const long long direct_grid = std::min<long long>((n + 3) / 4, spkm_gram_direct_max_grid);
+    long long T = std::min<long long>((p2 + 15) / 16 * 16, 1024);
+    if (x_tile > 0) T = std::min<long long>(T, std::max(16, x_tile / 16 * 16));
+    while (T >= 16 && spkm_gram_lds(T) > lds_max) T -= 16;
+    if (T < 16 || x_form == 2) { g.grid = direct_grid; return g; }
+    const long long nb = (p2 + T - 1) / T, pairs = nb * (nb + 1) / 2;
+    const long long per = std::max<long long>(1, spkm_gram_wgs / pairs); // chunks the target allows
+    const long long chunk = std::max<long long>(spkm_gram_min_chunk, (n + per - 1) / per);
+    const long long chunks = (n + chunk - 1) / chunk;
+    if (x_form != 1) {
+        const double share = std::min(1.0, 2.0 * (double)T / (double)p2);
+        const double t1 = (double)pairs * (double)nnz * (2.0 + 8.0 * share) / spkm_gram_stream_rate +
+                          (double)(pairs * chunks) * (double)(T * T) * 8.0 / spkm_gram_atomic_rate;
+        const double t2 = 4.0 * (double)nnz * ((double)nnz / (double)n + 1.0) / spkm_gram_atomic_rate;
+        if (t2 <= t1) { g.grid = direct_grid; return g; }
+    }
+    g.form = 1; g.T = (int)T; g.pairs = pairs; g.chunk = chunk; g.grid = pairs * chunks;
+    return g;
+}
 // ---- batched k-means++ seeding (spkm_kpp_seed_dev; kpp.hip) ----
 // R replicates are seeded RB at a time (RB = 8, 4, 2 or 1, at most the next power of two >= R), each batch sharing one read
 // of the shard per round.  form reported by spkm_last_kpp_plan:

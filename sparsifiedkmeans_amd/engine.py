@@ -1054,6 +1054,78 @@ def load_shard(ctx: Context, path: str, chunk_bytes: int = SHARD_CHUNK_BYTES, ch
     return Shard.from_device(ctx, p2, jc, ir, x, nnz=nnz), sf
 
 
+GRAM_MAX_P2 = 32768               # spkm_gram_csc_dev: G [p2, p2] float64 would pass 8 GiB beyond
+
+
+def last_gram_plan(ctx: Context) -> tuple[int, int, int, int]:
+    """(form, T, block pairs, workgroups) of the context's last ``gram_csc`` that launched a kernel (spkm_last_gram_plan):
+    form 1 = T x T tiles of G in LDS, one workgroup per pair of row blocks and chunk of points; 2 = one wave per point,
+    products straight to G (T and the pairs read 0); zeros before the first call."""
+    a = (C.c_int64 * 4)()
+    _lib.check(_lib.lib().spkm_last_gram_plan(ctx.handle, a), "spkm_last_gram_plan")
+    return int(a[0]), int(a[1]), int(a[2]), int(a[3])
+
+
+def gram_csc(ctx: Context, p2: int, ncols: int, jc: torch.Tensor, ir: torch.Tensor, x: torch.Tensor, G: torch.Tensor,
+             colsum: torch.Tensor | None = None, nnz: int | None = None) -> None:
+    """G += sum_i v_i v_i^T (upper triangle only: entries with row <= column) and colsum += sum_i v_i over the ``ncols``
+    columns of a CSC chunk on the device, as ``Shard.export`` delivers one.  G float64 [p2, p2] row-major, colsum float64
+    [p2] or None.  ``nnz``: the chunk's entry count, jc[ncols], where the caller knows it -- the call then never blocks
+    (spkm_gram_csc_nnz_dev); None: the library reads it back (spkm_gram_csc_dev).  The last bits depend on the order of
+    the atomic additions."""
+    assert jc.is_cuda and jc.dtype == torch.int64 and jc.is_contiguous() and jc.numel() >= ncols + 1
+    assert ir.is_cuda and ir.is_contiguous() and x.is_cuda and x.is_contiguous() and x.dtype == torch.float64
+    assert G.is_cuda and G.is_contiguous() and G.dtype == torch.float64 and tuple(G.shape) == (p2, p2)
+    assert colsum is None or (colsum.is_cuda and colsum.is_contiguous() and colsum.dtype == torch.float64 and colsum.numel() == p2)
+    L, bits, sm = _lib.lib(), ir.element_size() * 8, None if colsum is None else _p(colsum)
+    if nnz is None:
+        _lib.check(L.spkm_gram_csc_dev(ctx.handle, int(p2), int(ncols), _p(jc), _p(ir), bits, _p(x), _p(G), sm), "spkm_gram_csc_dev")
+    else:
+        _lib.check(L.spkm_gram_csc_nnz_dev(ctx.handle, int(p2), int(ncols), int(nnz), _p(jc), _p(ir), bits, _p(x), _p(G), sm),
+                   "spkm_gram_csc_nnz_dev")
+
+
+def gram_shard(shard: Shard, chunk_bytes: int = SHARD_CHUNK_BYTES) -> tuple[torch.Tensor, torch.Tensor]:
+    """(G, sum) of a resident shard: G = sum_i v_i v_i^T float64 [p2, p2], symmetric, and sum = sum_i v_i float64 [p2], both
+    on the device.  The columns leave the shard as CSC chunks of at most ``chunk_bytes`` of entries (Shard.export_into, from
+    the records or the CSC arrays, whichever the shard holds: a records-only shard stays records-only and nothing of the
+    shard's size is allocated) into two alternating device buffers, and ``gram_csc`` adds each chunk into G, which is
+    zeroed once; the kernels fill the upper triangle only, and it is mirrored at the end."""
+    ctx, dev = shard.ctx, torch.device("cuda", shard.ctx.device)
+    p2, n, nnz = int(shard.p), int(shard.n), int(shard.nnz)
+    if p2 > GRAM_MAX_P2:
+        raise ValueError(f"gram_shard: p2 = {p2} is past {GRAM_MAX_P2}, where G [p2, p2] would pass 8 GiB")
+    if shard.ir_bits != 16:
+        raise ValueError(f"gram_shard: the shard holds {shard.ir_bits}-bit row ids; the Gram kernels read 16-bit ids")
+    main = _ctx_stream(ctx, dev)
+    with torch.cuda.stream(main):
+        G = torch.zeros((p2, p2), dtype=torch.float64, device=dev)
+        colsum = torch.zeros(p2, dtype=torch.float64, device=dev)
+        s = shard.layout_info()[2] if nnz else 0
+        jc_h = None
+        if nnz and s == 0:
+            # a ragged shard's column starts first (8 bytes per point): the chunks are cut by them
+            jc_h = np.zeros(n + 1, np.int64)
+            step = max(1, int(chunk_bytes) // 8)
+            jc_d = torch.empty(min(n, step) + 1, dtype=torch.int64, device=dev)
+            for c0 in range(0, n, step):
+                m = min(step, n - c0)
+                shard._export_jc(c0, m, jc_d)
+                jc_h[c0 + 1:c0 + m + 1] = jc_d[1:m + 1].cpu().numpy() + jc_h[c0]
+        chunks = _column_chunks(n, nnz, s, jc_h, 8 + shard.ir_bits // 8, chunk_bytes) if nnz else []
+        cap = max((j1 - j0 for _, _, j0, j1 in chunks), default=0)
+        mcols = max((c1 - c0 for c0, c1, _, _ in chunks), default=0)
+        d_x = [torch.empty(max(cap, 1), dtype=torch.float64, device=dev) for _ in range(2)]
+        d_ir = [torch.empty(max(cap, 1), dtype=shard._ir_dtype(), device=dev) for _ in range(2)]
+        d_jc = [torch.empty(mcols + 1, dtype=torch.int64, device=dev) for _ in range(2)]
+        for k, (c0, c1, j0, j1) in enumerate(chunks):
+            b = k & 1
+            shard.export_into(c0, c1 - c0, d_jc[b], d_ir[b], d_x[b])
+            gram_csc(ctx, p2, c1 - c0, d_jc[b], d_ir[b], d_x[b], G, colsum, nnz=j1 - j0)   # (the host knows the count: no wait)
+        G = torch.triu(G) + torch.triu(G, 1).T
+    return G, colsum
+
+
 def _copy_threads() -> int:
     """threads of the host-side staging copy (SPKM_COPY_THREADS overrides).  Measured on the benchmark box (256 hardware
     threads, tools/ingest_probe2.py): torch's own parallel copy moves 93 GB/s into pinned memory with 16 threads, 21 GB/s

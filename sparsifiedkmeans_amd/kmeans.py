@@ -380,6 +380,109 @@ def sparsify(X, **options) -> SparsifiedData:
     return _ingest(X, o, ctx, rng, {})[0]                  # (nothing of the dense data is kept)
 
 
+def _covariance_device(data: SparsifiedData, center: bool, unmix: bool):
+    """covariance_sparsified on device tensors: (C float64 [q, q], mean float64 [q], OUTPUT), q = p with unmix, p2 without"""
+    from .engine import GRAM_MAX_P2, gram_shard, last_gram_plan
+
+    if not isinstance(data, SparsifiedData):
+        raise TypeError("covariance_sparsified takes a SparsifiedData (sparsify / SparsifiedData.load)")
+    if data.shard is None:
+        raise ValueError("the SparsifiedData is closed: its shard was freed")
+    if data.n_total != data.n:
+        raise NotImplementedError(f"the data is a block of a distributed run (n = {data.n} of n_total = {data.n_total}): "
+                                  "G, sum and n are additive, but their all-reduce is not implemented")
+    s, p2, n = data.small_p, int(data.p2), data.n
+    if s == 1:
+        raise ValueError("small_p = 1: one entry per point holds no product of two different rows, so the off-diagonal "
+                         "of the covariance cannot be estimated (raise SparsityLevel)")
+    if p2 > GRAM_MAX_P2:
+        raise ValueError(f"p2 = {p2} is past {GRAM_MAX_P2}: the p2 x p2 float64 Gram matrix would pass 8 GiB")
+    free = torch.cuda.mem_get_info(data.ctx.device)[0]
+    if 8 * p2 * p2 > free // 4:
+        raise ValueError(f"the p2 x p2 float64 Gram matrix ({8 * p2 * p2} bytes at p2 = {p2}) is more than a quarter of the "
+                         f"free device memory ({free} bytes)")
+    t1 = time.time()
+    G, colsum = gram_shard(data.shard)
+    torch.cuda.synchronize(data.ctx.device)
+    t_gram = time.time() - t1
+    # stored values are the samples times p2/s; a row is sampled with probability s/p2, two different rows together with
+    # s(s-1)/(p2(p2-1)): E[G_jj]/n = (p2/s) mean(y_j^2), E[G_jk]/n = (p2/s)^2 s(s-1)/(p2(p2-1)) mean(y_j y_k)
+    f_diag = s / p2
+    f_off = (s * (p2 - 1)) / (p2 * (s - 1))
+    C_ = G * (f_off / n)
+    C_.diagonal().copy_(G.diagonal() * (f_diag / n))
+    del G
+    mean = colsum / n
+    if center:
+        C_ -= torch.outer(mean, mean)
+    if unmix:
+        sk = data.sketch
+        C_ = sk.unmix(sk.unmix(C_).T.contiguous())
+        C_ = 0.5 * (C_ + C_.T)                 # (the two passes of the transform round differently: symmetric again)
+        mean = sk.unmix(mean[None, :])[0]
+    OUTPUT = dict(gramPlan=last_gram_plan(data.ctx), TimeGram=t_gram, n=n, s=s, diagFactor=f_diag, offDiagFactor=f_off)
+    return C_, mean, OUTPUT
+
+
+def covariance_sparsified(data: SparsifiedData, center: bool = True, unmix: bool = True):
+    """(C, mean, OUTPUT): the covariance estimator of the sparsification paper (Pourkamali-Anaraki & Becker) from the
+    resident shard alone -- no second look at the dense data.
+
+    With s = data.small_p entries kept per point out of p2 rows, stored as the samples times p2/s, G = sum_i v_i v_i^T and
+    sum = sum_i v_i over the shard's columns (engine.gram_shard: HIP kernels), the unbiased estimates in the mixed domain are
+        mean = sum / n,    C_jj = (s / p2) G_jj / n,    C_jk = s (p2 - 1) / (p2 (s - 1)) G_jk / n   (j != k)
+    for the second moment (1/n) sum_i y_i y_i^T.  (Not data.gamma, which divides by p.)  Exact zeros dropped from a ragged
+    shard contribute nothing to either side, so the same formulas hold.  ``center=True`` returns C - mean mean^T, the
+    covariance; its bias is O(1/n) (the product of the estimated means, as in the biased sample covariance).
+    ``unmix=True`` carries both back to the data's domain with the sketch's own inverse -- rows, transpose, rows again,
+    the leading p x p block -- the sketches being orthonormal, that is the estimate for the data as ingested (times the
+    ingest's (1 + 2 eps)^2); ``unmix=False`` leaves them p2 x p2 / p2 in the mixed domain.  numpy float64, like
+    kmeans_sparsified's C.  OUTPUT: gramPlan (form, T, block pairs, workgroups of the last Gram call), TimeGram, n, s,
+    diagFactor, offDiagFactor.
+
+    Raises ValueError for small_p = 1 (no off-diagonal can be estimated from one entry per point), p2 > 32768 or a Gram
+    matrix above a quarter of the free device memory, and closed data; NotImplementedError for a block of a distributed
+    run (n_total != n)."""
+    C_, mean, OUTPUT = _covariance_device(data, bool(center), bool(unmix))
+    return C_.cpu().numpy(), mean.cpu().numpy(), OUTPUT
+
+
+def pca_sparsified(data: SparsifiedData, k: int, center: bool = True, covariance=None):
+    """(components [k, p], explained_variance [k], mean [p], OUTPUT): the k leading principal components of the data from
+    ``covariance_sparsified(data, center)`` in the data's domain -- torch.linalg.eigh of the p x p estimate on the device,
+    the k largest eigenvalues in descending order, each component's sign fixed so that its entry of largest magnitude is
+    positive.  The estimate is unbiased (up to the O(1/n) of centering) but not positive semidefinite by construction:
+    trailing eigenvalues of a noisy estimate may be negative.
+
+    ``covariance``: the tuple covariance_sparsified(data, center) returned -- (C [p, p], mean [p]) or (C, mean, OUTPUT) --
+    to be decomposed as it is instead of running the Gram pass again: several k from one pass, and, because the sums'
+    last bits differ from pass to pass, the only way to hold a decomposition against the very matrix decomposed.
+    ``center`` is not read then (the matrix is centred or not as its maker chose); OUTPUT starts from a copy of the
+    tuple's OUTPUT, if it has one, and gains TimeEigh.  ValueError for a matrix or mean that is not p x p / p.
+    ValueError for k outside 1..p and whatever covariance_sparsified refuses."""
+    p = int(data.p)
+    if int(k) != k or not (1 <= int(k) <= p):
+        raise ValueError(f"k = {k} is outside 1..p = {p}")
+    k = int(k)
+    if covariance is None:
+        C_, mean, OUTPUT = _covariance_device(data, bool(center), True)
+    else:
+        dev = f"cuda:{data.ctx.device}"
+        C_ = torch.as_tensor(np.asarray(covariance[0], np.float64), device=dev)
+        mean = torch.as_tensor(np.asarray(covariance[1], np.float64), device=dev)
+        if tuple(C_.shape) != (p, p) or tuple(mean.shape) != (p,):
+            raise ValueError(f"covariance is {tuple(C_.shape)} with a mean of {tuple(mean.shape)}; the data has p = {p}")
+        OUTPUT = dict(covariance[2]) if len(covariance) > 2 else {}
+    t1 = time.time()
+    w, V = torch.linalg.eigh(C_)
+    w, V = w.flip(0)[:k], V.flip(1)[:, :k].T.contiguous()                 # [k], [k, p]: descending
+    big = V.gather(1, V.abs().argmax(dim=1, keepdim=True))                 # each component's entry of largest magnitude
+    V = torch.where(big < 0, -V, V)
+    torch.cuda.synchronize(data.ctx.device)
+    OUTPUT["TimeEigh"] = time.time() - t1
+    return V.cpu().numpy(), w.cpu().numpy(), mean.cpu().numpy(), OUTPUT
+
+
 def _device_index(device) -> int:
     """the ordinal of ``device`` in any form torch.cuda.set_device takes: an int, 'cuda:1', 'cuda', a torch.device"""
     if isinstance(device, (int, np.integer)) and not isinstance(device, bool):
