@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The paper's other application on the same sparsified data: a planted low-rank mixture (p = 512, n = 20000, five
 clusters whose centres lie in a 3-dimensional subspace) is sparsified ONCE (gamma = 0.1), then its principal components are
-estimated from the resident shard (pca_sparsified) and it is clustered (kmeans_sparsified) -- neither looks at the dense
-data again.
+estimated from the resident shard (pca_sparsified: once through the Gram matrix and a dense eigen-solve, once matrix-free
+by subspace iteration, method="subspace") and it is clustered (kmeans_sparsified) -- none looks at the dense data again.
 
     python examples/example_sparsePCA.py
 """
@@ -41,6 +41,15 @@ def main():
     print(f"dense PCA's variances {np.round(w[::-1][:r], 2).tolist()}; largest principal angle between the two "
           f"{r}-dimensional subspaces {np.degrees(np.arccos(min(1.0, sv.min()))):.2f} degrees; "
           f"max |mean - dense mean| = {np.abs(mean - mu).max():.3f}")
+
+    # the same components without the p2 x p2 matrix: subspace iteration on the shard's operator (any p2, either id width)
+    comp_s, var_s, _, out_s = pca_sparsified(data, r, method="subspace")
+    form, R, slices, wgs = out_s["covApplyPlan"]
+    sv = np.linalg.svd(comp_s @ comp.T, compute_uv=False)
+    print(f"matrix-free: {out_s['passes']} passes of a {out_s['blockWidth']}-column block (converged: {out_s['converged']}; form "
+          f"{form}, {R} rows per slab, {slices} slices, {wgs} workgroups), operator {out_s['TimeApply'] * 1e3:.1f} ms, the rest "
+          f"{out_s['TimeSmall'] * 1e3:.1f} ms; explained variance {np.round(var_s, 2).tolist()}; largest angle to the eigh "
+          f"components {np.degrees(np.arccos(min(1.0, sv.min()))):.2e} degrees; largest residual {out_s['residuals'].max():.2e}")
 
     IDX, C, SUMD, D, OUT = kmeans_sparsified(data, K, Replicates=5)
     M = np.zeros((K, K))

@@ -634,6 +634,37 @@ int spkm_gram_csc_nnz_dev(spkm_ctx *ctx, uint64_t p2, uint64_t ncols, uint64_t n
  * (form 2: 0), workgroups }; zeros before the first.  Stored values; does not block. */
 int spkm_last_gram_plan(spkm_ctx *ctx, int64_t info[4]);
 
+/* The Gram operator applied to a thin block, without the Gram matrix -- the hot loop of matrix-free PCA on sparsified
+ * data: over the ncols columns w_i of a CSC chunk in device memory, as spkm_shard_export_dev writes one (d_jc int64
+ * [ncols + 1] relative to the chunk's first entry; d_ir row ids of ir_bits = 16 (uint16) or 32 (uint32) bits, ascending
+ * within a column; d_x float64),
+ *     Z[r, :] += sum_i w_i[r] (w_i^T Q)            d_Q, d_Z float64 [p2, b] row-major, 1 <= b <= 32; Z is ADDED to
+ *     diag[r] += sum_i w_i[r]^2                    d_diag float64 [p2] or NULL
+ *     sum[r]  += sum_i w_i[r]                      d_sum  float64 [p2] or NULL
+ * so that Z = G Q for G = sum_i w_i w_i^T, in p2 b doubles instead of p2^2, and diag is G's diagonal.  There is no cap on
+ * p2 other than the id width.  nnz = d_jc[ncols], stated by the caller as in spkm_gram_csc_nnz_dev: only the choice of
+ * form depends on it, no access does; the call is asynchronous on the context's stream and never blocks.
+ * Every addition is a float64 atomic add whose order is not fixed: THE LAST BITS ARE NOT REPRODUCIBLE; each entry of Z
+ * stays within (m + s + 2) u |W| (|W|^T |Q|) of the exact sum over m columns of at most s entries.
+ * Two forms (csrc/gram_apply.hip), chosen by a byte model in csrc/policy.h (spkm_cov_apply_plan; its two rates come from
+ * profiles/cov_apply_ab.txt): 1 = the projections T = W^T Q written to d_work (float64 [ncols, b], contents undefined
+ * afterwards), then scattered through LDS slabs of R rows of Z, one workgroup per row slice and chunk of points; 2 = one
+ * wave per point, the projections in registers, every product straight to Z, the b adds of an entry on one contiguous
+ * row.  d_work == NULL means form 2.  SPKM_X_COVAPPLY_FORM=1|2 forces a form (1 without a workspace stays 2),
+ * SPKM_X_COVAPPLY_ROWS=r caps R at r, at least 8 -- experiments and tests only; read with the other switches
+ * (spkm_ctx_reload_switches).
+ * Rows are trusted to ascend and to lie below p2; a chunk that breaks this gives wrong sums, never an access outside the
+ * arrays.  d_Q must not overlap d_Z.
+ * SPKM_ERR_BAD_VALUE: p2 == 0, b == 0 or b > 32, ir_bits not 16 / 32, 16-bit ids with p2 > 65536, or d_jc / d_ir / d_x /
+ * d_Q / d_Z NULL with ncols > 0.  ncols == 0: nothing is done, SPKM_OK. */
+int spkm_cov_apply_csc_dev(spkm_ctx *ctx, uint64_t p2, uint64_t ncols, uint64_t nnz, const int64_t *d_jc, const void *d_ir,
+                           int ir_bits, const double *d_x, uint32_t b, const double *d_Q, double *d_Z,
+                           double *d_work /* [ncols*b] or NULL */, double *d_diag /* or NULL */, double *d_sum /* or NULL */);
+/* What the context's last spkm_cov_apply_csc_dev that launched a kernel ran: info = { form, rows per slab R (form 2: 0),
+ * row slices (form 2: 0), workgroups (form 1: of the scatter launch) }; zeros before the first.  Stored values; does not
+ * block. */
+int spkm_last_cov_apply_plan(spkm_ctx *ctx, int64_t info[4]);
+
 /* centers(:,k) = gamma*S(:,k) ./ (Cnt(:,k) + 1e-16) for clusters with nk > 0
  * (kmeans_sparsified.m:448); empty clusters keep their column.  d_centers is updated in place;
  * d_out double[2] (device) = { ||old-new||_F^2, obj2 } (kmeans_sparsified.m:470-471 before sqrt). */

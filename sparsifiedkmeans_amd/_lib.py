@@ -184,6 +184,8 @@ def lib():
     L.spkm_gram_csc_dev.argtypes = [_vp, _u64, _u64, _vp, _vp, C.c_int, _vp, _vp, _vp]
     L.spkm_gram_csc_nnz_dev.argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, C.c_int, _vp, _vp, _vp]
     L.spkm_last_gram_plan.argtypes = [_vp, C.POINTER(C.c_int64)]
+    L.spkm_cov_apply_csc_dev.argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, C.c_int, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
+    L.spkm_last_cov_apply_plan.argtypes = [_vp, C.POINTER(C.c_int64)]
     L.spkm_ctx_reload_switches.argtypes = [_vp]
     L.spkm_widen_f64_dev.argtypes = [_vp, C.c_int, _u64, _vp, _vp]
     L.spkm_comm_unique_id.argtypes = [_vp]

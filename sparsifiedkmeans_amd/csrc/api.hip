@@ -52,6 +52,8 @@ static spkm_switches read_switches()
     if (const char* v = getenv("SPKM_X_SLAB_ROWS")) w.x_slab_rows = std::max(0, atoi(v)); // rows per slab of k_accumulate_sliced (default: what the LDS holds)
     if (const char* v = getenv("SPKM_X_GRAM_TILE")) w.x_gram_tile = std::max(0, atoi(v)); // rows per block of k_gram_tiles, at most (default: what the LDS holds)
     if (const char* v = getenv("SPKM_X_GRAM_FORM")) { const int f = atoi(v); w.x_gram_form = (f == 1 || f == 2) ? f : 0; } // (experiments and tests, spkm.h)
+    if (const char* v = getenv("SPKM_X_COVAPPLY_ROWS")) w.x_covapply_rows = std::max(0, atoi(v)); // rows per slab of k_cov_scatter_slab, at most (default: what the LDS holds)
+    if (const char* v = getenv("SPKM_X_COVAPPLY_FORM")) { const int f = atoi(v); w.x_covapply_form = (f == 1 || f == 2) ? f : 0; } // (experiments and tests, spkm.h)
     if (const char* v = getenv("SPKM_FORCE_FORM")) w.force_form = std::max(0, std::min(3, atoi(v))); // (test aid, spkm.h)
     if (const char* v = getenv("SPKM_X_HINT_CHUNK")) w.x_hint_chunk = atoi(v);   // points per chunk in the two-phase screen launches (default 256)
     if (const char* v = getenv("SPKM_X_PLAIN_CHUNK")) w.x_plain_chunk = atoi(v); // ... in the plain launch (default: n / (8 x teams), at most 4096)

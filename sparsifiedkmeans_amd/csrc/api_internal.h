@@ -69,6 +69,8 @@ struct spkm_switches {
     int x_slab_rows = 0;          // SPKM_X_SLAB_ROWS: at most this many rows per slab of k_accumulate_sliced, at any p and any number of slices (0: the default, what the LDS holds; experiments and tests)
     int x_gram_tile = 0;          // SPKM_X_GRAM_TILE: at most this many rows per block of k_gram_tiles, rounded down to a multiple of 16, at least 16 (0: the default, what the LDS holds; experiments and tests)
     int x_gram_form = 0;          // SPKM_X_GRAM_FORM=1|2: spkm_gram_csc_dev takes the LDS tiles / the direct form whatever the byte model says (policy.h, spkm_gram_plan; experiments and tests)
+    int x_covapply_rows = 0;      // SPKM_X_COVAPPLY_ROWS: at most this many rows per slab of k_cov_scatter_slab, at least 8 (0: the default, what the LDS holds; experiments and tests)
+    int x_covapply_form = 0;      // SPKM_X_COVAPPLY_FORM=1|2: spkm_cov_apply_csc_dev takes the projected / the direct form whatever the byte model says (policy.h, spkm_cov_apply_plan; experiments and tests)
     bool force_point_list = false; // SPKM_FORCE_POINT_LIST: the carried-bounds test lists points whenever it runs (test aid, spkm.h)
     int mover_tile2 = 0;           // SPKM_NO_MOVER_TILE2: -1 / SPKM_MOVER_TILE2: +1, the second level -- steps that only the 64 largest movers unsettle, on two tiles of those (policy.h, spkm_plan_movers2); 0: the default
     int mover_tile = 0;            // SPKM_NO_MOVER_TILE: -1, steps that only the largest movers unsettle are screened like any other; SPKM_MOVER_TILE: +1, on one tile of those (policy.h, spkm_plan_movers); 0: the default
@@ -144,6 +146,7 @@ struct spkm_ctx {
     int last_kpp[4] = {0, 0, 0, 0};  // the last spkm_kpp_seed_dev: form (policy.h, spkm_kpp_plan / spkm_kpp_plan_ragged; 0: none yet or K = 1), RB, batches, points staged per wave
     int last_sparse[4] = {0, 0, 0, 0}; // the last spkm_assign_sparse_centers_dev: form, points per wave, waves per workgroup, LDS bytes (policy.h, spkm_sparse_plan); zeros after any other assignment call
     long long last_gram[4] = {0, 0, 0, 0}; // the last spkm_gram_csc_dev that launched: form, T, block pairs, workgroups (policy.h, spkm_gram_plan)
+    long long last_cov_apply[4] = {0, 0, 0, 0}; // the last spkm_cov_apply_csc_dev that launched: form, rows per slab, slices, workgroups (policy.h, spkm_cov_apply_plan)
     unsigned last_listed = 0;        // points sent to the exact list by the last screen (read lazily)
     bool sort_perm_valid = false;    // ... and perm / offs / items really hold that call's counting sort (not after an incremental call)
     char errmsg[256] = {0};

@@ -555,6 +555,84 @@ inline spkm_gram_geom spkm_gram_plan(long long p2, unsigned long long nnz, unsig
     g.form = 1; g.T = (int)T; g.pairs = pairs; g.chunk = chunk; g.grid = pairs * chunks;
     return g;
 }
+// ---- the Gram operator on a thin block (spkm_cov_apply_csc_dev; gram_apply.hip) ----
+// Z += sum_i w_i (w_i^T Q) over a chunk of sparse columns, Q and Z f64 [p2, b], 1 <= b <= spkm_cov_max_b; `extra` of diag
+// and sum (0, 1 or 2) are asked for as well.  form, as spkm_last_cov_apply_plan reports it:
+//  1  k_cov_project, then k_cov_scatter_slab: the projections T = W^T Q go to the caller's workspace [ncols, b]; the rows are
+//     cut into slices of R, a workgroup owning one slice and one chunk of the points, its R x bb slab in LDS, bb = b + extra
+//     (diag and sum ride as two more columns of the slab).  The kernel stages nothing else, so R is the largest count with
+//     8 R bb <= lds_max - spkm_cov_lds_reserve, the reserve being room for a kernel's static LDS as in the k-means++ table
+//     (R = 1272 at b = 16, 1130 with diag and sum, with 160 KB; 504 / 448 with 64 KB), at most p2.  slices = ceil(p2 / R).
+//     A workgroup zeroes and flushes its slab whatever it is given, so a chunk is as long as filling the device allows: about
+//     spkm_cov_wgs workgroups over all slices, never fewer than spkm_cov_min_chunk points per chunk; workgroups = slices x
+//     chunks.  Needs the workspace: without one (have_work false) the answer is form 2, forced or not.
+//  2  k_cov_apply_direct: one wave per point, the projections in registers, every product one f64 global add, the b adds of
+//     an entry on one contiguous row of Z.  Any p2, no LDS, no workspace.
+// The choice is a byte model, one rate a side:
+//   form 1 streams, per slice, the chunk's row ids and column bounds and the T rows -- slices x (nnz idb + ncols (16 + 8 b)),
+//     idb = 2 or 4 -- and once the values of the runs (nnz x 8); the projection launch in front reads the chunk and gathers
+//     the rows of Q (nnz (idb + 8 + 8 b)) and writes T (ncols x 8 b); the flush adds slices x chunks x R x bb x 8 B (an upper
+//     bound: zeros are skipped).  All of it is divided by spkm_cov_stream_rate;
+//   form 2 issues nnz x b x 8 B of row-contiguous atomics, divided by spkm_cov_row_atomic_rate (its gather, the same as the
+//     projection launch's, is not counted: the adds are what it waits for).
+// Both rates are fitted to profiles/cov_apply_ab.txt (tools/cov_apply_ab.py: b = 16, later pass, ONE run per form and
+// shape, no spread) and are EFFECTIVE rates of this model's bytes, not bandwidths of anything.
+// spkm_cov_row_atomic_rate = 1.44 TB/s: k_cov_apply_direct added its nnz x b x 8 B at 1.45 / 1.44 / 1.43 / 1.43 TB/s at
+// (N = 1e7, p2 = 1024, s = 51), (1e7, 8192, 82), (1e6, 65536, 66), (1e6, 70000, 70, 32-bit ids) -- eight times the 0.18 TB/s
+// of the Gram kernels' scattered adds.  spkm_cov_stream_rate = 1.85 TB/s: form 1 worked through this model's bytes at
+// 2.86 / 1.66 / 0.80 / 0.89 TB/s at the same shapes (1 / 7 / 52 / 56 slices), so no one constant describes it; 1.85 lies in
+// the only interval (1.73 .. 1.96) that gives the measured winner at all four -- form 1 at the first (27 against 45 ms),
+// form 2 at the others (73 against 86, 5.9 against 30, 6.3 against 39 ms) -- and overstates form 1 twofold at many slices,
+// where the model picks form 2 by a wide margin anyway.  Fitted to four points: that the model agrees with them is true
+// by construction; where the crossover lies in p2, s or b is NOT measured.
+// SPKM_X_COVAPPLY_ROWS=r (x_rows > 0: experiments and tests) caps R at max(r, 8); SPKM_X_COVAPPLY_FORM=1|2 (x_form) forces
+// a form -- form 1 without a workspace, or where no slab row fits the LDS, still answers form 2.
+constexpr int spkm_cov_max_b = 32;              // columns of Q per call, at most (one wave covers a row of 32)
+constexpr int spkm_cov_waves = 8;               // waves per workgroup of k_cov_scatter_slab (512 threads)
+constexpr long long spkm_cov_wgs = 1024;        // workgroups a launch of k_cov_scatter_slab aims at
+constexpr long long spkm_cov_min_chunk = 1024;  // points per chunk, at least
+constexpr long long spkm_cov_min_rows = 8;      // SPKM_X_COVAPPLY_ROWS below this reads as this
+constexpr size_t spkm_cov_lds_reserve = 1024;   // bytes of the LDS left beside the slab
+constexpr long long spkm_cov_direct_max_grid = 65536; // workgroups of k_cov_apply_direct / k_cov_project (4 points each per trip), at most
+constexpr double spkm_cov_row_atomic_rate = 1.44e12; // B/s of row-contiguous f64 global adds, effective (profiles/cov_apply_ab.txt)
+constexpr double spkm_cov_stream_rate = 1.85e12;     // B/s of the model's form-1 bytes, effective (profiles/cov_apply_ab.txt)
+struct spkm_cov_apply_geom {
+    int form = 2;          // 1 projected then slab-accumulated, 2 direct
+    int R = 0;             // rows per slab (form 2: 0)
+    long long slices = 0;  // row slices (form 2: 0)
+    long long chunk = 0;   // points per workgroup chunk (form 2: 0)
+    long long grid = 0;    // workgroups of the scatter (form 1) or of the direct kernel (form 2); ncols == 0: 0
+    long long pgrid = 0;   // workgroups of k_cov_project (form 2: 0)
+};
+inline size_t spkm_cov_apply_lds(long long R, int bb) { return (size_t)(8 * R * bb); }
+inline spkm_cov_apply_geom spkm_cov_apply_plan(unsigned long long p2, unsigned long long nnz, unsigned long long ncols, int b,
+                                               int extra, int ir_bits, bool have_work, size_t lds_max, int x_rows, int x_form)
+{
+    spkm_cov_apply_geom g;
+    if (p2 == 0 || ncols == 0 || b < 1 || b > spkm_cov_max_b || extra < 0 || extra > 2) return g;
+    const long long n = (long long)ncols;
+    const long long direct_grid = std::min<long long>((n + 3) / 4, spkm_cov_direct_max_grid);
+    const long long bb = b + extra;
+    long long R = lds_max > spkm_cov_lds_reserve ? (long long)((lds_max - spkm_cov_lds_reserve) / (size_t)(8 * bb)) : 0;
+    if ((unsigned long long)R > p2) R = (long long)p2;
+    if (x_rows > 0) R = std::min<long long>(R, std::max<long long>(spkm_cov_min_rows, x_rows));
+    if (R < 1 || !have_work || x_form == 2) { g.grid = direct_grid; return g; }
+    const long long slices = (long long)((p2 + (unsigned long long)R - 1) / (unsigned long long)R);
+    const long long per = std::max<long long>(1, spkm_cov_wgs / slices); // chunks the target allows
+    const long long chunk = std::max<long long>(spkm_cov_min_chunk, (n + per - 1) / per);
+    const long long chunks = (n + chunk - 1) / chunk;
+    if (x_form != 1) {
+        const double idb = ir_bits == 16 ? 2.0 : 4.0;
+        const double bytes1 = (double)slices * ((double)nnz * idb + (double)n * (16.0 + 8.0 * (double)b)) + (double)nnz * 8.0 +
+                              (double)nnz * (idb + 8.0 + 8.0 * (double)b) + (double)n * 8.0 * (double)b +
+                              (double)slices * (double)chunks * (double)R * (double)bb * 8.0;
+        const double t1 = bytes1 / spkm_cov_stream_rate;
+        const double t2 = (double)nnz * (double)b * 8.0 / spkm_cov_row_atomic_rate;
+        if (t2 <= t1) { g.grid = direct_grid; return g; }
+    }
+    g.form = 1; g.R = (int)R; g.slices = slices; g.chunk = chunk; g.grid = slices * chunks; g.pgrid = direct_grid;
+    return g;
+}
 // ---- batched k-means++ seeding (spkm_kpp_seed_dev; kpp.hip) ----
 // R replicates are seeded RB at a time (RB = 8, 4, 2 or 1, at most the next power of two >= R), each batch sharing one read
 // of the shard per round.  form reported by spkm_last_kpp_plan:

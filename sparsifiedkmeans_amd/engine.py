@@ -1126,6 +1126,127 @@ def gram_shard(shard: Shard, chunk_bytes: int = SHARD_CHUNK_BYTES) -> tuple[torc
     return G, colsum
 
 
+COV_APPLY_MAX_B = 32              # spkm_cov_apply_csc_dev: columns of Q per call, at most
+
+
+def last_cov_apply_plan(ctx: Context) -> tuple[int, int, int, int]:
+    """(form, rows per slab, row slices, workgroups) of the context's last ``cov_apply_csc`` that launched a kernel
+    (spkm_last_cov_apply_plan): form 1 = projections to the workspace, then LDS slabs of R rows of Z, one workgroup per row
+    slice and chunk of points; 2 = one wave per point, products straight to Z (R and the slices read 0); zeros before the
+    first call."""
+    a = (C.c_int64 * 4)()
+    _lib.check(_lib.lib().spkm_last_cov_apply_plan(ctx.handle, a), "spkm_last_cov_apply_plan")
+    return int(a[0]), int(a[1]), int(a[2]), int(a[3])
+
+
+def cov_apply_csc(ctx: Context, p2: int, ncols: int, nnz: int, jc: torch.Tensor, ir: torch.Tensor, x: torch.Tensor,
+                  Q: torch.Tensor, Z: torch.Tensor, work: torch.Tensor | None = None, diag: torch.Tensor | None = None,
+                  colsum: torch.Tensor | None = None) -> None:
+    """Z += sum_i w_i (w_i^T Q), diag += sum_i w_i^2, colsum += sum_i w_i over the ``ncols`` columns of a CSC chunk on the
+    device, as ``Shard.export`` delivers one (spkm_cov_apply_csc_dev).  Q, Z float64 [p2, b] row-major, b <= 32; work
+    float64 with room for ncols * b values, or None (the direct form); diag / colsum float64 [p2] or None; ``nnz`` the
+    chunk's entry count.  Asynchronous on the context's stream.  The last bits depend on the order of the atomic additions."""
+    b = int(Q.shape[1])
+    assert jc.is_cuda and jc.dtype == torch.int64 and jc.is_contiguous() and jc.numel() >= ncols + 1
+    assert ir.is_cuda and ir.is_contiguous() and x.is_cuda and x.is_contiguous() and x.dtype == torch.float64
+    for t in (Q, Z):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == (p2, b)
+    assert work is None or (work.is_cuda and work.is_contiguous() and work.dtype == torch.float64 and work.numel() >= ncols * b)
+    for t in (diag, colsum):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == p2)
+    opt = lambda t: None if t is None else _p(t)
+    _lib.check(_lib.lib().spkm_cov_apply_csc_dev(ctx.handle, int(p2), int(ncols), int(nnz), _p(jc), _p(ir), ir.element_size() * 8,
+                                                 _p(x), b, _p(Q), _p(Z), opt(work), opt(diag), opt(colsum)),
+               "spkm_cov_apply_csc_dev")
+
+
+class CovOperator:
+    """Q -> G Q for G = sum_i v_i v_i^T over a resident shard, without G: p2 * b doubles a pass instead of p2^2, at any p2 and
+    either id width.  The shard is cut into CSC chunks of at most ``chunk_bytes`` of entries, as ``gram_shard`` cuts it (a
+    ragged shard's column starts are fetched first); a records-only shard stays records-only.  If all chunks together
+    (entries and column starts) fit a quarter of the device memory free at construction, they are exported once, on the
+    first pass, and kept (``resident`` True); otherwise every pass re-exports each chunk through two alternating buffers.
+    The first pass also fills ``diag`` (G's diagonal) and ``sum`` (sum_i v_i), float64 [p2] on the device; later passes
+    leave them alone.  ``passes`` counts the calls of ``apply``; ``close()`` frees the buffers."""
+
+    def __init__(self, shard: Shard, chunk_bytes: int = SHARD_CHUNK_BYTES, resident: bool | None = None):
+        """``resident``: None decides by the free memory; True / False overrule it (tests; a caller who knows better)"""
+        self.shard, self.ctx = shard, shard.ctx
+        ctx, dev = shard.ctx, torch.device("cuda", shard.ctx.device)
+        self.dev = dev
+        self.p2, self.n, self.nnz = int(shard.p), int(shard.n), int(shard.nnz)
+        n, nnz = self.n, self.nnz
+        self._stream = _ctx_stream(ctx, dev)
+        entry = 8 + shard.ir_bits // 8
+        with torch.cuda.stream(self._stream):
+            s = shard.layout_info()[2] if nnz else 0
+            jc_h = None
+            if nnz and s == 0:
+                # a ragged shard's column starts first (8 bytes per point): the chunks are cut by them
+                jc_h = np.zeros(n + 1, np.int64)
+                step = max(1, int(chunk_bytes) // 8)
+                jc_d = torch.empty(min(n, step) + 1, dtype=torch.int64, device=dev)
+                for c0 in range(0, n, step):
+                    m = min(step, n - c0)
+                    shard._export_jc(c0, m, jc_d)
+                    jc_h[c0 + 1:c0 + m + 1] = jc_d[1:m + 1].cpu().numpy() + jc_h[c0]
+                del jc_d
+            self.chunks = _column_chunks(n, nnz, s, jc_h, entry, chunk_bytes) if nnz else []
+            self._mcols = max((c1 - c0 for c0, c1, _, _ in self.chunks), default=0)
+            cap = max((j1 - j0 for _, _, j0, j1 in self.chunks), default=0)
+            need = nnz * entry + 8 * (n + len(self.chunks))
+            self.resident = need <= torch.cuda.mem_get_info(ctx.device)[0] // 4 if resident is None else bool(resident)
+            mk = lambda cnt, cols: (torch.empty(cols + 1, dtype=torch.int64, device=dev),
+                                    torch.empty(max(cnt, 1), dtype=shard._ir_dtype(), device=dev),
+                                    torch.empty(max(cnt, 1), dtype=torch.float64, device=dev))
+            if self.resident:
+                self._buf = [mk(j1 - j0, c1 - c0) for c0, c1, j0, j1 in self.chunks]
+            else:
+                self._buf = [mk(cap, self._mcols) for _ in range(2)]
+            self._filled = False
+            self.diag = torch.zeros(self.p2, dtype=torch.float64, device=dev)
+            self.sum = torch.zeros(self.p2, dtype=torch.float64, device=dev)
+        self._work = None
+        self.passes = 0
+
+    def apply(self, Q: torch.Tensor) -> torch.Tensor:
+        """Z = G Q, float64 [p2, b] on the device, for Q [p2, b] with any b >= 1 (blocks wider than 32 go in column groups
+        of at most 32, each a pass over the chunks)"""
+        if self._buf is None:
+            raise ValueError("the CovOperator is closed")
+        assert Q.is_cuda and Q.dtype == torch.float64 and Q.dim() == 2 and Q.shape[0] == self.p2 and Q.shape[1] >= 1
+        first = self.passes == 0
+        with torch.cuda.stream(self._stream):
+            out = []
+            for g0 in range(0, Q.shape[1], COV_APPLY_MAX_B):
+                Qg = Q[:, g0:g0 + COV_APPLY_MAX_B].contiguous()
+                b = Qg.shape[1]
+                Zg = torch.zeros_like(Qg)
+                if self._work is None or self._work.numel() < self._mcols * b:
+                    self._work = torch.empty(max(1, self._mcols * b), dtype=torch.float64, device=self.dev)
+                stats = first and g0 == 0
+                for k, (c0, c1, j0, j1) in enumerate(self.chunks):
+                    jc, ir, x = self._buf[k if self.resident else k & 1]
+                    if not (self.resident and self._filled):
+                        self.shard.export_into(c0, c1 - c0, jc, ir, x)
+                    cov_apply_csc(self.ctx, self.p2, c1 - c0, j1 - j0, jc, ir, x, Qg, Zg, self._work,
+                                  self.diag if stats else None, self.sum if stats else None)
+                self._filled = True
+                out.append(Zg)
+            self.passes += 1
+            return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def close(self) -> None:
+        self._buf = self._work = None
+        self.chunks = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def _copy_threads() -> int:
     """threads of the host-side staging copy (SPKM_COPY_THREADS overrides).  Measured on the benchmark box (256 hardware
     threads, tools/ingest_probe2.py): torch's own parallel copy moves 93 GB/s into pinned memory with 16 threads, 21 GB/s

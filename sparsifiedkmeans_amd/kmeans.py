@@ -447,12 +447,134 @@ def covariance_sparsified(data: SparsifiedData, center: bool = True, unmix: bool
     return C_.cpu().numpy(), mean.cpu().numpy(), OUTPUT
 
 
-def pca_sparsified(data: SparsifiedData, k: int, center: bool = True, covariance=None):
+def _subspace_eig(apply, p: int, k: int, b: int, tol: float, max_passes: int, generator, device):
+    """Blocked subspace iteration with Rayleigh-Ritz for a symmetric operator given by its action: ``apply(Q)`` returns A Q
+    for Q float64 [p, b] on ``device``.  Nothing here depends on a GPU.
+
+    Start: Q = qr of a standard normal [p, b] block drawn from ``generator`` (on the generator's own device, then moved).
+    A pass is ONE application Y = A Q; B = Q^T Y is symmetrised and decomposed (eigh), the Ritz pairs are theta and
+    V = Q S, ordered by theta descending (algebraically), and their residuals R = Y S - V diag(theta) come from the same Y.
+    Converged: the k largest Ritz values all have ||r_j|| <= tol max|theta|.  Otherwise Q = qr(Y) and the next pass runs, at
+    most ``max_passes``.  Power iteration draws the block towards the eigenvalues of largest MAGNITUDE: the k pairs returned
+    are the leading ones when those are positive.
+
+    Returns (theta [k], V [p, k], residual norms [k], passes, converged) -- after ``max_passes`` without convergence the
+    last block, with a warning."""
+    g_dev = getattr(generator, "device", torch.device("cpu"))
+    Q = torch.randn((p, b), dtype=torch.float64, device=g_dev, generator=generator).to(device)
+    Q = torch.linalg.qr(Q)[0]
+    passes, converged = 0, False
+    while True:
+        Y = apply(Q)
+        passes += 1
+        Bm = Q.T @ Y
+        th, S = torch.linalg.eigh(0.5 * (Bm + Bm.T))
+        th, S = th.flip(0), S.flip(1)                                     # descending
+        V = Q @ S
+        res = torch.linalg.vector_norm(Y @ S - V * th, dim=0)
+        converged = bool((res[:k] <= tol * th.abs().max()).all().item())
+        if converged or passes >= max_passes:
+            break
+        Q = torch.linalg.qr(Y)[0]
+    if not converged:
+        warnings.warn(f"subspace iteration: the {k} leading Ritz pairs did not reach tol = {tol:g} within {max_passes} "
+                      f"passes (largest residual {float(res[:k].max().item()):.3e}, relative to "
+                      f"{float(th.abs().max().item()):.3e}); the last block is returned", RuntimeWarning, stacklevel=2)
+    return th[:k].clone(), V[:, :k].contiguous(), res[:k].clone(), passes, converged
+
+
+def _estimate_apply(op, Qm: torch.Tensor, n: int, f_diag: float, f_off: float, center: bool) -> torch.Tensor:
+    """The covariance estimate's action in the shard's (mixed) domain, Y = C Qm for Qm float64 [p2, b], from the operator
+    alone: with Z = G Qm, diag = diag(G) and sum (engine.CovOperator; the latter two filled by its first pass),
+        Y = (f_off / n) Z + ((f_diag - f_off) / n) diag o Qm - [center] mean (mean^T Qm),    mean = sum / n
+    which is covariance_sparsified(data, center, unmix=False)[0] @ Qm up to rounding: the off-diagonal factor on all of G,
+    the diagonal put right by the difference of the two factors."""
+    Z = op.apply(Qm)
+    Y = Z * (f_off / n) + (op.diag * ((f_diag - f_off) / n))[:, None] * Qm
+    if center:
+        mu = op.sum / n
+        Y -= torch.outer(mu, mu @ Qm)
+    return Y
+
+
+def _pca_subspace(data: SparsifiedData, k: int, center: bool, oversample: int, tol: float, max_passes: int, seed: int):
+    """pca_sparsified(method="subspace"): the estimate's action on a block through engine.CovOperator, never the matrix"""
+    from .engine import CovOperator, last_cov_apply_plan
+
+    if not isinstance(data, SparsifiedData):
+        raise TypeError("pca_sparsified takes a SparsifiedData (sparsify / SparsifiedData.load)")
+    if data.shard is None:
+        raise ValueError("the SparsifiedData is closed: its shard was freed")
+    if data.n_total != data.n:
+        raise NotImplementedError(f"the data is a block of a distributed run (n = {data.n} of n_total = {data.n_total}): "
+                                  "Z, diag, sum and n are additive, but their all-reduce is not implemented")
+    s, p, p2, n = data.small_p, int(data.p), int(data.p2), data.n
+    if s == 1:
+        raise ValueError("small_p = 1: one entry per point holds no product of two different rows, so the off-diagonal "
+                         "of the covariance cannot be estimated (raise SparsityLevel)")
+    if int(oversample) != oversample or oversample < 0 or int(max_passes) != max_passes or max_passes < 1 or not tol > 0:
+        raise ValueError(f"oversample = {oversample} must be an integer >= 0, max_passes = {max_passes} one >= 1, tol = {tol} > 0")
+    b = min(p, k + int(oversample))
+    f_diag = s / p2
+    f_off = (s * (p2 - 1)) / (p2 * (s - 1))
+    sk, dev = data.sketch, torch.device("cuda", data.ctx.device)
+    times = dict(apply=0.0)
+    op = CovOperator(data.shard)
+
+    def apply(Q):
+        t1 = time.time()
+        Qm = sk.mix(Q.T.contiguous()).T.contiguous()                      # [p2, b]: the sketch's own upsampling
+        Y = _estimate_apply(op, Qm, n, f_diag, f_off, center)
+        Y = sk.unmix(Y.T.contiguous()).T.contiguous()                     # [p, b]
+        torch.cuda.synchronize(data.ctx.device)
+        times["apply"] += time.time() - t1
+        return Y
+
+    t0 = time.time()
+    try:
+        th, V, res, passes, converged = _subspace_eig(apply, p, k, b, float(tol), int(max_passes),
+                                                      torch.Generator().manual_seed(int(seed)), dev)
+        mean = sk.unmix((op.sum / n)[None, :])[0]
+        plan, resident = last_cov_apply_plan(data.ctx), op.resident
+    finally:
+        op.close()
+    V = V.T.contiguous()                                                  # [k, p]
+    big = V.gather(1, V.abs().argmax(dim=1, keepdim=True))
+    V = torch.where(big < 0, -V, V)
+    torch.cuda.synchronize(data.ctx.device)
+    total = time.time() - t0
+    OUTPUT = dict(method="subspace", passes=passes, converged=converged, residuals=res.cpu().numpy(), blockWidth=b,
+                  covApplyPlan=plan, chunksResident=resident, TimeApply=times["apply"], TimeSmall=total - times["apply"],
+                  n=n, s=s, diagFactor=f_diag, offDiagFactor=f_off)
+    return V.cpu().numpy(), th.cpu().numpy(), mean.cpu().numpy(), OUTPUT
+
+
+def pca_sparsified(data: SparsifiedData, k: int, center: bool = True, covariance=None, method: str = "eigh", oversample: int = 8,
+                   tol: float = 1e-8, max_passes: int = 60, seed: int = 0):
     """(components [k, p], explained_variance [k], mean [p], OUTPUT): the k leading principal components of the data from
     ``covariance_sparsified(data, center)`` in the data's domain -- torch.linalg.eigh of the p x p estimate on the device,
     the k largest eigenvalues in descending order, each component's sign fixed so that its entry of largest magnitude is
     positive.  The estimate is unbiased (up to the O(1/n) of centering) but not positive semidefinite by construction:
     trailing eigenvalues of a noisy estimate may be negative.
+
+    ``method="eigh"`` (the default) is that: the Gram pass, the whole p2 x p2 matrix, a dense eigen-solve; p2 <= 32768 and
+    16-bit row ids.  ``oversample``, ``tol``, ``max_passes`` and ``seed`` are not read.
+
+    ``method="subspace"`` never forms the matrix: blocked subspace iteration with Rayleigh-Ritz (``_subspace_eig``) on the
+    estimate's ACTION on a block Q [p, b], b = min(p, k + oversample).  One application mixes Q's columns into the shard's
+    domain with the sketch's own transform, takes Z = G Q from the shard (engine.CovOperator: HIP kernels, p2 b doubles
+    instead of p2^2, any p2 the sparsifier ingests, either id width), forms (f_off / n) Z + ((f_diag - f_off) / n) diag o Q
+    - [center] mean (mean^T Q) with the factors of covariance_sparsified, and unmixes the rows back.  The sketches are
+    orthonormal, so this operator is symmetric and equals covariance_sparsified(data, center)[0] @ Q up to rounding.
+    A pass is one application; it stops when the k largest (algebraic) Ritz values all have residuals ||C v - theta v|| <=
+    tol max|theta|, or after ``max_passes`` -- then with OUTPUT["converged"] False and a warning, not an exception.  The
+    start block is drawn from a torch generator seeded with ``seed``: a call is repeatable up to the last bits of the
+    atomic sums.  Because the estimate is NOT positive semidefinite, and power iteration converges on the eigenvalues of
+    largest MAGNITUDE, the components returned are the leading ones when those eigenvalues are positive -- the case for any
+    estimate worth decomposing; OUTPUT["residuals"] shows when they are not (they stay large).  OUTPUT: method, passes,
+    converged, residuals [k], blockWidth, covApplyPlan (form, rows per slab, slices, workgroups of the last operator call),
+    chunksResident, TimeApply, TimeSmall, n, s, diagFactor, offDiagFactor.  ``covariance=`` is refused with it (there is
+    nothing to decompose matrix-free), as are closed data, small_p = 1 and a block of a distributed run.
 
     ``covariance``: the tuple covariance_sparsified(data, center) returned -- (C [p, p], mean [p]) or (C, mean, OUTPUT) --
     to be decomposed as it is instead of running the Gram pass again: several k from one pass, and, because the sums'
@@ -464,6 +586,13 @@ def pca_sparsified(data: SparsifiedData, k: int, center: bool = True, covariance
     if int(k) != k or not (1 <= int(k) <= p):
         raise ValueError(f"k = {k} is outside 1..p = {p}")
     k = int(k)
+    if method not in ("eigh", "subspace"):
+        raise ValueError(f"method = {method!r}: pca_sparsified knows 'eigh' and 'subspace'")
+    if method == "subspace":
+        if covariance is not None:
+            raise ValueError("covariance= with method='subspace': the subspace iteration works on the shard's operator and "
+                             "never forms a matrix, so there is nothing to decompose matrix-free (use method='eigh')")
+        return _pca_subspace(data, k, bool(center), oversample, tol, max_passes, seed)
     if covariance is None:
         C_, mean, OUTPUT = _covariance_device(data, bool(center), True)
     else:
